@@ -3,7 +3,7 @@
 1000-step DDPM with classifier-free guidance, synthetic inputs (BASELINE.json configs[1]:
 batch=64 per GPU).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one pass of the hot path over one batch: denoiser (CFG-doubled) + CFG combine +
@@ -17,6 +17,10 @@ where t_setup = once-per-batch work that the loop needs (RCCL broadcast of the c
 embeddings, FiLM/time tables for all 1000 steps, per-layer text K/V) and t_gather = RCCL
 all-gather of the finished sequences; both are measured here and reported in `config`.
 Inputs are resident in HBM when the timed region starts.
+
+--dump-outputs DIR writes what the K timed steps returned to their caller (rank 0's x [B,T,322], float32, at most 64 MB: the
+leading whole samples of a larger batch) as DIR/x.npy.  Weights, inputs and noise are seeded, so two builds run with the same
+arguments can be compared output for output.
 
 Extra objects on the JSON line:
   roofline      bound "mfma": algorithmic FLOPs of one step (SURVEY.md section 8d figure x samples)
@@ -39,6 +43,7 @@ sys.path.insert(0, ROOT)
 PEAK_FP32_MFMA_TFLOPS = 157.3
 PEAK_FP16_MFMA_TFLOPS = 2500.0        # dense (MI355X_MICROARCH.md)
 TOTAL_DDPM_STEPS = 1000
+DUMP_MAX_BYTES = 64 * 10 ** 6         # --dump-outputs size cap
 
 
 def measured_hbm_traffic():
@@ -228,7 +233,14 @@ def main():
     ap.add_argument('--no-extras', action='store_true', help='skip the side measurements (dominant-kernel probe, 2 batches in flight)')
     ap.add_argument('--no-full-loop', action='store_true', help='skip the complete 1000-step loop (measured-vs-extrapolated check, ~20 s)')
     ap.add_argument('--backend', default='nccl', help="'nccl' (= RCCL over xGMI); 'gloo' only for plumbing smoke tests")
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step returned (rank 0: x [B,T,322] after the K timed steps) as DIR/x.npy, float32, '
+                         'at most 64 MB')
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    if a.dump_outputs:
+        os.makedirs(a.dump_outputs, exist_ok=True)
 
     if 'WORLD_SIZE' not in os.environ and a.gpus > 1:
         # plain `python bench.py --gpus N`: become the launcher (one rank per GPU, mogen/apis/test.py:36-82 runs under
@@ -324,6 +336,9 @@ def main():
     barrier()
     t_loop = time.perf_counter() - t0
     ev_ms = ev[0].elapsed_time(ev[1]) / a.steps
+    # what the timed path handed its caller after its last step (x is updated in place and re-drawn below); the inputs are seeded, so
+    # the same arguments give the same inputs on every run.  Capped at DUMP_MAX_BYTES: the leading whole samples of the batch
+    x_timed = x[:max(1, DUMP_MAX_BYTES // (T * C * 4))].detach().cpu() if a.dump_outputs and rank == 0 else None
 
     # ---- the COMPLETE loop once, outside the K-step region: x_T -> x_0 over all 1000 steps, every step index used once
     # (`value` extrapolates 1000 * t_step from the K timed steps; this is the measured counterpart) ----
@@ -650,6 +665,9 @@ def main():
         }
         if world == 1 and not a.no_cpu_baseline:
             line['cpu_baseline'] = cpu_baseline()
+        if x_timed is not None:
+            import numpy as np
+            np.save(os.path.join(a.dump_outputs, 'x.npy'), x_timed.numpy().astype(np.float32))
         print(json.dumps(line), flush=True)
     if use_dist:
         dist.destroy_process_group()

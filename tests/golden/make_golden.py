@@ -12,7 +12,9 @@ What it does
      reference, loads the deterministic (seed, key) weights of oracle/weights.py and
      checks the key set + shapes against ``param_shapes``,
   3. pins oracle/stmogen_oracle.py against the reference (asserts max-abs <= 1e-5),
-  4. writes small .npz fixtures: inputs and REFERENCE outputs only (no source text).
+  4. writes small .npz fixtures: inputs and REFERENCE outputs only (no source text),
+  5. checks that the reference's configs/stmogen/*.py load and build through motioncraft_amd
+     (group ``reference_configs``; no fixture: the configs are reference source).
 
 Fixtures
   schedules.npz         a1/a2 tables for linear-1000 and respace '15,15,8,6,6'
@@ -120,6 +122,26 @@ def schedules():
         out[f'{tag}.timestep_map'] = np.array(tmap, dtype=np.int64)
     np.savez_compressed(os.path.join(OUT, 'schedules.npz'), **out)
     print('schedules.npz: oracle tables bit-equal to reference')
+
+
+def reference_configs():
+    """Check only, writes nothing: the reference's configs/stmogen/*.py load through motioncraft_amd's Config.fromfile
+    (``_base_`` merge included) and build through build_architecture."""
+    import motioncraft_amd as mc
+    d = os.path.join(ref_shim.REF, 'configs', 'stmogen')
+    names = sorted(f for f in os.listdir(d) if f.endswith('.py'))
+    assert len(names) == 11
+    for n in names:
+        cfg = mc.Config.fromfile(os.path.join(d, n))
+        assert cfg.model.type == 'MotionDiffusion'
+        arch = mc.build_architecture(cfg.model)
+        if n == 'T2M_humanml3d.py':                     # 263-d HumanML3D, 8 parts x 64 (SURVEY 8f.4)
+            dm = arch.model.dims
+            assert (dm['H'], dm['L'], dm['input_feats'], dm['dataset']) == (8, 64, 263, 'human_ml3d')
+        else:
+            assert arch.model.dims['H'] == 12 and arch.model.dims['L'] in (64, 128)
+        assert arch.diffusion_test.num_timesteps == 50 and arch.inference_type == 'ddim'
+    print(f'reference configs: {len(names)} load and build')
 
 
 def small_modules():
@@ -723,7 +745,7 @@ if __name__ == '__main__':
     ap.add_argument('--only', default=None, help='comma list of fixture groups to regenerate')
     a = ap.parse_args()
     torch.set_num_threads(min(32, os.cpu_count()))   # torch-CPU degrades badly on >64 threads
-    groups = dict(schedules=schedules, small_modules=small_modules, small_loops=small_loops, preseq=preseq, control=control,
+    groups = dict(schedules=schedules, reference_configs=reference_configs, small_modules=small_modules, small_loops=small_loops, preseq=preseq, control=control,
                   repaint=repaint, text_encoder=text_encoder, clip_tower=clip_tower, wav_encoder=wav_encoder, control_wav=control_wav, skeleton_parts=skeleton_parts, evaluator=evaluator, t2m_evaluator=t2m_evaluator, full=full)
     for name, fn in groups.items():
         if a.only is not None and name not in a.only.split(','):
