@@ -168,7 +168,7 @@ int mc_ctx_set_tie_policy(mc_ctx* c, int32_t policy);
 /* Kernel-selection switches of ONE context (no reference counterpart: the reference has one code path; these exist for A/B
  * measurement and for the tests that pin alternative kernels to each other).  The MC_* environment variables of the same
  * meaning only seed the defaults of contexts created afterwards; two contexts of one process may differ.  Keys:
- *   "chain" (bit mask), "big_tokens", "split_groups", "small_gemm_rows", "split_rows_expert",
+ *   "chain" (bit mask; the retired bits 3, 23, 25 and 28 -> MC_ERR_ARG), "big_tokens", "small_gemm_rows", "split_rows_expert",
  *   "split_rows_sffn", "split_expert", "split_sffn", "temporal_split", "rowchain_split", "gemm_tune", "small_tile_n",
  *   "gemm_wp_grid", "half_min_rows", "gate_small", "route_reg", "route_small", "route_coop", "route_per",
  *   "dbg_delay_us" (tests: holds the second sample group's stream that long in front of every layer tail, so the two-stream

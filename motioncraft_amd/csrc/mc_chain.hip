@@ -914,10 +914,8 @@ int mc_launch_projqkv(const RowChainArgs& g, hipStream_t s) {
 // NQ = H: the set produces all H parts of its frames; NQ < H: parts [h0, h0 + NQ) only (the fifth pass is cut 4 ways by parts:
 // every wave rebuilds A = k^T v of the two odd frames and projects H / 4 of their query rows)
 template <int L, int H>
-__global__ __launch_bounds__(256, 2) void pqbody_k(RowChainArgs g_in) {
-    RowChainArgs g = g_in;                       // (uniform copy: workgroups of the second token range swap in its bounds)
-    long bidx = blockIdx.x;
-    if (g.nblk1 > 0 && bidx >= g.nblk1) { bidx -= g.nblk1; g.tok0 = g.tok2; g.N = g.N2; }
+__global__ __launch_bounds__(256, 2) void pqbody_k(RowChainArgs g) {
+    const long bidx = blockIdx.x;
     if (g.alias.split_flag && *g.alias.split_flag == 0 && g.tok0 + bidx * (long)BodyPhase<L, H>::TR >= g.alias.from) return;      // (before anything is staged)
     constexpr int NJ = L / 8, NC0 = 4 * L / 32, NG = L / 32, NKEEP = L / 32, NSEQ = NC0 + 3 * NG;
     using BP = BodyPhase<L, H>;
@@ -1039,22 +1037,15 @@ int mc_launch_pqbody(const RowChainArgs& g, int H, hipStream_t s) {
     MC_REQUIRE(g.tok0 % H == 0 && g.N % H == 0, "pqbody: token range [%ld, %ld) is not made of whole frames", g.tok0, g.N);
     if (g.N <= g.tok0) return MC_OK;
     const long frames = (g.N - g.tok0) / H;
-    RowChainArgs gg = g;
     dim3 grid(cdiv(frames, 128 / H));
-    gg.nblk1 = 0;
-    if (g.nblk1 != 0) {           // second token range in the same launch (any non-zero nblk1 asks for it; the real count is set here)
-        MC_REQUIRE(g.tok2 % H == 0 && g.N2 % H == 0 && g.N2 >= g.tok2 && g.pad_row >= g.N2, "pqbody: bad second token range [%ld, %ld)", g.tok2, g.N2);
-        gg.nblk1 = (int)grid.x;
-        grid.x += cdiv((g.N2 - g.tok2) / H, 128 / H);
-    }
     if (mc_ledger_on) {       // proj + q/k/v per token; per frame the static topology (H x H mix of L-vectors) and the dynamic one (8 heads of linear attention over the H parts: k^T v and q (k^T v), [hd x hd] each)
         char name[32];
         snprintf(name, sizeof(name), "pqbody_k<%d", g.L);
-        const double toks = (double)(mc_ledger_tokens(g)), hd = g.L / 8.0;      // (aliased twins -- the tail of the range, or the optional second range -- exit at once in the usual case)
+        const double toks = (double)(mc_ledger_tokens(g)), hd = g.L / 8.0;      // (aliased twins -- the tail of the range -- exit at once in the usual case)
         MC_LEDGER(name, grid, 2.0 * toks * 7.0 * g.L * g.L + (toks / H) * (2.0 * H * H * g.L + 8 * 2.0 * (2.0 * H * hd * hd)));
     }
-    if (g.L == 128) hipLaunchKernelGGL((pqbody_k<128, 12>), grid, dim3(256), 0, s, gg);
-    else hipLaunchKernelGGL((pqbody_k<64, 12>), grid, dim3(256), 0, s, gg);
+    if (g.L == 128) hipLaunchKernelGGL((pqbody_k<128, 12>), grid, dim3(256), 0, s, g);
+    else hipLaunchKernelGGL((pqbody_k<64, 12>), grid, dim3(256), 0, s, g);
     MC_LAUNCH_CHECK();
     return MC_OK;
 }

@@ -196,7 +196,7 @@ __device__ __forceinline__ void dma16h(unsigned voff, const mc_half* sbase, unsi
                  : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_byte) : "memory");
 }
 
-template <bool SPLIT, bool INIT = false, bool PRE = false>
+template <bool SPLIT, bool PRE = false>
 __global__ __launch_bounds__(256, 2) void gemm_hd_k(GemmHArgs g) {
     constexpr int P = SPLIT ? 2 : 1;
     constexpr int BKH = SPLIT ? 32 : 64;            // halves per k-tile
@@ -257,30 +257,12 @@ __global__ __launch_bounds__(256, 2) void gemm_hd_k(GemmHArgs g) {
         __builtin_amdgcn_sched_barrier(0);
     }
     f32x16 acc[2][2];
-    if constexpr (INIT) {
-        // (round 6, tools/gemm_h6_lab.hip) the kernel runs at the package power cap, where the cost of its parts adds up; what the lab found movable is
-        // the load -> add -> store chain at the end of every tile: with R + bias as the accumulators' start value the loads fly during the DMA prologue
 #pragma unroll
-        for (int mi = 0; mi < 2; ++mi) {
-            const int m = min(wm * 64 + mi * 32 + frow, nrows - 1);
-            const float* rrow = g.R + (long)(row0 + m) * g.ldr;
+    for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
-            for (int ni = 0; ni < 2; ++ni)
+        for (int ni = 0; ni < 2; ++ni)
 #pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int n = tn * 128 + wn * 64 + ni * 32 + 8 * q + 4 * hf;
-                    const f32x4 v = *reinterpret_cast<const f32x4*>(rrow + n) + *reinterpret_cast<const f32x4*>(g.bias + n);
-                    acc[mi][ni][4 * q] = v[0]; acc[mi][ni][4 * q + 1] = v[1]; acc[mi][ni][4 * q + 2] = v[2]; acc[mi][ni][4 * q + 3] = v[3];
-                }
-        }
-    } else {
-#pragma unroll
-        for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
-    }
+            for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
     const int nk = g.K / BKH;
     const int sw = swz(frow);                        // rows frow, frow + 32, + 64, + 96 share the swizzle term
     issue(0, 0);
@@ -322,10 +304,6 @@ __global__ __launch_bounds__(256, 2) void gemm_hd_k(GemmHArgs g) {
             for (int q = 0; q < 4; ++q) {
                 const int n = tn * 128 + wn * 64 + ni * 32 + 8 * q + 4 * hf;
                 f32x4 v = {acc[mi][ni][4 * q], acc[mi][ni][4 * q + 1], acc[mi][ni][4 * q + 2], acc[mi][ni][4 * q + 3]};
-                if constexpr (INIT) {
-                    *reinterpret_cast<f32x4*>(crow + n) = v;
-                    continue;
-                }
                 if (g.bias) v += *reinterpret_cast<const f32x4*>(g.bias + n);
                 if (g.act != ACT_NONE) {
 #pragma unroll
@@ -346,7 +324,7 @@ __global__ __launch_bounds__(256, 2) void gemm_hd_k(GemmHArgs g) {
 // slab, A fragments and W pieces requested two slabs ahead and retired together by counted vmcnt (loads return in order; everything inline asm, so the compiler
 // neither counts nor drains them).  Lab, plain f16, same passes: 193 us against 218 at 25088 rows, 82 vs 92 at 12544, 48.5 vs 57 at 6272; bit-equal to
 // gemm_hd_k (the same k order per output, the same three products per operand pair in the split mode).
-// The residual rows are prefetched at the top of the tile as in gemm_hd_k<., ., true>.
+// The residual rows are prefetched at the top of the tile as in gemm_hd_k<., true>.
 // =================================================================================================
 __device__ __forceinline__ void gload16h(f16x8& dst, const mc_half* base, unsigned voff) {
     asm volatile("global_load_dwordx4 %0, %1, %2" : "=&v"(dst) : "v"(voff), "s"(base) : "memory");
@@ -915,12 +893,10 @@ __global__ __launch_bounds__(256, 2) void projqkv_h_k(RowChainArgs g, const mc_h
 // LDS slots; q/k/v never reach HBM, ys is written from here.  Body arithmetic fp32 (identical to body_reg_k's).
 // =================================================================================================
 template <int L, int H, bool SPLIT>
-__global__ __launch_bounds__(256, 2) void pqbody_h_k(RowChainArgs g_in, const mc_half* __restrict__ Wph, const mc_half* __restrict__ Wpl,
+__global__ __launch_bounds__(256, 2) void pqbody_h_k(RowChainArgs g, const mc_half* __restrict__ Wph, const mc_half* __restrict__ Wpl,
                                                      const mc_half* __restrict__ Wqh, const mc_half* __restrict__ Wql) {
     using BP = BodyPhase<L, H>;
-    RowChainArgs g = g_in;                       // (second token range: see pqbody_k)
-    long bidx = blockIdx.x;
-    if (g.nblk1 > 0 && bidx >= g.nblk1) { bidx -= g.nblk1; g.tok0 = g.tok2; g.N = g.N2; }
+    const long bidx = blockIdx.x;
     if (g.alias.split_flag && *g.alias.split_flag == 0 && g.tok0 + bidx * (long)BP::TR >= g.alias.from) return;
     constexpr int TR = BP::TR, XS = BP::XS;
     constexpr int P = SPLIT ? 2 : 1, NKB = L / 16, NJ = L / 8, NC0 = 4 * L / 32, NG = L / 32, NKEEP = L / 32, NSEQ = NC0 + 3 * NG;
@@ -1422,12 +1398,11 @@ int mc_launch_gemm_h(const GemmHArgs& g, bool split, hipStream_t s) {
             MC_LAUNCH_CHECK();
             return MC_OK;
         }
-        const bool pre = (g.acc_init & 1) && g.R, init = (g.acc_init & 2) && g.R && g.bias && g.act == ACT_NONE;
+        const bool pre = g.pre && g.R;
         if (split) {
-            if (pre) hipLaunchKernelGGL((gemm_hd_k<true, false, true>), grid, dim3(256), 0, s, g);
+            if (pre) hipLaunchKernelGGL((gemm_hd_k<true, true>), grid, dim3(256), 0, s, g);
             else hipLaunchKernelGGL(gemm_hd_k<true>, grid, dim3(256), 0, s, g);
-        } else if (init) hipLaunchKernelGGL((gemm_hd_k<false, true>), grid, dim3(256), 0, s, g);
-        else if (pre) hipLaunchKernelGGL((gemm_hd_k<false, false, true>), grid, dim3(256), 0, s, g);
+        } else if (pre) hipLaunchKernelGGL((gemm_hd_k<false, true>), grid, dim3(256), 0, s, g);
         else hipLaunchKernelGGL(gemm_hd_k<false>, grid, dim3(256), 0, s, g);
         MC_LAUNCH_CHECK();
         return MC_OK;
@@ -1506,25 +1481,18 @@ int mc_launch_pqbody_h(const RowChainArgs& g, int H, const mc_half* Wph, const m
     MC_REQUIRE(g.tok0 % H == 0 && g.N % H == 0, "fp16 pqbody: token range [%ld, %ld) is not made of whole frames", g.tok0, g.N);
     if (g.N <= g.tok0) return MC_OK;
     dim3 grid(cdiv((g.N - g.tok0) / H, 128 / H));
-    RowChainArgs gg = g;
-    gg.nblk1 = 0;
-    if (g.nblk1 != 0) {           // second token range in the same launch (mc_launch_pqbody)
-        MC_REQUIRE(g.tok2 % H == 0 && g.N2 % H == 0 && g.N2 >= g.tok2 && g.pad_row >= g.N2, "fp16 pqbody: bad second token range [%ld, %ld)", g.tok2, g.N2);
-        gg.nblk1 = (int)grid.x;
-        grid.x += cdiv((g.N2 - g.tok2) / H, 128 / H);
-    }
     if (mc_ledger_on) {
         char name[40];
         snprintf(name, sizeof(name), "pqbody_h_k<%d, 12, %s>", g.L, split ? "true" : "false");
-        const double toks = (double)(mc_ledger_tokens(g)), hd = g.L / 8.0;      // (aliased twins -- the tail of the range, or the optional second range -- exit at once in the usual case)
+        const double toks = (double)(mc_ledger_tokens(g)), hd = g.L / 8.0;      // (aliased twins -- the tail of the range -- exit at once in the usual case)
         MC_LEDGER(name, grid, 2.0 * toks * 7.0 * g.L * g.L + (toks / H) * (2.0 * H * H * g.L + 8 * 2.0 * (2.0 * H * hd * hd)));
     }
     if (g.L == 128) {
-        if (split) hipLaunchKernelGGL((pqbody_h_k<128, 12, true>), grid, dim3(256), 0, s, gg, Wph, Wpl, Wqh, Wql);
-        else hipLaunchKernelGGL((pqbody_h_k<128, 12, false>), grid, dim3(256), 0, s, gg, Wph, Wpl, Wqh, Wql);
+        if (split) hipLaunchKernelGGL((pqbody_h_k<128, 12, true>), grid, dim3(256), 0, s, g, Wph, Wpl, Wqh, Wql);
+        else hipLaunchKernelGGL((pqbody_h_k<128, 12, false>), grid, dim3(256), 0, s, g, Wph, Wpl, Wqh, Wql);
     } else {
-        if (split) hipLaunchKernelGGL((pqbody_h_k<64, 12, true>), grid, dim3(256), 0, s, gg, Wph, Wpl, Wqh, Wql);
-        else hipLaunchKernelGGL((pqbody_h_k<64, 12, false>), grid, dim3(256), 0, s, gg, Wph, Wpl, Wqh, Wql);
+        if (split) hipLaunchKernelGGL((pqbody_h_k<64, 12, true>), grid, dim3(256), 0, s, g, Wph, Wpl, Wqh, Wql);
+        else hipLaunchKernelGGL((pqbody_h_k<64, 12, false>), grid, dim3(256), 0, s, g, Wph, Wpl, Wqh, Wql);
     }
     MC_LAUNCH_CHECK();
     return MC_OK;

@@ -55,12 +55,11 @@ struct LayerW {
 };
 
 // Per-context switches (mc_ctx_set_option).  Defaults = the measured best; a variable of the same meaning in the environment
-// (MC_CHAIN, MC_SPLIT, MC_GEMM_TUNE, ...) overrides the default of contexts created afterwards, mc_ctx_set_option overrides both for
+// (MC_CHAIN, MC_GEMM_TUNE, ...) overrides the default of contexts created afterwards, mc_ctx_set_option overrides both for
 // one context -- two models of one process can run different kernel selections.
 struct McOptions {
-    // chain bits: 0 fused expert / SFFN MLP (mlp2_k), 1 fused gate (gate_k), 2 chained proj / qkv (rowchain_k), 3 temporal branch on the
-    // side stream at any batch size, 4 CFG twin dedupe in base layer 0, 5 two sample groups on two streams (large batches), 6 one
-    // expert-MLP launch per sample group, 7 last FiLM Linear + pose decoder on the CFG-combined rows (folded), 8 twin aliasing of the
+    // chain bits: 0 fused expert / SFFN MLP (mlp2_k), 1 fused gate (gate_k), 2 chained proj / qkv (rowchain_k), 4 CFG twin dedupe in base
+    // layer 0, 5 two sample groups (the CFG halves) on two streams (large batches), 6 one expert-MLP launch per sample group, 7 last FiLM Linear + pose decoder on the CFG-combined rows (folded), 8 twin aliasing of the
     // mf / qkv / ys rows in base layer 0, 9 the sample groups stay on their streams across the control-branch ops between layers,
     // 10 proj + body LN + q/k/v in one kernel (large batches), 11 folded decoder tail as one grouped GEMM + sum in the sampler kernel,
     // 12 small batches: the SFFN's split-hidden partial sums are added up by the FiLM row kernel, 13 B=1 sizes: the expert MLP picks
@@ -73,31 +72,22 @@ struct McOptions {
     // 20 (round 4) reduced-precision contexts: temporal linear attention on the fp16 MFMA (temporal_h_k)
     // 22 (round 4) L = 64 models: temporal_k takes two adjacent parts per workgroup (all four waves on the MFMA)
     // 21 (round 4) large batches: the folded decoder tail with the CFG combination in its A staging, one pass over both K groups (gemm_tail_k)
-    // 23 (round 5) two-stream schedule: the last sample group's gate launch is cut at a whole number of workgroup rounds; the partial last round
-    //    runs as gate_small_k (32-token workgroups, the same bits) on the OTHER group's stream, beside the big launch instead of behind it.
-    //    OFF by default: measured SLOWER (B=64 19.47 -> 19.55 ms/step, B=32 10.10 -> 10.14, same-box A/B twice): the 608 small workgroups
-    //    (each wave re-reads its projector chunks from L2, wave 0 walks the logit chain alone) take longer than the partial round they replace
     // 24 (round 5) temporal_k: the unconditional CFG half skips whole leading blocks of its text rows (keys at -1e6, values x 0: exact zeros
     //    as long as the sample has a valid frame) -- the same bits, ~20 % less of that half's kernel
-    // 25 (round 5) twin layer: the fused front of a sample sub-group covers that sub-group's aliased twins in the same launch (pqbody_k's second
-    //    token range) instead of a launch of its own behind the cross-join
-    //    OFF by default: the same bits, but measured SLOWER (B=64 19.20 -> 19.30, 19.25 -> 19.36 ms/step): the 125 us by which the separate no-op
-    //    launch held the second group's stream back were doing useful work -- they kept the two chains out of phase (see bit 26)
     // 26 (round 5) the second sample group's first FiLM block (proj_out) starts behind the first group's FiLM ROW kernel (one event per layer):
     //    the two HBM-bound row kernels never run against each other and the groups' GEMM / SFFN launches leave the seam half a kernel apart
     //    instead of in lockstep (B=64 19.08 -> 18.94, 19.14 -> 19.01, 19.12 -> 19.00 ms/step; a 60 us spin at the same place: the same).
     //    Only in exact-fp32 contexts at L = 128: measured slower in the fp16 modes (f16 6.86 -> 7.08) and at L = 64 (M2D 17.62 -> 18.00), neutral at batch 32
     // 27 (round 6) reduced-precision contexts: the FiLM plane GEMM requests the residual rows of its epilogue at the TOP of the tile, into registers of their own
-    //    (gemm_hd_k<., false, true>: in flight during the DMA prologue; no load -> add -> store chain at the end of every tile) -- the same order (sum + bias) + R,
+    //    (gemm_hd_k<., true>: in flight during the DMA prologue; no load -> add -> store chain at the end of every tile) -- the same order (sum + bias) + R,
     //    the same bits (tools/gemm_h6_lab.hip: the kernel runs at the package power cap, this chain is the part that moves).  Same-box A/B: f16 B=64 6.87 -> 6.82,
     //    B=32 3.98 -> 3.81 ms/step; f16x3 10.72 -> 10.62, 5.52 -> 5.45
-    // 28 (round 6, OFF) plain f16 only: the accumulators START as R + bias instead (stores-only epilogue; f16 B=32 3.75 against bit 27's 3.81) -- another fp32
-    //    summation order (2.6e-4 on h after one layer, 1.1e-3 on x0 against the exact order: inside plain f16's own error, but not free): a switch, not the default
     // 29 (round 6) reduced-precision contexts: the FiLM operand planes are written FRAGMENT-MAJOR and the plane GEMM reads its A fragments straight into registers
     //    (gemm_hf_k: only W rides the LDS-DMA ring; tools/gemm_h6_lab.hip ha_k); launches whose rows are whole 32-row blocks only; the same bits as gemm_hd_k.
     //    film_rows_k stages the 4 rows of a workgroup in LDS and writes 64-byte runs, the 8 workgroups of a 32-row block share an XCD.  Serial schedule: the GEMM
     //    198 -> 183 us (B=64 f16), the row kernel 74.7 -> 77.2; two-stream step, same-box A/B: f16x3 10.85 -> 10.56 (B=64), 5.50 -> 5.37 (B=32); f16 neutral (7.05 / 7.06, 3.76 / 3.75)
-    int chain = 65527 | (1 << 16) | (1 << 17) | (1 << 18) | (1 << 19) | (1 << 20) | (1 << 21) | (1 << 22) | (1 << 24) | (1 << 26) | (1 << 27) | (1 << 29);     // (all but bits 3, 23, 25 and 28)
+    // Bits 3, 23, 25 and 28 lost their A/B and were retired (kRetiredChainBits): a mask that sets one is rejected.
+    int chain = 65527 | (1 << 16) | (1 << 17) | (1 << 18) | (1 << 19) | (1 << 20) | (1 << 21) | (1 << 22) | (1 << 24) | (1 << 26) | (1 << 27) | (1 << 29);     // (all but the retired bits)
     long small_gemm_rows = 5600;       // plain GEMMs of up to this many rows take the small-M kernels (round 4: 6400 -> 5600, measured per batch: at
                                        // 6272 rows -- a sample group of 32 x 196 frames -- gemm_wp_k / gemm_tail_k now win: B=32 step 10.21 -> 10.03 ms,
                                        // S2G at 32 per GPU 27.65 -> 27.14; at 4704 rows (B=24) the small kernels still do, 7.85 vs 7.91)
@@ -162,15 +152,15 @@ struct mc_ctx {
     std::vector<ProfRec> prof;
     bool have_cond = false;
     // side stream: the temporal branch of STMA needs only the motion-MoE output, so it runs beside
-    // (LN + qkv -> body attention) of the same layer (fork after the MoE projection, join before proj_out)
+    // (LN + qkv -> body attention) of the same layer (fork after the MoE projection, join before proj_out);
+    // large batches: the second sample group (CFG half) runs on it, the first one on the caller's stream
     hipStream_t side = nullptr;
     bool xpad_ready = false;           // mc_sample_loop: xpad already holds this step's padded x_t (written by the previous sampler update)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    hipEvent_t ev_gate = nullptr;      // chain bit 23: the last group's rows are ready (recorded on its stream in front of its gate launch)
-    // large batches: the batch is cut into `nparts` groups of whole samples, group k > 0 runs on parts[k-1]
+    hipEvent_t ev_side = nullptr;      // the side stream's work so far (recorded on it for a join / cross-join)
+    hipEvent_t ev_stag = nullptr;      // chain bit 26: the first group's first FiLM row kernel is done (the second group's tail starts behind it)
     bool no_alias = false;          // introspection runs (stop_after_layers < num_layers): every intermediate row is materialised
     bool defer_last_gemm = false;   // sampler entry points: the last FiLM GEMM runs on the CFG-combined rows (see denoise_combined)
-    hipStream_t parts[3] = {nullptr, nullptr, nullptr};
     // Two HIP streams only overlap when the runtime maps them to different HARDWARE queues (GPU_MAX_HW_QUEUES, default 4, handed out round-robin as streams
     // are created): with an RCCL process group initialised in the host process the caller's stream and the one side stream of round 5 landed on the SAME
     // queue and the two-stream schedule ran serially (+7 % step time at B=64: 19.05 -> 20.47 ms, profiles/r06_hw_queue_collision.txt).  The context creates
@@ -185,8 +175,6 @@ struct mc_ctx {
     hipStream_t side_memo_for[SIDE_MEMO] = {nullptr, nullptr, nullptr, nullptr};
     int side_memo_pick[SIDE_MEMO] = {-1, -1, -1, -1};
     int side_memo_n = 0;
-    hipEvent_t ev_parts[3] = {nullptr, nullptr, nullptr};
-    int nparts = 2;
     // hipGraph replay of the sampler step (mc_ctx_graph_capture / _step): ONE graph for all steps of the schedule; the step
     // index lives in device memory (gstep) and the per-step tables are addressed inside the kernels (StepRef)
     int* gstep = nullptr;
@@ -405,6 +393,12 @@ static const McOptions& options_of(const mc_ctx* c) {
 }
 static long small_gemm_rows(const mc_ctx* c) { return options_of(c).small_gemm_rows; }
 static bool chain_on(const mc_ctx* c, int which) { return (options_of(c).chain >> which) & 1; }
+// chain bits that lost their A/B and were retired; the numbers stay reserved, a mask that sets one is an error
+constexpr int kRetiredChainBits = (1 << 3) | (1 << 23) | (1 << 25) | (1 << 28);
+static int check_chain(int chain) {
+    for (int b = 0; b < 31; ++b) MC_REQUIRE(!(((chain & kRetiredChainBits) >> b) & 1), "chain bit %d is retired (DESIGN.md section 5)", b);
+    return MC_OK;
+}
 static void gemm_opts(const mc_ctx* c, GemmArgs& g) {
     const McOptions& o = options_of(c);
     g.tune = o.gemm_tune; g.small_tile_n = o.small_tile_n; g.wp_grid = o.gemm_wp_grid;
@@ -606,7 +600,7 @@ int film_block(mc_ctx* c, float* hs, const float* y1, const float* y2, const flo
         g.Wh = hw->hi; g.Wl = hw->lo; g.bias = out_b; g.R = hs + o; g.ldr = D; g.C = hs + o; g.ldc = D;
         g.M = (int)nrows; g.N = D; g.K = D;
         g.a_fm = frag_major ? 1 : 0;
-        g.acc_init = (chain_on(c, 27) ? 1 : 0) | (chain_on(c, 28) ? 2 : 0);      // 1: residual rows prefetched into registers (same bits), 2: accumulators start as R + bias (plain f16 only)
+        g.pre = chain_on(c, 27);      // residual rows prefetched into registers (same bits)
         return mc_launch_gemm_h(g, c->prec == MC_PREC_F16X3, s);
     }
     if (half_gemm)
@@ -637,8 +631,7 @@ int film_block(mc_ctx* c, float* hs, const float* y1, const float* y2, const flo
 // FiLM block.  Every kernel here is row-independent, so disjoint row ranges can run on different streams.
 // `phase`: 0 = everything; 1 = the front only (combine + proj, LN + q/k/v, body topology); 2 = the temporal attention only
 // (the twin layer of the large-batch schedule runs the front per sample sub-group and the rest per CFG half: run_layer)
-int layer_rows(mc_ctx* c, int i, float* hs, int step, bool twin, long row0, long nrows, hipStream_t s, hipStream_t st, int phase = 0, long rows2_0 = -1) {
-    // rows2_0 >= 0 (phase 1, fused front only): the same launch also covers rows [rows2_0, rows2_0 + nrows) -- the aliased twins of this range
+int layer_rows(mc_ctx* c, int i, float* hs, int step, bool twin, long row0, long nrows, hipStream_t s, hipStream_t st, int phase = 0) {
     // twin layer: rows of the second CFG half whose routing equals their twin's are aliased, not recomputed
     TwinAlias tok_alias, frame_alias;
     const int* twin_flag = nullptr;
@@ -673,7 +666,6 @@ int layer_rows(mc_ctx* c, int i, float* hs, int step, bool twin, long row0, long
             p.pad_row = c->N;      // mf / qkv carry 128 padding rows (mc_ctx_create): projqkv_k's stores are unconditional
             if (body_fused) {
                 p.wsm = w.wsm; p.ys = c->ys;
-                if (rows2_0 >= 0) { p.tok2 = rows2_0 * H; p.N2 = (rows2_0 + nrows) * H; p.nblk1 = 1; }
                 if (use_half(c) && w.h_proj.hi && w.h_qkv.hi) {
                     if ((r = mc_launch_pqbody_h(p, H, w.h_proj.hi, w.h_proj.lo, w.h_qkv.hi, w.h_qkv.lo, c->prec == MC_PREC_F16X3, s))) return r;
                 } else if ((r = mc_launch_pqbody(p, H, s))) return r;
@@ -805,8 +797,6 @@ int layer_rows_tail(mc_ctx* c, int i, float* hs, int step, bool twin, long row0,
                       c->defer_last_gemm && i == g.num_layers - 1, TwinAlias(), &w.h_ffn_out, z2_parts);
 }
 
-// groups of whole samples for the multi-stream schedule: group k = rows [part_row0(k), part_row0(k + 1))
-long part_row0(const mc_ctx* c, int k) { return ((long)2 * c->B * k / c->nparts) * c->T; }
 // Pick the side stream that runs BESIDE the caller's stream `s` (see mc_ctx::side_cand): a 60 us spin kernel on `s` and one on the candidate, started
 // together -- ~65 us when the two streams sit on different hardware queues, ~125 us when they share one.  Once per (context, caller stream); host-synchronous
 // (~0.5 ms), so never inside a stream capture (a captured step keeps the stream picked by the eager calls before it).  MC_SIDE_PROBE=0 switches it off.
@@ -817,7 +807,6 @@ int pick_side_stream(mc_ctx* c, hipStream_t s) {
     for (int k = 0; k < c->side_memo_n; ++k)
         if (c->side_memo_for[k] == s) {          // answered before for this caller stream: switch without a probe (the previous call joined its side work)
             c->side = c->side_cand[c->side_memo_pick[k]];
-            c->parts[0] = c->side;
             c->side_for = s;
             return MC_OK;
         }
@@ -847,7 +836,6 @@ int pick_side_stream(mc_ctx* c, hipStream_t s) {
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipEventDestroy(eq);
     if (r != MC_OK) return r;
     c->side = c->side_cand[best];
-    c->parts[0] = c->side;
     c->side_for = s;
     c->side_picked = true;
     {
@@ -861,17 +849,16 @@ int pick_side_stream(mc_ctx* c, hipStream_t s) {
     return MC_OK;
 }
 
-hipStream_t part_stream(const mc_ctx* c, int k, hipStream_t s) { return k == 0 ? s : c->parts[k - 1]; }
-int parts_fork(mc_ctx* c, hipStream_t s) {
+// The two sample groups of the large-batch schedule are the CFG halves: group 0 = rows [0, B T) on the caller's stream, group 1 =
+// rows [B T, 2 B T) on the side stream.  side_fork / side_join: the side stream starts behind / the caller's stream waits for the other.
+int side_fork(mc_ctx* c, hipStream_t s) {
     MC_HIP(hipEventRecord(c->ev_fork, s));
-    for (int k = 1; k < c->nparts; ++k) MC_HIP(hipStreamWaitEvent(c->parts[k - 1], c->ev_fork, 0));
+    MC_HIP(hipStreamWaitEvent(c->side, c->ev_fork, 0));
     return MC_OK;
 }
-int parts_join(mc_ctx* c, hipStream_t s) {
-    for (int k = 1; k < c->nparts; ++k) {
-        MC_HIP(hipEventRecord(c->ev_parts[k - 1], c->parts[k - 1]));
-        MC_HIP(hipStreamWaitEvent(s, c->ev_parts[k - 1], 0));
-    }
+int side_join(mc_ctx* c, hipStream_t s) {
+    MC_HIP(hipEventRecord(c->ev_side, c->side));
+    MC_HIP(hipStreamWaitEvent(s, c->ev_side, 0));
     return MC_OK;
 }
 
@@ -896,9 +883,9 @@ int run_layer(mc_ctx* c, int i, float* hs, int step, bool twin_ok, int split, hi
     // aliases it), so the half is cut into two sample sub-groups that go down the two streams (otherwise one stream idles for the
     // first ~1.75 ms of every step at B=64); the streams cross-join behind the front (the temporal kernel of either CFG half reads
     // mf rows of the whole first half) and continue per CFG half as in every other layer.
+    const long half = (long)c->B * c->T;                    // rows of one CFG half (= one sample group of the two-stream schedule)
     const long sub_rows = ((long)c->B / 2) * c->T;          // rows of the first sub-group (whole samples)
-    const bool twin_split = twin && split == 2 && c->nparts == 2 && chain_on(c, 6) && chain_on(c, 8) && chain_on(c, 16) && !c->no_alias &&
-                            sub_rows > 0;
+    const bool twin_split = twin && split == 2 && chain_on(c, 6) && chain_on(c, 8) && chain_on(c, 16) && !c->no_alias && sub_rows > 0;
     if (fused_gate) {
         GateArgs ga;
         ga.X = hs; ga.ldx = L; ga.gamma = w.norm_g; ga.beta = w.norm_b; ga.emb = w.mm.emb; ga.emb_mod = c->T * H;
@@ -908,45 +895,27 @@ int run_layer(mc_ctx* c, int i, float* hs, int step, bool twin_ok, int split, hi
         if (split == 2 && (!twin || twin_split)) {
             if (!c->cnt_clean) MC_HIP(hipMemsetAsync(ga.cnt, 0, sizeof(int) * 32, s));
             c->cnt_clean = false;
-            if ((r = parts_fork(c, s))) return r;
+            if ((r = side_fork(c, s))) return r;
             ga.zero_cnt = 0;
-            for (int k = 0; k < c->nparts; ++k) {
-                if (twin_split) { ga.tok0 = k ? sub_rows * H : 0; ga.N = k ? c->N / 2 : sub_rows * H; }
-                else { ga.tok0 = part_row0(c, k) * H; ga.N = part_row0(c, k + 1) * H; }
-                // The group that reaches the join last runs its gate ALONE on the chip (the other stream already waits for the routing): 1176
-                // tiles of 128 tokens on 512 workgroup slots are 2.3 rounds -- the third one 30 % full.  Cut the launch at whole rounds; the
-                // rest goes to gate_small_k (32-token workgroups whose waves split the projector chunks: bit-identical scores, tested) on
-                // the waiting stream, so it runs BESIDE the big launch.
-                const long slots = 2L * mc_device_cus(), tiles = cdiv(ga.N - ga.tok0, 128L), rem = tiles % slots;
-                if (!twin_split && c->nparts == 2 && k == 1 && chain_on(c, 23) && tiles > slots && rem > 0 && 8 * rem <= 5 * slots) {
-                    hipStream_t sk = part_stream(c, k, s);
-                    MC_HIP(hipEventRecord(c->ev_gate, sk));                      // (the group's rows: behind its last FiLM GEMM)
-                    const long cut = ga.tok0 + (tiles - rem) * 128;
-                    GateArgs gb = ga;
-                    gb.N = cut;
-                    if ((r = mc_launch_gate(gb, sk))) return r;
-                    GateArgs gs = ga;
-                    gs.tok0 = cut;
-                    gs.small_tokens = ga.N - cut;                                // -> gate_small_k
-                    MC_HIP(hipStreamWaitEvent(s, c->ev_gate, 0));
-                    if ((r = mc_launch_gate(gs, s))) return r;
-                    continue;
-                }
-                if ((r = mc_launch_gate(ga, part_stream(c, k, s)))) return r;
-            }
+            // group 0 on `s`, group 1 on the side stream (twin layer: the two sub-groups of the first CFG half)
+            const long cut = twin_split ? sub_rows * H : half * H;
+            ga.tok0 = 0; ga.N = cut;
+            if ((r = mc_launch_gate(ga, s))) return r;
+            ga.tok0 = cut; ga.N = twin_split ? half * H : c->N;
+            if ((r = mc_launch_gate(ga, c->side))) return r;
         } else {
             ga.N = twin ? c->N / 2 : c->N;
             ga.zero_cnt = c->cnt_clean ? 0 : 1;      // small batches: the previous layer's routing kernel left the counts zeroed
             c->cnt_clean = false;
             if ((r = mc_launch_gate(ga, s))) return r;
         }
-        if (split == 2 && (r = parts_join(c, s))) return r;      // routing ranks the whole batch: every group must have arrived
+        if (split == 2 && (r = side_join(c, s))) return r;       // routing ranks the whole batch: both groups must have arrived
     } else {
         if ((r = mc_launch_ln_rows(hs, L, 0, w.norm_g, w.norm_b, w.mm.emb, c->T * H, c->z, L, c->N, L, s))) return r;
     }
     // two slot groups when the two sample groups run on two streams: each group's expert MLP joins its own chain
-    const bool grouped = split == 2 && c->nparts == 2 && chain_on(c, 6);
-    const long gsplit = twin_split ? sub_rows * H : grouped ? part_row0(c, 1) * H : c->N;
+    const bool grouped = split == 2 && chain_on(c, 6);
+    const long gsplit = twin_split ? sub_rows * H : grouped ? half * H : c->N;
     if ((r = run_moe(c, w.mm, c->z, c->N, nullptr, 0, fused_gate, twin, gsplit, s, &w.h_fc1, &w.h_fc2))) return r;   // routing (+ experts if one group)
     if (c->cap_idx) {
         if (twin) {     // expert ids exist for the first half only: the twins have the same ones
@@ -958,78 +927,60 @@ int run_layer(mc_ctx* c, int i, float* hs, int step, bool twin_ok, int split, hi
         MC_HIP(hipMemcpyAsync(c->cap_w + (long)i * 2 * c->N, c->rb.comb_w, sizeof(float) * 2 * c->N, hipMemcpyDeviceToDevice, s));
     }
     // ---- the row-independent rest of the layer ----
-    const long half = (long)c->B * c->T;        // rows of one CFG half
     // (measured per shape, same-box A/B: helps the exact-fp32 L = 128 step; the fp16 modes -- whose GEMMs are a small part of the chain -- lose 0.1 - 0.2 ms and the
     //  L = 64 models (M2D) 0.35 ms with it, batch 32 is neutral: applied where it helps)
-    const bool evstag = split == 2 && c->nparts == 2 && chain_on(c, 26) && !chain_on(c, 23) && !use_half(c) && L == 128;      // (bit 23 uses the same event)
+    const bool evstag = split == 2 && chain_on(c, 26) && !use_half(c) && L == 128;
     if (split) {
         // Large batches: the two CFG halves go down two streams.  Each kernel of the chain fills 4.59 "waves" of
         // workgroups at B=64, so ~8 % of every launch is a tail on a partly idle chip; with two independent chains in
         // flight the next kernel of one half starts inside the tail of the other (same effect as two batches in flight).
         if (twin_split) {
-            const long half_rows = (long)c->B * c->T;
-            hipStream_t s1 = c->parts[0];
-            if ((r = parts_fork(c, s))) return r;
+            if ((r = side_fork(c, s))) return r;
             if ((r = moe_experts(c, w.mm, c->z, c->N, 0, s, &w.h_fc1, &w.h_fc2))) return r;
-            if ((r = moe_experts(c, w.mm, c->z, c->N, 1, s1, &w.h_fc1, &w.h_fc2))) return r;
-            // (round 5, chain bit 25) the fused front of a sub-group also covers that sub-group's twins in the second CFG half: in the usual case
-            // (no twin pair split by a capacity cut) those workgroups exit at once, and as part of THIS launch they start inside its tail --
-            // as a launch of their own behind the cross-join they queued for LDS behind the other stream's temporal kernel (~125 us per step
-            // in front of the second group's temporal kernel: profiles/r05_b64_timeline.txt).  A twin reads its ORIGINAL's expert rows, and the
-            // original belongs to the same sub-group, i.e. the same stream: no new dependency.
-            const int L_ = g.latent_dim;
-            const bool front_covers_twins = chain_on(c, 25) && chain_on(c, 2) && chain_on(c, 10) && chain_on(c, 15) && c->N > c->opt.big_tokens &&
-                                            mc_mlp_supported(L_, 32) && H == 12 && g.dyn_heads == 8 && (L_ == 128 || L_ == 64);
-            if ((r = layer_rows(c, i, hs, step, twin, 0, sub_rows, s, s, 1, front_covers_twins ? half_rows : -1))) return r;
-            if ((r = layer_rows(c, i, hs, step, twin, sub_rows, half_rows - sub_rows, s1, s1, 1, front_covers_twins ? half_rows + sub_rows : -1))) return r;
+            if ((r = moe_experts(c, w.mm, c->z, c->N, 1, c->side, &w.h_fc1, &w.h_fc2))) return r;
+            if ((r = layer_rows(c, i, hs, step, twin, 0, sub_rows, s, s, 1))) return r;
+            if ((r = layer_rows(c, i, hs, step, twin, sub_rows, half - sub_rows, c->side, c->side, 1))) return r;
             // cross-join: each stream waits for the other's front
             MC_HIP(hipEventRecord(c->ev_join, s));
-            MC_HIP(hipEventRecord(c->ev_parts[0], s1));
-            MC_HIP(hipStreamWaitEvent(s1, c->ev_join, 0));
-            MC_HIP(hipStreamWaitEvent(s, c->ev_parts[0], 0));
+            MC_HIP(hipEventRecord(c->ev_side, c->side));
+            MC_HIP(hipStreamWaitEvent(c->side, c->ev_join, 0));
+            MC_HIP(hipStreamWaitEvent(s, c->ev_side, 0));
             // the second CFG half's own front: exits at once while no twin pair was split by a capacity cut (the usual case)
-            if (!front_covers_twins && (r = layer_rows(c, i, hs, step, twin, half_rows, half_rows, s1, s1, 1))) return r;
-            if ((r = layer_rows(c, i, hs, step, twin, 0, half_rows, s, s, 2))) return r;
-            if ((r = layer_rows(c, i, hs, step, twin, half_rows, half_rows, s1, s1, 2))) return r;
-            for (int k = 0; k < c->nparts; ++k) {
-                if (c->dbg_delay_us != 0 && k == (c->dbg_delay_us > 0 ? 1 : 0) &&
-                    (r = mc_launch_spin((c->dbg_delay_us > 0 ? c->dbg_delay_us : -c->dbg_delay_us) * 100, part_stream(c, k, s)))) return r;
-                if ((r = layer_rows_tail(c, i, hs, step, twin, part_row0(c, k), part_row0(c, k + 1) - part_row0(c, k), part_stream(c, k, s),
-                                         (evstag && k == 0) ? c->ev_gate : nullptr, (evstag && k == 1) ? c->ev_gate : nullptr))) return r;
-            }
-            return MC_OK;
-        }
-        if (grouped && twin) {         // group 1 combines group 0's expert rows (its own tokens have no slots): fork after them
-            if ((r = moe_experts(c, w.mm, c->z, c->N, 0, s, &w.h_fc1, &w.h_fc2))) return r;
-            if ((r = parts_fork(c, s))) return r;
+            if ((r = layer_rows(c, i, hs, step, twin, half, half, c->side, c->side, 1))) return r;
+            if ((r = layer_rows(c, i, hs, step, twin, 0, half, s, s, 2))) return r;
+            if ((r = layer_rows(c, i, hs, step, twin, half, half, c->side, c->side, 2))) return r;
         } else {
-            if ((r = parts_fork(c, s))) return r;
-            if (grouped) {
+            if (grouped && twin) {         // group 1 combines group 0's expert rows (its own tokens have no slots): fork after them
                 if ((r = moe_experts(c, w.mm, c->z, c->N, 0, s, &w.h_fc1, &w.h_fc2))) return r;
-                if ((r = moe_experts(c, w.mm, c->z, c->N, 1, c->parts[0], &w.h_fc1, &w.h_fc2))) return r;
+                if ((r = side_fork(c, s))) return r;
+            } else {
+                if ((r = side_fork(c, s))) return r;
+                if (grouped) {
+                    if ((r = moe_experts(c, w.mm, c->z, c->N, 0, s, &w.h_fc1, &w.h_fc2))) return r;
+                    if ((r = moe_experts(c, w.mm, c->z, c->N, 1, c->side, &w.h_fc1, &w.h_fc2))) return r;
+                }
             }
-        }
-        for (int k = 0; k < c->nparts; ++k) {
-            hipStream_t sk = part_stream(c, k, s);
-            if ((r = layer_rows(c, i, hs, step, twin, part_row0(c, k), part_row0(c, k + 1) - part_row0(c, k), sk, sk))) return r;
-            if (k == 0 && twin && chain_on(c, 8) && !c->no_alias) {
-                // twin aliasing: the other groups read group 0's mf / ys instead of producing their own
+            if ((r = layer_rows(c, i, hs, step, twin, 0, half, s, s))) return r;
+            if (twin && chain_on(c, 8) && !c->no_alias) {
+                // twin aliasing: group 1 reads group 0's mf / ys instead of producing its own
                 MC_HIP(hipEventRecord(c->ev_join, s));
-                for (int j = 1; j < c->nparts; ++j) MC_HIP(hipStreamWaitEvent(c->parts[j - 1], c->ev_join, 0));
+                MC_HIP(hipStreamWaitEvent(c->side, c->ev_join, 0));
             }
+            if ((r = layer_rows(c, i, hs, step, twin, half, half, c->side, c->side))) return r;
         }
-        for (int k = 0; k < c->nparts; ++k) {
+        for (int k = 0; k < 2; ++k) {
+            hipStream_t sk = k ? c->side : s;
             // (tests) hold one sample group's stream: > 0 the second group, < 0 the first
             if (c->dbg_delay_us != 0 && k == (c->dbg_delay_us > 0 ? 1 : 0) &&
-                (r = mc_launch_spin((c->dbg_delay_us > 0 ? c->dbg_delay_us : -c->dbg_delay_us) * 100, part_stream(c, k, s)))) return r;
-            if ((r = layer_rows_tail(c, i, hs, step, twin, part_row0(c, k), part_row0(c, k + 1) - part_row0(c, k), part_stream(c, k, s),
-                                     (evstag && k == 0) ? c->ev_gate : nullptr, (evstag && k == 1) ? c->ev_gate : nullptr))) return r;
+                (r = mc_launch_spin((c->dbg_delay_us > 0 ? c->dbg_delay_us : -c->dbg_delay_us) * 100, sk))) return r;
+            if ((r = layer_rows_tail(c, i, hs, step, twin, k * half, half, sk, (evstag && k == 0) ? c->ev_stag : nullptr,
+                                     (evstag && k == 1) ? c->ev_stag : nullptr))) return r;
         }
-        if (split == 1 && (r = parts_join(c, s))) return r;
+        if (split == 1 && (r = side_join(c, s))) return r;
         return MC_OK;
     }
     // Small batches: the temporal branch runs on the side stream beside LN + qkv + body (measured +2.4 % at B=8).
-    const bool side_temporal = c->side && (chain_on(c, 3) || c->N <= c->opt.big_tokens);
+    const bool side_temporal = c->side && c->N <= c->opt.big_tokens;
     if ((r = layer_rows(c, i, hs, step, twin, 0, 2 * half, s, side_temporal ? c->side : s))) return r;
     return layer_rows_tail(c, i, hs, step, twin, 0, 2 * half, s);
 }
@@ -1125,6 +1076,7 @@ int mc_ctx_create(mc_model* m, int32_t batch, int32_t frames, int32_t max_steps,
     MC_REQUIRE(max_steps >= 1, "max_steps < 1");
     const mc_model_config& g = m->cfg;
     mc_ctx* c = new mc_ctx();
+    if (int r = check_chain(c->opt.chain)) { mc_ctx_destroy(c); return r; }      // (MC_CHAIN)
     if (const char* e = getenv("MC_HALF_MIN_ROWS")) c->half_min_rows = atol(e);      // (the tests lift it to run the fp16 kernels at their small sizes)
     if (const char* e = getenv("MC_GATE_SMALL")) c->gate_small_tokens = atol(e);
     if (const char* e = getenv("MC_SPLIT_EXPERT")) c->split_expert = atoi(e);
@@ -1150,26 +1102,11 @@ int mc_ctx_create(mc_model* m, int32_t batch, int32_t frames, int32_t max_steps,
     if (!cand_ok ||
         hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_gate, hipEventDisableTiming) != hipSuccess) {
+        hipEventCreateWithFlags(&c->ev_side, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&c->ev_stag, hipEventDisableTiming) != hipSuccess) {
         mc_set_error("could not create the side stream / events");
         mc_ctx_destroy(c);
         return MC_ERR_HIP;
-    }
-    {
-        const char* e = getenv("MC_SPLIT");
-        c->nparts = e ? atoi(e) : 2;
-        if (c->nparts < 2) c->nparts = 2;
-        if (c->nparts > 4) c->nparts = 4;
-        if (c->nparts > 2 * batch) c->nparts = 2 * batch;
-        c->parts[0] = c->side;
-        for (int k = 0; k < c->nparts - 1; ++k) {
-            if ((k > 0 && hipStreamCreateWithFlags(&c->parts[k], hipStreamNonBlocking) != hipSuccess) ||
-                hipEventCreateWithFlags(&c->ev_parts[k], hipEventDisableTiming) != hipSuccess) {
-                mc_set_error("could not create the part streams / events");
-                mc_ctx_destroy(c);
-                return MC_ERR_HIP;
-            }
-        }
     }
     const long Nmax = c->N > c->Ntxt ? c->N : c->Ntxt;
     const size_t zsz = (size_t)(c->N * L > c->Ntxt * Dt ? c->N * L : c->Ntxt * Dt);
@@ -1243,13 +1180,10 @@ void mc_ctx_destroy(mc_ctx* c) {
     prof_clear(c);
     for (int k = 0; k < mc_ctx::SIDE_CAND; ++k)
         if (c->side_cand[k]) { (void)hipStreamSynchronize(c->side_cand[k]); (void)hipStreamDestroy(c->side_cand[k]); }
-    for (int k = 1; k < 3; ++k)
-        if (c->parts[k]) { (void)hipStreamSynchronize(c->parts[k]); (void)hipStreamDestroy(c->parts[k]); }
-    for (int k = 0; k < 3; ++k)
-        if (c->ev_parts[k]) (void)hipEventDestroy(c->ev_parts[k]);
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-    if (c->ev_gate) (void)hipEventDestroy(c->ev_gate);
+    if (c->ev_side) (void)hipEventDestroy(c->ev_side);
+    if (c->ev_stag) (void)hipEventDestroy(c->ev_stag);
     for (void* p : c->allocs) (void)hipFree(p);
     delete c;
 }
@@ -1334,6 +1268,7 @@ int mc_ctx_set_option(mc_ctx* c, const char* key, int64_t value) {
     const std::string k(key);
     McOptions& o = c->opt;
     if (k == "chain") {
+        if (int r = check_chain((int)value)) return r;
         o.chain = (int)value;
         c->hbuf_floats = (chain_on(c, 0) && mc_mlp_supported(c->m->cfg.latent_dim, 4 * c->m->cfg.latent_dim)) ? c->hbuf_cap : 0;
     } else if (k == "big_tokens") o.big_tokens = value;
@@ -1364,15 +1299,6 @@ int mc_ctx_set_option(mc_ctx* c, const char* key, int64_t value) {
             c->coop_reserved = nwg;
             c->rb.coop = nwg > 0;
         }
-    } else if (k == "split_groups") {
-        MC_REQUIRE(value >= 2 && value <= 4 && value <= 2 * c->B, "split_groups: 2..4 groups of whole samples (batch %d)", c->B);
-        for (int j = 1; j < (int)value - 1; ++j) {
-            if (!c->parts[j]) MC_HIP(hipStreamCreateWithFlags(&c->parts[j], hipStreamNonBlocking));
-        }
-        for (int j = 0; j < (int)value - 1; ++j) {
-            if (!c->ev_parts[j]) MC_HIP(hipEventCreateWithFlags(&c->ev_parts[j], hipEventDisableTiming));
-        }
-        c->nparts = (int)value;
     } else {
         mc_set_error("mc_ctx_set_option: unknown key '%s'", key);
         return MC_ERR_ARG;
@@ -1519,11 +1445,8 @@ static int denoise_impl(mc_ctx* c, const float* x_t, int32_t step, float* out2_d
     // row-wise op between layers, on the stream of the sample group that owns the rows (one launch when not split)
     auto by_group = [&](auto&& fn) -> int {
         if (split != 2) return fn(0L, c->rows, s);
-        for (int k = 0; k < c->nparts; ++k) {
-            const long r0 = part_row0(c, k);
-            if (int e = fn(r0, part_row0(c, k + 1) - r0, part_stream(c, k, s))) return e;
-        }
-        return MC_OK;
+        if (int e = fn(0L, BT, s)) return e;
+        return fn(BT, BT, c->side);
     };
     for (int i = 0; i < nl; ++i) {
         // ControlT2MHalf.forward_test (controlnet.py:372-413): base block 0, then for index 1..copy:
@@ -1545,7 +1468,7 @@ static int denoise_impl(mc_ctx* c, const float* x_t, int32_t step, float* out2_d
         }
         if ((r = run_layer(c, i, c->h, step, i == 0, split, s))) return r;
     }
-    if (split == 2 && (r = parts_join(c, s))) return r;      // the groups meet again before the pose decoder
+    if (split == 2 && (r = side_join(c, s))) return r;       // the groups meet again before the pose decoder
     if (stop_after >= 0) return MC_OK;
     // PoseDecoder as one dense [D -> C] GEMM (stmogen.py:505-544), /2 folded into the packed weight
     float* o = out2_dev ? out2_dev : c->out2;

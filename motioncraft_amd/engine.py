@@ -128,8 +128,8 @@ class NativeContext:
         self.precision = precision
 
     def set_option(self, key, value):
-        """Kernel-selection switch of THIS context (include/motioncraft_amd.h, mc_ctx_set_option): 'chain', 'big_tokens',
-        'split_groups', 'gemm_tune', 'route_coop', ... -- the MC_* environment variables only seed the defaults."""
+        """Kernel-selection switch of THIS context (include/motioncraft_amd.h, mc_ctx_set_option): 'chain' (the retired bits 3, 23, 25
+        and 28 raise), 'big_tokens', 'gemm_tune', 'route_coop', ... -- the MC_* environment variables only seed the defaults."""
         self._drop_graph()
         _lib.check(self.lib.mc_ctx_set_option(self.handle, str(key).encode(), int(value)), 'mc_ctx_set_option')
 

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 import torch
 
-DEFAULT_CHAIN = 8388599 | (1 << 24) | (1 << 26) | (1 << 27) | (1 << 29)        # McOptions::chain (mc_model.hip): every schedule / fusion bit but 3, 23, 25 and 28
+DEFAULT_CHAIN = 8388599 | (1 << 24) | (1 << 26) | (1 << 27) | (1 << 29)        # McOptions::chain (mc_model.hip): every schedule / fusion bit but the retired 3, 23, 25 and 28
 
 from helpers import (CTRL, CTRL_COPY, CTRL_FEATS, FULL, HML_FULL, HML_SMALL, KIT_SMALL, SMALL, SMALL_SEED, load,
                      step_noise_from_seed, synth_inputs)
@@ -878,6 +878,11 @@ def test_generic_fallback_path_vs_oracle(chain):
     assert e1 <= TOL_STEP and e2 <= TOL_FINAL
     with pytest.raises(RuntimeError):
         ctx.set_option('no_such_switch', 1)
+    for b in (3, 23, 25, 28):          # retired chain bits: rejected, not ignored
+        with pytest.raises(RuntimeError, match=f'chain bit {b} is retired'):
+            ctx.set_option('chain', DEFAULT_CHAIN | (1 << b))
+    with pytest.raises(RuntimeError):
+        ctx.set_option('split_groups', 2)      # the large-batch schedule has exactly two sample groups
     ctx.close()
     nm.close()
 
@@ -1028,9 +1033,9 @@ def test_fp16_fused_body_kernel_and_plane_gemm_equal_the_separate_kernels(prec):
     x, xf, mask = synth_inputs(dims, B, T, seed=5, lengths=[24, 20, 13])
     DFL = DEFAULT_CHAIN
     got = {}
-    # (round 6: bit 27 = the plane GEMM prefetches its residual rows into registers, the same bits; bit 28 = its accumulators start as R + bias, plain f16 only)
+    # (round 6: bit 27 = the plane GEMM prefetches its residual rows into registers, the same bits)
     for tag, chain in (('new', DFL), ('no_fused_body', DFL & ~(1 << 15)), ('no_planes', DFL & ~(1 << 17)), ('mlp_reg_staged', DFL & ~(1 << 18)),
-                       ('late_residual', DFL & ~(1 << 27)), ('acc_init', DFL | (1 << 28))):
+                       ('late_residual', DFL & ~(1 << 27))):
         ctx = nm.context(B, T, max_steps=2)
         ctx.set_option('big_tokens', 0)
         ctx.set_option('half_min_rows', 0)
@@ -1051,18 +1056,10 @@ def test_fp16_fused_body_kernel_and_plane_gemm_equal_the_separate_kernels(prec):
         assert torch.equal(got['new'][k], got['mlp_reg_staged'][k]), (name, float((got['new'][k] - got['mlp_reg_staged'][k]).abs().max()))
     assert torch.equal(got['new'][1], got['no_planes'][1]) and torch.equal(got['new'][2], got['no_planes'][2])
     e = maxabs(got['new'][3], got['no_planes'][3])
-    e28 = maxabs(got['acc_init'][3], got['new'][3])
-    print(f'{prec}: FiLM GEMM from fp16 planes vs in-kernel split: |dh| after layer 0 {e:.2e}, |dx0| {maxabs(got["new"][0], got["no_planes"][0]):.2e}; '
-          f'accumulators started as R + bias (chain bit 28) vs (sum + bias) + R: |dh| {e28:.2e}, |dx0| {maxabs(got["acc_init"][0], got["new"][0]):.2e}')
+    print(f'{prec}: FiLM GEMM from fp16 planes vs in-kernel split: |dh| after layer 0 {e:.2e}, |dx0| {maxabs(got["new"][0], got["no_planes"][0]):.2e}')
     assert e <= 2e-5
     # residual rows prefetched at the top of the tile (bit 27) vs loaded in the epilogue: the same order, the same bits
     assert all(torch.equal(a, b) for a, b in zip(got['new'], got['late_residual']))
-    if prec == 'f16x3':
-        assert all(torch.equal(a, b) for a, b in zip(got['new'], got['acc_init']))      # the split mode ignores bit 28
-    else:
-        # another summation order of the same fp32 terms: the small products are added INTO the O(10..100) residual row one MFMA at a time (measured 2.6e-4 on h
-        # after layer 0), against the 1e-2-level error one fp16 rounding per operand puts on the same rows
-        assert 0 < e28 <= 1e-3
     nm.close()
 
 
@@ -1890,42 +1887,6 @@ def test_unconditional_half_skips_its_text_rows_bit_identically(full_model):
             nm.close()
 
 
-def test_gate_launch_cut_at_whole_rounds_is_bit_identical(full_model):
-    """chain bit 23 (round 5; measured slower, off by default, kept as a switch): in the two-stream schedule the last sample group's gate launch is cut at a whole number of workgroup
-    rounds and the partial last round runs as gate_small_k on the other group's stream (beside the big launch).  gate_small_k
-    reproduces gate_k's accumulation order, so scores / expert choices / importance keys -- and with them everything downstream --
-    must be the SAME BITS: B=32 x 196 frames (588 tiles per group: 512 + 76), one denoiser call + routing of every layer, bit on / off;
-    and the same through two sampler steps."""
-    from motioncraft_amd.diffusion import build_diffusion
-    sd, nm = full_model
-    B, T = 32, 196
-    g = torch.Generator().manual_seed(15)
-    lengths = [int(v) for v in torch.randint(64, 197, (B,), generator=g)]
-    x_T, xf, mask = synth_inputs(FULL, B, T, seed=35, lengths=lengths)
-    d = build_diffusion(dict(beta_scheduler='linear', diffusion_steps=1000, model_mean_type='start_x', model_var_type='fixed_large'))
-    eps = torch.randn(B, T, 322, generator=g).cuda()
-    got = {}
-    for tag, chain in (('cut', DEFAULT_CHAIN | (1 << 23)), ('whole', DEFAULT_CHAIN)):
-        ctx = nm.context(B, T, max_steps=2)
-        ctx.set_option('chain', chain)
-        ctx.enable_capture()
-        ctx.set_timesteps(d.timestep_map[-2:])
-        ctx.set_condition(xf.cuda(), mask.cuda())
-        out2 = ctx.denoise(x_T.cuda(), 1).clone()
-        routes = [ctx.routing(i) for i in range(FULL['NL'])]
-        x = x_T.cuda()
-        for i in (1, 0):
-            x = ctx.sample_step(x, i, d.step_coefs(998 + i, 'ddpm', FULL['scale']), eps)
-        torch.cuda.synchronize()
-        got[tag] = (out2, routes, x.clone())
-        ctx.close()
-    assert bool(torch.isfinite(got['cut'][0]).all())
-    assert torch.equal(got['cut'][0], got['whole'][0]), maxabs(got['cut'][0], got['whole'][0])
-    for a, b in zip(got['cut'][1], got['whole'][1]):
-        assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
-    assert torch.equal(got['cut'][2], got['whole'][2])
-
-
 @pytest.mark.parametrize('L', [32, 128])
 def test_small_batch_gate_kernel_is_bit_identical_to_gate_k(L, monkeypatch):
     """gate_small_k (32-token workgroups, projector chunks split over the waves: batches of up to 12000 tokens) against
@@ -2379,9 +2340,8 @@ def test_twin_pairs_split_by_capacity_in_the_large_batch_schedule():
     free = cap['layer0']['routing']['free']
     N = 2 * B * T * dims['H']
     outs = []
-    # (default; then with the fused front of a sub-group also covering that sub-group's twins, chain bit 25 (off by default: slower); then without the
-    # event that orders the groups' FiLM blocks, bit 26; then the round-4 schedule bits off)
-    for chain in (DEFAULT_CHAIN, DEFAULT_CHAIN | (1 << 25), DEFAULT_CHAIN & ~(1 << 26), DEFAULT_CHAIN & ~((1 << 15) | (1 << 16))):
+    # (default; then without the event that orders the groups' FiLM blocks, bit 26; then the round-4 schedule bits off)
+    for chain in (DEFAULT_CHAIN, DEFAULT_CHAIN & ~(1 << 26), DEFAULT_CHAIN & ~((1 << 15) | (1 << 16))):
         ctx = nm.context(B, T, max_steps=1)
         ctx.set_option('big_tokens', 0)
         ctx.set_option('chain', chain)
