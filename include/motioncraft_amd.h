@@ -166,15 +166,22 @@ int mc_ctx_set_precision(mc_ctx* c, int32_t precision);
 #define MC_TIE_REVERSE 1
 int mc_ctx_set_tie_policy(mc_ctx* c, int32_t policy);
 /* Kernel-selection switches of ONE context (no reference counterpart: the reference has one code path; these exist for A/B
- * measurement and for the tests that pin alternative kernels to each other).  The MC_* environment variables of the same
- * meaning only seed the defaults of contexts created afterwards; two contexts of one process may differ.  Keys:
- *   "chain" (bit mask; the retired bits 3, 23, 25 and 28 -> MC_ERR_ARG), "big_tokens", "small_gemm_rows", "split_rows_expert",
- *   "split_rows_sffn", "split_expert", "split_sffn", "temporal_split", "rowchain_split", "gemm_tune", "small_tile_n",
- *   "gemm_wp_grid", "half_min_rows", "gate_small", "route_reg", "route_small", "route_coop", "route_per",
- *   "dbg_delay_us" (tests: holds the second sample group's stream that long in front of every layer tail, so the two-stream
- *   schedule runs far out of phase; results must not change).
- * Results never depend on them beyond fp32 summation order where DESIGN.md says so.  Unknown key -> MC_ERR_ARG.
- * Not while a captured graph exists (mc_ctx_graph_release first). */
+ * measurement and for the tests that pin alternative kernels to each other).  The MC_* environment variable of a key only seeds
+ * the default of contexts created afterwards (and of context-free calls such as mc_op_gemm, read once per process); two contexts
+ * of one process may differ.  Key (variable, default):
+ *   "chain" (MC_CHAIN, 763363319: bit mask; the retired bits 3, 23, 25, 28 and bits >= 30 are rejected),
+ *   "small_gemm_rows" (MC_SMALL_GEMM_ROWS, 5600), "split_rows_expert" (MC_SPLIT_ROWS_EXPERT, 2048),
+ *   "split_rows_sffn" (MC_SPLIT_ROWS_SFFN, 8192), "temporal_split" (MC_TEMPORAL_SPLIT, 96), "big_tokens" (MC_BIG_TOKENS, 65536),
+ *   "rowchain_split" (MC_ROWCHAIN_SPLIT, 20480), "gemm_tune" (MC_GEMM_TUNE, 1841: bits 0, 4, 5, 6, 8, 9, 10 only),
+ *   "small_tile_n" (MC_SMALL_TILE_N, 0: 0, 48, 64 or 96), "gemm_wp_grid" (MC_GEMM_WP_GRID, 512: <= 0 one workgroup per tile),
+ *   "half_min_rows" (MC_HALF_MIN_ROWS, 512), "gate_small" (MC_GATE_SMALL, 12000), "split_expert" (MC_SPLIT_EXPERT, 0),
+ *   "split_sffn" (MC_SPLIT_SFFN, 0), "route_reg" (MC_ROUTE_REG, 1), "route_coop" (MC_ROUTE_COOP, 1),
+ *   "route_small" (MC_ROUTE_SMALL_CTX, else MC_ROUTE_SMALL, 20480: 0 .. 131072), "route_per" (none, 0: 0, 10 or 16),
+ *   "dbg_delay_us" (none, 0: -100000 .. 100000; tests: holds one sample group's stream that long in front of every layer tail,
+ *   so the two-stream schedule runs far out of phase; results must not change).
+ * Results never depend on them beyond fp32 summation order where DESIGN.md says so.  An unknown key or a value outside the
+ * stated range -> MC_ERR_ARG; an environment variable outside it fails mc_ctx_create (or the context-free call) with MC_ERR_ARG
+ * naming the variable.  Not while a captured graph exists (mc_ctx_graph_release first). */
 int mc_ctx_set_option(mc_ctx* c, const char* key, int64_t value);
 int mc_ctx_set_timesteps(mc_ctx* c, const int32_t* t_orig_host, int32_t num_steps, void* stream);
 int mc_ctx_set_condition(mc_ctx* c, const float* xf_out_dev, const float* mask_dev, void* stream);

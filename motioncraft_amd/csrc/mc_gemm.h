@@ -1,8 +1,23 @@
 // Argument block + launcher of the fp32 MFMA GEMM family (mc_gemm.hip).
 #pragma once
 #include <hip/hip_runtime.h>
+#include "mc_options.h"
 
 enum { GM_PLAIN = 0, GM_EXP1 = 1, GM_EXP2 = 2, GM_COMB = 3, GM_ENC = 4 };
+
+// bits of GemmArgs::tune / TailArgs::tune (McOptions::gemm_tune)
+enum : int {
+    kTuneStaging = 1 << 0,       // mid-loop staging writes in gemm_k
+    kTuneDma = 1 << 4,           // the LDS-DMA kernels for full-tile plain launches
+    kTuneWp = 1 << 5,            // (with kTuneDma) the persistent wave-private pipeline gemm_wp_k instead of gemm_dma_k
+    kTuneNoXcd = 1 << 6,         // no XCD remap in gemm_dma_k / gemm_wp_k
+    kTuneSmallXcd = 1 << 8,      // XCD-aware tile order in gemm_small_k / gemm_small16_k / gemm_tail_k (a row block's column tiles share one L2)
+    kTuneEncWp = 1 << 9,         // the aligned pose-encoder GEMM on gemm_wp_k (table + duplicate rows in its epilogue)
+    kTuneTail2 = 1 << 10,        // the folded decoder tail as block ranges with A read once (gemm_tail2_k)
+    kTuneBits = kTuneStaging | kTuneDma | kTuneWp | kTuneNoXcd | kTuneSmallXcd | kTuneEncWp | kTuneTail2,
+    kTuneDefault = kTuneBits & ~kTuneNoXcd,
+};
+static_assert(kTuneDefault == 1841, "the default tune bits are public ABI");
 
 struct GemmArgs {
     // A operand: element (r,k) at A[grp*a_gstride + row(r)*lda + a_col + k]
@@ -39,11 +54,18 @@ struct GemmArgs {
     const int* src_row = nullptr;
     const int* dst_row = nullptr;
     const float* comb_w = nullptr;  // [M][2]
-    // launch options (a context passes its own, mc_ctx_set_option; the defaults come from the environment once per process)
-    int small_tile_n = 0;           // mc_launch_gemm_small: force the tile width (64, 48, 96); 0 = the load model's choice (env MC_SMALL_TILE_N)
-    int wp_grid = 0;                // workgroups of the persistent gemm_wp_k launch; 0 = default 512 (env MC_GEMM_WP_GRID), < 0 one per tile
-    int tune = -1;                  // -1 = process default (mc_gemm_default_tune(): env MC_GEMM_TUNE, else 1841 = 49 + 256 + 512 + 1024); bits: 0 mid-loop staging writes in gemm_k, 4 LDS-DMA kernels for full-tile plain launches, 5 (with 4) the persistent wave-private pipeline gemm_wp_k instead of gemm_dma_k, 6 no XCD remap in gemm_dma_k, 8 (round 4) XCD-aware tile order in gemm_small_k (a row block's column tiles share one L2), 9 (round 4) the aligned pose-encoder GEMM on gemm_wp_k (table + duplicate rows in its epilogue), 10 (round 5) the folded decoder tail as block ranges with A read once (gemm_tail2_k); bit 6 also switches the XCD remap of gemm_wp_k off
+    // launch options, host only: a context passes its own (mc_gemm_opts); the defaults below take the process options (mc_process_options)
+    int small_tile_n = 0;           // mc_launch_gemm_small: tile width 48, 64 or 96; < 0 = the load model's choice
+    int wp_grid = 0;                // workgroups of the persistent gemm_wp_k launch; < 0 = one per tile
+    int tune = -1;                  // kTune* bits; < 0 = the process options
 };
+
+// GemmArgs' launch options from resolved options (a context's, or the process snapshot's)
+inline void mc_gemm_opts(const McOptions& o, GemmArgs& g) {
+    g.tune = (int)o.gemm_tune;
+    g.small_tile_n = o.small_tile_n ? (int)o.small_tile_n : -1;
+    g.wp_grid = o.gemm_wp_grid > 0 ? (int)o.gemm_wp_grid : -1;
+}
 
 int mc_device_cus();      // compute units of the current device (cached)
 int mc_launch_gemm(int mode, const GemmArgs& g, int groups, int max_tiles, hipStream_t stream);
@@ -69,8 +91,7 @@ struct TailArgs {
     const float* coef_table = nullptr;   // ... or (graph replay) read from coef_table[*step_ptr * coef_stride + {0, 1}]
     const int* step_ptr = nullptr;
     long coef_stride = 0;
-    int tune = -1;
+    int tune = -1;                  // kTune* bits; every caller sets them (>= 0)
 };
 int mc_launch_gemm_tail(const TailArgs& g, hipStream_t stream);
-int mc_gemm_default_tune();          // the resolved process default of GemmArgs::tune / TailArgs::tune
 bool mc_gemm_tail_two_outputs(const TailArgs& g);      // true: this launch writes the two partial products C and C2 (x0 = C + C2), else C alone

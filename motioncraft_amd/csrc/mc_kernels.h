@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "mc_options.h"
 
 // CFG twin aliasing in base layer 0: while *split_flag == 0 the rows >= `from` of mf / qkv / ys are bit-identical to
 // rows (r - from); producers neither compute nor store them, consumers read the twin's.  flag == nullptr: off.
@@ -116,14 +117,11 @@ struct RouteBufs {
     int* state;        // small int block, layout in mc_route.hip
     int max_tiles;
     uint32_t tie_xor = 0xFFFFFFFFu;   // order of equal-importance tokens at the capacity cut: ~0 = lower index first (stable), 0 = higher first
-    bool coop = true;                 // larger batches: the cooperative one-launch routing kernel (false: the 12-launch sequence; env MC_ROUTE_COOP=0, tests)
-    int coop_per = 0;                 // route_coop_k: (token, choice) pairs per thread, 10 or 16 (0: 10 up to 256 workgroups, 16 beyond; option "route_per")
-    long small_pairs = -1;            // >= 0: overrides MC_ROUTE_SMALL for this context (tests force the large-batch paths on small configs)
-    bool reg_kernel = true;           // small batches: the register-resident one-workgroup routing kernel (false: the L2-streaming form at every size; env MC_ROUTE_REG=0, tests)
 };
 size_t mc_route_state_ints(int E);
-bool mc_route_is_small(long N);
-bool mc_route_cleans_counts(const RouteBufs& rb, long N);   // the routing kernel that will run for N tokens hands the (choice, expert) counts back zeroed
+// the routing kernels are picked by the options route_small, route_reg, route_coop and route_per
+bool mc_route_is_small(const McOptions& o, long N);        // routing of N tokens runs as one workgroup
+bool mc_route_cleans_counts(const McOptions& o, long N);   // the routing kernel that will run for N tokens hands the (choice, expert) counts back zeroed
 size_t mc_route_barrier_offset();                          // ints into the state block: grid-barrier words, to be zeroed once
 size_t mc_route_error_offset();                             // ints into the state block: sticky "grid barrier timed out" word of route_coop_k
 int mc_route_coop_wgs(long N);                              // workgroups route_coop_k launches for N tokens (0: beyond its size range)
@@ -136,7 +134,7 @@ int mc_launch_gate_finish(const float* proj, const float* sim_n, const float* lo
                           RouteBufs rb, hipStream_t s);
 // capacity/BPR drop decision + slot compaction + tile map (tile rows = 128)
 // Nsrc = N, or N/2 (twin mode); tokens >= gsplit get their own slot group (tile map at [max_tiles, 2 max_tiles))
-int mc_launch_route(long N, long Nsrc, long gsplit, int E, int capacity, RouteBufs rb, hipStream_t s);
+int mc_launch_route(long N, long Nsrc, long gsplit, int E, int capacity, RouteBufs rb, const McOptions& o, hipStream_t s);
 const int* mc_route_num_tiles_ptr(const RouteBufs& rb, int group = 0);
 // twin mode: 1 after routing iff some second-half token was kept/dropped differently from its first-half twin
 const int* mc_route_split_flag_ptr(const RouteBufs& rb);

@@ -20,6 +20,7 @@
 #include "mc_kernels.h"
 #include "mc_chain.h"
 #include "mc_half.h"
+#include "mc_options.h"
 
 struct HalfW {              // fp16 hi / lo planes of one weight (mc_half.h); lo directly behind hi in one allocation
     mc_half* hi = nullptr;
@@ -54,69 +55,11 @@ struct LayerW {
     HalfW h_ca_out, h_ffn_out, h_fc1, h_fc2, h_w1, h_w2, h_after, h_proj, h_qkv;
 };
 
-// Per-context switches (mc_ctx_set_option).  Defaults = the measured best; a variable of the same meaning in the environment
-// (MC_CHAIN, MC_GEMM_TUNE, ...) overrides the default of contexts created afterwards, mc_ctx_set_option overrides both for
-// one context -- two models of one process can run different kernel selections.
-struct McOptions {
-    // chain bits: 0 fused expert / SFFN MLP (mlp2_k), 1 fused gate (gate_k), 2 chained proj / qkv (rowchain_k), 4 CFG twin dedupe in base
-    // layer 0, 5 two sample groups (the CFG halves) on two streams (large batches), 6 one expert-MLP launch per sample group, 7 last FiLM Linear + pose decoder on the CFG-combined rows (folded), 8 twin aliasing of the
-    // mf / qkv / ys rows in base layer 0, 9 the sample groups stay on their streams across the control-branch ops between layers,
-    // 10 proj + body LN + q/k/v in one kernel (large batches), 11 folded decoder tail as one grouped GEMM + sum in the sampler kernel,
-    // 12 small batches: the SFFN's split-hidden partial sums are added up by the FiLM row kernel, 13 B=1 sizes: the expert MLP picks
-    // 3 or 4 hidden slices on the device, 14 small batches: temporal branch on the main stream, LN + q/k/v + body on the side stream,
-    // 15 (round 4) pqbody_k: bit 10's kernel also runs the body-topology attention (q/k/v never in HBM; L = 128, 12 parts, fp32),
-    // 16 (round 4) the twin layer's gate / experts / front kernels run as two sample sub-groups on the two streams
-    // 17 (round 4) reduced-precision contexts: film_rows_k writes the FiLM GEMM's A operand as fp16 planes, gemm_hd_k reads them by LDS-DMA
-    // 18 (round 4) the fused expert / SFFN MLPs (fp32 and fp16, L = 128 / 64) stage their weight chunks by LDS-DMA (mlp2d_k / mlp2hd_k; same bits)
-    // 19 (round 4) mc_sample_loop: the sampler update also writes x_{t-1} at the padded stride of the next step's pose-encoder GEMM
-    // 20 (round 4) reduced-precision contexts: temporal linear attention on the fp16 MFMA (temporal_h_k)
-    // 22 (round 4) L = 64 models: temporal_k takes two adjacent parts per workgroup (all four waves on the MFMA)
-    // 21 (round 4) large batches: the folded decoder tail with the CFG combination in its A staging, one pass over both K groups (gemm_tail_k)
-    // 24 (round 5) temporal_k: the unconditional CFG half skips whole leading blocks of its text rows (keys at -1e6, values x 0: exact zeros
-    //    as long as the sample has a valid frame) -- the same bits, ~20 % less of that half's kernel
-    // 26 (round 5) the second sample group's first FiLM block (proj_out) starts behind the first group's FiLM ROW kernel (one event per layer):
-    //    the two HBM-bound row kernels never run against each other and the groups' GEMM / SFFN launches leave the seam half a kernel apart
-    //    instead of in lockstep (B=64 19.08 -> 18.94, 19.14 -> 19.01, 19.12 -> 19.00 ms/step; a 60 us spin at the same place: the same).
-    //    Only in exact-fp32 contexts at L = 128: measured slower in the fp16 modes (f16 6.86 -> 7.08) and at L = 64 (M2D 17.62 -> 18.00), neutral at batch 32
-    // 27 (round 6) reduced-precision contexts: the FiLM plane GEMM requests the residual rows of its epilogue at the TOP of the tile, into registers of their own
-    //    (gemm_hd_k<., true>: in flight during the DMA prologue; no load -> add -> store chain at the end of every tile) -- the same order (sum + bias) + R,
-    //    the same bits (tools/gemm_h6_lab.hip: the kernel runs at the package power cap, this chain is the part that moves).  Same-box A/B: f16 B=64 6.87 -> 6.82,
-    //    B=32 3.98 -> 3.81 ms/step; f16x3 10.72 -> 10.62, 5.52 -> 5.45
-    // 29 (round 6) reduced-precision contexts: the FiLM operand planes are written FRAGMENT-MAJOR and the plane GEMM reads its A fragments straight into registers
-    //    (gemm_hf_k: only W rides the LDS-DMA ring; tools/gemm_h6_lab.hip ha_k); launches whose rows are whole 32-row blocks only; the same bits as gemm_hd_k.
-    //    film_rows_k stages the 4 rows of a workgroup in LDS and writes 64-byte runs, the 8 workgroups of a 32-row block share an XCD.  Serial schedule: the GEMM
-    //    198 -> 183 us (B=64 f16), the row kernel 74.7 -> 77.2; two-stream step, same-box A/B: f16x3 10.85 -> 10.56 (B=64), 5.50 -> 5.37 (B=32); f16 neutral (7.05 / 7.06, 3.76 / 3.75)
-    // Bits 3, 23, 25 and 28 lost their A/B and were retired (kRetiredChainBits): a mask that sets one is rejected.
-    int chain = 65527 | (1 << 16) | (1 << 17) | (1 << 18) | (1 << 19) | (1 << 20) | (1 << 21) | (1 << 22) | (1 << 24) | (1 << 26) | (1 << 27) | (1 << 29);     // (all but the retired bits)
-    long small_gemm_rows = 5600;       // plain GEMMs of up to this many rows take the small-M kernels (round 4: 6400 -> 5600, measured per batch: at
-                                       // 6272 rows -- a sample group of 32 x 196 frames -- gemm_wp_k / gemm_tail_k now win: B=32 step 10.21 -> 10.03 ms,
-                                       // S2G at 32 per GPU 27.65 -> 27.14; at 4704 rows (B=24) the small kernels still do, 7.85 vs 7.91)
-    long split_rows_expert = 2048, split_rows_sffn = 8192;      // residual rows up to which the fused MLPs split their hidden dimension
-    long temporal_split = 96;          // (sample, part) workgroups up to which temporal_k slices its output columns
-    long big_tokens = 65536;           // above this many motion tokens: the large-batch schedule (two sample groups on two streams, projqkv / pqbody)
-    long rowchain_split = 20480;       // tokens up to which rowchain_k slices its output chunks over blockIdx.y
-    int gemm_tune = -1, small_tile_n = 0, gemm_wp_grid = 0;      // GemmArgs::tune / small_tile_n / wp_grid (-1 / 0: library defaults)
-};
-static McOptions default_options() {
-    McOptions o;
-    if (const char* e = getenv("MC_CHAIN")) o.chain = atoi(e);
-    if (const char* e = getenv("MC_SMALL_GEMM_ROWS")) o.small_gemm_rows = atol(e);
-    if (const char* e = getenv("MC_SPLIT_ROWS_EXPERT")) o.split_rows_expert = atol(e);
-    if (const char* e = getenv("MC_SPLIT_ROWS_SFFN")) o.split_rows_sffn = atol(e);
-    if (const char* e = getenv("MC_TEMPORAL_SPLIT")) o.temporal_split = atol(e);
-    if (const char* e = getenv("MC_BIG_TOKENS")) o.big_tokens = atol(e);
-    if (const char* e = getenv("MC_ROWCHAIN_SPLIT")) o.rowchain_split = atol(e);
-    if (const char* e = getenv("MC_GEMM_TUNE")) o.gemm_tune = atoi(e);
-    if (const char* e = getenv("MC_SMALL_TILE_N")) o.small_tile_n = atoi(e);
-    if (const char* e = getenv("MC_GEMM_WP_GRID")) o.gemm_wp_grid = atoi(e);
-    return o;
-}
-
 struct ProfRec { hipEvent_t e0 = nullptr, e1 = nullptr; long rows = 0; };
 
 struct mc_ctx {
     mc_model* m = nullptr;
-    McOptions opt = default_options();
+    McOptions opt{};             // kernel selection (mc_ctx_set_option), seeded by mc_ctx_create from the option table
     int B = 0, T = 0, S = 0, maxS = 0;
     long N = 0, rows = 0, Ntxt = 0;
     std::vector<LayerW> lw;
@@ -135,7 +78,6 @@ struct mc_ctx {
     // fp16 hi | lo planes of BOTH sample groups there, and fp32 rows written into it by one group's stream would land on the plane rows
     // the other group's gemm_hd_k may still be reading; null in fp32 contexts (then `a` itself holds fp32 rows only)
     float* a_tail = nullptr;
-    long dbg_delay_us = 0;       // tests (option "dbg_delay_us"): hold the second (> 0) or the first (< 0) sample group's stream this long in front of every layer tail, so the groups run far out of phase
     size_t hbuf_cap = 0;        // floats allocated behind hbuf
     size_t hbuf_floats = 0;     // > 0: hbuf is free scratch (fused expert path), used for split-K partial sums
     bool cnt_clean = false;     // the routing state's (choice, expert) counts are known to be zero on the stream (route_small_k cleans up after itself)
@@ -184,10 +126,6 @@ struct mc_ctx {
     hipGraphExec_t graph_exec = nullptr;
     int graph_steps = 0;
     int prec = MC_PREC_F32;      // MFMA operand precision of the per-step GEMM-shaped kernels (mc_ctx_set_precision)
-    long half_min_rows = 512;    // env MC_HALF_MIN_ROWS at context creation: see use_half()
-    int split_sffn = 0;          // env MC_SPLIT_SFFN at context creation: hidden-dimension split of the SFFN (0 = load model)
-    int split_expert = 0;        // env MC_SPLIT_EXPERT at context creation: hidden-dimension split of the small-batch expert MLP (0 = load model)
-    long gate_small_tokens = 12000;   // env MC_GATE_SMALL at context creation: up to this many tokens the gate runs as gate_small_k
     int* cap_idx = nullptr;      // [NL][2N] routing capture (tests): expert ids ...
     float* cap_w = nullptr;      // ... and combine weights (0 = dropped) of every layer
 };
@@ -383,34 +321,22 @@ int bind_half_weights(mc_ctx* c) {
 // The fp16-MFMA kernels have no small-batch variants (128-row workgroups, no hidden / K split): up to this many residual
 // rows (B=1 at 196 frames: 392) the fp32 small-batch kernels are faster and the reduced-precision modes run on them
 // (B=1 50-step DDIM: 68.3 ms on the fp16 kernels, 57.3 ms on the fp32 ones; from B=2 the fp16 kernels win).
-static bool use_half(const mc_ctx* c) { return c->prec != MC_PREC_F32 && c->rows > c->half_min_rows; }
+static bool use_half(const mc_ctx* c) { return c->prec != MC_PREC_F32 && c->rows > c->opt.half_min_rows; }
 
 // residual rows up to which the fused MLPs split their hidden dimension over workgroups (which = 0 experts, 1 SFFN)
 static long split_rows(const mc_ctx* c, int which) { return which ? c->opt.split_rows_sffn : c->opt.split_rows_expert; }
-static const McOptions& options_of(const mc_ctx* c) {
-    static const McOptions dflt = default_options();      // context-free ops (mc_op_gemm)
-    return c ? c->opt : dflt;
-}
-static long small_gemm_rows(const mc_ctx* c) { return options_of(c).small_gemm_rows; }
-static bool chain_on(const mc_ctx* c, int which) { return (options_of(c).chain >> which) & 1; }
-// chain bits that lost their A/B and were retired; the numbers stay reserved, a mask that sets one is an error
-constexpr int kRetiredChainBits = (1 << 3) | (1 << 23) | (1 << 25) | (1 << 28);
-static int check_chain(int chain) {
-    for (int b = 0; b < 31; ++b) MC_REQUIRE(!(((chain & kRetiredChainBits) >> b) & 1), "chain bit %d is retired (DESIGN.md section 5)", b);
-    return MC_OK;
-}
-static void gemm_opts(const mc_ctx* c, GemmArgs& g) {
-    const McOptions& o = options_of(c);
-    g.tune = o.gemm_tune; g.small_tile_n = o.small_tile_n; g.wp_grid = o.gemm_wp_grid;
-}
+static bool chain_on(const mc_ctx* c, ChainBit which) { return (c->opt.chain >> which) & 1; }
 
+// c = nullptr: a context-free launch (mc_op_gemm) on the process options
 int dense(const mc_ctx* c, const float* A, long lda, const float* W, long ldw, const float* bias, const float* R, long ldr,
           float* C, long ldc, long M, int N, int K, int act, hipStream_t s) {
+    const McOptions* o = c ? &c->opt : mc_process_options();
+    if (!o) return MC_ERR_ARG;
     GemmArgs g;
-    gemm_opts(c, g);
+    mc_gemm_opts(*o, g);
     g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.bias = bias; g.R = R; g.ldr = ldr;
     g.C = C; g.ldc = ldc; g.M = (int)M; g.N = N; g.K = K; g.act = act;
-    if (M <= small_gemm_rows(c) && act == ACT_NONE && K % 32 == 0 && lda % 4 == 0 && ldw % 4 == 0)
+    if (M <= o->small_gemm_rows && act == ACT_NONE && K % 32 == 0 && lda % 4 == 0 && ldw % 4 == 0)
         return mc_launch_gemm_small(g, s);          // latency-bound sizes: 64 x 64 tiles (see gemm_small_k)
     return mc_launch_gemm(GM_PLAIN, g, 1, 0, s);
 }
@@ -435,7 +361,7 @@ int dense_splitk(const mc_ctx* c, const float* A, const float* W, const float* b
     while (S < 8 && tiles * (S * 2) <= 1024 && K % (S * 2 * 32) == 0 && (size_t)(S * 2) * M * N <= ws_floats) S *= 2;
     if (S == 1) return dense(c, A, K, W, K, bias, R, N, C, N, M, N, K, ACT_NONE, s);
     GemmArgs g;
-    gemm_opts(c, g);
+    mc_gemm_opts(c->opt, g);
     g.A = A; g.lda = K; g.a_gstride = K / S;          // split s reads columns [s K/S, (s+1) K/S) of A and of W
     g.W = W; g.ldw = K; g.w_gstride = K / S;
     g.C = ws; g.ldc = N; g.c_gstride = M * N;
@@ -455,10 +381,10 @@ int moe_experts(mc_ctx* c, const MoeW& w, const float* z, long Ntok, int group, 
     const int max_tiles = cdiv(2 * Ntok, 128) + E;
     const long to = (long)group * c->rb.max_tiles;
     int r;
-    if (chain_on(c, 0) && mc_mlp_supported(din, hid)) {
+    if (chain_on(c, kChainMlp) && mc_mlp_supported(din, hid)) {
         // fused expert FFN: hidden activations stay on chip (mc_chain.hip)
         MlpArgs m;
-        m.dma = chain_on(c, 18) ? 1 : 0;
+        m.dma = chain_on(c, kChainMlpDma) ? 1 : 0;
         {   // top-2 slots of this slot group's source tokens (twins of base layer 0 have no slots of their own)
             const long nsrc = c->led_nsrc > 0 ? c->led_nsrc : Ntok, gs = c->led_gsplit;
             m.ledger_rows = 2 * ((gs <= 0 || gs >= nsrc) ? nsrc : (group == 0 ? gs : nsrc - gs));
@@ -475,7 +401,7 @@ int moe_experts(mc_ctx* c, const MoeW& w, const float* z, long Ntok, int group, 
         // ones finish in 1.45x one -- the load model of mc_launch_gemm_small) times the hidden chunks per workgroup; ~2 Ntok / 128
         // + E / 2 tiles are real.  4 ways except where 3 take a whole round off: B = 2 at 196 frames (620 -> 465 workgroups,
         // 3 -> 2 rounds: 80.5 -> 77.7 ms per 50-step DDIM; at B = 1 the tile count straddles 256 / 3 and 3 ways lose 2 %).
-        int S = c->split_expert;                   // env MC_SPLIT_EXPERT at context creation (0: the model below)
+        int S = (int)c->opt.split_expert;          // (0: the model below)
         if (S <= 0) {
             const long tiles = 2 * Ntok / 128 + E / 2;
             auto load = [&](int ways) {
@@ -489,7 +415,7 @@ int moe_experts(mc_ctx* c, const MoeW& w, const float* z, long Ntok, int group, 
             c->hbuf_floats >= (size_t)S * 2 * Ntok * din) {
             m.Y = c->hbuf; m.nsplit = S; m.y_sstride = 2 * Ntok * din;
             // B = 1 sizes (the estimated tile count straddles 256 / 3): 3 or 4 ways decided on the device from the real count
-            const bool dyn = S == 4 && c->split_expert == 0 && (2 * Ntok / 128 + E / 2) * 3 <= 300 && chain_on(c, 13);
+            const bool dyn = S == 4 && c->opt.split_expert == 0 && (2 * Ntok / 128 + E / 2) * 3 <= 300 && chain_on(c, kChainDynSlices);
             m.dyn_split = dyn ? 1 : 0;
             if ((r = mc_launch_mlp(MLP_EXPERT, m, 1, max_tiles, s))) return r;
             return mc_launch_splitk_reduce(c->hbuf, S, 2 * Ntok, din, nullptr, nullptr, c->y2, s,
@@ -498,7 +424,7 @@ int moe_experts(mc_ctx* c, const MoeW& w, const float* z, long Ntok, int group, 
         return mc_launch_mlp(MLP_EXPERT, m, 1, max_tiles, s);
     }
     GemmArgs a;
-    gemm_opts(c, a);
+    mc_gemm_opts(c->opt, a);
     a.A = z; a.lda = din; a.src_row = c->rb.src_row;
     a.W = w.fc1_w; a.ldw = din; a.w_gstride = (long)hid * din;
     a.bias = w.fc1_b; a.b_gstride = hid; a.act = ACT_GELU;
@@ -507,7 +433,7 @@ int moe_experts(mc_ctx* c, const MoeW& w, const float* z, long Ntok, int group, 
     a.num_tiles = mc_route_num_tiles_ptr(c->rb, group);
     if ((r = mc_launch_gemm(GM_EXP1, a, 1, max_tiles, s))) return r;
     GemmArgs b;
-    gemm_opts(c, b);
+    mc_gemm_opts(c->opt, b);
     b.A = c->hbuf; b.lda = hid; b.W = w.fc2_wt; b.ldw = hid; b.w_gstride = (long)din * hid;
     b.bias = w.fc2_b; b.b_gstride = din; b.dst_row = c->rb.dst_row;
     b.C = c->y2; b.ldc = din; b.N = din; b.K = hid;
@@ -533,12 +459,12 @@ int run_moe(mc_ctx* c, const MoeW& w, const float* z, long Ntok, float* out, lon
     c->cnt_clean = false;
     c->led_nsrc = twin ? Ntok / 2 : Ntok;
     c->led_gsplit = gsplit;
-    if ((r = mc_launch_route(Ntok, twin ? Ntok / 2 : Ntok, gsplit, E, capacity, c->rb, s))) return r;
-    c->cnt_clean = mc_route_cleans_counts(c->rb, Ntok);
+    if ((r = mc_launch_route(Ntok, twin ? Ntok / 2 : Ntok, gsplit, E, capacity, c->rb, c->opt, s))) return r;
+    c->cnt_clean = mc_route_cleans_counts(c->opt, Ntok);
     if (gsplit < Ntok) return MC_OK;
     if ((r = moe_experts(c, w, z, Ntok, 0, s, hw, hw2))) return r;
     if (!out) return MC_OK;                        // the caller launches the projection itself (row ranges)
-    if (chain_on(c, 2) && mc_mlp_supported(din, 32) && w.dout % 32 == 0) {
+    if (chain_on(c, kChainRowchain) && mc_mlp_supported(din, 32) && w.dout % 32 == 0) {
         RowChainArgs p;
         p.split_tokens = c->opt.rowchain_split;
         p.X = c->y2; p.comb_w = c->rb.comb_w; p.W = w.proj_w; p.bias = w.proj_b;
@@ -547,7 +473,7 @@ int run_moe(mc_ctx* c, const MoeW& w, const float* z, long Ntok, float* out, lon
         return mc_launch_rowchain(0, p, s);
     }
     GemmArgs p;
-    gemm_opts(c, p);
+    mc_gemm_opts(c->opt, p);
     p.A = c->y2; p.lda = din; p.comb_w = c->rb.comb_w;
     p.W = w.proj_w; p.ldw = din; p.bias = w.proj_b;
     p.C = out; p.ldc = ldout; p.M = (int)Ntok; p.N = w.dout; p.K = din;
@@ -563,7 +489,7 @@ static float* deferred_a(const mc_ctx* c) { return c->a_tail ? c->a_tail : c->a;
 // context has planes (mc_ctx_set_precision builds them for all layers or fails), so the weight is not part of the answer.
 bool a_holds_planes(const mc_ctx* c) {
     const long D = (long)c->m->cfg.latent_dim * c->m->cfg.num_parts;
-    return use_half(c) && chain_on(c, 17) && D % 128 == 0 && c->rows * D * 2 < (1L << 31);
+    return use_half(c) && chain_on(c, kChainFilmPlanes) && D % 128 == 0 && c->rows * D * 2 < (1L << 31);
 }
 
 // rows [row0, row0 + nrows) of:  a = silu(LN(y1 (+ y2)) * (1 + scale) + shift);  h += Linear(a)   (StylizationBlock)
@@ -588,7 +514,7 @@ int film_block(mc_ctx* c, float* hs, const float* y1, const float* y2, const flo
     float* a_out = planes ? reinterpret_cast<float*>(reinterpret_cast<mc_half*>(c->a) + o) : a_rows + o;
     // chain bit 29 (round 6): the planes of THIS launch's rows are written fragment-major and the GEMM reads its A fragments straight into registers
     // (gemm_hf_k); needs whole 32-row blocks (a sample group of B x 196 frames with B % 8 == 0 has them), else the row-major planes + gemm_hd_k
-    const bool frag_major = planes && chain_on(c, 29) && row0 % 32 == 0 && nrows % 32 == 0 && D % 64 == 0 && D >= 192;
+    const bool frag_major = planes && chain_on(c, kChainFragMajor) && row0 % 32 == 0 && nrows % 32 == 0 && D % 64 == 0 && D >= 192;
     if ((r = mc_launch_film_rows(y1_parts > 1 ? y1 : y1 + o, y2 ? y2 + o : nullptr, ln_g, ln_b, ss, a_out, nrows, D, s, y1_alias, row0, sref,
                                  y1_parts, nrows * D, planes ? ((c->prec == MC_PREC_F16X3 ? 2 : 1) | (frag_major ? 4 : 0)) : 0, pstride))) return r;
     if (ev_after_rows) MC_HIP(hipEventRecord(ev_after_rows, s));
@@ -600,14 +526,14 @@ int film_block(mc_ctx* c, float* hs, const float* y1, const float* y2, const flo
         g.Wh = hw->hi; g.Wl = hw->lo; g.bias = out_b; g.R = hs + o; g.ldr = D; g.C = hs + o; g.ldc = D;
         g.M = (int)nrows; g.N = D; g.K = D;
         g.a_fm = frag_major ? 1 : 0;
-        g.pre = chain_on(c, 27);      // residual rows prefetched into registers (same bits)
+        g.pre = chain_on(c, kChainResidualPre);      // residual rows prefetched into registers (same bits)
         return mc_launch_gemm_h(g, c->prec == MC_PREC_F16X3, s);
     }
     if (half_gemm)
         return dense_h(c, c->a + o, *hw, out_b, hs + o, hs + o, nrows, D, D, s);
-    if (nrows <= small_gemm_rows(c) && D % 64 == 0) {     // up to a few thousand rows: 64 x 64 tiles, short MFMA chains, no K split (B=8: -11 % per step)
+    if (nrows <= c->opt.small_gemm_rows && D % 64 == 0) {     // up to a few thousand rows: 64 x 64 tiles, short MFMA chains, no K split (B=8: -11 % per step)
         GemmArgs q;
-        gemm_opts(c, q);
+        mc_gemm_opts(c->opt, q);
         q.A = c->a + o; q.lda = D; q.W = out_w; q.ldw = D; q.bias = out_b; q.R = hs + o; q.ldr = D; q.C = hs + o; q.ldc = D;
         q.M = (int)nrows; q.N = D; q.K = D;
         return mc_launch_gemm_small(q, s);
@@ -635,7 +561,7 @@ int layer_rows(mc_ctx* c, int i, float* hs, int step, bool twin, long row0, long
     // twin layer: rows of the second CFG half whose routing equals their twin's are aliased, not recomputed
     TwinAlias tok_alias, frame_alias;
     const int* twin_flag = nullptr;
-    if (twin && chain_on(c, 8) && !c->no_alias) {
+    if (twin && chain_on(c, kChainTwinAlias) && !c->no_alias) {
         twin_flag = mc_route_split_flag_ptr(c->rb);
         tok_alias.split_flag = frame_alias.split_flag = twin_flag;
         tok_alias.from = c->N / 2;
@@ -649,12 +575,12 @@ int layer_rows(mc_ctx* c, int i, float* hs, int step, bool twin, long row0, long
     // ---- post-score combine + GELU + MOE.proj -> mf [N][4L] ----
     // large batches: proj + body LayerNorm + q/k/v as one kernel (small ones keep them apart: the temporal branch then
     // starts on the side stream right after the projection)
-    const bool pq_fused = chain_on(c, 2) && chain_on(c, 10) && c->N > c->opt.big_tokens && mc_mlp_supported(L, 32) && (4 * L) % 32 == 0;
+    const bool pq_fused = chain_on(c, kChainRowchain) && chain_on(c, kChainProjQkv) && c->N > c->opt.big_tokens && mc_mlp_supported(L, 32) && (4 * L) % 32 == 0;
     // ... and the body-topology attention too (pqbody_k: frame-aligned tiles, q/k/v never leave the chip): fp32 path, L = 128, 12 parts
-    const bool body_fused = pq_fused && chain_on(c, 15) && H == 12 && g.dyn_heads == 8 && (L == 128 || L == 64);
+    const bool body_fused = pq_fused && chain_on(c, kChainPqBody) && H == 12 && g.dyn_heads == 8 && (L == 128 || L == 64);
     if (phase == 2) {
         // (front done elsewhere)
-    } else if (chain_on(c, 2) && mc_mlp_supported(L, 32) && (4 * L) % 32 == 0) {
+    } else if (chain_on(c, kChainRowchain) && mc_mlp_supported(L, 32) && (4 * L) % 32 == 0) {
         RowChainArgs p;
         p.split_tokens = c->opt.rowchain_split;
         p.X = c->y2; p.comb_w = c->rb.comb_w; p.W = w.mm.proj_w; p.bias = w.mm.proj_b;
@@ -675,7 +601,7 @@ int layer_rows(mc_ctx* c, int i, float* hs, int step, bool twin, long row0, long
         } else if ((r = mc_launch_rowchain(0, p, s))) return r;
     } else {
         GemmArgs p;
-        gemm_opts(c, p);
+        mc_gemm_opts(c->opt, p);
         p.A = c->y2 + 2 * tok0 * L; p.lda = L; p.comb_w = c->rb.comb_w + 2 * tok0;
         p.W = w.mm.proj_w; p.ldw = L; p.bias = w.mm.proj_b;
         p.C = c->mf + tok0 * 4 * L; p.ldc = 4 * L; p.M = (int)ntok; p.N = 4 * L; p.K = L;
@@ -691,16 +617,16 @@ int layer_rows(mc_ctx* c, int i, float* hs, int step, bool twin, long row0, long
     if (st != s) {
         MC_HIP(hipEventRecord(c->ev_fork, s));
         MC_HIP(hipStreamWaitEvent(st, c->ev_fork, 0));
-        if (chain_on(c, 14) && c->rows <= 1200) sb = st; else stt = st;      // (B <= 3 at 196 frames: -1.5 .. -3 %; B = 4: +1 %)
-        if (c->dbg_delay_us != 0) {        // (tests) hold the side stream (> 0) or the main stream (< 0) behind the fork
-            int r2 = mc_launch_spin((c->dbg_delay_us > 0 ? c->dbg_delay_us : -c->dbg_delay_us) * 100, c->dbg_delay_us > 0 ? st : s);
+        if (chain_on(c, kChainSideBody) && c->rows <= 1200) sb = st; else stt = st;      // (B <= 3 at 196 frames: -1.5 .. -3 %; B = 4: +1 %)
+        if (c->opt.dbg_delay_us != 0) {        // (tests) hold the side stream (> 0) or the main stream (< 0) behind the fork
+            int r2 = mc_launch_spin((c->opt.dbg_delay_us > 0 ? c->opt.dbg_delay_us : -c->opt.dbg_delay_us) * 100, c->opt.dbg_delay_us > 0 ? st : s);
             if (r2 != MC_OK) return r2;
         }
     }
     // ---- dynamic body topology: shared LayerNorm + q/k/v ----
     if (pq_fused || phase == 2) {
         // q/k/v were produced by projqkv_k above
-    } else if (chain_on(c, 2) && mc_mlp_supported(L, 32)) {
+    } else if (chain_on(c, kChainRowchain) && mc_mlp_supported(L, 32)) {
         RowChainArgs q;
         q.split_tokens = c->opt.rowchain_split;
         q.X = c->mf; q.ldx = 4 * L; q.gamma = w.dyn_g; q.beta = w.dyn_b; q.W = w.qkv_w; q.bias = w.qkv_b;
@@ -717,12 +643,12 @@ int layer_rows(mc_ctx* c, int i, float* hs, int step, bool twin, long row0, long
     if (sb != s) MC_HIP(hipEventRecord(c->ev_join, sb));
     if (phase == 1) return MC_OK;
     const int tnb = (int)(nrows / c->T);
-    if (use_half(c) && chain_on(c, 20) && (L == 128 || L == 64) && (long)tnb * H > c->opt.temporal_split) {
+    if (use_half(c) && chain_on(c, kChainTemporalHalf) && (L == 128 || L == 64) && (long)tnb * H > c->opt.temporal_split) {
         // reduced-precision mode: both contractions on the fp16 MFMA (whole-(sample, part) workgroups; the sliced small-batch form stays fp32)
         if ((r = mc_launch_temporal_h(c->mf, tfl, c->mask, c->yt, (int)(row0 / c->T), tnb, c->B, c->T, g.max_text_len, H, L,
-                                      c->prec == MC_PREC_F16X3, stt, twin_flag, chain_on(c, 24)))) return r;
+                                      c->prec == MC_PREC_F16X3, stt, twin_flag, chain_on(c, kChainSkipText)))) return r;
     } else if ((r = mc_launch_temporal(c->mf, tfl, c->mask, c->yt, (int)(row0 / c->T), tnb, c->B, c->T,
-                                       g.max_text_len, H, L, stt, twin_flag, c->opt.temporal_split, chain_on(c, 22), chain_on(c, 24)))) return r;
+                                       g.max_text_len, H, L, stt, twin_flag, c->opt.temporal_split, chain_on(c, kChainTemporalPair), chain_on(c, kChainSkipText)))) return r;
     if (stt != s) MC_HIP(hipEventRecord(c->ev_join, stt));
     if (st != s) MC_HIP(hipStreamWaitEvent(s, c->ev_join, 0));
     return MC_OK;
@@ -738,21 +664,21 @@ int layer_rows_tail(mc_ctx* c, int i, float* hs, int step, bool twin, long row0,
     int r;
     const float* ss0 = c->ss + ((long)(i * 2 + 0) * c->maxS + step) * 2 * D;
     TwinAlias ys_alias;
-    if (twin && chain_on(c, 8) && !c->no_alias) { ys_alias.split_flag = mc_route_split_flag_ptr(c->rb); ys_alias.from = c->rows / 2; }
+    if (twin && chain_on(c, kChainTwinAlias) && !c->no_alias) { ys_alias.split_flag = mc_route_split_flag_ptr(c->rb); ys_alias.from = c->rows / 2; }
     if ((r = film_block(c, hs, c->ys, c->yt, w.ca_ln_g, w.ca_ln_b, ss0, w.ca_out_w, w.ca_out_b, row0, nrows, s, false, ys_alias, &w.h_ca_out, 1, ev_rows))) return r;
     // ---- SFFN (stmogen.py:596-607): 12 part-wise FFNs as grouped GEMMs ----
     const long o = row0 * D;
     int z2_parts = 1;
-    if (chain_on(c, 0) && mc_mlp_supported(L, F)) {
+    if (chain_on(c, kChainMlp) && mc_mlp_supported(L, F)) {
         MlpArgs m;
-        m.dma = chain_on(c, 18) ? 1 : 0;
+        m.dma = chain_on(c, kChainMlpDma) ? 1 : 0;
         m.X = hs + o; m.ldx = D; m.x_gstride = L;
         m.W1 = w.ffn_w1; m.b1 = w.ffn_b1; m.W2t = w.ffn_w2; m.b2 = w.ffn_b2;
         m.Y = c->z2 + o; m.ldy = D; m.y_gstride = L; m.M = (int)nrows; m.L = L; m.hidden = F;
         // hidden split of the part-wise FFNs (partial sums folded into the FiLM row kernel): ways by the load model of
         // mc_launch_gemm_small plus ~2 chunk times of fixed cost per workgroup -- 4 ways up to B = 5 (and at B = 8: 184.5 -> 178.0 ms
         // per 50-step DDIM), 2 at B = 6 and B = 16 (293.7 -> 287.5), none at B = 12 or beyond 8192 rows
-        int S = c->split_sffn;                     // env MC_SPLIT_SFFN at context creation (0: the model below)
+        int S = (int)c->opt.split_sffn;            // (0: the model below)
         if (S <= 0) {
             S = 1;
             if (nrows <= split_rows(c, 1) && nrows == c->rows) {      // (one launch over the whole batch: the partial planes live in the one hbuf -- not in the two-stream schedule)
@@ -771,12 +697,12 @@ int layer_rows_tail(mc_ctx* c, int i, float* hs, int step, bool twin, long row0,
         if (nrows <= split_rows(c, 1) && nrows == c->rows && S > 1 && F / 32 >= S && c->hbuf_floats >= (size_t)S * nrows * D) {     // small batches: see moe_experts
             m.Y = c->hbuf; m.nsplit = S; m.y_sstride = nrows * D;
             if ((r = mc_launch_mlp(MLP_PARTS, m, H, 0, s))) return r;
-            if (chain_on(c, 12)) z2_parts = S;          // the FiLM row kernel adds the partial planes up itself
+            if (chain_on(c, kChainSffnPartials)) z2_parts = S;          // the FiLM row kernel adds the partial planes up itself
             else if ((r = mc_launch_splitk_reduce(c->hbuf, S, nrows, D, nullptr, nullptr, c->z2 + o, s))) return r;
         } else if ((r = mc_launch_mlp(MLP_PARTS, m, H, 0, s))) return r;
     } else {
         GemmArgs f1;
-        gemm_opts(c, f1);
+        mc_gemm_opts(c->opt, f1);
         f1.A = hs + o; f1.lda = D; f1.a_gstride = L;
         f1.W = w.ffn_w1; f1.ldw = L; f1.w_gstride = (long)F * L;
         f1.bias = w.ffn_b1; f1.b_gstride = F; f1.act = ACT_GELU;
@@ -784,7 +710,7 @@ int layer_rows_tail(mc_ctx* c, int i, float* hs, int step, bool twin, long row0,
         f1.M = (int)nrows; f1.N = F; f1.K = L;
         if ((r = mc_launch_gemm(GM_PLAIN, f1, H, 0, s))) return r;
         GemmArgs f2;
-        gemm_opts(c, f2);
+        mc_gemm_opts(c->opt, f2);
         f2.A = c->fh + row0 * H * F; f2.lda = (long)H * F; f2.a_gstride = F;
         f2.W = w.ffn_w2; f2.ldw = F; f2.w_gstride = (long)L * F;
         f2.bias = w.ffn_b2; f2.b_gstride = L;
@@ -873,11 +799,11 @@ int run_layer(mc_ctx* c, int i, float* hs, int step, bool twin_ok, int split, hi
     const LayerW& w = c->lw[i];
     int r;
     // ---- STMA: gate + routing + experts (the only part that couples tokens across the batch) ----
-    const bool fused_gate = chain_on(c, 1) && mc_mlp_supported(L, 32);
+    const bool fused_gate = chain_on(c, kChainGate) && mc_mlp_supported(L, 32);
     // The two CFG halves enter base layer 0 with the same residual stream (the pose encoder output is written to
     // both, stmogen.py:736-740), so gate scores and expert outputs of token i + N/2 equal those of token i:
     // gate and experts run on the first half only, routing still ranks all N tokens ("twin" mode, mc_route.hip).
-    const bool twin = twin_ok && fused_gate && chain_on(c, 2) && chain_on(c, 4) && (c->N % 2 == 0) &&
+    const bool twin = twin_ok && fused_gate && chain_on(c, kChainRowchain) && chain_on(c, kChainTwin) && (c->N % 2 == 0) &&
                       c->rb.tie_xor == 0xFFFFFFFFu;   // (the dedupe relies on a twin ranking right behind its original: stable tie order)
     // Twin layer of the large-batch schedule: gate, experts and the front kernels exist for the FIRST CFG half only (the second one
     // aliases it), so the half is cut into two sample sub-groups that go down the two streams (otherwise one stream idles for the
@@ -885,12 +811,12 @@ int run_layer(mc_ctx* c, int i, float* hs, int step, bool twin_ok, int split, hi
     // mf rows of the whole first half) and continue per CFG half as in every other layer.
     const long half = (long)c->B * c->T;                    // rows of one CFG half (= one sample group of the two-stream schedule)
     const long sub_rows = ((long)c->B / 2) * c->T;          // rows of the first sub-group (whole samples)
-    const bool twin_split = twin && split == 2 && chain_on(c, 6) && chain_on(c, 8) && chain_on(c, 16) && !c->no_alias && sub_rows > 0;
+    const bool twin_split = twin && split == 2 && chain_on(c, kChainGroupExperts) && chain_on(c, kChainTwinAlias) && chain_on(c, kChainTwinSplit) && !c->no_alias && sub_rows > 0;
     if (fused_gate) {
         GateArgs ga;
         ga.X = hs; ga.ldx = L; ga.gamma = w.norm_g; ga.beta = w.norm_b; ga.emb = w.mm.emb; ga.emb_mod = c->T * H;
         ga.Z = c->z; ga.Wp = w.mm.gate_w; ga.bp = w.mm.gate_b; ga.sim_nT = w.mm.sim_nT; ga.logit_scale = w.mm.scale;
-        ga.E = g.num_experts; ga.L = L; ga.small_tokens = c->gate_small_tokens;
+        ga.E = g.num_experts; ga.L = L; ga.small_tokens = c->opt.gate_small;
         ga.idx = c->rb.idx; ga.gate = c->rb.gate; ga.key = c->rb.key; ga.cnt = c->rb.state;
         if (split == 2 && (!twin || twin_split)) {
             if (!c->cnt_clean) MC_HIP(hipMemsetAsync(ga.cnt, 0, sizeof(int) * 32, s));
@@ -914,7 +840,7 @@ int run_layer(mc_ctx* c, int i, float* hs, int step, bool twin_ok, int split, hi
         if ((r = mc_launch_ln_rows(hs, L, 0, w.norm_g, w.norm_b, w.mm.emb, c->T * H, c->z, L, c->N, L, s))) return r;
     }
     // two slot groups when the two sample groups run on two streams: each group's expert MLP joins its own chain
-    const bool grouped = split == 2 && chain_on(c, 6);
+    const bool grouped = split == 2 && chain_on(c, kChainGroupExperts);
     const long gsplit = twin_split ? sub_rows * H : grouped ? half * H : c->N;
     if ((r = run_moe(c, w.mm, c->z, c->N, nullptr, 0, fused_gate, twin, gsplit, s, &w.h_fc1, &w.h_fc2))) return r;   // routing (+ experts if one group)
     if (c->cap_idx) {
@@ -929,7 +855,7 @@ int run_layer(mc_ctx* c, int i, float* hs, int step, bool twin_ok, int split, hi
     // ---- the row-independent rest of the layer ----
     // (measured per shape, same-box A/B: helps the exact-fp32 L = 128 step; the fp16 modes -- whose GEMMs are a small part of the chain -- lose 0.1 - 0.2 ms and the
     //  L = 64 models (M2D) 0.35 ms with it, batch 32 is neutral: applied where it helps)
-    const bool evstag = split == 2 && chain_on(c, 26) && !use_half(c) && L == 128;
+    const bool evstag = split == 2 && chain_on(c, kChainStagger) && !use_half(c) && L == 128;
     if (split) {
         // Large batches: the two CFG halves go down two streams.  Each kernel of the chain fills 4.59 "waves" of
         // workgroups at B=64, so ~8 % of every launch is a tail on a partly idle chip; with two independent chains in
@@ -961,7 +887,7 @@ int run_layer(mc_ctx* c, int i, float* hs, int step, bool twin_ok, int split, hi
                 }
             }
             if ((r = layer_rows(c, i, hs, step, twin, 0, half, s, s))) return r;
-            if (twin && chain_on(c, 8) && !c->no_alias) {
+            if (twin && chain_on(c, kChainTwinAlias) && !c->no_alias) {
                 // twin aliasing: group 1 reads group 0's mf / ys instead of producing its own
                 MC_HIP(hipEventRecord(c->ev_join, s));
                 MC_HIP(hipStreamWaitEvent(c->side, c->ev_join, 0));
@@ -971,8 +897,8 @@ int run_layer(mc_ctx* c, int i, float* hs, int step, bool twin_ok, int split, hi
         for (int k = 0; k < 2; ++k) {
             hipStream_t sk = k ? c->side : s;
             // (tests) hold one sample group's stream: > 0 the second group, < 0 the first
-            if (c->dbg_delay_us != 0 && k == (c->dbg_delay_us > 0 ? 1 : 0) &&
-                (r = mc_launch_spin((c->dbg_delay_us > 0 ? c->dbg_delay_us : -c->dbg_delay_us) * 100, sk))) return r;
+            if (c->opt.dbg_delay_us != 0 && k == (c->opt.dbg_delay_us > 0 ? 1 : 0) &&
+                (r = mc_launch_spin((c->opt.dbg_delay_us > 0 ? c->opt.dbg_delay_us : -c->opt.dbg_delay_us) * 100, sk))) return r;
             if ((r = layer_rows_tail(c, i, hs, step, twin, k * half, half, sk, (evstag && k == 0) ? c->ev_stag : nullptr,
                                      (evstag && k == 1) ? c->ev_stag : nullptr))) return r;
         }
@@ -990,16 +916,100 @@ int run_layer(mc_ctx* c, int i, float* hs, int step, bool twin_ok, int split, hi
 // range; sizes in the one-workgroup regime or beyond the kernel's range need nothing.  Counted at 10 pairs per thread, the larger of
 // the two grids the launch may pick.
 int coop_grid_needed(const mc_ctx* c) {
-    const long small = c->rb.small_pairs >= 0 ? c->rb.small_pairs : -1;
     int nwg = 0;
-    for (long n : {c->N, c->Ntxt}) {
-        const bool one_wg = small >= 0 ? 2 * n <= small : mc_route_is_small(n);
-        if (!one_wg && mc_route_coop_wgs(n) > nwg) nwg = mc_route_coop_wgs(n);
-    }
+    for (long n : {c->N, c->Ntxt})
+        if (!mc_route_is_small(c->opt, n) && mc_route_coop_wgs(n) > nwg) nwg = mc_route_coop_wgs(n);
     return nwg;
 }
 
+// ---- runtime options: one row per option (key, variable, alternative variable read when the first is unset, field, built-in
+// default, validity check: "" = valid, else why not).  The check runs on mc_ctx_set_option and on every environment value; the docs
+// (include/motioncraft_amd.h, NativeContext.set_option) list the same keys and defaults.
+struct OptionDef {
+    const char *key, *env, *env_alt;
+    long McOptions::*field;
+    long dflt;
+    std::string (*check)(long v);
+    int (*hook)(mc_ctx* c, long& v);      // mc_ctx_set_option only, before the store (c->opt still holds the old value); may adjust v
+};
+
+std::string check_chain(long v) {
+    const long bad = v & ~kChainDefault;
+    const int b = bad ? __builtin_ctzl((unsigned long)bad) : 0;
+    return !bad ? "" : "chain bit " + std::to_string(b) + (b < kChainBits ? " is retired (DESIGN.md section 5)" : " is not defined");
+}
+std::string check_tune(long v) {
+    const long bad = v & ~(long)kTuneBits;      // (v < 0: the sign bits)
+    return !bad ? "" : v < 0 ? "gemm_tune: a bit mask (>= 0)" : "gemm_tune bit " + std::to_string(__builtin_ctzl(bad)) + " is not defined";
+}
+int chain_hook(mc_ctx* c, long& v) {       // bit 0 (the fused expert MLP) decides whether hbuf is free split-K scratch
+    const int L = c->m->cfg.latent_dim;
+    c->hbuf_floats = ((v >> kChainMlp) & 1) && mc_mlp_supported(L, 4 * L) ? c->hbuf_cap : 0;
+    return MC_OK;
+}
+int route_coop_hook(mc_ctx* c, long& v) {      // off: give the reservation back; on: only if the grid can be reserved now
+    if (!v) {
+        if (c->coop_reserved) { mc_route_coop_release(c->device, c->coop_reserved); c->coop_reserved = 0; }
+    } else if (!c->opt.route_coop) {
+        const int nwg = coop_grid_needed(c);       // 0: no routing call of this context is in route_coop_k's size range (nothing to switch on)
+        MC_REQUIRE(nwg == 0 || mc_route_coop_reserve(c->device, nwg), "route_coop: the cooperative routing grid cannot be reserved on this device");
+        c->coop_reserved = nwg;
+        v = nwg > 0;
+    }
+    return MC_OK;
+}
+
+const OptionDef kOptions[] = {
+    {"chain", "MC_CHAIN", nullptr, &McOptions::chain, kChainDefault, check_chain, chain_hook},      // ChainBit mask (mc_options.h)
+    // plain GEMMs of up to this many rows take the small-M kernels (round 4: 6400 -> 5600, measured per batch: at 6272 rows -- a sample
+    // group of 32 x 196 frames -- gemm_wp_k / gemm_tail_k win, B=32 step 10.21 -> 10.03 ms; at 4704 rows (B=24) the small kernels, 7.85 vs 7.91)
+    {"small_gemm_rows", "MC_SMALL_GEMM_ROWS", nullptr, &McOptions::small_gemm_rows, 5600},
+    {"split_rows_expert", "MC_SPLIT_ROWS_EXPERT", nullptr, &McOptions::split_rows_expert, 2048},   // residual rows up to which the fused expert MLP
+    {"split_rows_sffn", "MC_SPLIT_ROWS_SFFN", nullptr, &McOptions::split_rows_sffn, 8192},         // ... and the SFFN split their hidden dimension
+    {"temporal_split", "MC_TEMPORAL_SPLIT", nullptr, &McOptions::temporal_split, 96},      // (sample, part) workgroups up to which temporal_k slices its columns
+    {"big_tokens", "MC_BIG_TOKENS", nullptr, &McOptions::big_tokens, 65536},               // above this many motion tokens: the large-batch schedule
+    {"rowchain_split", "MC_ROWCHAIN_SPLIT", nullptr, &McOptions::rowchain_split, 20480},   // tokens up to which rowchain_k slices its chunks over blockIdx.y
+    {"gemm_tune", "MC_GEMM_TUNE", nullptr, &McOptions::gemm_tune, kTuneDefault, check_tune},       // kTune* bits (mc_gemm.h)
+    {"small_tile_n", "MC_SMALL_TILE_N", nullptr, &McOptions::small_tile_n, 0,                      // small-M tile width; 0: the load model's per launch
+     [](long v) -> std::string { return v == 0 || v == 48 || v == 64 || v == 96 ? "" : "small_tile_n: 0 (per-launch choice), 48, 64 or 96"; }},
+    {"gemm_wp_grid", "MC_GEMM_WP_GRID", nullptr, &McOptions::gemm_wp_grid, 512},           // workgroups of the persistent gemm_wp_k; <= 0: one per tile
+    {"half_min_rows", "MC_HALF_MIN_ROWS", nullptr, &McOptions::half_min_rows, 512},        // reduced precision: the fp32 kernels up to this many rows (use_half)
+    {"gate_small", "MC_GATE_SMALL", nullptr, &McOptions::gate_small, 12000},               // up to this many tokens the gate runs as gate_small_k
+    {"split_expert", "MC_SPLIT_EXPERT", nullptr, &McOptions::split_expert, 0},             // hidden split of the small-batch expert MLP (0: load model)
+    {"split_sffn", "MC_SPLIT_SFFN", nullptr, &McOptions::split_sffn, 0},                   // ... of the SFFN (0: load model)
+    {"route_reg", "MC_ROUTE_REG", nullptr, &McOptions::route_reg, 1},                      // 0: the L2-streaming one-workgroup routing kernel at every size
+    {"route_coop", "MC_ROUTE_COOP", nullptr, &McOptions::route_coop, 1, nullptr, route_coop_hook},       // 0: the routing launch sequence, not route_coop_k
+    // up to this many (token, choice) pairs the routing is one workgroup; those kernels assume token indices < 2^16.  Default = what fits
+    // the register kernels (beyond: route_coop_k; B=3: 97.5 -> 90.4 ms vs the streaming form).  The tests set MC_ROUTE_SMALL_CTX
+    {"route_small", "MC_ROUTE_SMALL_CTX", "MC_ROUTE_SMALL", &McOptions::route_small, 20480,
+     [](long v) -> std::string { return v >= 0 && v <= 131072 ? "" : "route_small: 0 .. 131072 pairs (the one-workgroup kernels hold at most 131072)"; }},
+    {"route_per", nullptr, nullptr, &McOptions::route_per, 0,                              // route_coop_k pairs per thread (0: 10 up to 256 workgroups, 16 beyond)
+     [](long v) -> std::string { return v == 0 || v == 10 || v == 16 ? "" : "route_per: 0 (default), 10 or 16"; }},
+    {"dbg_delay_us", nullptr, nullptr, &McOptions::dbg_delay_us, 0,                        // tests: hold the second (> 0) or first (< 0) group's stream
+     [](long v) -> std::string { return v >= -100000 && v <= 100000 ? "" : "dbg_delay_us: -100000 .. 100000"; }},      // in front of every layer tail
+};
+
+// the built-in defaults, overridden by the environment; an invalid value is an error naming the variable
+int seed_options(McOptions& o) {
+    for (const OptionDef& d : kOptions) {
+        const char *var = nullptr, *e = nullptr;
+        for (const char* v : {d.env, d.env_alt})
+            if (v && !e && (e = getenv(v))) var = v;
+        const std::string why = e && d.check ? d.check(atol(e)) : "";
+        MC_REQUIRE(why.empty(), "%s=%s: %s", var, e, why.c_str());
+        o.*d.field = e ? atol(e) : d.dflt;
+    }
+    return MC_OK;
+}
+
 }  // namespace
+
+const McOptions* mc_process_options() {
+    static McOptions o;
+    static const std::string err = seed_options(o) == MC_OK ? "" : mc_last_error();
+    if (!err.empty()) mc_set_error("%s", err.c_str());
+    return err.empty() ? &o : nullptr;
+}
 
 extern "C" {
 
@@ -1076,14 +1086,7 @@ int mc_ctx_create(mc_model* m, int32_t batch, int32_t frames, int32_t max_steps,
     MC_REQUIRE(max_steps >= 1, "max_steps < 1");
     const mc_model_config& g = m->cfg;
     mc_ctx* c = new mc_ctx();
-    if (int r = check_chain(c->opt.chain)) { mc_ctx_destroy(c); return r; }      // (MC_CHAIN)
-    if (const char* e = getenv("MC_HALF_MIN_ROWS")) c->half_min_rows = atol(e);      // (the tests lift it to run the fp16 kernels at their small sizes)
-    if (const char* e = getenv("MC_GATE_SMALL")) c->gate_small_tokens = atol(e);
-    if (const char* e = getenv("MC_SPLIT_EXPERT")) c->split_expert = atoi(e);
-    if (const char* e = getenv("MC_SPLIT_SFFN")) c->split_sffn = atoi(e);
-    if (const char* e = getenv("MC_ROUTE_REG")) c->rb.reg_kernel = atoi(e) != 0;
-    if (const char* e = getenv("MC_ROUTE_COOP")) c->rb.coop = atoi(e) != 0;
-    if (const char* e = getenv("MC_ROUTE_SMALL_CTX")) c->rb.small_pairs = atol(e);
+    if (int r = seed_options(c->opt)) { mc_ctx_destroy(c); return r; }
     c->m = m;
     c->B = batch;
     c->T = frames;
@@ -1117,7 +1120,7 @@ int mc_ctx_create(mc_model* m, int32_t batch, int32_t frames, int32_t max_steps,
     WS(c->proj, Nmax * 256);
     WS(c->hbuf, hsz);
     c->hbuf_cap = hsz;
-    if (chain_on(c, 0) && mc_mlp_supported(L, 4 * L)) c->hbuf_floats = hsz;   // (the text MoE only touches hbuf in set_condition)
+    if (chain_on(c, kChainMlp) && mc_mlp_supported(L, 4 * L)) c->hbuf_floats = hsz;   // (the text MoE only touches hbuf in set_condition)
     WS(c->y2, 2 * zsz);
     WS(c->mf, (c->N + 128) * 4 * L);        // + 128 padding rows: projqkv_k stores unconditionally (invalid lanes land there)
     WS(c->qkv, (c->N + 128) * 3 * L);
@@ -1160,10 +1163,10 @@ int mc_ctx_create(mc_model* m, int32_t batch, int32_t frames, int32_t max_steps,
     // text MoE (mc_ctx_set_condition) Ntxt -- either may be the one inside route_coop_k's size range.  Nothing to reserve (both in
     // the one-workgroup regime or beyond the kernel's range) or no room -> coop off for the context, so no unreserved grid can launch.
     MC_HIP(hipGetDevice(&c->device));
-    if (c->rb.coop) {
+    if (c->opt.route_coop) {
         const int nwg = coop_grid_needed(c);
         if (nwg > 0 && mc_route_coop_reserve(c->device, nwg)) c->coop_reserved = nwg;
-        else c->rb.coop = false;
+        else c->opt.route_coop = 0;
     }
 #undef WS
     *out = c;
@@ -1206,7 +1209,7 @@ int mc_ctx_check(mc_ctx* c, void* stream) {
 
 int mc_ctx_effective_precision(const mc_ctx* c) { return c ? (use_half(c) ? c->prec : MC_PREC_F32) : MC_PREC_F32; }
 
-int mc_ctx_uses_coop_routing(const mc_ctx* c) { return c && c->rb.coop && c->coop_reserved > 0 ? 1 : 0; }
+int mc_ctx_uses_coop_routing(const mc_ctx* c) { return c && c->opt.route_coop && c->coop_reserved > 0 ? 1 : 0; }
 
 static void prof_clear(mc_ctx* c) {
     for (auto& p : c->prof) { if (p.e0) (void)hipEventDestroy(p.e0); if (p.e1) (void)hipEventDestroy(p.e1); }
@@ -1261,49 +1264,22 @@ int mc_ctx_set_precision(mc_ctx* c, int32_t precision) {
     return MC_OK;
 }
 
-// Per-context kernel-selection switches (the MC_* environment variables only seed the defaults of contexts created later).
+// Per-context kernel-selection switches (the MC_* environment variables only seed the defaults of contexts created later): kOptions.
 int mc_ctx_set_option(mc_ctx* c, const char* key, int64_t value) {
     MC_REQUIRE(c && key, "null argument");
     MC_REQUIRE(!c->graph_exec, "mc_ctx_set_option: a captured graph holds the old kernel selection (mc_ctx_graph_release first)");
-    const std::string k(key);
-    McOptions& o = c->opt;
-    if (k == "chain") {
-        if (int r = check_chain((int)value)) return r;
-        o.chain = (int)value;
-        c->hbuf_floats = (chain_on(c, 0) && mc_mlp_supported(c->m->cfg.latent_dim, 4 * c->m->cfg.latent_dim)) ? c->hbuf_cap : 0;
-    } else if (k == "big_tokens") o.big_tokens = value;
-    else if (k == "small_gemm_rows") o.small_gemm_rows = value;
-    else if (k == "split_rows_expert") o.split_rows_expert = value;
-    else if (k == "split_rows_sffn") o.split_rows_sffn = value;
-    else if (k == "temporal_split") o.temporal_split = value;
-    else if (k == "rowchain_split") o.rowchain_split = value;
-    else if (k == "gemm_tune") o.gemm_tune = (int)value;
-    else if (k == "small_tile_n") o.small_tile_n = (int)value;
-    else if (k == "gemm_wp_grid") o.gemm_wp_grid = (int)value;
-    else if (k == "half_min_rows") c->half_min_rows = value;
-    else if (k == "dbg_delay_us") { MC_REQUIRE(value >= -100000 && value <= 100000, "dbg_delay_us: -100000 .. 100000"); c->dbg_delay_us = value; }
-    else if (k == "gate_small") c->gate_small_tokens = value;
-    else if (k == "split_expert") c->split_expert = (int)value;
-    else if (k == "split_sffn") c->split_sffn = (int)value;
-    else if (k == "route_reg") c->rb.reg_kernel = value != 0;
-    else if (k == "route_per") { MC_REQUIRE(value == 0 || value == 10 || value == 16, "route_per: 0 (default), 10 or 16"); c->rb.coop_per = (int)value; }
-    else if (k == "route_small") { MC_REQUIRE(value <= 131072, "route_small: the one-workgroup kernels hold at most 131072 pairs"); c->rb.small_pairs = value; }
-    else if (k == "route_coop") {
-        // off: give the reservation back; on: only if the grid can be reserved now
-        if (!value) {
-            if (c->coop_reserved) { mc_route_coop_release(c->device, c->coop_reserved); c->coop_reserved = 0; }
-            c->rb.coop = false;
-        } else if (!c->rb.coop) {
-            const int nwg = coop_grid_needed(c);       // 0: no routing call of this context is in route_coop_k's size range (nothing to switch on)
-            MC_REQUIRE(nwg == 0 || mc_route_coop_reserve(c->device, nwg), "route_coop: the cooperative routing grid cannot be reserved on this device");
-            c->coop_reserved = nwg;
-            c->rb.coop = nwg > 0;
-        }
-    } else {
-        mc_set_error("mc_ctx_set_option: unknown key '%s'", key);
-        return MC_ERR_ARG;
+    for (const OptionDef& d : kOptions) {
+        if (std::string(d.key) != key) continue;
+        long v = (long)value;
+        const std::string why = d.check ? d.check(v) : "";
+        MC_REQUIRE(why.empty(), "%s", why.c_str());
+        if (d.hook)
+            if (int r = d.hook(c, v)) return r;
+        c->opt.*d.field = v;
+        return MC_OK;
     }
-    return MC_OK;
+    mc_set_error("mc_ctx_set_option: unknown key '%s'", key);
+    return MC_ERR_ARG;
 }
 
 int mc_ctx_enable_capture(mc_ctx* c) {
@@ -1378,7 +1354,7 @@ int mc_ctx_set_control(mc_ctx* c, const float* c_feat_dev, int32_t Tc, void* str
     MC_HIP(hipMemsetAsync(c->cenc, 0, sizeof(float) * BT * D, s));           // zero padding for t >= Tc
     {
         GemmArgs e;
-        gemm_opts(c, e);   // per sample: [Tc, Fc] x [D, Fc]^T + bias + sequence_embedding[:Tc]
+        mc_gemm_opts(c->opt, e);   // per sample: [Tc, Fc] x [D, Fc]^T + bias + sequence_embedding[:Tc]
         e.A = c_feat_dev; e.lda = Fc; e.a_gstride = (long)Tc * Fc;
         e.W = c->ctrl_in_w; e.ldw = (Fc + 3) / 4 * 4; e.bias = c->ctrl_in_b;
         e.add = c->seq_emb; e.add_mod = Tc; e.ld_add = D;
@@ -1426,13 +1402,13 @@ static int denoise_impl(mc_ctx* c, const float* x_t, int32_t step, float* out2_d
         if (seed) { if ((r = mc_launch_pad_rows_seeded(const_cast<float*>(x_t), c->xpad, BT, C, c->m->Cp, *seed, s))) return r; }
         else if (!padded && (r = mc_launch_pad_rows(x_t, c->xpad, BT, C, c->m->Cp, s))) return r;
         GemmArgs e;
-        gemm_opts(c, e);
+        mc_gemm_opts(c->opt, e);
         e.A = c->xpad; e.lda = c->m->Cp;
         e.W = c->enc_w; e.ldw = c->m->Cp; e.bias = c->enc_b;
         e.add = c->seq_emb; e.add_mod = c->T; e.ld_add = D;
         e.C = c->h; e.ldc = D; e.dup_rows = BT;
         e.M = (int)BT; e.N = D; e.K = c->m->Cp;
-        if (BT <= small_gemm_rows(c) && D % 64 == 0 && c->m->Cp % 32 == 0) { if ((r = mc_launch_gemm_small(e, s))) return r; }
+        if (BT <= c->opt.small_gemm_rows && D % 64 == 0 && c->m->Cp % 32 == 0) { if ((r = mc_launch_gemm_small(e, s))) return r; }
         else if ((r = mc_launch_gemm(GM_ENC, e, 1, 0, s))) return r;
     }
     const int nl = stop_after >= 0 ? (stop_after < g.num_layers ? stop_after : g.num_layers) : g.num_layers;
@@ -1440,8 +1416,8 @@ static int denoise_impl(mc_ctx* c, const float* x_t, int32_t step, float* out2_d
     const int NC = c->have_ctrl ? g.num_ctrl_layers : 0;
     // large batches: the CFG halves run on two streams (see run_layer); with a control branch the extra whole-batch
     // ops between layers need both halves, so the halves re-join after every layer
-    const bool fused = chain_on(c, 1) && chain_on(c, 2) && mc_mlp_supported(L, 32);
-    const int split = (c->side && chain_on(c, 5) && c->N > c->opt.big_tokens && fused) ? ((NC > 0 && !chain_on(c, 9)) ? 1 : 2) : 0;
+    const bool fused = chain_on(c, kChainGate) && chain_on(c, kChainRowchain) && mc_mlp_supported(L, 32);
+    const int split = (c->side && chain_on(c, kChainTwoStreams) && c->N > c->opt.big_tokens && fused) ? ((NC > 0 && !chain_on(c, kChainCtrlGroups)) ? 1 : 2) : 0;
     // row-wise op between layers, on the stream of the sample group that owns the rows (one launch when not split)
     auto by_group = [&](auto&& fn) -> int {
         if (split != 2) return fn(0L, c->rows, s);
@@ -1492,7 +1468,7 @@ static int denoise_combined(mc_ctx* c, const float* x_t, int32_t step, const mc_
     const mc_model_config& g = c->m->cfg;
     // ... and so is the Linear of the very last StylizationBlock (h += a W^T + b): it, too, runs once on the combined
     // rows  h_c = comb(h) + comb(a) W^T + b  instead of on both halves.
-    const bool defer = chain_on(c, 7);
+    const bool defer = chain_on(c, kChainDeferTail);
     c->defer_last_gemm = defer;
     int r = denoise_impl(c, x_t, step, nullptr, g.num_layers, stream, seed);   // all layers (minus that GEMM), no decoder
     c->defer_last_gemm = false;
@@ -1506,7 +1482,7 @@ static int denoise_combined(mc_ctx* c, const float* x_t, int32_t step, const mc_
         if (c->graph_mode) return mc_launch_cfg_combine_tab(x, y, c->gcoefs, c->gstep, out, BT * D, s);
         return mc_launch_axpby(x, y, k->text_coef, k->none_coef, out, BT * D, s);
     };
-    if (defer && c->dec_cat_w && chain_on(c, 11) && chain_on(c, 21) && BT > c->opt.small_gemm_rows && D % 32 == 0) {
+    if (defer && c->dec_cat_w && chain_on(c, kChainTailGrouped) && chain_on(c, kChainTailOnePass) && BT > c->opt.small_gemm_rows && D % 32 == 0) {
         // large batches: CFG combination, both K groups and the biases in ONE GEMM pass (gemm_tail_k): no axpby_pair_k, no partial outputs
         TailArgs t;
         t.H = c->h; t.Af = deferred_a(c); t.half = BT * D; t.lda = D;
@@ -1519,26 +1495,26 @@ static int denoise_combined(mc_ctx* c, const float* x_t, int32_t step, const mc_
             t.coef_stride = sizeof(SamplerCoefs) / sizeof(float);
             t.step_ptr = c->gstep;
         }
-        t.tune = options_of(c).gemm_tune;
+        t.tune = (int)c->opt.gemm_tune;
         t.C2 = c->out2 + BT * C;               // (out2 holds [2 B T][C]: room for one partial product per K group)
         if ((r = mc_launch_gemm_tail(t, s))) return r;
         *x0a = c->out2;
         if (mc_gemm_tail_two_outputs(t)) *x0b = t.C2;      // gemm_tail2_k: x0 = C + C2, added by the sampler-update kernel
         return MC_OK;
     }
-    if (defer && c->dec_cat_w && chain_on(c, 11)) {
+    if (defer && c->dec_cat_w && chain_on(c, kChainTailGrouped)) {
         // h_c and a_c in one launch
         if ((r = mc_launch_axpby_pair(c->h, c->h + BT * D, c->z2, deferred_a(c), deferred_a(c) + BT * D, c->z2 + BT * D, k->text_coef, k->none_coef,
                                       c->graph_mode ? c->gcoefs : nullptr, c->graph_mode ? c->gstep : nullptr, BT * D, s))) return r;
     } else if ((r = combine(c->h, c->h + BT * D, c->z2))) return r;     // h_c
     if (defer) {
-        if (c->dec_cat_w && chain_on(c, 11)) {
+        if (c->dec_cat_w && chain_on(c, kChainTailGrouped)) {
             // ... and that Linear composed with the decoder is one [C, D] matrix (folded at pack time):
             //   x0 = [dec(h_c) + Wd b] + [a_c (Wd W)^T]
             // the two skinny products (N = C = 322: 294 tiles each, half a chip) are the two groups of ONE grouped GEMM
             // over (h_c | a_c) x (Wd | Wd W); the sampler kernel adds the two partial outputs
             GemmArgs t;
-            gemm_opts(c, t);
+            mc_gemm_opts(c->opt, t);
             t.A = c->z2; t.lda = D; t.a_gstride = BT * D; t.W = c->dec_cat_w; t.ldw = D; t.w_gstride = (long)C * D;
             t.bias = c->dec_cat_b; t.b_gstride = C; t.C = c->out2; t.ldc = C; t.c_gstride = BT * C;
             t.M = (int)BT; t.N = C; t.K = D;
@@ -1601,7 +1577,7 @@ int mc_sample_loop(mc_ctx* c, float* x, const int32_t* step_indices, const mc_st
     // (chain bit 19: no pad_rows_k launch between the steps; the first step of a loop pads, which also zeroes the pad columns)
     PadOut po;
     po.xpad = c->xpad; po.C = c->m->cfg.input_feats; po.Cp = c->m->Cp;
-    const bool fold_pad = chain_on(c, 19) && c->xpad;
+    const bool fold_pad = chain_on(c, kChainPadX) && c->xpad;
     c->xpad_ready = false;
     for (int k = 0; k < num_steps; ++k) {
         const float *x0a = nullptr, *x0b = nullptr;
@@ -1813,11 +1789,10 @@ int mc_op_gemm_tail(const float* h, const float* a, const float* w, const float*
     TailArgs t;
     t.H = h; t.Af = a; t.half = (long)M * K; t.lda = K; t.W = w; t.ldw = K; t.w_gstride = (long)N * K; t.bias = bias; t.b_gstride = N;
     t.C = cdev; t.ldc = N; t.M = M; t.N = N; t.K = K; t.wc = wc; t.wu = wu;
-    t.tune = options_of(nullptr).gemm_tune;
-    if (variant) {
-        if (t.tune < 0) t.tune = mc_gemm_default_tune();       // MC_GEMM_TUNE, or the built-in default
-        t.tune = variant == 1 ? (t.tune & ~1024) : (t.tune | 1024);
-    }
+    const McOptions* o = mc_process_options();
+    if (!o) return MC_ERR_ARG;
+    t.tune = (int)o->gemm_tune;
+    if (variant) t.tune = variant == 1 ? (t.tune & ~kTuneTail2) : (t.tune | kTuneTail2);
     t.C2 = c2dev;
     MC_REQUIRE(variant != 2 || c2dev, "gemm_tail variant 2 needs the scratch output c2_dev [M][N]");
     MC_REQUIRE(variant != 2 || mc_gemm_tail_two_outputs(t),

@@ -937,15 +937,10 @@ __global__ __launch_bounds__(SMALL_THREADS) void route_small_stream_k(const int*
 
 }  // namespace
 
-static long route_small_pairs() {
-    static const long v = [] { const char* e = getenv("MC_ROUTE_SMALL"); const long x = e ? atol(e) : 20480L; return x > 131072L ? 131072L : x; }();   // the one-workgroup kernels assume token indices < 2^16; default = what fits the register kernels (beyond: route_coop_k; B=3: 97.5 -> 90.4 ms vs the streaming form)
-    return v;
-}
-
 size_t mc_route_state_ints(int) { return ST_TOTAL; }
-bool mc_route_is_small(long N) { return 2 * N <= route_small_pairs(); }
-bool mc_route_cleans_counts(const RouteBufs& rb, long N) {
-    return 2 * N <= (rb.small_pairs >= 0 ? rb.small_pairs : route_small_pairs()) || (rb.coop && 2 * N <= COOP_MAX_WG * 256 * COOP_PER);
+bool mc_route_is_small(const McOptions& o, long N) { return 2 * N <= o.route_small; }
+bool mc_route_cleans_counts(const McOptions& o, long N) {
+    return mc_route_is_small(o, N) || (o.route_coop && 2 * N <= COOP_MAX_WG * 256 * COOP_PER);
 }
 size_t mc_route_barrier_offset() { return ST_BAR; }
 size_t mc_route_barrier_ints() { return 17 * 32; }
@@ -955,7 +950,7 @@ size_t mc_route_error_offset() { return ST_BAR + 1; }
 // route_coop_k meets at a hand-rolled grid barrier, so ALL its workgroups have to be resident at once.  A context launches at
 // most one such kernel at a time (stream order), so the library reserves a context's workgroups out of what the device can
 // hold -- occupancy query x compute units of the VISIBLE device (a CPX partition reports its own 32 CUs) -- when the context
-// is created, and a context that does not fit runs the launch sequence instead (RouteBufs::coop = false).  Other kernels in
+// is created, and a context that does not fit runs the launch sequence instead (McOptions::route_coop = 0).  Other kernels in
 // flight only delay the barrier (they finish); only barrier kernels the library does not know of (another process on the same
 // GPU) can still starve it, and then the barrier times out into an error flag (grid_sync) instead of hanging.
 #include <atomic>
@@ -1010,25 +1005,25 @@ int mc_launch_gate_finish(const float* proj, const float* sim_n, const float* lo
 // the capacity test still ranks all N tokens (a twin ranks right behind its original: same score, larger index, so
 // "twin kept => original kept"), combine weights are produced for all N, expert slots only for the first half.
 // gsplit: tokens >= gsplit form slot group 1 (own slot ranges and tile map at [max_tiles, 2 max_tiles)); >= N: one group.
-int mc_launch_route(long N, long Nsrc, long gsplit, int E, int capacity, RouteBufs rb, hipStream_t s) {
+int mc_launch_route(long N, long Nsrc, long gsplit, int E, int capacity, RouteBufs rb, const McOptions& o, hipStream_t s) {
     MC_REQUIRE(Nsrc == N || 2 * Nsrc == N, "route: Nsrc=%ld must be N or N/2 (N=%ld)", Nsrc, N);
     MC_REQUIRE(Nsrc == N || rb.tie_xor == 0xFFFFFFFFu, "route: the twin mode needs the stable tie order (a twin must rank right behind its original)");
-    if (2 * N <= (rb.small_pairs >= 0 ? rb.small_pairs : route_small_pairs())) {
+    if (mc_route_is_small(o, N)) {
 #define MC_ROUTE_SMALL(KERNEL)                                                                                                       \
     hipLaunchKernelGGL(KERNEL, dim3(1), dim3(SMALL_THREADS), 0, s, rb.idx, rb.gate, rb.key, N, Nsrc, gsplit, E, capacity,   \
                        (int)(N / Nsrc), rb.comb_w, rb.state, rb.src_row, rb.dst_row, rb.tile_group, rb.tile_row0, rb.tile_nrows,        \
                        rb.max_tiles, rb.tie_xor)
-        if (rb.reg_kernel && 2 * N <= 10L * SMALL_THREADS) MC_ROUTE_SMALL(route_small_k<10>);
-        else if (rb.reg_kernel && 2 * N <= 20L * SMALL_THREADS) MC_ROUTE_SMALL(route_small_k<20>);      // (25 registers spill to scratch: still -4 % per step at B=2 vs the streaming form)
+        if (o.route_reg && 2 * N <= 10L * SMALL_THREADS) MC_ROUTE_SMALL(route_small_k<10>);
+        else if (o.route_reg && 2 * N <= 20L * SMALL_THREADS) MC_ROUTE_SMALL(route_small_k<20>);      // (25 registers spill to scratch: still -4 % per step at B=2 vs the streaming form)
         else MC_ROUTE_SMALL(route_small_stream_k);
 #undef MC_ROUTE_SMALL
         MC_LAUNCH_CHECK();
         return MC_OK;
     }
-    if (rb.coop && 2 * N <= COOP_MAX_WG * 256 * COOP_PER) {
+    if (o.route_coop && 2 * N <= COOP_MAX_WG * 256 * COOP_PER) {
         // pairs per thread: 10 while that is at most one workgroup per CU (<= 256; B=64 at 196 frames: 236 workgroups, 45 us either way --
         // the ~6 grid barriers set the time), 16 beyond (M2D at 160 windows per GPU: 360 -> 225 workgroups, 88 -> 80 us per routing)
-        const int per = rb.coop_per == 10 || rb.coop_per == 16 ? rb.coop_per : (cdiv(2 * N, 256L * COOP_PER) > 256 ? 16 : 10);
+        const int per = o.route_per ? (int)o.route_per : (cdiv(2 * N, 256L * COOP_PER) > 256 ? 16 : 10);
         const int nwg = cdiv(2 * N, 256L * per);              // (<= the PER = 10 count the context reserved)
 #define MC_ROUTE_COOP(P)                                                                                                             \
     hipLaunchKernelGGL(route_coop_k<P>, dim3(nwg), dim3(256), 0, s, rb.idx, rb.gate, rb.key, N, Nsrc, gsplit, E, capacity, (int)(N / Nsrc), \

@@ -128,8 +128,17 @@ class NativeContext:
         self.precision = precision
 
     def set_option(self, key, value):
-        """Kernel-selection switch of THIS context (include/motioncraft_amd.h, mc_ctx_set_option): 'chain' (the retired bits 3, 23, 25
-        and 28 raise), 'big_tokens', 'gemm_tune', 'route_coop', ... -- the MC_* environment variables only seed the defaults."""
+        """Kernel-selection switch of THIS context (mc_ctx_set_option); the MC_* variable of a key only seeds the default of
+        contexts created afterwards.  Key (variable, default):
+        'chain' (MC_CHAIN, 763363319; retired bits 3, 23, 25, 28 and bits >= 30 raise), 'small_gemm_rows' (MC_SMALL_GEMM_ROWS, 5600),
+        'split_rows_expert' (MC_SPLIT_ROWS_EXPERT, 2048), 'split_rows_sffn' (MC_SPLIT_ROWS_SFFN, 8192),
+        'temporal_split' (MC_TEMPORAL_SPLIT, 96), 'big_tokens' (MC_BIG_TOKENS, 65536), 'rowchain_split' (MC_ROWCHAIN_SPLIT, 20480),
+        'gemm_tune' (MC_GEMM_TUNE, 1841; bits 0, 4, 5, 6, 8, 9, 10), 'small_tile_n' (MC_SMALL_TILE_N, 0; 0, 48, 64 or 96),
+        'gemm_wp_grid' (MC_GEMM_WP_GRID, 512; <= 0 one workgroup per tile), 'half_min_rows' (MC_HALF_MIN_ROWS, 512),
+        'gate_small' (MC_GATE_SMALL, 12000), 'split_expert' (MC_SPLIT_EXPERT, 0), 'split_sffn' (MC_SPLIT_SFFN, 0),
+        'route_reg' (MC_ROUTE_REG, 1), 'route_coop' (MC_ROUTE_COOP, 1),
+        'route_small' (MC_ROUTE_SMALL_CTX, else MC_ROUTE_SMALL, 20480; 0 .. 131072), 'route_per' (no variable, 0; 0, 10 or 16),
+        'dbg_delay_us' (no variable, 0; -100000 .. 100000).  An unknown key or an invalid value raises."""
         self._drop_graph()
         _lib.check(self.lib.mc_ctx_set_option(self.handle, str(key).encode(), int(value)), 'mc_ctx_set_option')
 

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 import torch
 
-DEFAULT_CHAIN = 8388599 | (1 << 24) | (1 << 26) | (1 << 27) | (1 << 29)        # McOptions::chain (mc_model.hip): every schedule / fusion bit but the retired 3, 23, 25 and 28
+DEFAULT_CHAIN = 8388599 | (1 << 24) | (1 << 26) | (1 << 27) | (1 << 29)        # kChainDefault (mc_options.h): every schedule / fusion bit but the retired 3, 23, 25 and 28
 
 from helpers import (CTRL, CTRL_COPY, CTRL_FEATS, FULL, HML_FULL, HML_SMALL, KIT_SMALL, SMALL, SMALL_SEED, load,
                      step_noise_from_seed, synth_inputs)
@@ -883,6 +883,12 @@ def test_generic_fallback_path_vs_oracle(chain):
             ctx.set_option('chain', DEFAULT_CHAIN | (1 << b))
     with pytest.raises(RuntimeError):
         ctx.set_option('split_groups', 2)      # the large-batch schedule has exactly two sample groups
+    with pytest.raises(RuntimeError, match='chain bit 30 is not defined'):
+        ctx.set_option('chain', DEFAULT_CHAIN | 1 << 30)
+    with pytest.raises(RuntimeError, match='gemm_tune bit 1 is not defined'):
+        ctx.set_option('gemm_tune', 1841 | 2)
+    with pytest.raises(RuntimeError, match='small_tile_n'):
+        ctx.set_option('small_tile_n', 32)
     ctx.close()
     nm.close()
 
@@ -2421,6 +2427,9 @@ def test_cooperative_routing_kernel_equals_the_launch_sequence(regime, B, monkey
     nm = NativeModel(dims, sd, cfg_scale=dims['scale'], capacity_factor=0.3 if regime == 'tiny_capacity' else 1.5)
     x, xf, mask = synth_inputs(dims, B, 24, seed=6, lengths=([24, 20, 7] * 3)[:B])
     got = {}
+    monkeypatch.setenv('MC_ROUTE_SMALL_CTX', '200000')         # beyond the one-workgroup kernels' range: the context is refused
+    with pytest.raises(RuntimeError, match='MC_ROUTE_SMALL_CTX=200000'):
+        nm.context(B, 24, max_steps=1)
     monkeypatch.setenv('MC_ROUTE_SMALL_CTX', '0')
     for coop in ('0', '1'):
         monkeypatch.setenv('MC_ROUTE_COOP', coop)              # read when the context is created
