@@ -238,7 +238,8 @@ int mc_sample_step_inpaint(mc_ctx* c, const float* x_t_dev, int32_t step_index, 
 /* ---- introspection for tests --------------------------------------------------------- */
 /* named context buffers: "h","z","proj","mf","qkv","ys","yt","a" (fp32 rows; refused while a reduced-precision context keeps fp16
  * planes there),"a_tail" (the deferred last FiLM block's fp32 rows),"z2","out2","emb","ss","tf",
- * "idx","gate","comb_w","key","cap_idx","cap_w" (layer selects tf / ss / cap slices) */
+ * "idx","gate","comb_w","key","cap_idx","cap_w" (layer selects tf / ss / cap slices),
+ * "route_split" (one int: the last routing call's twin-split flag, nonzero if a capacity cut separated a token from its CFG twin) */
 int mc_ctx_get_buffer(mc_ctx* c, const char* name, int32_t layer, void** dev_ptr, int64_t* numel);
 
 /* FLOP ledger for the per-kernel roofline (tools/kernel_roofline.py; off by default): while enabled, every launcher books the useful

@@ -1752,6 +1752,7 @@ int mc_ctx_get_buffer(mc_ctx* c, const char* name, int32_t layer, void** dev_ptr
     else if (n == "cb" && c->cb) { p = c->cb; cnt = c->rows * D; }
     else if (n == "cap_idx" && c->cap_idx) { p = c->cap_idx + (long)layer * 2 * c->N; cnt = 2 * c->N; }
     else if (n == "cap_w" && c->cap_w) { p = c->cap_w + (long)layer * 2 * c->N; cnt = 2 * c->N; }
+    else if (n == "route_split") { p = const_cast<int*>(mc_route_split_flag_ptr(c->rb)); cnt = 1; }
     else { mc_set_error("unknown buffer '%s'", name); return MC_ERR_ARG; }
     *dev_ptr = p;
     *numel = cnt;

@@ -223,6 +223,59 @@ def test_moe_capacity_and_ties():
     assert float((y - yy).abs().max()) < 1e-4
 
 
+def _bpr_scores(regime, N, E, g):
+    if regime == 'random':
+        return torch.softmax(3 * torch.randn(N, E, generator=g), 1)
+    if regime == 'all_tied':                                      # every token has the same score vector
+        return torch.softmax(torch.randn(1, E, generator=g), 1).repeat(N, 1)
+    if regime == 'tied_groups':                                   # tokens drawn from 5 score vectors: ties inside every expert
+        pool = torch.softmax(2 * torch.randn(5, E, generator=g), 1)
+        return pool[torch.randint(0, 5, (N,), generator=g)]
+    assert regime == 'hot_pair'                                   # two experts take ~all first and second choices
+    logits = torch.randn(N, E, generator=g)
+    logits[:, :2] += 6
+    return torch.softmax(logits, 1)
+
+
+@pytest.mark.parametrize('N', [7, 130, 4704, 301056])
+@pytest.mark.parametrize('regime', ['random', 'all_tied', 'tied_groups', 'hot_pair'])
+def test_bpr_keep_equals_the_restated_tutel_drop_decision(regime, N):
+    """tests/helpers.bpr_keep (the exact integer keep reference the GPU routing tests use, from a kernel's own expert ids
+    and importance-key bits) against tutel_restated.extract_critical's `locations < capacity`, under both tie policies:
+    random scores, one score vector for all tokens, a few score vectors shared by many tokens, and two experts that take
+    almost every first and second choice (second choices of an expert whose first choices fill it: limit <= 0)."""
+    from helpers import bpr_keep
+    import time
+    E = 16
+    scores = _bpr_scores(regime, N, E, torch.Generator().manual_seed(N + len(regime)))
+    top = torch.topk(scores, 2, dim=1).indices
+    key = scores.max(1)[0]
+    capacity = TR.capacity_of(N, E, 2, 1.5)
+    dropped = {}
+    for tie in ('stable', 'reverse'):
+        TR.TIE_POLICY = tie
+        try:
+            idx_s, loc_s, _, cap = TR.extract_critical(scores, 2, 1.5)
+        finally:
+            TR.TIE_POLICY = 'stable'
+        assert cap == capacity and torch.equal(torch.stack(idx_s, 1), top)
+        ref = torch.stack([l < cap for l in loc_s], 1).numpy()
+        t0 = time.perf_counter()
+        got = bpr_keep(top, key, E, capacity, tie)
+        dt = time.perf_counter() - t0
+        assert got.dtype == np.bool_ and got.shape == (N, 2)
+        assert np.array_equal(got, ref), (tie, int((got != ref).sum()))
+        assert dt < 0.5, dt
+        dropped[tie] = got
+    if regime == 'hot_pair' and N >= 130:
+        assert (~dropped['stable'][:, 1]).mean() > 0.9 and (~dropped['stable'][:, 0]).mean() > 0.3
+    if regime == 'all_tied' and N >= 130:        # the cut keeps the lowest token indices, or the highest
+        for k in range(2):
+            assert dropped['stable'][:, k].sum() == capacity and dropped['stable'][:capacity, k].all()
+            assert dropped['reverse'][:, k].sum() == capacity and dropped['reverse'][N - capacity:, k].all()
+    assert TR.TIE_POLICY == 'stable'
+
+
 def test_control_branch_against_reference_golden():
     g = load('control_small.npz')
     sd = W.make_state_dict(CTRL, SMALL_SEED, shapes=W.control_param_shapes(CTRL, CTRL_COPY, CTRL_FEATS))
