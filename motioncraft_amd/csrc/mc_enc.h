@@ -3,10 +3,19 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string>
+
+class ParamStore;
 
 struct EncLayer {
     const float *in_w, *in_b, *out_w, *out_b, *l1_w, *l1_b, *l2_w, *l2_b, *n1_g, *n1_b, *n2_g, *n2_b;
 };
+
+// parameter names of one layer: torch nn.TransformerEncoderLayer, CLIP ResidualAttentionBlock, DistilBERT TransformerBlock
+enum EncScheme { ENC_TORCH, ENC_CLIP, ENC_DISTILBERT };
+// points L at the parameters `prefix` + <the scheme's names> of a layer of width d and hidden size ff; DistilBERT's separate
+// q_lin | k_lin | v_lin are stacked into one [3d][d] projection in a derived buffer of the store
+int bind_enc_layer(ParamStore& store, const std::string& prefix, EncScheme scheme, int d, int ff, EncLayer& L);
 
 // C[M][N] = act(A[M][K] W[N][K]^T + bias) + R
 int mc_enc_dense(const float* A, long lda, const float* W, long ldw, const float* bias, const float* R, long ldr, float* C,

@@ -10,8 +10,8 @@
 #include "mc_gemm.h"
 #include "mc_kernels.h"
 #include "mc_enc.h"
+#include "mc_params.h"
 #include "../../include/motioncraft_amd.h"
-#include <map>
 #include <string>
 #include <vector>
 
@@ -58,59 +58,28 @@ struct Tail {                       // mu/logvar tokens + sinusoid table + seqTr
 
 struct mc_evalenc {
     mc_evalenc_config cfg;
-    std::map<std::string, std::pair<float*, int64_t>> params;
-    std::vector<float*> owned;       // buffers packed at finalize
+    ParamStore params{"evaluation encoder"};      // derived: the padded skel_w and DistilBERT's stacked q | k | v
     Tail motion, text;
     const float *skel_w = nullptr, *skel_b = nullptr;        // skel_w zero padded to [d][Cp]
     const float *tok = nullptr, *pos = nullptr, *eln_g = nullptr, *eln_b = nullptr, *proj_w = nullptr, *proj_b = nullptr;
     std::vector<EncLayer> bert;
     int Cp = 0;
     bool finalized = false, has_text = false;
-    float* ws = nullptr;
-    size_t ws_floats = 0;
+    Workspace ws;
 };
 
 namespace {
 
-int getp(mc_evalenc* e, const std::string& name, int64_t numel, const float** out) {
-    auto it = e->params.find(name);
-    if (it == e->params.end()) { mc_set_error("evaluation encoder: missing parameter '%s'", name.c_str()); return MC_ERR_STATE; }
-    if (it->second.second != numel) {
-        mc_set_error("evaluation encoder: parameter '%s' has %ld elements, expected %ld", name.c_str(), (long)it->second.second, (long)numel);
-        return MC_ERR_STATE;
-    }
-    *out = it->second.first;
-    return MC_OK;
-}
-
-int ensure_ws(mc_evalenc* e, size_t floats, hipStream_t s) {
-    if (floats <= e->ws_floats) return MC_OK;
-    if (e->ws) { MC_HIP(hipStreamSynchronize(s)); MC_HIP(hipFree(e->ws)); e->ws = nullptr; e->ws_floats = 0; }
-    MC_HIP(hipMalloc((void**)&e->ws, floats * sizeof(float)));
-    e->ws_floats = floats;
-    return MC_OK;
-}
-
-#define TP(ptr, name, n) if ((r = getp(e, (name), (int64_t)(n), &(ptr)))) return r
-
-int bind_tail(mc_evalenc* e, const std::string& pre, Tail& t) {
-    const mc_evalenc_config& c = e->cfg;
-    const int d = c.latent_dim, ff = c.ff_size;
+int bind_tail(ParamStore& ps, const mc_evalenc_config& c, const std::string& pre, Tail& t) {
+    const int d = c.latent_dim;
     int r;
-    TP(t.mu, pre + "mu_token", d);
-    TP(t.lv, pre + "logvar_token", d);
-    TP(t.pe, pre + "sequence_pos_encoding.pe", (int64_t)c.pe_len * d);
+    if ((r = ps.bind({{&t.mu, pre + "mu_token", d}, {&t.lv, pre + "logvar_token", d},
+                      {&t.pe, pre + "sequence_pos_encoding.pe", (int64_t)c.pe_len * d}})))
+        return r;
     t.layers.assign(c.num_layers, EncLayer());
-    for (int i = 0; i < c.num_layers; ++i) {
-        const std::string p = pre + "seqTransEncoder.layers." + std::to_string(i) + ".";
-        EncLayer& L = t.layers[i];
-        TP(L.in_w, p + "self_attn.in_proj_weight", (int64_t)3 * d * d);  TP(L.in_b, p + "self_attn.in_proj_bias", 3 * d);
-        TP(L.out_w, p + "self_attn.out_proj.weight", (int64_t)d * d);    TP(L.out_b, p + "self_attn.out_proj.bias", d);
-        TP(L.l1_w, p + "linear1.weight", (int64_t)ff * d);               TP(L.l1_b, p + "linear1.bias", ff);
-        TP(L.l2_w, p + "linear2.weight", (int64_t)d * ff);               TP(L.l2_b, p + "linear2.bias", d);
-        TP(L.n1_g, p + "norm1.weight", d);  TP(L.n1_b, p + "norm1.bias", d);
-        TP(L.n2_g, p + "norm2.weight", d);  TP(L.n2_b, p + "norm2.bias", d);
-    }
+    for (int i = 0; i < c.num_layers; ++i)
+        if ((r = bind_enc_layer(ps, pre + "seqTransEncoder.layers." + std::to_string(i) + ".", ENC_TORCH, d, c.ff_size, t.layers[i])))
+            return r;
     return MC_OK;
 }
 
@@ -161,87 +130,58 @@ int mc_evalenc_create(const mc_evalenc_config* cfg, mc_evalenc** out) {
     return MC_OK;
 }
 
-void mc_evalenc_destroy(mc_evalenc* e) {
-    if (!e) return;
-    for (auto& kv : e->params) (void)hipFree(kv.second.first);
-    for (float* p : e->owned) (void)hipFree(p);
-    if (e->ws) (void)hipFree(e->ws);
-    delete e;
-}
+void mc_evalenc_destroy(mc_evalenc* e) { delete e; }
 
 int mc_evalenc_set_param(mc_evalenc* e, const char* name, const float* host, int64_t numel) {
     MC_REQUIRE(e && name && host && numel > 0, "bad argument");
-    float* d = nullptr;
-    MC_HIP(hipMalloc((void**)&d, (size_t)numel * sizeof(float)));
-    MC_HIP(hipMemcpy(d, host, (size_t)numel * sizeof(float), hipMemcpyHostToDevice));
-    auto it = e->params.find(name);
-    if (it != e->params.end()) (void)hipFree(it->second.first);
-    e->params[name] = {d, numel};
-    e->finalized = false;
-    return MC_OK;
+    const int r = e->params.set(name, host, numel);
+    if (r == MC_OK) e->finalized = false;
+    return r;
 }
 
 int mc_evalenc_finalize(mc_evalenc* e) {
     MC_REQUIRE(e, "null encoder");
+    e->finalized = false;
+    ParamStore& ps = e->params;
+    ps.clear_derived();
     const mc_evalenc_config& c = e->cfg;
     const int d = c.latent_dim;
     int r;
-    for (float* p : e->owned) (void)hipFree(p);
-    e->owned.clear();
     const float* w = nullptr;
-    TP(w, "motionencoder.skel_embedding.weight", (int64_t)d * c.nfeats);
-    TP(e->skel_b, "motionencoder.skel_embedding.bias", d);
+    if ((r = ps.bind({{&w, "motionencoder.skel_embedding.weight", (int64_t)d * c.nfeats},
+                      {&e->skel_b, "motionencoder.skel_embedding.bias", d}})))
+        return r;
     if (e->Cp != c.nfeats) {                                   // GEMM rows are read 16 bytes at a time
         float* wp = nullptr;
-        MC_HIP(hipMalloc((void**)&wp, (size_t)d * e->Cp * sizeof(float)));
-        e->owned.push_back(wp);
+        if ((r = ps.derived((size_t)d * e->Cp, &wp))) return r;
         MC_HIP(hipMemset(wp, 0, (size_t)d * e->Cp * sizeof(float)));
         MC_HIP(hipMemcpy2D(wp, (size_t)e->Cp * sizeof(float), w, (size_t)c.nfeats * sizeof(float), (size_t)c.nfeats * sizeof(float), d,
                            hipMemcpyDeviceToDevice));
         w = wp;
     }
     e->skel_w = w;
-    if ((r = bind_tail(e, "motionencoder.", e->motion))) return r;
+    if ((r = bind_tail(ps, c, "motionencoder.", e->motion))) return r;
     e->has_text = false;
-    if (c.bert_dim > 0 && e->params.count("textencoder.projection.1.weight")) {
-        const int bw = c.bert_dim, bf = c.bert_ff;
+    if (c.bert_dim > 0 && ps.has("textencoder.projection.1.weight")) {
+        const int bw = c.bert_dim;
         const std::string t = "textencoder.text_model.";
-        TP(e->tok, t + "embeddings.word_embeddings.weight", (int64_t)c.bert_vocab * bw);
-        TP(e->pos, t + "embeddings.position_embeddings.weight", (int64_t)c.bert_max_pos * bw);
-        TP(e->eln_g, t + "embeddings.LayerNorm.weight", bw);
-        TP(e->eln_b, t + "embeddings.LayerNorm.bias", bw);
+        if ((r = ps.bind({{&e->tok, t + "embeddings.word_embeddings.weight", (int64_t)c.bert_vocab * bw},
+                          {&e->pos, t + "embeddings.position_embeddings.weight", (int64_t)c.bert_max_pos * bw},
+                          {&e->eln_g, t + "embeddings.LayerNorm.weight", bw}, {&e->eln_b, t + "embeddings.LayerNorm.bias", bw}})))
+            return r;
         e->bert.assign(c.bert_layers, EncLayer());
-        for (int i = 0; i < c.bert_layers; ++i) {
-            const std::string p = t + "transformer.layer." + std::to_string(i) + ".";
-            EncLayer& L = e->bert[i];
-            // q_lin | k_lin | v_lin stacked into one [3w][w] projection (the order mc_enc_layer's attention expects)
-            float *pw = nullptr, *pb = nullptr;
-            MC_HIP(hipMalloc((void**)&pw, (size_t)3 * bw * bw * sizeof(float)));  e->owned.push_back(pw);
-            MC_HIP(hipMalloc((void**)&pb, (size_t)3 * bw * sizeof(float)));       e->owned.push_back(pb);
-            const char* names[3] = {"q_lin", "k_lin", "v_lin"};
-            for (int j = 0; j < 3; ++j) {
-                const float *sw = nullptr, *sb = nullptr;
-                TP(sw, p + "attention." + names[j] + ".weight", (int64_t)bw * bw);
-                TP(sb, p + "attention." + names[j] + ".bias", bw);
-                MC_HIP(hipMemcpy(pw + (size_t)j * bw * bw, sw, (size_t)bw * bw * sizeof(float), hipMemcpyDeviceToDevice));
-                MC_HIP(hipMemcpy(pb + (size_t)j * bw, sb, (size_t)bw * sizeof(float), hipMemcpyDeviceToDevice));
-            }
-            L.in_w = pw; L.in_b = pb;
-            TP(L.out_w, p + "attention.out_lin.weight", (int64_t)bw * bw);  TP(L.out_b, p + "attention.out_lin.bias", bw);
-            TP(L.n1_g, p + "sa_layer_norm.weight", bw);                     TP(L.n1_b, p + "sa_layer_norm.bias", bw);
-            TP(L.l1_w, p + "ffn.lin1.weight", (int64_t)bf * bw);            TP(L.l1_b, p + "ffn.lin1.bias", bf);
-            TP(L.l2_w, p + "ffn.lin2.weight", (int64_t)bw * bf);            TP(L.l2_b, p + "ffn.lin2.bias", bw);
-            TP(L.n2_g, p + "output_layer_norm.weight", bw);                 TP(L.n2_b, p + "output_layer_norm.bias", bw);
-        }
-        TP(e->proj_w, "textencoder.projection.1.weight", (int64_t)d * bw);
-        TP(e->proj_b, "textencoder.projection.1.bias", d);
-        if ((r = bind_tail(e, "textencoder.", e->text))) return r;
+        for (int i = 0; i < c.bert_layers; ++i)
+            if ((r = bind_enc_layer(ps, t + "transformer.layer." + std::to_string(i) + ".", ENC_DISTILBERT, bw, c.bert_ff, e->bert[i])))
+                return r;
+        if ((r = ps.bind({{&e->proj_w, "textencoder.projection.1.weight", (int64_t)d * bw},
+                          {&e->proj_b, "textencoder.projection.1.bias", d}})) ||
+            (r = bind_tail(ps, c, "textencoder.", e->text)))
+            return r;
         e->has_text = true;
     }
     e->finalized = true;
     return MC_OK;
 }
-#undef TP
 
 int mc_evalenc_encode_motion(mc_evalenc* e, const float* motion, const int32_t* lengths, int32_t B, int32_t T, float* mu_out,
                              void* stream) {
@@ -254,8 +194,8 @@ int mc_evalenc_encode_motion(mc_evalenc* e, const float* motion, const int32_t* 
     const long rows = (long)B * T;
     int r;
     const size_t head = (size_t)rows * (Cp + d) + 64;
-    if ((r = ensure_ws(e, head + tail_floats(c, B, T), s))) return r;
-    float* pad = e->ws;
+    if ((r = e->ws.ensure(head + tail_floats(c, B, T), s))) return r;
+    float* pad = e->ws.buf;
     float* emb = pad + rows * Cp;
     const float* A = motion;
     if (Cp != c.nfeats) {
@@ -267,7 +207,7 @@ int mc_evalenc_encode_motion(mc_evalenc* e, const float* motion, const int32_t* 
     g.M = (int)rows; g.N = d; g.K = Cp; g.act = ACT_NONE;
     g.add = e->motion.pe + 2 * d; g.add_mod = T; g.ld_add = d;
     if ((r = mc_launch_gemm(GM_ENC, g, 1, 0, s))) return r;
-    return run_tail(e, e->motion, emb, lengths, nullptr, B, T, e->ws + head, mu_out, s);
+    return run_tail(e, e->motion, emb, lengths, nullptr, B, T, e->ws.buf + head, mu_out, s);
 }
 
 int mc_evalenc_encode_text(mc_evalenc* e, const int32_t* ids, const uint8_t* mask, int32_t B, int32_t S, float* mu_out, void* stream) {
@@ -281,8 +221,8 @@ int mc_evalenc_encode_text(mc_evalenc* e, const int32_t* ids, const uint8_t* mas
     const long rows = (long)B * S;
     int r;
     const size_t head = (size_t)rows * (w * 6 + bf + d) + 64;
-    if ((r = ensure_ws(e, head + tail_floats(c, B, S), s))) return r;
-    float* x = e->ws;
+    if ((r = e->ws.ensure(head + tail_floats(c, B, S), s))) return r;
+    float* x = e->ws.buf;
     float* qkv = x + rows * w;
     float* att = qkv + rows * 3 * w;
     float* y = att + rows * w;
@@ -300,7 +240,7 @@ int mc_evalenc_encode_text(mc_evalenc* e, const int32_t* ids, const uint8_t* mas
     g.M = (int)rows; g.N = d; g.K = w; g.act = ACT_NONE;
     g.add = e->text.pe + 2 * d; g.add_mod = S; g.ld_add = d;
     if ((r = mc_launch_gemm(GM_ENC, g, 1, 0, s))) return r;
-    return run_tail(e, e->text, emb, nullptr, mask, B, S, e->ws + head, mu_out, s);
+    return run_tail(e, e->text, emb, nullptr, mask, B, S, e->ws.buf + head, mu_out, s);
 }
 
 }  // extern "C"

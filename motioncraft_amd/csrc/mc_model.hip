@@ -21,6 +21,7 @@
 #include "mc_chain.h"
 #include "mc_half.h"
 #include "mc_options.h"
+#include "mc_params.h"
 
 struct HalfW {              // fp16 hi / lo planes of one weight (mc_half.h); lo directly behind hi in one allocation
     mc_half* hi = nullptr;
@@ -29,7 +30,7 @@ struct HalfW {              // fp16 hi / lo planes of one weight (mc_half.h); lo
 
 struct mc_model {
     mc_model_config cfg;
-    std::map<std::string, std::pair<float*, int64_t>> params;
+    ParamStore params{""};
     std::map<std::string, HalfW> half;     // built on the first mc_ctx_set_precision(.., MC_PREC_F16*) (shared by all contexts)
     std::mutex half_mu;                    // guards `half` (filled from per-context calls)
     size_t half_bytes = 0;                 // device bytes of the fp16 hi / lo planes (reported by mc_ctx_workspace_bytes of a reduced-precision context)
@@ -144,109 +145,65 @@ int ws_alloc(mc_ctx* c, T** p, size_t n) {
     return MC_OK;
 }
 
-int get_param(mc_model* m, const std::string& name, int64_t numel, const float** out) {
-    auto it = m->params.find(name);
-    if (it == m->params.end()) {
-        mc_set_error("missing parameter '%s'", name.c_str());
-        return MC_ERR_STATE;
-    }
-    if (it->second.second != numel) {
-        mc_set_error("parameter '%s' has %ld elements, expected %ld", name.c_str(), (long)it->second.second, (long)numel);
-        return MC_ERR_STATE;
-    }
-    *out = it->second.first;
-    return MC_OK;
-}
-
-#define GP(ptr, name, numel)                                         \
-    do {                                                             \
-        int _r = get_param(m, (name), (int64_t)(numel), &(ptr));     \
-        if (_r != MC_OK) return _r;                                  \
-    } while (0)
-
-int bind_moe(mc_model* m, const std::string& pre, int din, int dout, int seq_rows, MoeW* w) {
-    const int E = m->cfg.num_experts;
+int bind_moe(const mc_model* m, const std::string& pre, int din, int dout, int seq_rows, MoeW* w) {
+    const int64_t E = m->cfg.num_experts;
     w->din = din;
     w->dout = dout;
-    GP(w->emb, pre + "emb", (int64_t)seq_rows * din);
-    GP(w->gate_w, pre + "gate_w", 256 * din);
-    GP(w->gate_b, pre + "gate_b", 256);
-    GP(w->sim_n, pre + "sim_n", 256 * E);
-    GP(w->sim_nT, pre + "sim_nT", 32 * 256);
-    GP(w->scale, pre + "scale", 1);
-    GP(w->fc1_w, pre + "fc1_w", (int64_t)E * 4 * din * din);
-    GP(w->fc1_b, pre + "fc1_b", (int64_t)E * 4 * din);
-    GP(w->fc2_wt, pre + "fc2_wt", (int64_t)E * din * 4 * din);
-    GP(w->fc2_b, pre + "fc2_b", (int64_t)E * din);
-    GP(w->proj_w, pre + "proj_w", (int64_t)dout * din);
-    GP(w->proj_b, pre + "proj_b", dout);
-    return MC_OK;
+    return m->params.bind({{&w->emb, pre + "emb", (int64_t)seq_rows * din},       {&w->gate_w, pre + "gate_w", 256 * din},
+                           {&w->gate_b, pre + "gate_b", 256},                      {&w->sim_n, pre + "sim_n", 256 * E},
+                           {&w->sim_nT, pre + "sim_nT", 32 * 256},                 {&w->scale, pre + "scale", 1},
+                           {&w->fc1_w, pre + "fc1_w", E * 4 * din * din},          {&w->fc1_b, pre + "fc1_b", E * 4 * din},
+                           {&w->fc2_wt, pre + "fc2_wt", E * din * 4 * din},        {&w->fc2_b, pre + "fc2_b", E * din},
+                           {&w->proj_w, pre + "proj_w", (int64_t)dout * din},      {&w->proj_b, pre + "proj_b", dout}});
 }
 
 int bind_weights(mc_ctx* c) {
-    mc_model* m = c->m;
+    const mc_model* m = c->m;
+    const ParamStore& ps = m->params;
     const mc_model_config& g = m->cfg;
-    const int L = g.latent_dim, H = g.num_parts, D = L * H, F = g.ffn_dim, Te = g.time_embed_dim;
-    GP(c->enc_w, "enc.w", (int64_t)D * m->Cp);
-    GP(c->enc_b, "enc.b", D);
-    GP(c->seq_emb, "seq_emb", (int64_t)g.max_seq_len * D);
-    GP(c->time_w0, "time.w0", (int64_t)Te * D);
-    GP(c->time_b0, "time.b0", Te);
-    GP(c->time_w2, "time.w2", (int64_t)Te * Te);
-    GP(c->time_b2, "time.b2", Te);
-    GP(c->dec_w, "dec.w", (int64_t)g.input_feats * D);
-    GP(c->dec_b, "dec.b", g.input_feats);
-    if (m->params.count("dec.wf") && m->params.count("dec.bf")) {
-        GP(c->dec_wf, "dec.wf", (int64_t)g.input_feats * D);
-        GP(c->dec_bf, "dec.bf", g.input_feats);
+    const int L = g.latent_dim, H = g.num_parts, D = L * H, F = g.ffn_dim, Te = g.time_embed_dim, C = g.input_feats;
+    const int64_t DD = (int64_t)D * D;
+    int r;
+    if ((r = ps.bind({{&c->enc_w, "enc.w", (int64_t)D * m->Cp},                 {&c->enc_b, "enc.b", D},
+                      {&c->seq_emb, "seq_emb", (int64_t)g.max_seq_len * D},
+                      {&c->time_w0, "time.w0", (int64_t)Te * D},                {&c->time_b0, "time.b0", Te},
+                      {&c->time_w2, "time.w2", (int64_t)Te * Te},               {&c->time_b2, "time.b2", Te},
+                      {&c->dec_w, "dec.w", (int64_t)C * D},                     {&c->dec_b, "dec.b", C}})))
+        return r;
+    if (ps.has("dec.wf") && ps.has("dec.bf")) {
+        if ((r = ps.bind({{&c->dec_wf, "dec.wf", (int64_t)C * D}, {&c->dec_bf, "dec.bf", C}}))) return r;
     }
     c->NLA = g.num_layers + g.num_ctrl_layers;
     c->lw.resize(c->NLA);
     if (g.num_ctrl_layers > 0) {
-        GP(c->ctrl_in_w, "ctrl_in.w", (int64_t)D * ((g.ctrl_cond_feats + 3) / 4 * 4));
-        GP(c->ctrl_in_b, "ctrl_in.b", D);
+        const int64_t n = (int64_t)D * ((g.ctrl_cond_feats + 3) / 4 * 4);
+        if ((r = ps.bind({{&c->ctrl_in_w, "ctrl_in.w", n}, {&c->ctrl_in_b, "ctrl_in.b", D}}))) return r;
     }
     for (int i = 0; i < c->NLA; ++i) {
         LayerW& w = c->lw[i];
         const bool is_ctrl = i >= g.num_layers;
         const std::string p = (is_ctrl ? "c" + std::to_string(i - g.num_layers) : "l" + std::to_string(i)) + ".";
         if (is_ctrl) {
-            if (i == g.num_layers) {
-                GP(w.before_w, p + "before_w", (int64_t)D * D);
-                GP(w.before_b, p + "before_b", D);
-            }
-            GP(w.after_w, p + "after_w", (int64_t)D * D);
-            GP(w.after_b, p + "after_b", D);
+            if (i == g.num_layers && (r = ps.bind({{&w.before_w, p + "before_w", DD}, {&w.before_b, p + "before_b", D}}))) return r;
+            if ((r = ps.bind({{&w.after_w, p + "after_w", DD}, {&w.after_b, p + "after_b", D}}))) return r;
         }
-        GP(w.norm_g, p + "norm.g", L);
-        GP(w.norm_b, p + "norm.b", L);
-        GP(w.tnorm_g, p + "text_norm.g", g.text_latent_dim);
-        GP(w.tnorm_b, p + "text_norm.b", g.text_latent_dim);
-        GP(w.wsm, p + "body_wsm", H * H);
-        int r = bind_moe(m, p + "mm.", L, 4 * L, g.max_seq_len * H, &w.mm);
-        if (r != MC_OK) return r;
-        r = bind_moe(m, p + "tm.", g.text_latent_dim, 2 * L, g.max_text_len, &w.tm);
-        if (r != MC_OK) return r;
-        GP(w.dyn_g, p + "dyn.norm.g", L);
-        GP(w.dyn_b, p + "dyn.norm.b", L);
-        GP(w.qkv_w, p + "dyn.qkv_w", 3 * L * L);
-        GP(w.qkv_b, p + "dyn.qkv_b", 3 * L);
-        GP(w.ca_film_w, p + "ca.film_w", (int64_t)2 * D * Te);
-        GP(w.ca_film_b, p + "ca.film_b", 2 * D);
-        GP(w.ca_ln_g, p + "ca.ln_g", D);
-        GP(w.ca_ln_b, p + "ca.ln_b", D);
-        GP(w.ca_out_w, p + "ca.out_w", (int64_t)D * D);
-        GP(w.ca_out_b, p + "ca.out_b", D);
-        GP(w.ffn_w1, p + "ffn.w1", (int64_t)H * F * L);
-        GP(w.ffn_b1, p + "ffn.b1", H * F);
-        GP(w.ffn_w2, p + "ffn.w2", (int64_t)H * L * F);
-        GP(w.ffn_b2, p + "ffn.b2", H * L);
-        GP(w.ffn_film_w, p + "ffn.film_w", (int64_t)2 * D * Te);
-        GP(w.ffn_film_b, p + "ffn.film_b", 2 * D);
-        GP(w.ffn_ln_g, p + "ffn.ln_g", D);
-        GP(w.ffn_ln_b, p + "ffn.ln_b", D);
-        GP(w.ffn_out_w, p + "ffn.out_w", (int64_t)D * D);
-        GP(w.ffn_out_b, p + "ffn.out_b", D);
+        if ((r = ps.bind({{&w.norm_g, p + "norm.g", L},                         {&w.norm_b, p + "norm.b", L},
+                          {&w.tnorm_g, p + "text_norm.g", g.text_latent_dim},   {&w.tnorm_b, p + "text_norm.b", g.text_latent_dim},
+                          {&w.wsm, p + "body_wsm", H * H}})))
+            return r;
+        if ((r = bind_moe(m, p + "mm.", L, 4 * L, g.max_seq_len * H, &w.mm))) return r;
+        if ((r = bind_moe(m, p + "tm.", g.text_latent_dim, 2 * L, g.max_text_len, &w.tm))) return r;
+        if ((r = ps.bind({{&w.dyn_g, p + "dyn.norm.g", L},                      {&w.dyn_b, p + "dyn.norm.b", L},
+                          {&w.qkv_w, p + "dyn.qkv_w", 3 * L * L},               {&w.qkv_b, p + "dyn.qkv_b", 3 * L},
+                          {&w.ca_film_w, p + "ca.film_w", (int64_t)2 * D * Te}, {&w.ca_film_b, p + "ca.film_b", 2 * D},
+                          {&w.ca_ln_g, p + "ca.ln_g", D},                       {&w.ca_ln_b, p + "ca.ln_b", D},
+                          {&w.ca_out_w, p + "ca.out_w", DD},                    {&w.ca_out_b, p + "ca.out_b", D},
+                          {&w.ffn_w1, p + "ffn.w1", (int64_t)H * F * L},        {&w.ffn_b1, p + "ffn.b1", H * F},
+                          {&w.ffn_w2, p + "ffn.w2", (int64_t)H * L * F},        {&w.ffn_b2, p + "ffn.b2", H * L},
+                          {&w.ffn_film_w, p + "ffn.film_w", (int64_t)2 * D * Te}, {&w.ffn_film_b, p + "ffn.film_b", 2 * D},
+                          {&w.ffn_ln_g, p + "ffn.ln_g", D},                     {&w.ffn_ln_b, p + "ffn.ln_b", D},
+                          {&w.ffn_out_w, p + "ffn.out_w", DD},                  {&w.ffn_out_b, p + "ffn.out_b", D}})))
+            return r;
     }
     return MC_OK;
 }
@@ -276,7 +233,7 @@ int half_weight(mc_model* m, const std::string& name, long rows, int K, bool cha
     auto it = m->half.find(name);
     if (it != m->half.end()) { *out = it->second; return MC_OK; }
     const float* src = nullptr;
-    int r = get_param(m, name, (int64_t)rows * K, &src);
+    int r = m->params.get(name, (int64_t)rows * K, &src);
     if (r != MC_OK) return r;
     HalfW h;
     MC_HIP(hipMalloc((void**)&h.hi, sizeof(mc_half) * 2 * (size_t)rows * K));
@@ -1045,28 +1002,17 @@ int mc_model_create(const mc_model_config* cfg, mc_model** out) {
 
 void mc_model_destroy(mc_model* m) {
     if (!m) return;
-    for (auto& kv : m->params) (void)hipFree(kv.second.first);
     for (auto& kv : m->half) (void)hipFree(kv.second.hi);
     delete m;
 }
 
 int mc_model_set_param(mc_model* m, const char* name, const float* host, int64_t numel) {
     MC_REQUIRE(m && name && host && numel > 0, "bad argument");
-    auto it = m->params.find(name);
     // replacing a weight of a finalized model: contexts hold raw pointers into the old allocation and the fp16 planes built from it
     // would go stale -- the model is immutable once contexts can exist (build a new model for new weights).  Checked BEFORE anything
     // is allocated (a rejected call must not leak the new buffer).
-    MC_REQUIRE(it == m->params.end() || !m->finalized, "mc_model_set_param(%s): the model is finalized; weights are immutable from then on", name);
-    float* d = nullptr;
-    MC_HIP(hipMalloc(&d, (size_t)numel * sizeof(float)));
-    if (hipMemcpy(d, host, (size_t)numel * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(d);
-        mc_set_error("mc_model_set_param(%s): host-to-device copy failed", name);
-        return MC_ERR_HIP;
-    }
-    if (it != m->params.end()) (void)hipFree(it->second.first);
-    m->params[name] = std::make_pair(d, numel);
-    return MC_OK;
+    MC_REQUIRE(!m->finalized || !m->params.has(name), "mc_model_set_param(%s): the model is finalized; weights are immutable from then on", name);
+    return m->params.set(name, host, numel);
 }
 
 int mc_model_finalize(mc_model* m) {

@@ -11,8 +11,8 @@
 #include "mc_gemm.h"
 #include "mc_kernels.h"
 #include "mc_enc.h"
+#include "mc_params.h"
 #include "../../include/motioncraft_amd.h"
-#include <map>
 #include <string>
 #include <vector>
 
@@ -74,58 +74,35 @@ int grid_for(long n) { return (int)std::min<long>(cdiv(n, 256), 4096); }
 
 struct mc_t2meval {
     mc_t2meval_config cfg;
-    std::map<std::string, std::pair<float*, int64_t>> params;
-    std::vector<float*> owned;
+    ParamStore params{"t2m evaluator"};           // derived: the heads' GRU weights packed per direction
     const float *c1_w = nullptr, *c1_b = nullptr, *c2_w = nullptr, *c2_b = nullptr, *mo_w = nullptr, *mo_b = nullptr;
     const float *pos_w = nullptr, *pos_b = nullptr;
     Head motion, text;
     int Cp = 0, Pp = 0;
     bool finalized = false, has_text = false;
-    float* ws = nullptr;
-    size_t ws_floats = 0;
+    Workspace ws;
 };
 
 namespace {
 
-int getp(mc_t2meval* e, const std::string& name, int64_t numel, const float** out) {
-    auto it = e->params.find(name);
-    if (it == e->params.end()) { mc_set_error("t2m evaluator: missing parameter '%s'", name.c_str()); return MC_ERR_STATE; }
-    if (it->second.second != numel) {
-        mc_set_error("t2m evaluator: parameter '%s' has %ld elements, expected %ld", name.c_str(), (long)it->second.second, (long)numel);
-        return MC_ERR_STATE;
-    }
-    *out = it->second.first;
-    return MC_OK;
-}
-
-int ensure_ws(mc_t2meval* e, size_t floats, hipStream_t s) {
-    if (floats <= e->ws_floats) return MC_OK;
-    if (e->ws) { MC_HIP(hipStreamSynchronize(s)); MC_HIP(hipFree(e->ws)); e->ws = nullptr; e->ws_floats = 0; }
-    MC_HIP(hipMalloc((void**)&e->ws, floats * sizeof(float)));
-    e->ws_floats = floats;
-    return MC_OK;
-}
-
-#define TP(ptr, name, n) if ((r = getp(e, (name), (int64_t)(n), &(ptr)))) return r
-
-int bind_head(mc_t2meval* e, const std::string& pre, int din, int hid, int dout, Head& h) {
+int bind_head(ParamStore& ps, const std::string& pre, int din, int hid, int dout, Head& h) {
     int r;
     h.din = din; h.hid = hid; h.dout = dout;
-    TP(h.in_w, pre + "input_emb.weight", (int64_t)hid * din);  TP(h.in_b, pre + "input_emb.bias", hid);
-    TP(h.hidden, pre + "hidden", 2 * hid);
-    TP(h.o0_w, pre + "output_net.0.weight", (int64_t)hid * 2 * hid);  TP(h.o0_b, pre + "output_net.0.bias", hid);
-    TP(h.ln_g, pre + "output_net.1.weight", hid);  TP(h.ln_b, pre + "output_net.1.bias", hid);
-    TP(h.o3_w, pre + "output_net.3.weight", (int64_t)dout * hid);  TP(h.o3_b, pre + "output_net.3.bias", dout);
+    if ((r = ps.bind({{&h.in_w, pre + "input_emb.weight", (int64_t)hid * din}, {&h.in_b, pre + "input_emb.bias", hid},
+                      {&h.hidden, pre + "hidden", 2 * hid},
+                      {&h.o0_w, pre + "output_net.0.weight", (int64_t)hid * 2 * hid}, {&h.o0_b, pre + "output_net.0.bias", hid},
+                      {&h.ln_g, pre + "output_net.1.weight", hid}, {&h.ln_b, pre + "output_net.1.bias", hid},
+                      {&h.o3_w, pre + "output_net.3.weight", (int64_t)dout * hid}, {&h.o3_b, pre + "output_net.3.bias", dout}})))
+        return r;
     const size_t wn = (size_t)3 * hid * hid, bn = (size_t)3 * hid;
     float** dst[4] = {&h.wih, &h.whh, &h.bih, &h.bhh};
     const char* base[4] = {"gru.weight_ih_l0", "gru.weight_hh_l0", "gru.bias_ih_l0", "gru.bias_hh_l0"};
     for (int k = 0; k < 4; ++k) {
         const size_t n = k < 2 ? wn : bn;
-        MC_HIP(hipMalloc((void**)dst[k], 2 * n * sizeof(float)));
-        e->owned.push_back(*dst[k]);
+        if ((r = ps.derived(2 * n, dst[k]))) return r;
         for (int d = 0; d < 2; ++d) {
             const float* src = nullptr;
-            TP(src, pre + base[k] + (d ? "_reverse" : ""), (int64_t)n);
+            if ((r = ps.get(pre + base[k] + (d ? "_reverse" : ""), (int64_t)n, &src))) return r;
             MC_HIP(hipMemcpy(*dst[k] + d * n, src, n * sizeof(float), hipMemcpyDeviceToDevice));
         }
     }
@@ -196,13 +173,7 @@ int mc_t2meval_create(const mc_t2meval_config* cfg, mc_t2meval** out) {
     return MC_OK;
 }
 
-void mc_t2meval_destroy(mc_t2meval* e) {
-    if (!e) return;
-    for (auto& kv : e->params) (void)hipFree(kv.second.first);
-    for (float* p : e->owned) (void)hipFree(p);
-    if (e->ws) (void)hipFree(e->ws);
-    delete e;
-}
+void mc_t2meval_destroy(mc_t2meval* e) { delete e; }
 
 int mc_t2meval_set_param(mc_t2meval* e, const char* name, const float* host, int64_t numel) {
     MC_REQUIRE(e && name && host && numel > 0, "bad argument");
@@ -223,40 +194,37 @@ int mc_t2meval_set_param(mc_t2meval* e, const char* name, const float* host, int
             for (int k = 0; k < c.pos_size; ++k) packed[(size_t)o * e->Pp + k] = host[(size_t)o * c.pos_size + k];
     }
     if (!packed.empty()) { host = packed.data(); numel = (int64_t)packed.size(); }
-    float* d = nullptr;
-    MC_HIP(hipMalloc((void**)&d, (size_t)numel * sizeof(float)));
-    MC_HIP(hipMemcpy(d, host, (size_t)numel * sizeof(float), hipMemcpyHostToDevice));
-    auto it = e->params.find(n);
-    if (it != e->params.end()) (void)hipFree(it->second.first);
-    e->params[n] = {d, numel};
-    e->finalized = false;
-    return MC_OK;
+    const int r = e->params.set(n, host, numel);
+    if (r == MC_OK) e->finalized = false;
+    return r;
 }
 
 int mc_t2meval_finalize(mc_t2meval* e) {
     MC_REQUIRE(e, "null evaluator");
+    e->finalized = false;
+    ParamStore& ps = e->params;
+    ps.clear_derived();
     const mc_t2meval_config& c = e->cfg;
     int r;
-    for (float* p : e->owned) (void)hipFree(p);
-    e->owned.clear();
-    TP(e->c1_w, "movement_encoder.main.0.weight", (int64_t)c.movement_hidden * 4 * e->Cp);
-    TP(e->c1_b, "movement_encoder.main.0.bias", c.movement_hidden);
-    TP(e->c2_w, "movement_encoder.main.3.weight", (int64_t)c.movement_latent * 4 * c.movement_hidden);
-    TP(e->c2_b, "movement_encoder.main.3.bias", c.movement_latent);
-    TP(e->mo_w, "movement_encoder.out_net.weight", (int64_t)c.movement_latent * c.movement_latent);
-    TP(e->mo_b, "movement_encoder.out_net.bias", c.movement_latent);
-    if ((r = bind_head(e, "motion_encoder.", c.movement_latent, c.motion_hidden, c.motion_latent, e->motion))) return r;
+    if ((r = ps.bind({{&e->c1_w, "movement_encoder.main.0.weight", (int64_t)c.movement_hidden * 4 * e->Cp},
+                      {&e->c1_b, "movement_encoder.main.0.bias", c.movement_hidden},
+                      {&e->c2_w, "movement_encoder.main.3.weight", (int64_t)c.movement_latent * 4 * c.movement_hidden},
+                      {&e->c2_b, "movement_encoder.main.3.bias", c.movement_latent},
+                      {&e->mo_w, "movement_encoder.out_net.weight", (int64_t)c.movement_latent * c.movement_latent},
+                      {&e->mo_b, "movement_encoder.out_net.bias", c.movement_latent}})))
+        return r;
+    if ((r = bind_head(ps, "motion_encoder.", c.movement_latent, c.motion_hidden, c.motion_latent, e->motion))) return r;
     e->has_text = false;
-    if (c.word_size > 0 && e->params.count("text_encoder.pos_emb.weight")) {
-        TP(e->pos_w, "text_encoder.pos_emb.weight", (int64_t)c.word_size * e->Pp);
-        TP(e->pos_b, "text_encoder.pos_emb.bias", c.word_size);
-        if ((r = bind_head(e, "text_encoder.", c.word_size, c.text_hidden, c.text_out, e->text))) return r;
+    if (c.word_size > 0 && ps.has("text_encoder.pos_emb.weight")) {
+        if ((r = ps.bind({{&e->pos_w, "text_encoder.pos_emb.weight", (int64_t)c.word_size * e->Pp},
+                          {&e->pos_b, "text_encoder.pos_emb.bias", c.word_size}})) ||
+            (r = bind_head(ps, "text_encoder.", c.word_size, c.text_hidden, c.text_out, e->text)))
+            return r;
         e->has_text = true;
     }
     e->finalized = true;
     return MC_OK;
 }
-#undef TP
 
 int mc_t2meval_encode_motion(mc_t2meval* e, const float* motion, const int32_t* lengths, int32_t B, int32_t T, float* out, void* stream) {
     MC_REQUIRE(e && motion && lengths && out && B >= 1 && T >= 4, "bad argument");
@@ -268,8 +236,8 @@ int mc_t2meval_encode_motion(mc_t2meval* e, const float* motion, const int32_t* 
     MC_REQUIRE(T2 >= 1, "t2m evaluator: %d frames are too few", T);
     const size_t n_pad1 = (size_t)B * (T + 2) * Cp + 4 * Cp, n_pad2 = (size_t)B * (T1 + 2) * Hm + 4 * Hm, n_c2 = (size_t)B * T2 * Lm;
     int r;
-    if ((r = ensure_ws(e, n_pad1 + n_pad2 + 2 * n_c2 + head_floats(e->motion, B, T2) + 64, s))) return r;
-    float* pad1 = e->ws;
+    if ((r = e->ws.ensure(n_pad1 + n_pad2 + 2 * n_c2 + head_floats(e->motion, B, T2) + 64, s))) return r;
+    float* pad1 = e->ws.buf;
     float* pad2 = pad1 + n_pad1;
     float* c2 = pad2 + n_pad2;
     float* mov = c2 + n_c2;
@@ -303,8 +271,8 @@ int mc_t2meval_encode_text(mc_t2meval* e, const float* word_emb, const float* po
     hipStream_t s = (hipStream_t)stream;
     const long BS = (long)B * S;
     int r;
-    if ((r = ensure_ws(e, (size_t)BS * c.word_size + head_floats(e->text, B, S) + 64, s))) return r;
-    float* x = e->ws;
+    if ((r = e->ws.ensure((size_t)BS * c.word_size + head_floats(e->text, B, S) + 64, s))) return r;
+    float* x = e->ws.buf;
     GemmArgs g;                                        // x = word_emb + pos_emb(pos_onehot)   (K = pos_size: unaligned rows)
     g.A = pos_onehot; g.lda = c.pos_size; g.W = e->pos_w; g.ldw = e->Pp; g.bias = e->pos_b; g.R = word_emb; g.ldr = c.word_size;
     g.C = x; g.ldc = c.word_size; g.M = (int)BS; g.N = c.word_size; g.K = c.pos_size;

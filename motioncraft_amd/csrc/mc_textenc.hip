@@ -11,8 +11,8 @@
 #include "mc_gemm.h"
 #include "mc_kernels.h"
 #include "mc_enc.h"
+#include "mc_params.h"
 #include "../../include/motioncraft_amd.h"
-#include <map>
 #include <string>
 #include <vector>
 
@@ -233,39 +233,53 @@ int mc_enc_layer(const EncLayer& p, float* x, float* qkv, float* att, float* y, 
     return mc_enc_ln(y, p.n2_g, p.n2_b, x, rows, d, eps, 0, s);
 }
 
+// one name table per scheme, each in the reference's parameter order
+int bind_enc_layer(ParamStore& ps, const std::string& p, EncScheme scheme, int d, int ff, EncLayer& L) {
+    const int64_t dd = (int64_t)d * d, fd = (int64_t)ff * d;
+    if (scheme == ENC_TORCH)
+        return ps.bind({{&L.in_w, p + "self_attn.in_proj_weight", 3 * dd}, {&L.in_b, p + "self_attn.in_proj_bias", 3 * d},
+                        {&L.out_w, p + "self_attn.out_proj.weight", dd},   {&L.out_b, p + "self_attn.out_proj.bias", d},
+                        {&L.l1_w, p + "linear1.weight", fd},               {&L.l1_b, p + "linear1.bias", ff},
+                        {&L.l2_w, p + "linear2.weight", fd},               {&L.l2_b, p + "linear2.bias", d},
+                        {&L.n1_g, p + "norm1.weight", d},                  {&L.n1_b, p + "norm1.bias", d},
+                        {&L.n2_g, p + "norm2.weight", d},                  {&L.n2_b, p + "norm2.bias", d}});
+    if (scheme == ENC_CLIP)
+        return ps.bind({{&L.in_w, p + "attn.in_proj_weight", 3 * dd},  {&L.in_b, p + "attn.in_proj_bias", 3 * d},
+                        {&L.out_w, p + "attn.out_proj.weight", dd},    {&L.out_b, p + "attn.out_proj.bias", d},
+                        {&L.l1_w, p + "mlp.c_fc.weight", fd},          {&L.l1_b, p + "mlp.c_fc.bias", ff},
+                        {&L.l2_w, p + "mlp.c_proj.weight", fd},        {&L.l2_b, p + "mlp.c_proj.bias", d},
+                        {&L.n1_g, p + "ln_1.weight", d},               {&L.n1_b, p + "ln_1.bias", d},
+                        {&L.n2_g, p + "ln_2.weight", d},               {&L.n2_b, p + "ln_2.bias", d}});
+    // DistilBERT: q_lin | k_lin | v_lin stacked into one [3d][d] projection (the order mc_enc_layer's attention expects)
+    float *pw = nullptr, *pb = nullptr;
+    int r;
+    if ((r = ps.derived((size_t)3 * dd, &pw)) || (r = ps.derived((size_t)3 * d, &pb))) return r;
+    const char* names[3] = {"q_lin", "k_lin", "v_lin"};
+    for (int j = 0; j < 3; ++j) {
+        const std::string q = p + "attention." + names[j];
+        const float *sw = nullptr, *sb = nullptr;
+        if ((r = ps.bind({{&sw, q + ".weight", dd}, {&sb, q + ".bias", d}}))) return r;
+        MC_HIP(hipMemcpy(pw + (size_t)j * dd, sw, (size_t)dd * sizeof(float), hipMemcpyDeviceToDevice));
+        MC_HIP(hipMemcpy(pb + (size_t)j * d, sb, (size_t)d * sizeof(float), hipMemcpyDeviceToDevice));
+    }
+    L.in_w = pw;
+    L.in_b = pb;
+    return ps.bind({{&L.out_w, p + "attention.out_lin.weight", dd}, {&L.out_b, p + "attention.out_lin.bias", d},
+                    {&L.n1_g, p + "sa_layer_norm.weight", d},       {&L.n1_b, p + "sa_layer_norm.bias", d},
+                    {&L.l1_w, p + "ffn.lin1.weight", fd},           {&L.l1_b, p + "ffn.lin1.bias", ff},
+                    {&L.l2_w, p + "ffn.lin2.weight", fd},           {&L.l2_b, p + "ffn.lin2.bias", d},
+                    {&L.n2_g, p + "output_layer_norm.weight", d},   {&L.n2_b, p + "output_layer_norm.bias", d}});
+}
+
 struct mc_textenc {
     mc_textenc_config cfg;
-    std::map<std::string, std::pair<float*, int64_t>> params;
+    ParamStore params{"text encoder"};
     std::vector<EncLayer> ft, clip;
     const float *pre_w = nullptr, *pre_b = nullptr, *ln_g = nullptr, *ln_b = nullptr;
     const float *tok = nullptr, *pos = nullptr, *lnf_g = nullptr, *lnf_b = nullptr;
     bool finalized = false, has_clip = false;
-    float* ws = nullptr;
-    size_t ws_floats = 0;
+    Workspace ws;
 };
-
-namespace {
-
-int getp(mc_textenc* e, const std::string& name, int64_t numel, const float** out) {
-    auto it = e->params.find(name);
-    if (it == e->params.end()) { mc_set_error("text encoder: missing parameter '%s'", name.c_str()); return MC_ERR_STATE; }
-    if (it->second.second != numel) {
-        mc_set_error("text encoder: parameter '%s' has %ld elements, expected %ld", name.c_str(), (long)it->second.second, (long)numel);
-        return MC_ERR_STATE;
-    }
-    *out = it->second.first;
-    return MC_OK;
-}
-
-int ensure_ws(mc_textenc* e, size_t floats, hipStream_t s) {
-    if (floats <= e->ws_floats) return MC_OK;
-    if (e->ws) { MC_HIP(hipStreamSynchronize(s)); MC_HIP(hipFree(e->ws)); e->ws = nullptr; e->ws_floats = 0; }
-    MC_HIP(hipMalloc((void**)&e->ws, floats * sizeof(float)));
-    e->ws_floats = floats;
-    return MC_OK;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -282,70 +296,43 @@ int mc_textenc_create(const mc_textenc_config* cfg, mc_textenc** out) {
     return MC_OK;
 }
 
-void mc_textenc_destroy(mc_textenc* e) {
-    if (!e) return;
-    for (auto& kv : e->params) (void)hipFree(kv.second.first);
-    if (e->ws) (void)hipFree(e->ws);
-    delete e;
-}
+void mc_textenc_destroy(mc_textenc* e) { delete e; }
 
 int mc_textenc_set_param(mc_textenc* e, const char* name, const float* host, int64_t numel) {
     MC_REQUIRE(e && name && host && numel > 0, "bad argument");
-    float* d = nullptr;
-    MC_HIP(hipMalloc((void**)&d, (size_t)numel * sizeof(float)));
-    MC_HIP(hipMemcpy(d, host, (size_t)numel * sizeof(float), hipMemcpyHostToDevice));
-    auto it = e->params.find(name);
-    if (it != e->params.end()) (void)hipFree(it->second.first);
-    e->params[name] = {d, numel};
-    e->finalized = false;
-    return MC_OK;
+    const int r = e->params.set(name, host, numel);
+    if (r == MC_OK) e->finalized = false;
+    return r;
 }
 
 int mc_textenc_finalize(mc_textenc* e) {
     MC_REQUIRE(e, "null encoder");
+    e->finalized = false;
+    ParamStore& ps = e->params;
+    ps.clear_derived();
     const mc_textenc_config& c = e->cfg;
-    const int d = c.text_latent_dim, ff = c.ff_size;
+    const int d = c.text_latent_dim, w = c.clip_dim;
     int r;
-#define TP(ptr, name, n) if ((r = getp(e, (name), (int64_t)(n), &(ptr)))) return r
     e->pre_w = e->pre_b = nullptr;
-    if (c.clip_dim != d) {                       // text_pre_proj is nn.Identity when the widths agree (:124-127)
-        TP(e->pre_w, "text_pre_proj.weight", (int64_t)d * c.clip_dim);
-        TP(e->pre_b, "text_pre_proj.bias", d);
+    if (w != d) {                                // text_pre_proj is nn.Identity when the widths agree (:124-127)
+        if ((r = ps.bind({{&e->pre_w, "text_pre_proj.weight", (int64_t)d * w}, {&e->pre_b, "text_pre_proj.bias", d}}))) return r;
     }
     e->ft.assign(c.num_layers, EncLayer());
-    for (int i = 0; i < c.num_layers; ++i) {
-        const std::string p = "textTransEncoder.layers." + std::to_string(i) + ".";
-        EncLayer& L = e->ft[i];
-        TP(L.in_w, p + "self_attn.in_proj_weight", (int64_t)3 * d * d);  TP(L.in_b, p + "self_attn.in_proj_bias", 3 * d);
-        TP(L.out_w, p + "self_attn.out_proj.weight", (int64_t)d * d);    TP(L.out_b, p + "self_attn.out_proj.bias", d);
-        TP(L.l1_w, p + "linear1.weight", (int64_t)ff * d);               TP(L.l1_b, p + "linear1.bias", ff);
-        TP(L.l2_w, p + "linear2.weight", (int64_t)d * ff);               TP(L.l2_b, p + "linear2.bias", d);
-        TP(L.n1_g, p + "norm1.weight", d);  TP(L.n1_b, p + "norm1.bias", d);
-        TP(L.n2_g, p + "norm2.weight", d);  TP(L.n2_b, p + "norm2.bias", d);
-    }
-    TP(e->ln_g, "text_ln.weight", d);
-    TP(e->ln_b, "text_ln.bias", d);
+    for (int i = 0; i < c.num_layers; ++i)
+        if ((r = bind_enc_layer(ps, "textTransEncoder.layers." + std::to_string(i) + ".", ENC_TORCH, d, c.ff_size, e->ft[i]))) return r;
+    if ((r = ps.bind({{&e->ln_g, "text_ln.weight", d}, {&e->ln_b, "text_ln.bias", d}}))) return r;
     e->has_clip = false;
-    if (c.clip_layers > 0 && e->params.count("clip.token_embedding.weight")) {
-        const int w = c.clip_dim, cf = c.clip_ff;
-        TP(e->tok, "clip.token_embedding.weight", (int64_t)c.vocab * w);
-        TP(e->pos, "clip.positional_embedding", (int64_t)c.max_len * w);
-        TP(e->lnf_g, "clip.ln_final.weight", w);
-        TP(e->lnf_b, "clip.ln_final.bias", w);
+    if (c.clip_layers > 0 && ps.has("clip.token_embedding.weight")) {
+        if ((r = ps.bind({{&e->tok, "clip.token_embedding.weight", (int64_t)c.vocab * w},
+                          {&e->pos, "clip.positional_embedding", (int64_t)c.max_len * w},
+                          {&e->lnf_g, "clip.ln_final.weight", w}, {&e->lnf_b, "clip.ln_final.bias", w}})))
+            return r;
         e->clip.assign(c.clip_layers, EncLayer());
-        for (int i = 0; i < c.clip_layers; ++i) {
-            const std::string p = "clip.transformer.resblocks." + std::to_string(i) + ".";
-            EncLayer& L = e->clip[i];
-            TP(L.in_w, p + "attn.in_proj_weight", (int64_t)3 * w * w);  TP(L.in_b, p + "attn.in_proj_bias", 3 * w);
-            TP(L.out_w, p + "attn.out_proj.weight", (int64_t)w * w);    TP(L.out_b, p + "attn.out_proj.bias", w);
-            TP(L.l1_w, p + "mlp.c_fc.weight", (int64_t)cf * w);         TP(L.l1_b, p + "mlp.c_fc.bias", cf);
-            TP(L.l2_w, p + "mlp.c_proj.weight", (int64_t)w * cf);       TP(L.l2_b, p + "mlp.c_proj.bias", w);
-            TP(L.n1_g, p + "ln_1.weight", w);  TP(L.n1_b, p + "ln_1.bias", w);
-            TP(L.n2_g, p + "ln_2.weight", w);  TP(L.n2_b, p + "ln_2.bias", w);
-        }
+        for (int i = 0; i < c.clip_layers; ++i)
+            if ((r = bind_enc_layer(ps, "clip.transformer.resblocks." + std::to_string(i) + ".", ENC_CLIP, w, c.clip_ff, e->clip[i])))
+                return r;
         e->has_clip = true;
     }
-#undef TP
     e->finalized = true;
     return MC_OK;
 }
@@ -359,8 +346,8 @@ int mc_textenc_forward_feat(mc_textenc* e, const float* clip_feat, int32_t B, fl
     const int S = c.max_len, d = c.text_latent_dim, ff = c.ff_size;
     const long rows = (long)B * S;
     int r;
-    if ((r = ensure_ws(e, (size_t)rows * (d + 3 * d + d + d + ff) + 256, s))) return r;
-    float* x = e->ws;
+    if ((r = e->ws.ensure((size_t)rows * (d + 3 * d + d + d + ff) + 256, s))) return r;
+    float* x = e->ws.buf;
     float* qkv = x + rows * d;
     float* att = qkv + rows * 3 * d;
     float* y = att + rows * d;
@@ -387,8 +374,8 @@ int mc_textenc_forward_tokens(mc_textenc* e, const int32_t* tokens, int32_t B, f
     int r;
     const size_t stageA = (size_t)rows * (d + 3 * d + d + d + c.ff_size) + 256;
     const size_t stageB = (size_t)rows * (w + 3 * w + w + w + cf + w) + 256;
-    if ((r = ensure_ws(e, stageA + stageB, s))) return r;
-    float* x = e->ws + stageA;
+    if ((r = e->ws.ensure(stageA + stageB, s))) return r;
+    float* x = e->ws.buf + stageA;
     float* qkv = x + rows * w;
     float* att = qkv + rows * 3 * w;
     float* y = att + rows * w;

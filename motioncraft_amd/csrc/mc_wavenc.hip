@@ -11,8 +11,8 @@
 // it) run in the GEMM epilogue, and each block writes straight into the interior of the next block's padded buffer.
 #include "mc_common.h"
 #include "mc_gemm.h"
+#include "mc_params.h"
 #include "../../include/motioncraft_amd.h"
-#include <map>
 #include <string>
 #include <vector>
 
@@ -26,10 +26,9 @@ struct mc_wavenc {
     int audio_in = 0, out_dim = 0;
     BlockSpec spec[6];
     ConvW c1[6], c2[6], dn[6];
-    std::map<std::string, std::pair<float*, int64_t>> params;
+    ParamStore params{"wav encoder"};
     bool finalized = false;
-    float* ws = nullptr;
-    size_t ws_floats = 0;
+    Workspace ws;
 };
 
 namespace {
@@ -51,17 +50,6 @@ int conv_gemm(const float* X, long Tp, int Cin, int stride, const ConvW& w, int 
     return mc_launch_gemm(aligned ? GM_PLAIN : GM_ENC, g, B, 0, s);
 }
 
-int get(mc_wavenc* e, const std::string& name, int64_t numel, const float** out) {
-    auto it = e->params.find(name);
-    if (it == e->params.end()) { mc_set_error("wav encoder: missing parameter '%s'", name.c_str()); return MC_ERR_STATE; }
-    if (it->second.second != numel) {
-        mc_set_error("wav encoder: parameter '%s' has %ld elements, expected %ld", name.c_str(), (long)it->second.second, (long)numel);
-        return MC_ERR_STATE;
-    }
-    *out = it->second.first;
-    return MC_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -80,23 +68,13 @@ int mc_wavenc_create(int32_t audio_in, int32_t out_dim, mc_wavenc** out) {
     return MC_OK;
 }
 
-void mc_wavenc_destroy(mc_wavenc* e) {
-    if (!e) return;
-    for (auto& kv : e->params) (void)hipFree(kv.second.first);
-    if (e->ws) (void)hipFree(e->ws);
-    delete e;
-}
+void mc_wavenc_destroy(mc_wavenc* e) { delete e; }
 
 int mc_wavenc_set_param(mc_wavenc* e, const char* name, const float* host, int64_t numel) {
     MC_REQUIRE(e && name && host && numel > 0, "bad argument");
-    float* d = nullptr;
-    MC_HIP(hipMalloc((void**)&d, (size_t)numel * sizeof(float)));
-    MC_HIP(hipMemcpy(d, host, (size_t)numel * sizeof(float), hipMemcpyHostToDevice));
-    auto it = e->params.find(name);
-    if (it != e->params.end()) (void)hipFree(it->second.first);
-    e->params[name] = {d, numel};
-    e->finalized = false;
-    return MC_OK;
+    const int r = e->params.set(name, host, numel);
+    if (r == MC_OK) e->finalized = false;
+    return r;
 }
 
 // parameters (BatchNorm folded, kernel-tap-major): b{i}.conv1.w [planes][ld(15*cin)], b{i}.conv1.b [planes],
@@ -104,20 +82,22 @@ int mc_wavenc_set_param(mc_wavenc* e, const char* name, const float* host, int64
 // rows padded to a multiple of 4 floats (ld = ceil4(15*cin)).
 int mc_wavenc_finalize(mc_wavenc* e) {
     MC_REQUIRE(e, "null encoder");
+    e->finalized = false;
+    ParamStore& ps = e->params;
+    ps.clear_derived();
     for (int i = 0; i < 6; ++i) {
         const BlockSpec& b = e->spec[i];
         const std::string pre = "b" + std::to_string(i) + ".";
         const long ld1 = (KS * b.cin + 3) / 4 * 4, ld2 = (long)KS * b.planes;
         int r;
-        if ((r = get(e, pre + "conv1.w", (int64_t)b.planes * ld1, &e->c1[i].w))) return r;
-        if ((r = get(e, pre + "conv1.b", b.planes, &e->c1[i].b))) return r;
+        if ((r = ps.bind({{&e->c1[i].w, pre + "conv1.w", (int64_t)b.planes * ld1}, {&e->c1[i].b, pre + "conv1.b", b.planes},
+                          {&e->c2[i].w, pre + "conv2.w", (int64_t)b.planes * ld2}, {&e->c2[i].b, pre + "conv2.b", b.planes}})))
+            return r;
         e->c1[i].ldw = ld1;
-        if ((r = get(e, pre + "conv2.w", (int64_t)b.planes * ld2, &e->c2[i].w))) return r;
-        if ((r = get(e, pre + "conv2.b", b.planes, &e->c2[i].b))) return r;
         e->c2[i].ldw = ld2;
         if (b.down) {
-            if ((r = get(e, pre + "down.w", (int64_t)b.planes * ld1, &e->dn[i].w))) return r;
-            if ((r = get(e, pre + "down.b", b.planes, &e->dn[i].b))) return r;
+            if ((r = ps.bind({{&e->dn[i].w, pre + "down.w", (int64_t)b.planes * ld1}, {&e->dn[i].b, pre + "down.b", b.planes}})))
+                return r;
             e->dn[i].ldw = ld1;
         }
     }
@@ -156,25 +136,22 @@ int mc_wavenc_forward(mc_wavenc* e, const float* wav, int32_t B, int32_t samples
         offS[i] = need; if (b.down) need += (size_t)B * Tin[i + 1] * b.planes;
         need = (need + 63) & ~(size_t)63;
     }
-    if (need > e->ws_floats) {
-        if (e->ws) { MC_HIP(hipStreamSynchronize(s)); MC_HIP(hipFree(e->ws)); e->ws = nullptr; e->ws_floats = 0; }
-        MC_HIP(hipMalloc((void**)&e->ws, need * sizeof(float)));
-        e->ws_floats = need;
-    }
+    int r;
+    if ((r = e->ws.ensure(need, s))) return r;
+    float* ws = e->ws.buf;
     // zero everything once (padding borders), then drop the audio into the interior of X0
-    MC_HIP(hipMemsetAsync(e->ws, 0, need * sizeof(float), s));
+    MC_HIP(hipMemsetAsync(ws, 0, need * sizeof(float), s));
     {
         const BlockSpec& b = e->spec[0];
         const size_t row = (size_t)samples * b.cin * sizeof(float);
-        MC_HIP(hipMemcpy2DAsync(e->ws + offX[0] + (size_t)b.pad * b.cin, (size_t)(samples + 2 * b.pad) * b.cin * sizeof(float),
+        MC_HIP(hipMemcpy2DAsync(ws + offX[0] + (size_t)b.pad * b.cin, (size_t)(samples + 2 * b.pad) * b.cin * sizeof(float),
                                 wav, row, row, B, hipMemcpyDeviceToDevice, s));
     }
-    int r;
     for (int i = 0; i < 6; ++i) {
         const BlockSpec& b = e->spec[i];
         const long Tp = Tin[i] + 2 * b.pad, T1 = Tin[i + 1], Hp = T1 + 2 * (KS / 2);
-        const float* X = e->ws + offX[i];
-        float* H = e->ws + offH[i];
+        const float* X = ws + offX[i];
+        float* H = ws + offH[i];
         // conv1 + bn1 + LeakyReLU -> interior of H
         if ((r = conv_gemm(X, Tp, b.cin, b.stride, e->c1[i], b.planes, B, (int)T1, H + (KS / 2) * b.planes, Hp, nullptr, 0, -1,
                            ACT_LRELU, 0, s))) return r;
@@ -182,7 +159,7 @@ int mc_wavenc_forward(mc_wavenc* e, const float* wav, int32_t B, int32_t samples
         const float* R;
         long ldr, rstride;
         if (b.down) {
-            float* S = e->ws + offS[i];
+            float* S = ws + offS[i];
             if ((r = conv_gemm(X, Tp, b.cin, b.stride, e->dn[i], b.planes, B, (int)T1, S, T1, nullptr, 0, -1, ACT_NONE, 0, s))) return r;
             R = S; ldr = b.planes; rstride = T1 * b.planes;
         } else {
@@ -193,7 +170,7 @@ int mc_wavenc_forward(mc_wavenc* e, const float* wav, int32_t B, int32_t samples
         long crows;
         if (i + 1 < 6) {
             const int pn = e->spec[i + 1].pad;
-            C = e->ws + offX[i + 1] + (long)pn * b.planes;
+            C = ws + offX[i + 1] + (long)pn * b.planes;
             crows = T1 + 2 * pn;
         } else {
             C = out;

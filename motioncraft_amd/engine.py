@@ -27,13 +27,13 @@ def _dev_f32(t, name):
     return t
 
 
-class NativeModel:
+class NativeModel(_lib.NativeObject):
     def __init__(self, dims, state_dict, cfg_scale=6.5, capacity_factor=1.5, dyn_heads=8, device=None,
                  condition_cfg=True):
-        self.lib = _lib.load(require_gpu=True)
+        lib = _lib.load(require_gpu=True)
         if device is not None:
             torch.cuda.set_device(device)
-            _lib.check(self.lib.mc_set_device(torch.cuda.current_device()), 'mc_set_device')
+            _lib.check(lib.mc_set_device(torch.cuda.current_device()), 'mc_set_device')
         self.dims = dict(dims)
         self.copy_blocks_num, self.control_cond_feats = control_info(state_dict)
         cfg = _lib.ModelConfig(
@@ -43,29 +43,13 @@ class NativeModel:
             dyn_heads=dyn_heads, capacity_factor=capacity_factor, cfg_scale=cfg_scale,
             num_ctrl_layers=self.copy_blocks_num, ctrl_cond_feats=self.control_cond_feats,
             ctrl_condition_cfg=int(bool(condition_cfg)))
-        self.cfg_scale = float(cfg_scale)
-        h = ctypes.c_void_p()
-        _lib.check(self.lib.mc_model_create(ctypes.byref(cfg), ctypes.byref(h)), 'mc_model_create')
-        self.handle = h
-        for name, arr in pack_state_dict(state_dict, dims).items():
-            arr = np.ascontiguousarray(arr, dtype=np.float32)
-            _lib.check(self.lib.mc_model_set_param(self.handle, name.encode(), arr.ctypes.data_as(ctypes.c_void_p),
-                                                   arr.size), f'mc_model_set_param({name})')
-        _lib.check(self.lib.mc_model_finalize(self.handle), 'mc_model_finalize')
+        self.cfg, self.cfg_scale = cfg, float(cfg_scale)
+        super().__init__('model', ctypes.byref(cfg))
+        self.upload(pack_state_dict(state_dict, dims).items())
+        self.finalize()
 
     def context(self, batch, frames, max_steps=1000):
         return NativeContext(self, batch, frames, max_steps)
-
-    def close(self):
-        if getattr(self, 'handle', None):
-            self.lib.mc_model_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class NativeContext:

@@ -25,11 +25,10 @@ from .wordpiece import WordPieceTokenizer
 DISTILBERT_BASE = dict(dim=768, n_layers=6, n_heads=12, hidden_dim=3072, vocab_size=30522, max_position_embeddings=512)
 
 
-class NativeEvalEncoder:
+class NativeEvalEncoder(_lib.NativeObject):
     """Device encoders over the evaluator checkpoint's own keys (``motionencoder.*``, ``textencoder.*``)."""
 
     def __init__(self, state_dict, nfeats=322, latent_dim=256, ff_size=1024, num_layers=4, num_heads=4, bert=None):
-        self.lib = _lib.load(require_gpu=True)
         sd = dict(state_dict)
         has_text = bert is not None and 'textencoder.projection.1.weight' in sd
         cfg = _lib.EvalEncConfig()
@@ -46,18 +45,12 @@ class NativeEvalEncoder:
             cfg.bert_vocab = int(sd['textencoder.text_model.embeddings.word_embeddings.weight'].shape[0])
             cfg.bert_max_pos = int(sd['textencoder.text_model.embeddings.position_embeddings.weight'].shape[0])
         self.cfg, self.has_text = cfg, has_text
-        h = ctypes.c_void_p()
-        _lib.check(self.lib.mc_evalenc_create(ctypes.byref(cfg), ctypes.byref(h)), 'mc_evalenc_create')
-        self.handle = h
-        for k, v in sd.items():
-            if not (k.startswith('motionencoder.') or (has_text and k.startswith('textencoder.'))):
-                continue
-            if not torch.is_floating_point(torch.as_tensor(v)):
-                continue                                            # e.g. embeddings.position_ids of older transformers
-            a = np.ascontiguousarray(torch.as_tensor(v).detach().cpu().float().numpy())
-            _lib.check(self.lib.mc_evalenc_set_param(self.handle, k.encode(), a.ctypes.data_as(ctypes.c_void_p), a.size),
-                       f'mc_evalenc_set_param({k})')
-        _lib.check(self.lib.mc_evalenc_finalize(self.handle), 'mc_evalenc_finalize')
+        super().__init__('evalenc', ctypes.byref(cfg))
+        # (non-float entries are skipped: e.g. embeddings.position_ids of older transformers)
+        self.upload((k, torch.as_tensor(v).detach().cpu().float().numpy()) for k, v in sd.items()
+                    if (k.startswith('motionencoder.') or (has_text and k.startswith('textencoder.')))
+                    and torch.is_floating_point(torch.as_tensor(v)))
+        self.finalize()
 
     def encode_motion(self, motion, motion_length):
         """motion [B, T, nfeats] float32 device tensor, motion_length [B] -> mu [B, latent_dim] (device)."""
@@ -88,17 +81,6 @@ class NativeEvalEncoder:
                                                    ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
                    'mc_evalenc_encode_text')
         return out
-
-    def close(self):
-        if getattr(self, 'handle', None):
-            self.lib.mc_evalenc_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _bert_config(modelpath):
@@ -451,13 +433,12 @@ class EvaluationPlan:
 
 
 # ---- HumanML3D / KIT evaluator (mogen/models/rnns/t2m_bigru.py) ------------------------------------------------------
-class NativeT2MEvaluator:
+class NativeT2MEvaluator(_lib.NativeObject):
     """Device encoders of ``T2MContrastiveModel`` over the checkpoint's three state dicts flattened with their names as
     prefixes (``movement_encoder.*``, ``motion_encoder.*``, ``text_encoder.*``)."""
 
     def __init__(self, state_dict, input_size=263, movement_hidden_size=512, movement_latent_size=512, motion_hidden_size=1024,
                  motion_latent_size=512, word_size=300, pos_size=15, hidden_size=512, output_size=512):
-        self.lib = _lib.load(require_gpu=True)
         sd = dict(state_dict)
         self.has_text = 'text_encoder.pos_emb.weight' in sd
         cfg = _lib.T2MEvalConfig()
@@ -465,16 +446,10 @@ class NativeT2MEvaluator:
         cfg.motion_hidden, cfg.motion_latent = motion_hidden_size, motion_latent_size
         cfg.word_size, cfg.pos_size, cfg.text_hidden, cfg.text_out = (word_size if self.has_text else 0), pos_size, hidden_size, output_size
         self.cfg = cfg
-        h = ctypes.c_void_p()
-        _lib.check(self.lib.mc_t2meval_create(ctypes.byref(cfg), ctypes.byref(h)), 'mc_t2meval_create')
-        self.handle = h
-        for k, v in sd.items():
-            if not k.startswith(('movement_encoder.', 'motion_encoder.', 'text_encoder.')):
-                continue
-            a = np.ascontiguousarray(torch.as_tensor(v).detach().cpu().float().numpy())
-            _lib.check(self.lib.mc_t2meval_set_param(self.handle, k.encode(), a.ctypes.data_as(ctypes.c_void_p), a.size),
-                       f'mc_t2meval_set_param({k})')
-        _lib.check(self.lib.mc_t2meval_finalize(self.handle), 'mc_t2meval_finalize')
+        super().__init__('t2meval', ctypes.byref(cfg))
+        self.upload((k, torch.as_tensor(v).detach().cpu().float().numpy()) for k, v in sd.items()
+                    if k.startswith(('movement_encoder.', 'motion_encoder.', 'text_encoder.')))
+        self.finalize()
 
     def encode_motion(self, motion, motion_length):
         if not (motion.is_cuda and motion.dim() == 3 and motion.shape[2] == self.cfg.input_size):
@@ -507,17 +482,6 @@ class NativeT2MEvaluator:
                                                    ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
                    'mc_t2meval_encode_text')
         return out
-
-    def close(self):
-        if getattr(self, 'handle', None):
-            self.lib.mc_t2meval_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def vectorize_tokens(token, w_vectorizer, max_text_len):

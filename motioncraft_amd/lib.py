@@ -7,6 +7,8 @@ to run the path raises ``RuntimeError`` when the HIP library is missing or no MI
 import ctypes
 import os
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libmotioncraft_amd.so')
 
@@ -65,9 +67,6 @@ _SIGNATURES = {
     'mc_device_count': (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)]),
     'mc_set_device': (ctypes.c_int, [ctypes.c_int]),
     'mc_model_create': (ctypes.c_int, [ctypes.POINTER(ModelConfig), ctypes.POINTER(_P)]),
-    'mc_model_destroy': (None, [_P]),
-    'mc_model_set_param': (ctypes.c_int, [_P, ctypes.c_char_p, _P, ctypes.c_int64]),
-    'mc_model_finalize': (ctypes.c_int, [_P]),
     'mc_ctx_create': (ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_P)]),
     'mc_ctx_destroy': (None, [_P]),
     'mc_ctx_workspace_bytes': (ctypes.c_int64, [_P]),
@@ -110,33 +109,26 @@ _SIGNATURES = {
     'mc_postprocess_smplx_stitched': (ctypes.c_int, [_P, _P, ctypes.c_int32, _P, _P, _P, ctypes.POINTER(ctypes.c_int32 * 4),
                                                      ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P]),
     'mc_textenc_create': (ctypes.c_int, [ctypes.POINTER(TextEncConfig), ctypes.POINTER(_P)]),
-    'mc_textenc_destroy': (None, [_P]),
-    'mc_textenc_set_param': (ctypes.c_int, [_P, ctypes.c_char_p, _P, ctypes.c_int64]),
-    'mc_textenc_finalize': (ctypes.c_int, [_P]),
     'mc_textenc_forward_feat': (ctypes.c_int, [_P, _P, ctypes.c_int32, _P, _P]),
     'mc_textenc_forward_tokens': (ctypes.c_int, [_P, _P, ctypes.c_int32, _P, _P, _P]),
     'mc_evalenc_create': (ctypes.c_int, [ctypes.POINTER(EvalEncConfig), ctypes.POINTER(_P)]),
-    'mc_evalenc_destroy': (None, [_P]),
-    'mc_evalenc_set_param': (ctypes.c_int, [_P, ctypes.c_char_p, _P, ctypes.c_int64]),
-    'mc_evalenc_finalize': (ctypes.c_int, [_P]),
     'mc_evalenc_encode_motion': (ctypes.c_int, [_P, _P, _P, ctypes.c_int32, ctypes.c_int32, _P, _P]),
     'mc_evalenc_encode_text': (ctypes.c_int, [_P, _P, _P, ctypes.c_int32, ctypes.c_int32, _P, _P]),
     'mc_t2meval_create': (ctypes.c_int, [ctypes.POINTER(T2MEvalConfig), ctypes.POINTER(_P)]),
-    'mc_t2meval_destroy': (None, [_P]),
-    'mc_t2meval_set_param': (ctypes.c_int, [_P, ctypes.c_char_p, _P, ctypes.c_int64]),
-    'mc_t2meval_finalize': (ctypes.c_int, [_P]),
     'mc_t2meval_encode_motion': (ctypes.c_int, [_P, _P, _P, ctypes.c_int32, ctypes.c_int32, _P, _P]),
     'mc_t2meval_encode_text': (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_int32, ctypes.c_int32, _P, _P]),
     'mc_wavenc_create': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_P)]),
-    'mc_wavenc_destroy': (None, [_P]),
-    'mc_wavenc_set_param': (ctypes.c_int, [_P, ctypes.c_char_p, _P, ctypes.c_int64]),
-    'mc_wavenc_finalize': (ctypes.c_int, [_P]),
     'mc_wavenc_out_len': (ctypes.c_int, [_P, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)]),
     'mc_wavenc_forward': (ctypes.c_int, [_P, _P, ctypes.c_int32, ctypes.c_int32, _P, _P]),
     'mc_op_renoise': (ctypes.c_int, [_P, _P, ctypes.c_float, ctypes.c_float, _P, ctypes.c_int64, _P]),
     'mc_debug_flop_ledger': (ctypes.c_int, [ctypes.c_int32]),
     'mc_debug_flop_ledger_dump': (ctypes.c_int64, [ctypes.c_char_p, ctypes.c_int64]),
 }
+NATIVE_OBJECTS = ('model', 'textenc', 'evalenc', 't2meval', 'wavenc')       # the handles with a parameter store (NativeObject)
+for _kind in NATIVE_OBJECTS:
+    _SIGNATURES.update({f'mc_{_kind}_destroy': (None, [_P]),
+                        f'mc_{_kind}_set_param': (ctypes.c_int, [_P, ctypes.c_char_p, _P, ctypes.c_int64]),
+                        f'mc_{_kind}_finalize': (ctypes.c_int, [_P])})
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 POST_MAXTAP = 129            # MC_POST_MAXTAP
@@ -174,3 +166,36 @@ def last_error():
 def check(rc, what=''):
     if rc != MC_OK:
         raise RuntimeError(f'motioncraft_amd {what} failed (code {rc}): {last_error()}')
+
+
+class NativeObject:
+    """Owner of one handle of kind ``mc_<kind>`` (``NATIVE_OBJECTS``): created from ``cfg_args`` (mc_<kind>_create's
+    arguments before the out handle), filled by ``upload``, made usable by ``finalize``, freed by ``close``."""
+    handle = None                             # stays None when create fails: close() and __del__ then do nothing
+
+    def __init__(self, kind, *cfg_args):
+        self.lib, self.kind = load(require_gpu=True), kind
+        h = ctypes.c_void_p()
+        check(getattr(self.lib, f'mc_{kind}_create')(*cfg_args, ctypes.byref(h)), f'mc_{kind}_create')
+        self.handle = h
+
+    def upload(self, items):
+        """(name, array) pairs -> mc_<kind>_set_param, as contiguous float32 host arrays."""
+        set_param = getattr(self.lib, f'mc_{self.kind}_set_param')
+        for name, a in items:
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            check(set_param(self.handle, name.encode(), a.ctypes.data_as(ctypes.c_void_p), a.size), f'mc_{self.kind}_set_param({name})')
+
+    def finalize(self):
+        check(getattr(self.lib, f'mc_{self.kind}_finalize')(self.handle), f'mc_{self.kind}_finalize')
+
+    def close(self):
+        if self.handle:
+            getattr(self.lib, f'mc_{self.kind}_destroy')(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

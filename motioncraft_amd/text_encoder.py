@@ -10,7 +10,6 @@ supplied.
 """
 import ctypes
 
-import numpy as np
 import torch
 
 from . import lib as _lib
@@ -36,7 +35,7 @@ def text_encoder_keys(num_layers, clip_layers=0):
     return ks
 
 
-class NativeTextEncoder:
+class NativeTextEncoder(_lib.NativeObject):
     def __init__(self, text_encoder_cfg, state_dict, max_len=77, clip=None):
         """text_encoder_cfg: the configs' ``text_encoder=dict(pretrained_model='clip', latent_dim, num_layers, ff_size,
         num_heads=4, ...)``; ``clip``: dict(width, layers, heads, ff, vocab) of the text tower (default ViT-B/32).
@@ -48,7 +47,6 @@ class NativeTextEncoder:
             raise NotImplementedError('use_text_proj=True is not used by the shipped configs')
         if c.get('activation', 'gelu') != 'gelu' or c.get('num_layers', 0) < 1:
             raise NotImplementedError('the shipped configs use a >=1-layer GELU nn.TransformerEncoder')
-        self.lib = _lib.load(require_gpu=True)
         clip = dict(CLIP_TEXT, **(clip or {}))
         sd = {k: v for k, v in state_dict.items()}
         has_clip = 'clip.token_embedding.weight' in sd
@@ -59,18 +57,17 @@ class NativeTextEncoder:
         cfg.clip_layers, cfg.clip_heads, cfg.clip_ff = (clip['layers'] if has_clip else 0), clip['heads'], clip['ff']
         cfg.vocab = int(sd['clip.token_embedding.weight'].shape[0]) if has_clip else clip['vocab']
         self.cfg, self.has_clip = cfg, has_clip
-        h = ctypes.c_void_p()
-        _lib.check(self.lib.mc_textenc_create(ctypes.byref(cfg), ctypes.byref(h)), 'mc_textenc_create')
-        self.handle = h
-        for k in text_encoder_keys(cfg.num_layers, cfg.clip_layers):
-            if k not in sd:
-                if k.startswith('text_pre_proj') and cfg.clip_dim == cfg.text_latent_dim:
-                    continue                                       # nn.Identity (diffusion_transformer.py:124-127)
-                raise KeyError(f'text encoder weight {k!r} is missing from the checkpoint')
-            a = np.ascontiguousarray(sd[k].detach().cpu().float().numpy())
-            _lib.check(self.lib.mc_textenc_set_param(self.handle, k.encode(), a.ctypes.data_as(ctypes.c_void_p), a.size),
-                       f'mc_textenc_set_param({k})')
-        _lib.check(self.lib.mc_textenc_finalize(self.handle), 'mc_textenc_finalize')
+        super().__init__('textenc', ctypes.byref(cfg))
+
+        def weights():
+            for k in text_encoder_keys(cfg.num_layers, cfg.clip_layers):
+                if k not in sd:
+                    if k.startswith('text_pre_proj') and cfg.clip_dim == cfg.text_latent_dim:
+                        continue                                   # nn.Identity (diffusion_transformer.py:124-127)
+                    raise KeyError(f'text encoder weight {k!r} is missing from the checkpoint')
+                yield k, sd[k].detach().cpu().float().numpy()
+        self.upload(weights())
+        self.finalize()
 
     def _out(self, B, dev):
         return torch.empty(B, self.cfg.max_len, self.cfg.text_latent_dim, device=dev, dtype=torch.float32)
@@ -122,14 +119,3 @@ class NativeTextEncoder:
                 self._bpe, self._bpe_path = ClipBPE(bpe_path, vocab_size=self.cfg.vocab), bpe_path
             tokens = torch.from_numpy(self._bpe.tokenize(list(text), context_length=self.cfg.max_len, truncate=True))
         return self.encode_tokens(tokens.to(device))
-
-    def close(self):
-        if self.handle:
-            self.lib.mc_textenc_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -8,7 +8,6 @@ the convolutions themselves run as MFMA GEMMs in libmotioncraft_amd.so.
 import ctypes
 from collections import OrderedDict
 
-import numpy as np
 import torch
 
 from . import lib as _lib
@@ -63,18 +62,12 @@ def pack_wav_encoder(state_dict, prefix=''):
     return out
 
 
-class NativeWavEncoder:
+class NativeWavEncoder(_lib.NativeObject):
     def __init__(self, out_dim, audio_in, state_dict, prefix=''):
-        self.lib = _lib.load(require_gpu=True)
         self.out_dim, self.audio_in = int(out_dim), int(audio_in)
-        h = ctypes.c_void_p()
-        _lib.check(self.lib.mc_wavenc_create(self.audio_in, self.out_dim, ctypes.byref(h)), 'mc_wavenc_create')
-        self.handle = h
-        for name, t in pack_wav_encoder(state_dict, prefix).items():
-            a = np.ascontiguousarray(t.numpy(), dtype=np.float32)
-            _lib.check(self.lib.mc_wavenc_set_param(self.handle, name.encode(), a.ctypes.data_as(ctypes.c_void_p), a.size),
-                       f'mc_wavenc_set_param({name})')
-        _lib.check(self.lib.mc_wavenc_finalize(self.handle), 'mc_wavenc_finalize')
+        super().__init__('wavenc', self.audio_in, self.out_dim)
+        self.upload((name, t.numpy()) for name, t in pack_wav_encoder(state_dict, prefix).items())
+        self.finalize()
 
     def out_len(self, samples):
         n = ctypes.c_int32()
@@ -99,14 +92,3 @@ class NativeWavEncoder:
         return out
 
     forward = __call__
-
-    def close(self):
-        if self.handle:
-            self.lib.mc_wavenc_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
