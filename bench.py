@@ -3,8 +3,12 @@
 1000-step DDPM with classifier-free guidance, synthetic inputs (BASELINE.json configs[1]:
 batch=64 per GPU).
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does only what `value` needs: set-up, W warm-up steps, the K timed steps, the gather, the outputs of
+--dump-outputs and the JSON line.  --full adds every side measurement listed below (the complete 1000-step loop, the other
+precisions and configs, the CPU oracle); --no-full-loop / --no-extras / --no-cpu-baseline leave parts of it out.
 
 A "step" is one pass of the hot path over one batch: denoiser (CFG-doubled) + CFG combine +
 p_sample update, including the per-step noise draw (on the device, inside the sampler-update
@@ -25,9 +29,15 @@ arguments can be compared output for output.
 Extra objects on the JSON line:
   roofline      bound "mfma": algorithmic FLOPs of one step (SURVEY.md section 8d figure x samples)
                 / mean step duration from HIP events on the launch stream, vs the 157.3 TFLOP/s
-                fp32-matrix peak (v_mfma_f32_32x32x2_f32; MI355X_MICROARCH.md)
-  cpu_baseline  the CPU oracle (oracle/stmogen_oracle.py, kind "port") timed on this host's cores,
-                rank 0, N=1 only, bounded sample
+                fp32-matrix peak (v_mfma_f32_32x32x2_f32; MI355X_MICROARCH.md); traffic and dominant
+                kernel are read from the tracked profiles/ tables
+  --full only (null / absent otherwise):
+  config.full_loop                 the complete 1000-step loop, measured against the extrapolated `value`
+  config.two_batches_in_flight, config.reduced_precision_modes, config.configs0_gpu, config.configs4,
+  config.control_configs           side measurements of other schedules, precisions and BASELINE configs
+                                   (rank 0, N=1 only)
+  cpu_baseline                     the CPU oracle (oracle/stmogen_oracle.py, kind "port") timed on this
+                                   host's cores, rank 0, N=1 only, bounded sample
 """
 import argparse
 import json
@@ -229,9 +239,12 @@ def main():
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--batch', type=int, default=64, help='samples per GPU (BASELINE configs[1]: 64)')
     ap.add_argument('--frames', type=int, default=196)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extras', action='store_true', help='skip the side measurements (dominant-kernel probe, 2 batches in flight)')
-    ap.add_argument('--no-full-loop', action='store_true', help='skip the complete 1000-step loop (measured-vs-extrapolated check, ~20 s)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also run the side measurements: the complete 1000-step loop, 2 batches in flight, the '
+                         'reduced-precision modes, BASELINE configs[0] / [2] / [3] / [4] and the CPU oracle (off: the headline alone)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU oracle')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: skip the side measurements of other schedules, precisions and configs')
+    ap.add_argument('--no-full-loop', action='store_true', help='with --full: skip the complete 1000-step loop (measured-vs-extrapolated check, ~20 s)')
     ap.add_argument('--backend', default='nccl', help="'nccl' (= RCCL over xGMI); 'gloo' only for plumbing smoke tests")
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='write what the last timed step returned (rank 0: x [B,T,322] after the K timed steps) as DIR/x.npy, float32, '
@@ -251,6 +264,10 @@ def main():
     world = int(os.environ.get('WORLD_SIZE', 1))
     if a.gpus != world:
         raise SystemExit(f'--gpus {a.gpus} but WORLD_SIZE={world}: launch one rank per GPU')
+    # what runs besides the headline: nothing unless --full (the side measurements and the CPU oracle on rank 0 at N=1 only)
+    full_loop_on = a.full and not a.no_full_loop
+    extras_on = a.full and not a.no_extras and rank == 0 and world == 1
+    cpu_baseline_on = a.full and not a.no_cpu_baseline and world == 1
     if os.environ.get('MC_BENCH_ALL_ON_DEVICE0'):      # plumbing smoke test of the N>1 path on a 1-GPU box (gloo)
         local_rank = 0
     torch.cuda.set_device(local_rank)
@@ -280,7 +297,9 @@ def main():
     sd = make_state_dict(DIMS, 0)
     nm = NativeModel(DIMS, sd, cfg_scale=DIMS['scale'], device=local_rank)
     del sd
-    side_streams = [torch.cuda.Stream(), torch.cuda.Stream()]      # for the 2-batches-in-flight side measurement
+    # for the 2-batches-in-flight side measurement; created here in every run, so the timed steps find the same hardware-queue
+    # layout with or without --full (HIP hands streams to hardware queues round-robin as they are created)
+    side_streams = [torch.cuda.Stream(), torch.cuda.Stream()]
     ctx = nm.context(B, T, max_steps=TOTAL_DDPM_STEPS)
     diff = build_diffusion(dict(beta_scheduler='linear', diffusion_steps=1000, model_mean_type='start_x',
                                 model_var_type='fixed_large'))
@@ -343,7 +362,7 @@ def main():
     # ---- the COMPLETE loop once, outside the K-step region: x_T -> x_0 over all 1000 steps, every step index used once
     # (`value` extrapolates 1000 * t_step from the K timed steps; this is the measured counterpart) ----
     t_full = None
-    if not a.no_full_loop:
+    if full_loop_on:
         x.normal_(generator=gen)
         barrier()
         t0 = time.perf_counter()
@@ -368,7 +387,7 @@ def main():
     # ---- side measurement (NOT `value`): two independent batches of B in flight on this GPU, one HIP stream and one
     # context each -- what a test loop over many batches of 64 can do; each batch keeps its own MoE capacity domain ----
     inflight2 = None
-    if rank == 0 and world == 1 and not a.no_extras:
+    if extras_on:
         try:
             s2 = side_streams
             c2, x2, n2 = [], [], []
@@ -406,7 +425,7 @@ def main():
     # 'f16x3' = fp16 hi/lo split operands, three products, fp32 accumulate (fp32-class results: tests hold it to the same
     # 1e-3 lockstep bound, observed 1.3e-5); 'f16' = one fp16 rounding per operand.  Gate / routing / normalisations fp32. ----
     reduced = None
-    if rank == 0 and world == 1 and not a.no_extras:
+    if extras_on:
         try:
             reduced = {}
             for prec in ('f16x3', 'f16'):
@@ -440,7 +459,7 @@ def main():
 
     # ---- BASELINE configs[0] on the GPU (NOT `value`): batch 1, 196 frames, the complete 50-step DDIM loop, one library call ----
     configs0 = None
-    if rank == 0 and world == 1 and not a.no_extras:
+    if extras_on:
         try:
             d50 = build_diffusion(dict(beta_scheduler='linear', diffusion_steps=1000, model_mean_type='start_x',
                                        model_var_type='fixed_large', respace='15,15,8,6,6'))
@@ -468,7 +487,7 @@ def main():
     # (tools/test.py:95-97 wrap_fp16_model), the COMPLETE 50-step DDIM loop as hipGraph replays (one captured step, device-side step
     # index), per-GPU batch 32 (configs[2]'s 256 / 8), 196 frames ----
     configs4 = None
-    if rank == 0 and world == 1 and not a.no_extras:
+    if extras_on:
         try:
             from motioncraft_amd.synthetic import control_param_shapes
             copy, feats, B4 = 2, DIMS['L'] * DIMS['H'], 32
@@ -536,7 +555,7 @@ def main():
     #               encoded once per batch: tools/control_bench.py times it), batch 256 over 8 GPUs = 32 x 196 frames per GPU
     #   configs[3]  M2D_finedance: L=64, F=256, 4 + 3 layers, 35-d music features, 128 sequences x 5 windows of 120 frames over 4 GPUs = 160 windows
     control_cfgs = None
-    if rank == 0 and world == 1 and not a.no_extras:
+    if extras_on:
         try:
             from motioncraft_amd.synthetic import control_param_shapes
             control_cfgs = {}
@@ -663,7 +682,7 @@ def main():
                          'algorithmic_gflop_per_sample_step': round(algorithmic_flops_per_sample_step(DIMS, T) / 1e9, 3),
                          'event_ms_per_step': round(ev_ms, 4), 'dominant_kernel': dom},
         }
-        if world == 1 and not a.no_cpu_baseline:
+        if cpu_baseline_on:
             line['cpu_baseline'] = cpu_baseline()
         if x_timed is not None:
             import numpy as np

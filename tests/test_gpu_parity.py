@@ -1543,6 +1543,26 @@ def test_sample_tool_writes_the_amass_style_npz(tmp_path):
     assert np.load(path)['poses'].shape == (24, 165)
 
 
+def test_plain_bench_run_prints_the_headline_alone(tmp_path):
+    """`bench.py` without --full (a small batch here) runs the timed steps and nothing else: the JSON line carries the headline fields,
+    every --full object is null or absent, and --dump-outputs writes the x the timed steps returned."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(HERE)
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1', '--batch', '4',
+                        '--dump-outputs', str(tmp_path)], cwd=root, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line['value'] > 0 and line['ms_per_step'] > 0 and line['unit'] == 'frames/s' and line['higher_is_better'] is True
+    assert line['dtype'] == 'f32' and line['steps'] == 2 and line['warmup'] == 1
+    assert 'cpu_baseline' not in line
+    for k in ('full_loop', 'reduced_precision_modes', 'configs0_gpu', 'configs4', 'control_configs', 'two_batches_in_flight'):
+        assert line['config'][k] is None, k
+    x = np.load(os.path.join(str(tmp_path), 'x.npy'))
+    assert x.shape == (4, 196, 322) and x.dtype == np.float32 and np.isfinite(x).all()
+
+
 def test_smplx_postprocessing_vs_scipy_restatement(tmp_path):
     """de-normalise + 322 -> poses/expressions/trans + scipy gaussian_filter(mode='nearest') on the
     device, against oracle/postprocess_oracle.py (the reference tools' own numpy/scipy lines), for float32 stats files
