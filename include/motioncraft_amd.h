@@ -254,6 +254,12 @@ int mc_op_gemm(const float* a_dev, const float* w_dev, const float* bias_dev, co
 /* C = A W^T + bias + res on the fp16 MFMA (split != 0: hi/lo three-product form); N % 128 == 0, K % 32 == 0; synchronises */
 int mc_op_gemm_f16(const float* a_dev, const float* w_dev, const float* bias_dev, const float* res_dev, float* c_dev,
                    int32_t M, int32_t N, int32_t K, int32_t split, void* stream);
+/* the same product from caller-built fp16 planes of A (the kernels a reduced-precision context feeds from film_rows_k's planes; tests):
+ * a_hi / a_lo [M][K] halves, or fragment-major (frag_major != 0: half (((r >> 5) (K >> 4) + s) 64 + (r & 31) + 32 h) 8 + e holds column
+ * 16 s + 8 h + e of row r); a_lo is read only when split != 0; W fp32, split here; pre != 0: the row-major kernel prefetches res.
+ * N % 128 == 0, K % 64 == 0 (fragment-major: M % 32 == 0, K >= 192); synchronises */
+int mc_op_gemm_f16_planes(const void* a_hi_dev, const void* a_lo_dev, const float* w_dev, const float* bias_dev, const float* res_dev,
+                          float* c_dev, int32_t M, int32_t N, int32_t K, int32_t split, int32_t pre, int32_t frag_major, void* stream);
 /* the folded decoder tail as one op (stmogen.py:505-544 + 757-760 after the CFG combination, motioncraft_amd/csrc/mc_gemm.hip):
  *   C[r] = (wc h[r] + wu h[r + M]) W[0]^T + (wc a[r] + wu a[r + M]) W[1]^T + bias[0] + bias[1]
  * h, a [2 M][K] (conditional rows, then the unconditional ones), W [2][N][K], bias [2][N], C [M][N]; c2_dev: scratch [M][N] (the

@@ -1729,6 +1729,25 @@ int mc_op_gemm_f16(const float* a, const float* w, const float* bias, const floa
     return r;
 }
 
+int mc_op_gemm_f16_planes(const void* a_hi, const void* a_lo, const float* w, const float* bias, const float* res, float* cdev, int32_t M,
+                          int32_t N, int32_t K, int32_t split, int32_t pre, int32_t frag_major, void* stream) {
+    MC_REQUIRE(a_hi && (!split || a_lo) && w && cdev && M > 0 && N > 0 && K > 0, "bad gemm args");
+    hipStream_t s = (hipStream_t)stream;
+    mc_half* planes = nullptr;
+    MC_HIP(hipMalloc((void**)&planes, sizeof(mc_half) * 2 * (size_t)N * K));
+    int r = mc_launch_split_f16(w, planes, planes + (size_t)N * K, (long)N * K, s);
+    if (r == MC_OK) {
+        GemmHArgs g;
+        g.Ah = (const mc_half*)a_hi; g.Al = (const mc_half*)a_lo; g.Wh = planes; g.Wl = planes + (size_t)N * K;
+        g.bias = bias; g.R = res; g.ldr = N; g.C = cdev; g.ldc = N;
+        g.M = M; g.N = N; g.K = K; g.a_fm = frag_major != 0; g.pre = pre != 0;
+        r = mc_launch_gemm_h(g, split != 0, s);
+    }
+    (void)hipStreamSynchronize(s);
+    (void)hipFree(planes);
+    return r;
+}
+
 int mc_op_gemm_tail(const float* h, const float* a, const float* w, const float* bias, float* cdev, float* c2dev, int32_t M, int32_t N,
                     int32_t K, float wc, float wu, int32_t variant, void* stream) {
     MC_REQUIRE(h && a && w && bias && cdev && M > 0 && N > 0 && K > 0 && K % 32 == 0, "bad gemm_tail args");

@@ -952,13 +952,25 @@ def test_fp16_mfma_gemm_op_vs_fp64():
         ref = a.double() @ w.double().T + b.double() + r.double()
         scale = float(ref.abs().max())
         ad, wd, bd, rd = a.cuda(), w.cuda(), b.cuda(), r.cuda()          # (kept alive: the ABI takes raw pointers)
+        # the products the kernel forms, in fp64 (rows ::7 and the last one): hi Wh, + hi Wl + lo Wh in the split form; what is left
+        # is fp32 accumulation, u (n K (|products| + |b|) + 4 |pre| + |R| + 4 |ref|) with n = 3 / 1 products per k
+        rows = torch.cat([torch.arange(0, M, 7), torch.tensor([M - 1])])
+        hi, wh = a[rows].half(), w.half()
+        lo, wl = (a[rows] - hi.float()).half(), (w - wh.float()).half()
+        hi, lo, wh, wl = hi.double(), lo.double(), wh.double(), wl.double()
         for split, tol in ((1, 4e-6), (0, 4e-3)):
             c = torch.full((M, N), float('nan'), device='cuda')
             L_.check(lib.mc_op_gemm_f16(_ptr(ad), _ptr(wd), _ptr(bd), _ptr(rd), _ptr(c), M, N, K, split, st))
             torch.cuda.synchronize()
             err = float((c.cpu().double() - ref).abs().max()) / scale
-            print(f'fp16 MFMA gemm {M}x{N}x{K} split={split}: max rel err {err:.2e}')
+            pre = hi @ wh.T + ((hi @ wl.T + lo @ wh.T) if split else 0) + b.double()
+            absdot = hi.abs() @ wh.abs().T + ((hi.abs() @ wl.abs().T + lo.abs() @ wh.abs().T) if split else 0)
+            ref_p = pre + r[rows].double()
+            bound = 2.0 ** -24 * ((3 if split else 1) * K * (absdot + b.double().abs()) + 4 * pre.abs() + r[rows].double().abs() + 4 * ref_p.abs())
+            ratio = float(((c.cpu()[rows].double() - ref_p).abs() / bound).max())
+            print(f'fp16 MFMA gemm {M}x{N}x{K} split={split}: max rel err {err:.2e}; vs its own products: max err / bound {ratio:.3f}')
             assert err <= tol, (M, N, K, split, err)
+            assert ratio <= 1.0, (M, N, K, split, ratio)
     c32 = torch.empty(M, N, device='cuda')          # the exact fp32 MFMA path on the same operands for comparison
     L_.check(lib.mc_op_gemm(_ptr(ad), _ptr(wd), _ptr(bd), _ptr(rd), _ptr(c32), M, N, K, K, 0, st))
     torch.cuda.synchronize()
