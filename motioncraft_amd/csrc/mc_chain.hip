@@ -16,6 +16,7 @@
 #include "mc_common.h"
 #include "mc_chain.h"
 #include "mc_bodyphase.h"
+#include "mc_dispatch.h"
 #include <stdlib.h>
 
 namespace {
@@ -732,29 +733,18 @@ int mc_launch_mlp(int mode, const MlpArgs& g, int groups, int max_tiles, hipStre
         const double rows = mode == MLP_EXPERT ? (double)g.ledger_rows : (double)g.M * groups;
         MC_LEDGER(name, grid, rows * 4.0 * g.L * g.hidden);          // FC1 + FC2, multiply-add = 2
     }
+    const int m = mode == MLP_EXPERT ? MLP_EXPERT : MLP_PARTS;
     if (dma_form) {
-        if (g.L == 128) {
-            if (mode == MLP_EXPERT) hipLaunchKernelGGL((mlp2d_k<128, MLP_EXPERT>), grid, dim3(256), 0, s, g);
-            else hipLaunchKernelGGL((mlp2d_k<128, MLP_PARTS>), grid, dim3(256), 0, s, g);
-        } else {
-            if (mode == MLP_EXPERT) hipLaunchKernelGGL((mlp2d_k<64, MLP_EXPERT>), grid, dim3(256), 0, s, g);
-            else hipLaunchKernelGGL((mlp2d_k<64, MLP_PARTS>), grid, dim3(256), 0, s, g);
-        }
+        mc_dispatch<128, 64>(g.L, [&](auto L) {
+            mc_dispatch<MLP_EXPERT, MLP_PARTS>(m, [&](auto M) { hipLaunchKernelGGL((mlp2d_k<MC_V(L), MC_V(M)>), grid, dim3(256), 0, s, g); });
+        });
         MC_LAUNCH_CHECK();
         return MC_OK;
     }
-#define MC_MLP_CASE(LL)                                                                              \
-    case LL:                                                                                         \
-        if (mode == MLP_EXPERT) hipLaunchKernelGGL((mlp2_k<LL, MLP_EXPERT>), grid, dim3(256), 0, s, g); \
-        else hipLaunchKernelGGL((mlp2_k<LL, MLP_PARTS>), grid, dim3(256), 0, s, g);                  \
-        break;
-    switch (g.L) {
-        MC_MLP_CASE(128)
-        MC_MLP_CASE(64)
-        MC_MLP_CASE(32)
-        default: mc_set_error("fused mlp: L=%d unsupported", g.L); return MC_ERR_ARG;
-    }
-#undef MC_MLP_CASE
+    const bool known = mc_dispatch<128, 64, 32>(g.L, [&](auto L) {
+        mc_dispatch<MLP_EXPERT, MLP_PARTS>(m, [&](auto M) { hipLaunchKernelGGL((mlp2_k<MC_V(L), MC_V(M)>), grid, dim3(256), 0, s, g); });
+    });
+    MC_REQUIRE(known, "fused mlp: L=%d unsupported", g.L);
     MC_LAUNCH_CHECK();
     return MC_OK;
 }
@@ -771,22 +761,14 @@ int mc_launch_gate(const GateArgs& g, hipStream_t s) {
     }
     if (g.N - g.tok0 <= g.small_tokens) {        // latency-bound sizes (B <= 2 at 196 frames; B=1 -2.8 ms per 50 steps, B=4 +1 ms): 32-token workgroups
         dim3 grid(cdiv(g.N - g.tok0, 32));
-        switch (g.L) {
-            case 128: hipLaunchKernelGGL(gate_small_k<128>, grid, dim3(256), 0, s, g); break;
-            case 64: hipLaunchKernelGGL(gate_small_k<64>, grid, dim3(256), 0, s, g); break;
-            case 32: hipLaunchKernelGGL(gate_small_k<32>, grid, dim3(256), 0, s, g); break;
-            default: mc_set_error("gate: L=%d unsupported", g.L); return MC_ERR_ARG;
-        }
+        const bool known = mc_dispatch<128, 64, 32>(g.L, [&](auto L) { hipLaunchKernelGGL(gate_small_k<MC_V(L)>, grid, dim3(256), 0, s, g); });
+        MC_REQUIRE(known, "gate: L=%d unsupported", g.L);
         MC_LAUNCH_CHECK();
         return MC_OK;
     }
     dim3 grid(cdiv(g.N - g.tok0, 128));
-    switch (g.L) {
-        case 128: hipLaunchKernelGGL(gate_k<128>, grid, dim3(256), 0, s, g); break;
-        case 64: hipLaunchKernelGGL(gate_k<64>, grid, dim3(256), 0, s, g); break;
-        case 32: hipLaunchKernelGGL(gate_k<32>, grid, dim3(256), 0, s, g); break;
-        default: mc_set_error("gate: L=%d unsupported", g.L); return MC_ERR_ARG;
-    }
+    const bool known = mc_dispatch<128, 64, 32>(g.L, [&](auto L) { hipLaunchKernelGGL(gate_k<MC_V(L)>, grid, dim3(256), 0, s, g); });
+    MC_REQUIRE(known, "gate: L=%d unsupported", g.L);
     MC_LAUNCH_CHECK();
     return MC_OK;
 }
@@ -887,12 +869,8 @@ int mc_launch_projqkv(const RowChainArgs& g, hipStream_t s) {
         snprintf(name, sizeof(name), "projqkv_k<%d>", g.L);
         MC_LEDGER(name, grid, 2.0 * (double)mc_ledger_tokens(g) * 7.0 * g.L * g.L);        // proj [4L, L] + q/k/v [3L, L]
     }
-    switch (g.L) {
-        case 128: hipLaunchKernelGGL(projqkv_k<128>, grid, dim3(256), 0, s, g); break;
-        case 64: hipLaunchKernelGGL(projqkv_k<64>, grid, dim3(256), 0, s, g); break;
-        case 32: hipLaunchKernelGGL(projqkv_k<32>, grid, dim3(256), 0, s, g); break;
-        default: mc_set_error("projqkv: L=%d unsupported", g.L); return MC_ERR_ARG;
-    }
+    const bool known = mc_dispatch<128, 64, 32>(g.L, [&](auto L) { hipLaunchKernelGGL(projqkv_k<MC_V(L)>, grid, dim3(256), 0, s, g); });
+    MC_REQUIRE(known, "projqkv: L=%d unsupported", g.L);
     MC_LAUNCH_CHECK();
     return MC_OK;
 }
@@ -1044,8 +1022,7 @@ int mc_launch_pqbody(const RowChainArgs& g, int H, hipStream_t s) {
         const double toks = (double)(mc_ledger_tokens(g)), hd = g.L / 8.0;      // (aliased twins -- the tail of the range -- exit at once in the usual case)
         MC_LEDGER(name, grid, 2.0 * toks * 7.0 * g.L * g.L + (toks / H) * (2.0 * H * H * g.L + 8 * 2.0 * (2.0 * H * hd * hd)));
     }
-    if (g.L == 128) hipLaunchKernelGGL((pqbody_k<128, 12>), grid, dim3(256), 0, s, g);
-    else hipLaunchKernelGGL((pqbody_k<64, 12>), grid, dim3(256), 0, s, g);
+    mc_dispatch<128, 64>(g.L, [&](auto L) { hipLaunchKernelGGL((pqbody_k<MC_V(L), 12>), grid, dim3(256), 0, s, g); });      // (L, H checked above)
     MC_LAUNCH_CHECK();
     return MC_OK;
 }
@@ -1059,18 +1036,10 @@ int mc_launch_rowchain(int kind, const RowChainArgs& g, hipStream_t s) {
         snprintf(name, sizeof(name), "rowchain_k<%d, %d>", g.L, kind ? 1 : 0);
         MC_LEDGER(name, grid, 2.0 * (double)mc_ledger_tokens(g) * g.Nout * g.L);
     }
-#define MC_RC_CASE(LL)                                                                    \
-    case LL:                                                                              \
-        if (kind == 0) hipLaunchKernelGGL((rowchain_k<LL, 0>), grid, dim3(256), 0, s, g);  \
-        else hipLaunchKernelGGL((rowchain_k<LL, 1>), grid, dim3(256), 0, s, g);            \
-        break;
-    switch (g.L) {
-        MC_RC_CASE(128)
-        MC_RC_CASE(64)
-        MC_RC_CASE(32)
-        default: mc_set_error("rowchain: L=%d unsupported", g.L); return MC_ERR_ARG;
-    }
-#undef MC_RC_CASE
+    const bool known = mc_dispatch<128, 64, 32>(g.L, [&](auto L) {
+        mc_dispatch<0, 1>(kind ? 1 : 0, [&](auto K) { hipLaunchKernelGGL((rowchain_k<MC_V(L), MC_V(K)>), grid, dim3(256), 0, s, g); });
+    });
+    MC_REQUIRE(known, "rowchain: L=%d unsupported", g.L);
     MC_LAUNCH_CHECK();
     return MC_OK;
 }

@@ -14,6 +14,7 @@
 #include "mc_common.h"
 #include "mc_half.h"
 #include "mc_bodyphase.h"
+#include "mc_dispatch.h"
 
 namespace {
 
@@ -1441,33 +1442,26 @@ int mc_launch_mlp_h(int mode, const MlpArgs& g, const mc_half* W1h, const mc_hal
         const double rows = mode == MLP_EXPERT ? (double)g.ledger_rows : (double)g.M * groups;
         MC_LEDGER(name, grid, rows * 4.0 * g.L * g.hidden);
     }
+    const int m = mode == MLP_EXPERT ? MLP_EXPERT : MLP_PARTS;
     if (g.dma && (g.L == 128 || g.L == 64)) {     // LDS-DMA staged weight chunks (chain bit 18): the same bits
-#define MC_MLPHD(LL, MM, SS) hipLaunchKernelGGL((mlp2hd_k<LL, MM, SS>), grid, dim3(256), 0, s, g, W1h, W1l, W2h, W2l)
-        if (g.L == 128) {
-            if (mode == MLP_EXPERT) { if (split) MC_MLPHD(128, MLP_EXPERT, true); else MC_MLPHD(128, MLP_EXPERT, false); }
-            else { if (split) MC_MLPHD(128, MLP_PARTS, true); else MC_MLPHD(128, MLP_PARTS, false); }
-        } else {
-            if (mode == MLP_EXPERT) { if (split) MC_MLPHD(64, MLP_EXPERT, true); else MC_MLPHD(64, MLP_EXPERT, false); }
-            else { if (split) MC_MLPHD(64, MLP_PARTS, true); else MC_MLPHD(64, MLP_PARTS, false); }
-        }
-#undef MC_MLPHD
+        mc_dispatch<128, 64>(g.L, [&](auto L) {
+            mc_dispatch<MLP_EXPERT, MLP_PARTS>(m, [&](auto M) {
+                mc_dispatch<0, 1>(split, [&](auto S) {
+                    hipLaunchKernelGGL((mlp2hd_k<MC_V(L), MC_V(M), bool(MC_V(S))>), grid, dim3(256), 0, s, g, W1h, W1l, W2h, W2l);
+                });
+            });
+        });
         MC_LAUNCH_CHECK();
         return MC_OK;
     }
-#define MC_MLPH(LL, MM, SS) hipLaunchKernelGGL((mlp2_h_k<LL, MM, SS>), grid, dim3(256), 0, s, g, W1h, W1l, W2h, W2l)
-#define MC_MLPH_CASE(LL)                                                       \
-    case LL:                                                                   \
-        if (mode == MLP_EXPERT) { if (split) MC_MLPH(LL, MLP_EXPERT, true); else MC_MLPH(LL, MLP_EXPERT, false); } \
-        else { if (split) MC_MLPH(LL, MLP_PARTS, true); else MC_MLPH(LL, MLP_PARTS, false); }                      \
-        break;
-    switch (g.L) {
-        MC_MLPH_CASE(128)
-        MC_MLPH_CASE(64)
-        MC_MLPH_CASE(32)
-        default: mc_set_error("fp16 fused mlp: L=%d unsupported", g.L); return MC_ERR_ARG;
-    }
-#undef MC_MLPH_CASE
-#undef MC_MLPH
+    const bool known = mc_dispatch<128, 64, 32>(g.L, [&](auto L) {
+        mc_dispatch<MLP_EXPERT, MLP_PARTS>(m, [&](auto M) {
+            mc_dispatch<0, 1>(split, [&](auto S) {
+                hipLaunchKernelGGL((mlp2_h_k<MC_V(L), MC_V(M), bool(MC_V(S))>), grid, dim3(256), 0, s, g, W1h, W1l, W2h, W2l);
+            });
+        });
+    });
+    MC_REQUIRE(known, "fp16 fused mlp: L=%d unsupported", g.L);
     MC_LAUNCH_CHECK();
     return MC_OK;
 }
@@ -1487,13 +1481,11 @@ int mc_launch_pqbody_h(const RowChainArgs& g, int H, const mc_half* Wph, const m
         const double toks = (double)(mc_ledger_tokens(g)), hd = g.L / 8.0;      // (aliased twins -- the tail of the range -- exit at once in the usual case)
         MC_LEDGER(name, grid, 2.0 * toks * 7.0 * g.L * g.L + (toks / H) * (2.0 * H * H * g.L + 8 * 2.0 * (2.0 * H * hd * hd)));
     }
-    if (g.L == 128) {
-        if (split) hipLaunchKernelGGL((pqbody_h_k<128, 12, true>), grid, dim3(256), 0, s, g, Wph, Wpl, Wqh, Wql);
-        else hipLaunchKernelGGL((pqbody_h_k<128, 12, false>), grid, dim3(256), 0, s, g, Wph, Wpl, Wqh, Wql);
-    } else {
-        if (split) hipLaunchKernelGGL((pqbody_h_k<64, 12, true>), grid, dim3(256), 0, s, g, Wph, Wpl, Wqh, Wql);
-        else hipLaunchKernelGGL((pqbody_h_k<64, 12, false>), grid, dim3(256), 0, s, g, Wph, Wpl, Wqh, Wql);
-    }
+    mc_dispatch<128, 64>(g.L, [&](auto L) {      // (L, H checked above)
+        mc_dispatch<0, 1>(split, [&](auto S) {
+            hipLaunchKernelGGL((pqbody_h_k<MC_V(L), 12, bool(MC_V(S))>), grid, dim3(256), 0, s, g, Wph, Wpl, Wqh, Wql);
+        });
+    });
     MC_LAUNCH_CHECK();
     return MC_OK;
 }
@@ -1509,15 +1501,12 @@ int mc_launch_projqkv_h(const RowChainArgs& g, const mc_half* Wph, const mc_half
         snprintf(name, sizeof(name), "projqkv_h_k<%d, %s>", g.L, split ? "true" : "false");
         MC_LEDGER(name, grid, 2.0 * (double)mc_ledger_tokens(g) * 7.0 * g.L * g.L);
     }
-#define MC_PQH(LL) case LL: if (split) hipLaunchKernelGGL((projqkv_h_k<LL, true>), grid, dim3(256), 0, s, g, Wph, Wpl, Wqh, Wql); \
-                            else hipLaunchKernelGGL((projqkv_h_k<LL, false>), grid, dim3(256), 0, s, g, Wph, Wpl, Wqh, Wql); break;
-    switch (g.L) {
-        MC_PQH(128)
-        MC_PQH(64)
-        MC_PQH(32)
-        default: mc_set_error("fp16 projqkv: L=%d unsupported", g.L); return MC_ERR_ARG;
-    }
-#undef MC_PQH
+    const bool known = mc_dispatch<128, 64, 32>(g.L, [&](auto L) {
+        mc_dispatch<0, 1>(split, [&](auto S) {
+            hipLaunchKernelGGL((projqkv_h_k<MC_V(L), bool(MC_V(S))>), grid, dim3(256), 0, s, g, Wph, Wpl, Wqh, Wql);
+        });
+    });
+    MC_REQUIRE(known, "fp16 projqkv: L=%d unsupported", g.L);
     MC_LAUNCH_CHECK();
     return MC_OK;
 }
