@@ -24,6 +24,8 @@
  *                                                                      mogen/models/rnns/t2m_bigru.py:72-299
  *   mc_wavenc_*           WavEncoder (audio condition pre-encoder)     mogen/models/utils/blocks.py:11-71; controlnet.py:90-105,187
  *   mc_postprocess_smplx  de-normalise + SMPL-X re-pack + temporal filter  tools/visualize.py:39-44,217-246; tools/s2g_test.py:289-297
+ *   mc_postprocess_t2m_joints  HumanML3D / KIT features -> filtered joint positions (plot_t2m, recover_from_ric)
+ *                                                                      tools/visualize.py:46-56; mogen/utils/plot_utils.py:40-104
  *   mc_op_renoise         GaussianDiffusion._undo (resampling jumps)   gaussian_diffusion.py:429-435, 1113-1118
  *
  * Conventions: plain pointers and sizes only.  `*_dev` pointers are device (HBM) addresses owned
@@ -292,6 +294,27 @@ int mc_postprocess_smplx_stitched(const float* pred_dev, const int32_t* rows_dev
                                   const double* mean_dev, const double* std_dev, const double* taps_dev,
                                   const int32_t radius[4], int32_t stats_f32, int32_t C, double* poses_dev,
                                   double* expr_dev, double* trans_dev, void* stream);
+
+/* Joint positions from the HumanML3D (263-d, 22 joints) / KIT (251-d, 21 joints) feature vector: what the sampling
+ * tool saves as --pose_npy (tools/visualize.py:46-56 -> recover_from_ric, mogen/utils/plot_utils.py:40-104).
+ * data = float(pred * std + mean); yaw[t] = sum_{s<t} data[s,0]; root xz = running sum of the yaw-rotated velocities
+ * data[t-1,1:3], root y = data[t,3]; joint j >= 1 = yaw-rotated data[t, 4+3(j-1) : 4+3j] + root xz; then every
+ * (joint, axis) track is filtered over time with the normalised Gaussian taps_dev [MC_POST_MAXTAP] fp64 centred at
+ * `radius` (edge frames replicated; radius < 0: unfiltered, taps_dev may be NULL).  Arithmetic after the fp32 rounding
+ * of `data` is fp64.  pred_dev [B,T,C] normalised, lengths_dev [B] int32 valid frames (NULL = T): each sample is a
+ * sequence of its own; mean/std_dev [C] fp64, stats_f32 as above.  C must equal 4 + 9 (J-1) + 3 J + 4 for
+ * J = joints_num >= 2, and T <= 1024.  joints_out_dev fp32 [B,T,J,3]; frames >= length are 0. */
+int mc_postprocess_t2m_joints(const float* pred_dev, const int32_t* lengths_dev, const double* mean_dev,
+                              const double* std_dev, const double* taps_dev, int32_t radius, int32_t stats_f32,
+                              int32_t B, int32_t T, int32_t C, int32_t joints_num, float* joints_out_dev, void* stream);
+/* The same over the STITCHED sequence of several intervals (tools/visualize.py:217-232): rows_dev as in
+ * mc_postprocess_smplx_stitched; the yaw and root sums AND the filter run over all n_frames (any number), so the
+ * motion carries across the seams.  work_dev: caller-owned scratch of 4 * n_frames doubles (per-frame root state).
+ * joints_out_dev fp32 [n_frames,J,3]. */
+int mc_postprocess_t2m_joints_stitched(const float* pred_dev, const int32_t* rows_dev, int32_t n_frames,
+                                       const double* mean_dev, const double* std_dev, const double* taps_dev,
+                                       int32_t radius, int32_t stats_f32, int32_t C, int32_t joints_num,
+                                       double* work_dev, float* joints_out_dev, void* stream);
 
 /* ---- text condition encoder (encode_text, diffusion_transformer.py:142-172); run once per prompt batch -------- */
 typedef struct mc_textenc mc_textenc;

@@ -102,6 +102,11 @@ int mc_launch_smplx_post(const float* pred, const int* lengths, const int* rows,
                          const double* taps, const int* radius, int stats_f32, int B, int T, int C,
                          double* poses, double* expr, double* trans, hipStream_t s);
 int mc_smplx_post_maxtap();
+// HumanML3D / KIT features [B][T][C] -> filtered joint positions [B][T][J][3] (recover_from_ric + tools/visualize.py:46-48);
+// rows != null: the stitched sequence (B == 1, T mapped frames, root_work [T][4])
+int mc_launch_t2m_joints(const float* pred, const int* lengths, const int* rows, const double* mean, const double* stdv,
+                         const double* taps, int radius, int stats_f32, int B, int T, int C, int J, double* root_work,
+                         float* joints, hipStream_t s);
 
 // ---- mc_route.hip ---------------------------------------------------------------------
 struct RouteBufs {

@@ -1659,6 +1659,24 @@ int mc_postprocess_smplx_stitched(const float* pred, const int32_t* rows, int32_
                                 trans, (hipStream_t)stream);
 }
 
+int mc_postprocess_t2m_joints(const float* pred, const int32_t* lengths, const double* mean, const double* stdv,
+                              const double* taps, int32_t radius, int32_t stats_f32, int32_t B, int32_t T, int32_t C,
+                              int32_t joints_num, float* joints, void* stream) {
+    MC_REQUIRE(pred && mean && stdv && joints && (taps || radius < 0), "null argument");
+    MC_REQUIRE(mc_smplx_post_maxtap() == MC_POST_MAXTAP, "tap table size mismatch");
+    return mc_launch_t2m_joints(pred, lengths, nullptr, mean, stdv, taps, radius, stats_f32, B, T, C, joints_num, nullptr,
+                                joints, (hipStream_t)stream);
+}
+
+int mc_postprocess_t2m_joints_stitched(const float* pred, const int32_t* rows, int32_t n_frames, const double* mean,
+                                       const double* stdv, const double* taps, int32_t radius, int32_t stats_f32,
+                                       int32_t C, int32_t joints_num, double* work, float* joints, void* stream) {
+    MC_REQUIRE(pred && rows && mean && stdv && work && joints && (taps || radius < 0) && n_frames >= 0, "bad argument");
+    MC_REQUIRE(mc_smplx_post_maxtap() == MC_POST_MAXTAP, "tap table size mismatch");
+    return mc_launch_t2m_joints(pred, nullptr, rows, mean, stdv, taps, radius, stats_f32, 1, n_frames, C, joints_num, work,
+                                joints, (hipStream_t)stream);
+}
+
 int mc_op_renoise(const float* x, const float* noise, float a, float b, float* out, int64_t n, void* stream) {
     MC_REQUIRE(x && noise && out && n >= 0, "bad argument");
     return mc_launch_axpby(x, noise, a, b, out, (long)n, (hipStream_t)stream);

@@ -1,4 +1,5 @@
-"""Result post-processing + on-disk format of the 322-d SMPL-X motion.
+"""Result post-processing + on-disk formats: the 322-d SMPL-X motion and the joint positions
+of the HumanML3D / KIT feature vectors.
 
 Mirrors what the reference tools do with ``output[i]['pred_motion']`` on the host
 (``tools/visualize.py:217-263``, ``tools/s2g_visualize.py:236-246``, ``tools/s2g_test.py:289-297,431-448``):
@@ -7,6 +8,11 @@ de-normalise with the dataset's ``mean.npy`` / ``std.npy``, re-pack the 322 chan
 ``scipy.ndimage.gaussian_filter(sigma, mode="nearest")`` and ``np.savez`` the AMASS-style file.  Here the
 arithmetic runs in one HIP kernel (``mc_postprocess_smplx``) on the sampler's output while it is still in HBM;
 only the finished arrays cross PCIe.
+
+For ``dataset_name == "human_ml3d"`` the reference tool instead recovers 3-D joint positions from the 263-d features
+(``plot_t2m``, ``tools/visualize.py:46-56``: ``recover_from_ric`` of ``mogen/utils/plot_utils.py:40-104``, then the
+temporal filter at sigma 2.5) and saves them as ``--pose_npy``: ``recover_joints`` / ``recover_joints_stitched`` /
+``save_joints_npy`` (``mc_postprocess_t2m_joints``), also for the 251-d KIT layout.
 """
 import ctypes
 import os
@@ -19,6 +25,8 @@ from . import lib as _lib
 # per-tool filter widths: (body + jaw, hands, trans, expressions); None = unfiltered
 SIGMAS_T2M = (3.5, 3.5, 3.0, 2.0)      # tools/visualize.py:244-246 (whole poses array at 3.5)
 SIGMAS_S2G = (3.5, 1.0, 3.5, None)     # tools/s2g_visualize.py:243-245
+JOINTS_T2M, JOINTS_KIT = 22, 21        # joints of the 263-d human_ml3d / 251-d kit_ml feature vectors
+SIGMA_T2M_JOINTS = 2.5                 # tools/visualize.py:48
 
 
 def gaussian_taps(sigma, truncate=4.0):
@@ -133,4 +141,93 @@ def save_smplx_npz(save_path, text, pred_motion, motion_length, mean=None, std=N
     lens = torch.as_tensor(motion_length).reshape(-1)
     path = os.path.join(save_path, result_name(text, lens[0]) + '.npz')
     np.savez(path, **d)
+    return path
+
+
+def _joint_feats(J):
+    return 4 + 9 * (J - 1) + 3 * J + 4          # root (4) + ric + rot6d (J - 1 joints) + velocities (J) + foot contacts (4)
+
+
+def _joints_operands(x, motion_length, mean, std, joints_num, sigma):
+    """Argument checks of the joint recovery + the host-side operands; everything here runs before the library is
+    loaded, and the device check comes last so that every other message can be reached with a host tensor."""
+    if not (isinstance(x, torch.Tensor) and x.dim() == 3):
+        raise ValueError('pred_motion must be a [B,T,C] tensor')
+    if x.dtype != torch.float32:
+        raise ValueError(f'pred_motion must be float32, got {x.dtype}')
+    B, T, C = x.shape
+    by_feats = {_joint_feats(JOINTS_T2M): JOINTS_T2M, _joint_feats(JOINTS_KIT): JOINTS_KIT}
+    if C not in by_feats:
+        raise ValueError(f'joint recovery expects the 263-d human_ml3d or the 251-d kit_ml layout, got {C}')
+    if joints_num is not None and int(joints_num) != by_feats[C]:
+        raise ValueError(f'joints_num={joints_num} contradicts the {C}-d layout ({by_feats[C]} joints)')
+    mean = np.zeros(C) if mean is None else np.asarray(mean)
+    std = np.ones(C) if std is None else np.asarray(std)
+    if mean.shape != (C,) or std.shape != (C,):
+        raise ValueError(f'mean / std must have shape ({C},)')
+    lens = None
+    if motion_length is not None:
+        lens = [int(v) for v in torch.as_tensor(motion_length).reshape(-1)]
+        if len(lens) != B or any(n < 0 or n > T for n in lens):
+            raise ValueError(f'motion_length must have one entry in [0, {T}] per sample')
+    taps, radius = np.zeros(_lib.POST_MAXTAP, np.float64), -1
+    if sigma is not None and sigma > 0:
+        radius, w = gaussian_taps(sigma)
+        if 2 * radius + 1 > _lib.POST_MAXTAP:
+            raise ValueError(f'sigma={sigma} needs {2 * radius + 1} taps (max {_lib.POST_MAXTAP})')
+        taps[:2 * radius + 1] = w
+    if not (x.is_cuda and x.is_contiguous()):
+        raise ValueError('pred_motion must be a contiguous tensor in device (HBM) memory')
+    stats_f32 = int(mean.dtype == np.float32 and std.dtype == np.float32)
+    return by_feats[C], lens, mean.astype(np.float64), std.astype(np.float64), taps, radius, stats_f32
+
+
+def recover_joints(pred_motion, motion_length=None, mean=None, std=None, joints_num=None, sigma=SIGMA_T2M_JOINTS):
+    """Every sample on its own: pred_motion [B,T,263|251] fp32 device tensor (normalised sampler output) -> device fp32
+    joint positions [B,T,J,3] (J = 22 | 21) of ``pred[b, :motion_length[b]]``, filtered over time at ``sigma`` (None =
+    unfiltered); frames >= motion_length[b] are zero."""
+    x = pred_motion
+    J, lens, mean, std, taps, radius, stats_f32 = _joints_operands(x, motion_length, mean, std, joints_num, sigma)
+    B, T, C = x.shape
+    lib = _lib.load(require_gpu=True)
+    dev = x.device
+    to_dev = lambda a: torch.from_numpy(a).to(dev)
+    mean_d, std_d, taps_d = to_dev(mean), to_dev(std), to_dev(taps)
+    len_d = None if lens is None else torch.tensor(lens, dtype=torch.int32, device=dev)
+    joints = torch.empty(B, T, J, 3, device=dev, dtype=torch.float32)
+    _lib.check(lib.mc_postprocess_t2m_joints(_p(x), _p(len_d), _p(mean_d), _p(std_d), _p(taps_d), radius, stats_f32, B, T, C, J,
+                                             _p(joints), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
+               'mc_postprocess_t2m_joints')
+    return joints
+
+
+def recover_joints_stitched(pred_motion, motion_length, mean=None, std=None, joints_num=None, sigma=SIGMA_T2M_JOINTS):
+    """tools/visualize.py:217-232 + plot_t2m: the valid frames ``pred[b, :motion_length[b]]`` of all intervals are
+    concatenated FIRST; yaw, root position and the filter then run over the stitched sequence, so the motion carries
+    across the seams.  Returns the device fp32 tensor [sum(motion_length), J, 3]."""
+    x = pred_motion
+    if motion_length is None:
+        raise ValueError('the stitched form needs the motion_length of every interval')
+    J, lens, mean, std, taps, radius, stats_f32 = _joints_operands(x, motion_length, mean, std, joints_num, sigma)
+    B, T, C = x.shape
+    lib = _lib.load(require_gpu=True)
+    dev = x.device
+    rows = np.concatenate([b * T + np.arange(n, dtype=np.int32) for b, n in enumerate(lens)] or [np.zeros(0, np.int32)])
+    n = int(rows.size)
+    joints = torch.empty(n, J, 3, device=dev, dtype=torch.float32)
+    if n:
+        to_dev = lambda a: torch.from_numpy(a).to(dev)
+        rows_d, mean_d, std_d, taps_d = to_dev(rows.astype(np.int32)), to_dev(mean), to_dev(std), to_dev(taps)
+        work = torch.empty(n, 4, device=dev, dtype=torch.float64)
+        _lib.check(lib.mc_postprocess_t2m_joints_stitched(_p(x), _p(rows_d), n, _p(mean_d), _p(std_d), _p(taps_d), radius, stats_f32,
+                                                          C, J, _p(work), _p(joints),
+                                                          ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                   'mc_postprocess_t2m_joints_stitched')
+    return joints
+
+
+def save_joints_npy(path, pred_motion, motion_length, mean=None, std=None, joints_num=None, sigma=SIGMA_T2M_JOINTS):
+    """The --pose_npy file of the reference tool (visualize.py:55-56): stitched, filtered joints [sum(len), J, 3] fp32."""
+    joints = recover_joints_stitched(pred_motion, motion_length, mean, std, joints_num, sigma)
+    np.save(path, joints.cpu().numpy())
     return path

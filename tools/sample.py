@@ -1,10 +1,10 @@
 #!/usr/bin/env python
 """Thin counterpart of the reference's tools/visualize.py for the MI355X path: config + checkpoint -> sampled motion
--> de-normalised SMPL-X .npz (motionx) or raw .npy, everything between the condition features and the finished
-arrays on the device.
+-> de-normalised SMPL-X .npz (motionx) or feature .npy (+ joint positions with --pose_npy), everything between the
+condition features and the finished arrays on the device.
 
     python tools/sample.py CONFIG CHECKPOINT --text "a person walks" --motion_length 120 --out ./samples \\
-        [--clip_feat feats.npy | --xf_out xf.npy | --random-condition SEED]  [--mean mean.npy --std std.npy]
+        [--clip_feat feats.npy | --xf_out xf.npy | --random-condition SEED]  [--mean mean.npy --std std.npy]  [--pose_npy joints.npy]
 
 The CLIP tokenizer is not available offline: prompts only name the output file unless the `clip` package is importable
 (then they are tokenized and encoded by the device CLIP tower when the checkpoint carries clip.* weights).
@@ -32,6 +32,8 @@ def parse_args():
     p.add_argument('--text', nargs='+', required=True)
     p.add_argument('--motion_length', type=int, nargs='+', required=True)
     p.add_argument('--out', default='./samples')
+    p.add_argument('--pose_npy', default=None, metavar='PATH',
+                   help='human_ml3d / kit_ml configs: also save the stitched, filtered joint positions [frames, J, 3] (tools/visualize.py:55-56)')
     p.add_argument('--clip_feat', help='.npy [n,77,512] CLIP text features (ln_final output)')
     p.add_argument('--xf_out', help='.npy [n,77,text_latent_dim] frozen condition embedding')
     p.add_argument('--random-condition', type=int, default=None, metavar='SEED')
@@ -64,6 +66,9 @@ def main():
     if a.fp16 or cfg.get('fp16', None) is not None:
         mc.wrap_fp16_model(model, split=(a.fp16 != 'plain'))
     dims = model.model.dims
+    if a.pose_npy and dims.get('dataset', 'motionx') == 'motionx':
+        raise ValueError('--pose_npy saves joint positions recovered from human_ml3d / kit_ml features; a motionx config '
+                         'writes the SMPL-X .npz instead')
     n, T, C = len(a.text), max(a.motion_length), dims['input_feats']
     if not 1 <= T <= dims['max_seq_len']:
         raise ValueError(f'motion_length must be in [1, {dims["max_seq_len"]}]')
@@ -94,6 +99,9 @@ def main():
                 for o, m in zip(out, a.motion_length)]
         path = os.path.join(a.out, postprocess.result_name(a.text[0], a.motion_length[0]) + '.npy')
         np.save(path, np.concatenate(arrs, axis=0))
+        if a.pose_npy:
+            pred = torch.stack([o['pred_motion'] for o in out]).to(dev).contiguous()
+            postprocess.save_joints_npy(a.pose_npy, pred, a.motion_length, mean, std)
     print(f'pred_motion: {n} x {T} x {C} -> {path}')
 
 
