@@ -26,6 +26,8 @@
  *   mc_postprocess_smplx  de-normalise + SMPL-X re-pack + temporal filter  tools/visualize.py:39-44,217-246; tools/s2g_test.py:289-297
  *   mc_postprocess_t2m_joints  HumanML3D / KIT features -> filtered joint positions (plot_t2m, recover_from_ric)
  *                                                                      tools/visualize.py:46-56; mogen/utils/plot_utils.py:40-104
+ *   mc_smplx_*            the SMPL-X body model (55 joints, vertices) the tools run on the saved poses / expressions / trans
+ *                                                                      tools/s2g_test.py:76-85,364-412; tools/visualize.py:71-86
  *   mc_op_renoise         GaussianDiffusion._undo (resampling jumps)   gaussian_diffusion.py:429-435, 1113-1118
  *
  * Conventions: plain pointers and sizes only.  `*_dev` pointers are device (HBM) addresses owned
@@ -416,6 +418,48 @@ int mc_wavenc_finalize(mc_wavenc* e);
 int mc_wavenc_out_len(const mc_wavenc* e, int32_t samples, int32_t* frames);
 /* wav_dev [B, samples, audio_in] -> out_dev [B, frames, out_dim] (channels-last, like WavEncoder.forward's return) */
 int mc_wavenc_forward(mc_wavenc* e, const float* wav_dev, int32_t B, int32_t samples, float* out_dev, void* stream);
+
+/* ---- SMPL-X body model: linear blend skinning of the published model (what smplx.lbs.lbs computes), fed from what
+ * mc_postprocess_smplx leaves on the device (tools/s2g_test.py:76-85,364-412; tools/visualize.py:71-86).  Per frame:
+ * R_j = rodrigues(theta_j) with the angle taken as |theta_j + 1e-8|; v_shaped = v_template + shapedirs [beta; psi];
+ * J = J_regressor v_shaped; v_posed = v_shaped + posedirs^T vec(R_1..54 - I); G_0 = [R_0 | J_0], G_j = G_parent
+ * [R_j | J_j - J_parent], A_j = G_j [I | -J_j]; joints_j = G_j[:3,3] + transl; verts_v = (sum_j W[v,j] A_j) [v_posed_v; 1]
+ * + transl.  Only the 55 kinematic joints are produced (tools/s2g_test.py:406 keeps [:55*3]).  This is lbs() itself: the
+ * package's forward adds the model file's mean hand pose to theta first unless flat_hand_mean is set (the reference
+ * leaves it unset); a caller who wants that adds it to poses_dev (body_model.SMPLXBodyModel does, from hands_meanl/r). */
+typedef struct mc_smplx mc_smplx;
+typedef struct mc_smplx_config {
+    int32_t num_vertices;     /* 10475 for the published model                                                     */
+    int32_t num_joints;       /* 55                                                                                */
+    int32_t num_betas;        /* 1..300 shape coefficients in use                                                  */
+    int32_t num_expr;         /* 1..100 expression coefficients in use                                             */
+    int32_t num_pose_feats;   /* 486 = 9 * 54                                                                      */
+} mc_smplx_config;
+int mc_smplx_create(const mc_smplx_config* cfg, mc_smplx** out);
+void mc_smplx_destroy(mc_smplx* m);
+/* fp32 parameters from host memory, as the model file stores them: "v_template" [V,3], "shapedirs" [V,3,num_betas],
+ * "expr_dirs" [V,3,num_expr], "posedirs" [V,3,486], "J_regressor" [55,V], "weights" [V,55], "parents" [55]
+ * (kintree_table[0] as floats; entry 0 is ignored) */
+int mc_smplx_set_param(mc_smplx* m, const char* name, const float* host, int64_t numel);
+/* MC_ERR_ARG for a tree with parents[j] >= j (j > 0).  Folds the
+ * regressor into J0 = J_regressor v_template and Jdirs = J_regressor [shapedirs | expr_dirs] in fp64, compacts the skin
+ * weights to their nonzeros, builds the level table of the tree and the K-contiguous blend-shape weight of the GEMM. */
+int mc_smplx_finalize(mc_smplx* m);
+/* poses_dev fp64 [n,165] (global 0:3, body 3:66, jaw 66:69, leye 69:72, reye 72:75, left hand 75:120, right hand
+ * 120:165), expr_dev fp64 [n,num_expr] or NULL (zeros), trans_dev fp64 [n,3] or NULL (zeros), betas_dev fp64 [num_betas]
+ * (betas_per_frame = 0) or [n,num_betas] -> joints_out_dev fp32 [n,55,3].  One kernel, fp64 arithmetic with one
+ * rounding at the fp32 store. */
+int mc_smplx_joints(mc_smplx* m, const double* poses_dev, const double* expr_dev, const double* trans_dev,
+                    const double* betas_dev, int32_t betas_per_frame, int32_t n, float* joints_out_dev, void* stream);
+/* bytes of workspace with which mc_smplx_vertices runs n_frames frames as one chunk (-1: bad argument) */
+int64_t mc_smplx_work_bytes(const mc_smplx* m, int32_t n_frames, int32_t betas_per_frame);
+/* The same inputs -> verts_out_dev fp32 [n,V,3] (16-byte aligned) and, if not NULL, joints_out_dev fp32 [n,55,3] (bit for
+ * bit what mc_smplx_joints writes: the same kernel also produces the skinning transforms).  fp32 like the package: blend
+ * shapes on the fp32 MFMA GEMM, then the skinning kernel.  Frames run in chunks of as many as work_dev (16-byte aligned,
+ * work_bytes >= mc_smplx_work_bytes(m, 1, .)) holds; the result does not depend on the chunk size. */
+int mc_smplx_vertices(mc_smplx* m, const double* poses_dev, const double* expr_dev, const double* trans_dev,
+                      const double* betas_dev, int32_t betas_per_frame, int32_t n, void* work_dev, int64_t work_bytes,
+                      float* verts_out_dev, float* joints_out_dev, void* stream);
 
 /* out = a * x + b * noise over n elements (out may alias x) */
 int mc_op_renoise(const float* x_dev, const float* noise_dev, float a, float b, float* out_dev, int64_t n, void* stream);

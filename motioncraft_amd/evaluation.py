@@ -545,3 +545,27 @@ class T2MContrastiveModel:
             w, p, n = vectorize_tokens(token, self.w_vectorizer, self.max_text_len)
         device = device if device is not None else 'cuda'
         return self.encoder.encode_word_vectors(w.to(device), p.to(device), n.to(device))
+
+
+class L1div:
+    """The joint-diversity score of the speech-to-gesture test (``mogen/datasets/EMAGE_2024/utils/metric.py:12-27``, fed the
+    55 SMPL-X joints of each sequence at ``tools/s2g_test.py:414``): ``run`` adds sum |x - mean over frames| of one sequence
+    [frames, D], ``avg`` divides by the frames seen.  The reference's ``run`` overwrites its argument with the deviations;
+    this one leaves it alone and accumulates the same numbers."""
+
+    def __init__(self):
+        self.reset()
+
+    def run(self, results):
+        results = np.asarray(results.detach().cpu() if isinstance(results, torch.Tensor) else results)
+        results = results.reshape(results.shape[0], -1)
+        self.counter += results.shape[0]
+        mean = np.mean(results, 0)
+        self.sum += np.sum(np.abs(results - mean))          # the dtype of `results` throughout, like the in-place original
+
+    def avg(self):
+        return self.sum / self.counter
+
+    def reset(self):
+        self.counter = 0
+        self.sum = 0

@@ -57,6 +57,10 @@ class T2MEvalConfig(ctypes.Structure):
                                               'word_size', 'pos_size', 'text_hidden', 'text_out')]
 
 
+class SMPLXConfig(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ('num_vertices', 'num_joints', 'num_betas', 'num_expr', 'num_pose_feats')]
+
+
 class TextEncConfig(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ('clip_dim', 'text_latent_dim', 'num_layers', 'ff_size', 'num_heads', 'max_len',
                                               'clip_layers', 'clip_heads', 'clip_ff', 'vocab')]
@@ -126,11 +130,15 @@ _SIGNATURES = {
     'mc_wavenc_create': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_P)]),
     'mc_wavenc_out_len': (ctypes.c_int, [_P, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)]),
     'mc_wavenc_forward': (ctypes.c_int, [_P, _P, ctypes.c_int32, ctypes.c_int32, _P, _P]),
+    'mc_smplx_create': (ctypes.c_int, [ctypes.POINTER(SMPLXConfig), ctypes.POINTER(_P)]),
+    'mc_smplx_joints': (ctypes.c_int, [_P, _P, _P, _P, _P, ctypes.c_int32, ctypes.c_int32, _P, _P]),
+    'mc_smplx_work_bytes': (ctypes.c_int64, [_P, ctypes.c_int32, ctypes.c_int32]),
+    'mc_smplx_vertices': (ctypes.c_int, [_P, _P, _P, _P, _P, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_int64, _P, _P, _P]),
     'mc_op_renoise': (ctypes.c_int, [_P, _P, ctypes.c_float, ctypes.c_float, _P, ctypes.c_int64, _P]),
     'mc_debug_flop_ledger': (ctypes.c_int, [ctypes.c_int32]),
     'mc_debug_flop_ledger_dump': (ctypes.c_int64, [ctypes.c_char_p, ctypes.c_int64]),
 }
-NATIVE_OBJECTS = ('model', 'textenc', 'evalenc', 't2meval', 'wavenc')       # the handles with a parameter store (NativeObject)
+NATIVE_OBJECTS = ('model', 'textenc', 'evalenc', 't2meval', 'wavenc', 'smplx')       # the handles with a parameter store (NativeObject)
 for _kind in NATIVE_OBJECTS:
     _SIGNATURES.update({f'mc_{_kind}_destroy': (None, [_P]),
                         f'mc_{_kind}_set_param': (ctypes.c_int, [_P, ctypes.c_char_p, _P, ctypes.c_int64]),

@@ -13,6 +13,9 @@ For ``dataset_name == "human_ml3d"`` the reference tool instead recovers 3-D joi
 (``plot_t2m``, ``tools/visualize.py:46-56``: ``recover_from_ric`` of ``mogen/utils/plot_utils.py:40-104``, then the
 temporal filter at sigma 2.5) and saves them as ``--pose_npy``: ``recover_joints`` / ``recover_joints_stitched`` /
 ``save_joints_npy`` (``mc_postprocess_t2m_joints``), also for the 251-d KIT layout.
+
+For the 322-d layout the tools go on through the SMPL-X body model (``tools/s2g_test.py:364-412``): ``smplx_joints`` /
+``smplx_vertices`` run ``body_model.SMPLXBodyModel`` (``mc_smplx_*``) on the arrays ``postprocess_smplx[_stitched]`` returns.
 """
 import ctypes
 import os
@@ -128,6 +131,18 @@ def smplx_npz_dict(post):
     dt = np.float32 if post['stats_f32'] else np.float64
     return dict(betas=np.zeros(300), poses=post['poses'].cpu().numpy(), expressions=post['expressions'].cpu().numpy().astype(dt),
                 trans=post['trans'].cpu().numpy().astype(dt), model='smplx2020', gender='neutral', mocap_frame_rate=30)
+
+
+def smplx_joints(post, model, betas=None):
+    """The 55 SMPL-X joints of every frame of ``post`` (the dict ``postprocess_smplx[_stitched]`` returns) under ``model``
+    (``body_model.SMPLXBodyModel``): device fp32 [..., 55, 3].  ``betas`` [nb] or one row per frame; default zeros, as the
+    tool saves them (tools/visualize.py:242)."""
+    return model.joints(post['poses'], post['expressions'], post['trans'], betas)
+
+
+def smplx_vertices(post, model, betas=None, return_joints=False):
+    """The skinned SMPL-X vertices of every frame of ``post``: device fp32 [..., V, 3] (``model.faces`` indexes them)."""
+    return model.vertices(post['poses'], post['expressions'], post['trans'], betas, return_joints=return_joints)
 
 
 def result_name(text, motion_length):

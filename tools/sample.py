@@ -1,10 +1,11 @@
 #!/usr/bin/env python
 """Thin counterpart of the reference's tools/visualize.py for the MI355X path: config + checkpoint -> sampled motion
--> de-normalised SMPL-X .npz (motionx) or feature .npy (+ joint positions with --pose_npy), everything between the
-condition features and the finished arrays on the device.
+-> de-normalised SMPL-X .npz (motionx; + the body model's joints / vertices with --smplx_model) or feature .npy (+ joint
+positions with --pose_npy), everything between the condition features and the finished arrays on the device.
 
     python tools/sample.py CONFIG CHECKPOINT --text "a person walks" --motion_length 120 --out ./samples \\
         [--clip_feat feats.npy | --xf_out xf.npy | --random-condition SEED]  [--mean mean.npy --std std.npy]  [--pose_npy joints.npy]
+        [--smplx_model SMPLX_NEUTRAL.npz --joints_npy joints.npy [--verts_npy verts.npy]]
 
 The CLIP tokenizer is not available offline: prompts only name the output file unless the `clip` package is importable
 (then they are tokenized and encoded by the device CLIP tower when the checkpoint carries clip.* weights).
@@ -34,6 +35,10 @@ def parse_args():
     p.add_argument('--out', default='./samples')
     p.add_argument('--pose_npy', default=None, metavar='PATH',
                    help='human_ml3d / kit_ml configs: also save the stitched, filtered joint positions [frames, J, 3] (tools/visualize.py:55-56)')
+    p.add_argument('--smplx_model', default=None, metavar='PATH', help='motionx configs: the published SMPL-X model file (.npz)')
+    p.add_argument('--joints_npy', default=None, metavar='PATH',
+                   help='with --smplx_model: save the 55 SMPL-X joints [frames, 55, 3] of the stitched, filtered motion (tools/s2g_test.py:406)')
+    p.add_argument('--verts_npy', default=None, metavar='PATH', help='with --smplx_model: save the skinned vertices [frames, V, 3]')
     p.add_argument('--clip_feat', help='.npy [n,77,512] CLIP text features (ln_final output)')
     p.add_argument('--xf_out', help='.npy [n,77,text_latent_dim] frozen condition embedding')
     p.add_argument('--random-condition', type=int, default=None, metavar='SEED')
@@ -69,6 +74,13 @@ def main():
     if a.pose_npy and dims.get('dataset', 'motionx') == 'motionx':
         raise ValueError('--pose_npy saves joint positions recovered from human_ml3d / kit_ml features; a motionx config '
                          'writes the SMPL-X .npz instead')
+    if (a.joints_npy or a.verts_npy or a.smplx_model) and dims.get('dataset', 'motionx') != 'motionx':
+        raise ValueError('--smplx_model / --joints_npy / --verts_npy run the SMPL-X body model on a motionx sample; a human_ml3d / '
+                         'kit_ml config saves joints with --pose_npy')
+    if (a.joints_npy or a.verts_npy) and not a.smplx_model:
+        raise ValueError('--joints_npy / --verts_npy need the body model file: --smplx_model PATH')
+    if a.smplx_model and not (a.joints_npy or a.verts_npy):
+        raise ValueError('--smplx_model alone writes nothing: name an output with --joints_npy PATH and / or --verts_npy PATH')
     n, T, C = len(a.text), max(a.motion_length), dims['input_feats']
     if not 1 <= T <= dims['max_seq_len']:
         raise ValueError(f'motion_length must be in [1, {dims["max_seq_len"]}]')
@@ -93,7 +105,16 @@ def main():
     std = np.load(a.std) if a.std else None
     if dims.get('dataset', 'motionx') == 'motionx':
         pred = torch.stack([o['pred_motion'] for o in out]).to(dev).contiguous()
-        path = postprocess.save_smplx_npz(a.out, a.text[0], pred, a.motion_length, mean, std)
+        post = postprocess.postprocess_smplx_stitched(pred, a.motion_length, mean, std)          # what save_smplx_npz writes
+        path = os.path.join(a.out, postprocess.result_name(a.text[0], a.motion_length[0]) + '.npz')
+        np.savez(path, **postprocess.smplx_npz_dict(post))
+        if a.smplx_model:
+            from motioncraft_amd.body_model import SMPLXBodyModel
+            body = SMPLXBodyModel.from_npz(a.smplx_model)
+            if a.joints_npy:
+                np.save(a.joints_npy, postprocess.smplx_joints(post, body).cpu().numpy())
+            if a.verts_npy:
+                np.save(a.verts_npy, postprocess.smplx_vertices(post, body).cpu().numpy())
     else:
         arrs = [o['pred_motion'][:m].numpy() * (std if std is not None else 1.0) + (mean if mean is not None else 0.0)
                 for o, m in zip(out, a.motion_length)]
