@@ -67,6 +67,15 @@ inline void mc_gemm_opts(const McOptions& o, GemmArgs& g) {
     g.wp_grid = o.gemm_wp_grid > 0 ? (int)o.gemm_wp_grid : -1;
 }
 
+// The load model of the latency-bound launches: equal workgroups over 256 CUs are bound by the busiest CU -- n = ceil(workgroups / 256)
+// of them land on it, and two co-resident ones share the MFMA pipe and finish in the factor below (measured; not 2x) times the time
+// of one.  Returned in workgroup times; the callers multiply by their own workgroup cost (mc_launch_gemm_small's tile width, the
+// hidden splits of the expert MLP and of the SFFN in mc_step.hip): ONE function, so those choices cannot drift apart.
+inline double mc_cu_load(long workgroups) {
+    const long n = (workgroups + 255) / 256;
+    return (1.45 * (double)(n / 2) + (double)(n % 2));
+}
+
 int mc_device_cus();      // compute units of the current device (cached)
 int mc_launch_gemm(int mode, const GemmArgs& g, int groups, int max_tiles, hipStream_t stream);
 // small-M plain GEMM (64 x 64 tiles, one MFMA tile per wave): C = A W^T + bias (+ add) + R, K % 32 == 0; any N (guarded scalar

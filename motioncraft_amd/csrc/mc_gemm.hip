@@ -1164,9 +1164,8 @@ int mc_launch_gemm_small(const GemmArgs& g, hipStream_t stream, int groups) {
                "gemm_small: operands beyond 4 GB (the DMA takes 32-bit byte offsets into A and W; this kernel is for a few thousand rows)");
     const bool vec = g.N % SN == 0 && g.ldc % 4 == 0 && g.c_col % 4 == 0 && g.c_gstride % 4 == 0 && (!g.R || (g.ldr % 4 == 0 && (g.r_gstride < 0 || g.r_gstride % 4 == 0))) &&
                      (!g.add || g.ld_add % 4 == 0) && g.b_gstride % 4 == 0;
-    // Tile width per launch.  The launch is bound by the MFMA pipe of the busiest CU: n = ceil(tiles / 256) tiles land on it,
-    // two co-resident tiles share the pipe and finish in 1.45x (not 2x) the time of one, so its load is
-    // (1.45 floor(n / 2) + n mod 2) tile times; a 64 x 48 / 64 x 64 / 64 x 96 tile costs 23 / 30 / 41 units (the 32x32-MFMA
+    // Tile width per launch.  The launch is bound by the MFMA pipe of the busiest CU: mc_cu_load (mc_gemm.h) gives its load
+    // in tile times; a 64 x 48 / 64 x 64 / 64 x 96 tile costs 23 / 30 / 41 units (the 32x32-MFMA
     // kernel is ~15 % more efficient per flop than the 16x16 one).  Fitted on 392 B x 1536 x 1536 for B = 1 .. 16
     // (tools/gemm_sweep.py): picks the measured-best width in every case, e.g. 48 at B = 1, 2, 7, 96 at B = 4, 5, 10, else 64.
     // (only widths that divide N: the decoder tail, N = 322, would be 7 x 48 instead of 6 x 64 tiles and 5 us faster at B=1,
@@ -1176,10 +1175,7 @@ int mc_launch_gemm_small(const GemmArgs& g, hipStream_t stream, int groups) {
     const int ng = groups > 0 ? groups : 1;
     GemmArgs gg = g;
     if (int r = resolve_opts(gg)) return r;
-    auto cost = [&](int nb, double unit) {
-        const long n = cdiv((long)cdiv(g.M, SM) * cdiv(g.N, nb) * ng, 256);
-        return (1.45 * (double)(n / 2) + (double)(n % 2)) * unit;
-    };
+    auto cost = [&](int nb, double unit) { return mc_cu_load((long)cdiv(g.M, SM) * cdiv(g.N, nb) * ng) * unit; };
     int nb = SN;
     double best = cost(SN, 30.0);
     // (beyond the small-batch sizes -- M > 6400 rows, i.e. the folded decoder tail of a large batch, whose goldens are lockstep

@@ -21,6 +21,11 @@ int mc_launch_split_f16(const float* x, mc_half* hi, mc_half* lo, long n, hipStr
 // order in which an MFMA C^T accumulator fragment presents its 32 rows (mc_half.hip, mlp2_h_k).
 int mc_launch_split_f16_chainperm(const float* x, mc_half* hi, mc_half* lo, long rows, int K, hipStream_t s);
 
+struct HalfW {              // fp16 hi / lo planes of one weight (split once per model); lo directly behind hi in one allocation
+    const mc_half* hi = nullptr;
+    const mc_half* lo = nullptr;
+};
+
 struct GemmHArgs {
     const float* A = nullptr;     // [M][lda] fp32 activations (converted while staging) ...
     long lda = 0;
@@ -41,19 +46,16 @@ struct GemmHArgs {
 // C = act(A W^T + bias) + R with fp16 MFMA; split = three-product hi/lo form
 int mc_launch_gemm_h(const GemmHArgs& g, bool split, hipStream_t s);
 
-// mlp2_k (mc_chain.hip) on the fp16 MFMA: W1h/W1l [groups][hidden][L] and W2h/W2l [groups][L][hidden] (chain-permuted)
-// fp16 planes replace MlpArgs::W1 / W2t; biases, X and Y stay fp32; GELU in fp32.  nsplit must be 1.
-int mc_launch_mlp_h(int mode, const MlpArgs& g, const mc_half* W1h, const mc_half* W1l, const mc_half* W2h, const mc_half* W2l,
-                    bool split, int groups, int max_tiles, hipStream_t s);
+// mlp2_k (mc_chain.hip) on the fp16 MFMA: the planes W1 [groups][hidden][L] and W2 [groups][L][hidden] (chain-permuted)
+// replace MlpArgs::W1 / W2t; biases, X and Y stay fp32; GELU in fp32.  nsplit must be 1.
+int mc_launch_mlp_h(int mode, const MlpArgs& g, const HalfW& W1, const HalfW& W2, bool split, int groups, int max_tiles, hipStream_t s);
 bool mc_mlp_h_supported(int L, int hidden);
 
-// projqkv_k (mc_chain.hip) on the fp16 MFMA: Wph/Wpl [4L][L] planes of MOE.proj, Wqh/Wql [3L][L] planes of the q/k/v weight with
+// projqkv_k (mc_chain.hip) on the fp16 MFMA: Wp = the [4L][L] planes of MOE.proj, Wq = the [3L][L] planes of the q/k/v weight with
 // the K axis chain-permuted; combine + GELU + LayerNorm stay fp32
-int mc_launch_projqkv_h(const RowChainArgs& g, const mc_half* Wph, const mc_half* Wpl, const mc_half* Wqh, const mc_half* Wql, bool split,
-                        hipStream_t s);
+int mc_launch_projqkv_h(const RowChainArgs& g, const HalfW& Wp, const HalfW& Wq, bool split, hipStream_t s);
 // projqkv_h + the body-topology attention over frame-aligned tiles (pqbody_k's fp16-MFMA twin; L = 128, H = 12): q/k/v stay on chip
-int mc_launch_pqbody_h(const RowChainArgs& g, int H, const mc_half* Wph, const mc_half* Wpl, const mc_half* Wqh, const mc_half* Wql, bool split,
-                       hipStream_t s);
+int mc_launch_pqbody_h(const RowChainArgs& g, int H, const HalfW& Wp, const HalfW& Wq, bool split, hipStream_t s);
 
 // temporal_k (mc_attn.hip) with both contractions on the fp16 MFMA (softmax statistics, masks and scalings fp32); L = 128 / 64,
 // whole-(sample, part) workgroups only (the column-sliced small-batch form stays on temporal_k)

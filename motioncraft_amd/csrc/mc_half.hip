@@ -1422,11 +1422,10 @@ int mc_launch_gemm_h(const GemmHArgs& g, bool split, hipStream_t s) {
 
 bool mc_mlp_h_supported(int L, int hidden) { return (L == 32 || L == 64 || L == 128) && hidden % 32 == 0 && hidden >= 32 && hidden <= 1024; }
 
-int mc_launch_mlp_h(int mode, const MlpArgs& g, const mc_half* W1h, const mc_half* W1l, const mc_half* W2h, const mc_half* W2l,
-                    bool split, int groups, int max_tiles, hipStream_t s) {
+int mc_launch_mlp_h(int mode, const MlpArgs& g, const HalfW& W1, const HalfW& W2, bool split, int groups, int max_tiles, hipStream_t s) {
     MC_REQUIRE(mc_mlp_h_supported(g.L, g.hidden), "fp16 fused mlp: L=%d hidden=%d unsupported", g.L, g.hidden);
     MC_REQUIRE(g.ldx % 4 == 0 && g.ldy % 4 == 0 && g.x_gstride % 4 == 0 && g.y_gstride % 4 == 0 && g.nsplit == 1, "fp16 fused mlp: strides / nsplit");
-    MC_REQUIRE(W1h && W2h && (!split || (W1l && W2l)), "fp16 fused mlp: null weight plane");
+    MC_REQUIRE(W1.hi && W2.hi && (!split || (W1.lo && W2.lo)), "fp16 fused mlp: null weight plane");
     dim3 grid;
     if (mode == MLP_EXPERT) {
         if (max_tiles <= 0) return MC_OK;
@@ -1447,7 +1446,7 @@ int mc_launch_mlp_h(int mode, const MlpArgs& g, const mc_half* W1h, const mc_hal
         mc_dispatch<128, 64>(g.L, [&](auto L) {
             mc_dispatch<MLP_EXPERT, MLP_PARTS>(m, [&](auto M) {
                 mc_dispatch<0, 1>(split, [&](auto S) {
-                    hipLaunchKernelGGL((mlp2hd_k<MC_V(L), MC_V(M), bool(MC_V(S))>), grid, dim3(256), 0, s, g, W1h, W1l, W2h, W2l);
+                    hipLaunchKernelGGL((mlp2hd_k<MC_V(L), MC_V(M), bool(MC_V(S))>), grid, dim3(256), 0, s, g, W1.hi, W1.lo, W2.hi, W2.lo);
                 });
             });
         });
@@ -1457,7 +1456,7 @@ int mc_launch_mlp_h(int mode, const MlpArgs& g, const mc_half* W1h, const mc_hal
     const bool known = mc_dispatch<128, 64, 32>(g.L, [&](auto L) {
         mc_dispatch<MLP_EXPERT, MLP_PARTS>(m, [&](auto M) {
             mc_dispatch<0, 1>(split, [&](auto S) {
-                hipLaunchKernelGGL((mlp2_h_k<MC_V(L), MC_V(M), bool(MC_V(S))>), grid, dim3(256), 0, s, g, W1h, W1l, W2h, W2l);
+                hipLaunchKernelGGL((mlp2_h_k<MC_V(L), MC_V(M), bool(MC_V(S))>), grid, dim3(256), 0, s, g, W1.hi, W1.lo, W2.hi, W2.lo);
             });
         });
     });
@@ -1466,10 +1465,9 @@ int mc_launch_mlp_h(int mode, const MlpArgs& g, const mc_half* W1h, const mc_hal
     return MC_OK;
 }
 
-int mc_launch_pqbody_h(const RowChainArgs& g, int H, const mc_half* Wph, const mc_half* Wpl, const mc_half* Wqh, const mc_half* Wql, bool split,
-                       hipStream_t s) {
+int mc_launch_pqbody_h(const RowChainArgs& g, int H, const HalfW& Wp, const HalfW& Wq, bool split, hipStream_t s) {
     MC_REQUIRE((g.L == 128 || g.L == 64) && H == 12, "fp16 pqbody: L=%d H=%d unsupported (128 / 64, 12)", g.L, H);
-    MC_REQUIRE(g.Nout == 4 * g.L && g.ldy == 4 * g.L && g.bias && g.bias2 && g.wsm && g.ys && Wph && Wqh && (!split || (Wpl && Wql)),
+    MC_REQUIRE(g.Nout == 4 * g.L && g.ldy == 4 * g.L && g.bias && g.bias2 && g.wsm && g.ys && Wp.hi && Wq.hi && (!split || (Wp.lo && Wq.lo)),
                "fp16 pqbody: bad arguments");
     MC_REQUIRE(g.pad_row >= g.N, "fp16 pqbody: pad_row (128 padding rows of Y behind the last token) not set");
     MC_REQUIRE(g.tok0 % H == 0 && g.N % H == 0, "fp16 pqbody: token range [%ld, %ld) is not made of whole frames", g.tok0, g.N);
@@ -1483,16 +1481,15 @@ int mc_launch_pqbody_h(const RowChainArgs& g, int H, const mc_half* Wph, const m
     }
     mc_dispatch<128, 64>(g.L, [&](auto L) {      // (L, H checked above)
         mc_dispatch<0, 1>(split, [&](auto S) {
-            hipLaunchKernelGGL((pqbody_h_k<MC_V(L), 12, bool(MC_V(S))>), grid, dim3(256), 0, s, g, Wph, Wpl, Wqh, Wql);
+            hipLaunchKernelGGL((pqbody_h_k<MC_V(L), 12, bool(MC_V(S))>), grid, dim3(256), 0, s, g, Wp.hi, Wp.lo, Wq.hi, Wq.lo);
         });
     });
     MC_LAUNCH_CHECK();
     return MC_OK;
 }
 
-int mc_launch_projqkv_h(const RowChainArgs& g, const mc_half* Wph, const mc_half* Wpl, const mc_half* Wqh, const mc_half* Wql, bool split,
-                        hipStream_t s) {
-    MC_REQUIRE(g.Nout == 4 * g.L && g.ldy % 4 == 0 && g.ldy2 % 4 == 0 && g.bias && g.bias2 && g.Y2 && Wph && Wqh && (!split || (Wpl && Wql)),
+int mc_launch_projqkv_h(const RowChainArgs& g, const HalfW& Wp, const HalfW& Wq, bool split, hipStream_t s) {
+    MC_REQUIRE(g.Nout == 4 * g.L && g.ldy % 4 == 0 && g.ldy2 % 4 == 0 && g.bias && g.bias2 && g.Y2 && Wp.hi && Wq.hi && (!split || (Wp.lo && Wq.lo)),
                "fp16 projqkv: bad arguments");
     if (g.N <= g.tok0) return MC_OK;
     dim3 grid(cdiv(g.N - g.tok0, 128));
@@ -1503,7 +1500,7 @@ int mc_launch_projqkv_h(const RowChainArgs& g, const mc_half* Wph, const mc_half
     }
     const bool known = mc_dispatch<128, 64, 32>(g.L, [&](auto L) {
         mc_dispatch<0, 1>(split, [&](auto S) {
-            hipLaunchKernelGGL((projqkv_h_k<MC_V(L), bool(MC_V(S))>), grid, dim3(256), 0, s, g, Wph, Wpl, Wqh, Wql);
+            hipLaunchKernelGGL((projqkv_h_k<MC_V(L), bool(MC_V(S))>), grid, dim3(256), 0, s, g, Wp.hi, Wp.lo, Wq.hi, Wq.lo);
         });
     });
     MC_REQUIRE(known, "fp16 projqkv: L=%d unsupported", g.L);

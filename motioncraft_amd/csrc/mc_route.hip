@@ -27,7 +27,7 @@ constexpr int TILE_ROWS = 128;
 enum {
     ST_CNT = 0,                   // [2][MAXE]   tokens per (choice, expert)
     // slots are laid out per (slot group g, expert e), g = 0/1 = token below / at-or-above `gsplit`: the expert MLP of
-    // each sample group can then be launched on its own stream (mc_model.hip); one group when gsplit >= N
+    // each sample group can then be launched on its own stream (mc_step.hip); one group when gsplit >= N
     ST_KEPT = ST_CNT + MAXP,      // [2][MAXE]   kept pairs per (slot group, expert)
     ST_FILL = ST_KEPT + 2 * MAXE, // [2][MAXE]   compaction cursors
     ST_OFF = ST_FILL + 2 * MAXE,  // [2*MAXE+1]  slot range starts

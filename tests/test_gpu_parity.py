@@ -2400,6 +2400,40 @@ def test_twin_pairs_split_by_capacity_in_the_large_batch_schedule():
     nm.close()
 
 
+PARENT_TWIN_PAIR_MAXABS = (2.384185791015625e-07, 3.0994415283203125e-06)      # |dx_prev|, |dx0| measured on the parent commit 991b20b (MI355X)
+
+
+def test_twin_split_pieces_equal_the_same_pieces_through_the_fork_join_wrapper(small_model):
+    """One mc_sample_step of the small model at B = 4, T = 8, twice: with big_tokens = 0 (the two-stream schedule with the twin split:
+    base layer 0 calls layer_proj / layer_body / layer_temporal one by one, front per sample sub-group, cross-join, temporal attention
+    per CFG half; L = 32, so the projqkv path) and with big_tokens high (the one-stream schedule: the same pieces through layer_rows'
+    fork / join wrapper).  The two schedules pick different kernels for the same arithmetic (projqkv_k vs two row-chain launches, no
+    hidden split of the SFFN per sample group), so they need not agree bit for bit; the bound is what the commit before the schedule
+    moved into mc_step.hip measured for this pair (x_prev 2.38e-07 at |x| <= 3.9, x0 3.10e-06 at |x0| <= 4.4), with no margin: the refactor
+    reproduces the parent's outputs of both schedules bit for bit."""
+    from motioncraft_amd.diffusion import build_diffusion
+    sd, nm = small_model
+    B, T, C = 4, 8, SMALL['input_feats']
+    d = build_diffusion(dict(beta_scheduler='linear', diffusion_steps=1000, model_mean_type='start_x', model_var_type='fixed_large'))
+    x, xf, mask = synth_inputs(SMALL, B, T, seed=31, lengths=[8, 7, 5, 3])
+    coef = d.step_coefs(333, 'ddpm', SMALL['scale'], 0.0)
+    noise = torch.randn(B, T, C, generator=torch.Generator().manual_seed(32)).cuda()
+    outs = []
+    for big in (0, 1 << 30):
+        ctx = nm.context(B, T, max_steps=1)
+        ctx.set_option('big_tokens', big)
+        ctx.set_timesteps([333])
+        ctx.set_condition(xf.cuda(), mask.cuda())
+        x0 = torch.empty(B, T, C, device='cuda')
+        xp = ctx.sample_step(x.cuda(), 0, coef, noise, x0=x0)
+        torch.cuda.synchronize()
+        outs.append((xp.clone(), x0.clone()))
+        ctx.close()
+    e_prev, e_x0 = maxabs(outs[0][0], outs[1][0]), maxabs(outs[0][1], outs[1][1])
+    print(f'twin split vs fork / join wrapper: |dx_prev| {e_prev!r}, |dx0| {e_x0!r}')
+    assert bool(torch.isfinite(outs[0][0]).all()) and e_prev <= PARENT_TWIN_PAIR_MAXABS[0] and e_x0 <= PARENT_TWIN_PAIR_MAXABS[1]
+
+
 @pytest.mark.parametrize('regime,B', [('random_scores', 3), ('exact_ties', 3), ('tiny_capacity', 3), ('reverse_ties', 3),
                                       ('random_scores', 9), ('tiny_capacity', 9), ('exact_ties', 9)])
 def test_register_routing_kernel_equals_the_streaming_form(regime, B, monkeypatch):
