@@ -28,6 +28,9 @@
  *                                                                      tools/visualize.py:46-56; mogen/utils/plot_utils.py:40-104
  *   mc_smplx_*            the SMPL-X body model (55 joints, vertices) the tools run on the saved poses / expressions / trans
  *                                                                      tools/s2g_test.py:76-85,364-412; tools/visualize.py:71-86
+ *   mc_smplx_vertex_errors  the face l2 / lvel sums over the vertices of sample and target   tools/s2g_test.py:377-412
+ *   mc_beat_mask, mc_beat_align  alignment.load_pose / calculate_align (beat alignment score)
+ *                                                                      mogen/datasets/EMAGE_2024/utils/metric.py:78-127,199-242
  *   mc_op_renoise         GaussianDiffusion._undo (resampling jumps)   gaussian_diffusion.py:429-435, 1113-1118
  *
  * Conventions: plain pointers and sizes only.  `*_dev` pointers are device (HBM) addresses owned
@@ -460,6 +463,40 @@ int64_t mc_smplx_work_bytes(const mc_smplx* m, int32_t n_frames, int32_t betas_p
 int mc_smplx_vertices(mc_smplx* m, const double* poses_dev, const double* expr_dev, const double* trans_dev,
                       const double* betas_dev, int32_t betas_per_frame, int32_t n, void* work_dev, int64_t work_bytes,
                       float* verts_out_dev, float* joints_out_dev, void* stream);
+/* The two sums behind the face errors of tools/s2g_test.py:407-412 (reclatent_loss = MSELoss, vel_loss = L1Loss, :99-100) with
+ * the vertices never leaving the device: the vertex path above runs for pose set a (the sample) and pose set b (the target),
+ * both with betas_dev, chunk by chunk, and sums_out_dev fp64 [2] receives
+ *   [0] sum over n V 3 of (a - b)^2          [1] sum over (n - 1) V 3 of |(a[t+1] - b[t]) - (b[t+1] - b[t])|
+ * with fp32 element operations (the reference's tensors) and fp64 sums: one partial per frame, then one fixed-order pass over
+ * the frames, so the sums do not depend on work_bytes and two runs give the same bits.  The caller divides ([1] is 0 for n < 2).
+ * work_dev: 16-byte aligned, work_bytes >= mc_smplx_vertex_errors_work_bytes(m, 1, n, .); that function gives the bytes with
+ * which the n frames run in chunks of chunk_frames (-1: bad argument). */
+int64_t mc_smplx_vertex_errors_work_bytes(const mc_smplx* m, int32_t chunk_frames, int32_t n_frames, int32_t betas_per_frame);
+int mc_smplx_vertex_errors(mc_smplx* m, const double* poses_a_dev, const double* expr_a_dev, const double* trans_a_dev,
+                           const double* poses_b_dev, const double* expr_b_dev, const double* trans_b_dev, const double* betas_dev,
+                           int32_t betas_per_frame, int32_t n, void* work_dev, int64_t work_bytes, double* sums_out_dev, void* stream);
+
+/* ---- Beat alignment of the speech-to-gesture test (alignment.load_pose + alignment.calculate_align,
+ * mogen/datasets/EMAGE_2024/utils/metric.py:78-127,199-242; called at tools/s2g_test.py:418-422 on the 55 joints of
+ * mc_smplx_joints).  Audio onset detection (load_audio, librosa) stays with the caller: onset times are an input.
+ * mc_beat_mask: joints_dev fp32 [n_frames, num_joints, 3] (n_frames >= 2), mean_vel_dev fp64 [num_joints] ->
+ * mask_out_dev uint8 [num_joints, t_end - t_start].  speed = |velocity| / mean_vel with forward / central / backward
+ * differences in fp32 (dt = 1 / pose_fps rounded to fp32, sqrt((x x + y y) + z z), no fused multiply-add: numpy on fp32 joints),
+ * the division in fp32 when mean_vel_fp32 is set (the values are then fp32 numbers held as doubles) and in fp64 otherwise.
+ * Over s = speed[t_start:t_end, j], index i is a beat iff s[i] < s[clip(i +- k, 0, n - 1)] for every k = 1..order (1..64;
+ * scipy.signal.argrelextrema(np.less, mode='clip')) and speed[i, j] > threshold, where i is slice-relative but looked up in the
+ * unsliced array, like metric.py:113-123. */
+int mc_beat_mask(const float* joints_dev, int32_t n_frames, int32_t num_joints, const double* mean_vel_dev, int32_t mean_vel_fp32,
+                 int32_t t_start, int32_t t_end, double pose_fps, int32_t order, double threshold, uint8_t* mask_out_dev, void* stream);
+/* bytes of workspace of mc_beat_align (-1: bad argument) */
+int64_t mc_beat_align_work_bytes(int32_t n_slice, int32_t n_upper);
+/* mask_dev [num_joints, n_slice] as written by mc_beat_mask, upper_body_host: n_upper (1..64) joint indices in HOST memory,
+ * onsets_dev fp64 [n_onsets] seconds (n_onsets >= 1) -> score_out_dev fp64 [1]: the mean over the upper-body joints of the mean
+ * over onsets of exp(-d^2 / (2 sigma^2)), d = |onset - nearest beat time i / pose_fps| (GAHR, metric.py:204-216); a joint
+ * without beats contributes 0.  Fixed-order fp64 sums, no atomics: two runs give the same bits.  work_dev 8-byte aligned. */
+int mc_beat_align(const uint8_t* mask_dev, int32_t num_joints, int32_t n_slice, const int32_t* upper_body_host, int32_t n_upper,
+                  const double* onsets_dev, int32_t n_onsets, double pose_fps, double sigma, void* work_dev, int64_t work_bytes,
+                  double* score_out_dev, void* stream);
 
 /* out = a * x + b * noise over n elements (out may alias x) */
 int mc_op_renoise(const float* x_dev, const float* noise_dev, float a, float b, float* out_dev, int64_t n, void* stream);

@@ -174,3 +174,22 @@ class SMPLXBodyModel:
                    'mc_smplx_vertices')
         verts = verts.reshape(lead + (self.num_vertices, 3))
         return (verts, jout.reshape(lead + (NUM_JOINTS, 3))) if return_joints else verts
+
+    def vertex_error_sums(self, poses_a, expr_a, trans_a, poses_b, expr_b, trans_b, betas=None, work_bytes=DEFAULT_WORK_BYTES):
+        """The vertices of pose sets a and b (one ``betas`` for both) reduced on the device to the fp64 pair
+        ``[sum (a - b)^2, sum |(a[t+1] - b[t]) - (b[t+1] - b[t])|]`` over all frames, vertices and coordinates
+        (``mc_smplx_vertex_errors``): a device tensor [2]; the vertices never leave the device, and the result does not depend
+        on ``work_bytes``."""
+        obj = self.native()
+        dev, lead, n, pa, ea, ta, betas_d, per_frame = self._operands(poses_a, expr_a, trans_a, betas)
+        _, lead_b, nb_, pb, eb, tb, _, _ = self._operands(poses_b, expr_b, trans_b, betas)
+        if nb_ != n:
+            raise ValueError(f'the two pose sets hold {n} and {nb_} frames')
+        need = lambda frames: int(obj.lib.mc_smplx_vertex_errors_work_bytes(obj.handle, frames, n, per_frame))
+        wb = max(min(int(work_bytes), need(max(n, 1))), need(1))
+        work = torch.empty(wb, device=dev, dtype=torch.uint8)
+        sums = torch.empty(2, device=dev, dtype=torch.float64)
+        _lib.check(obj.lib.mc_smplx_vertex_errors(obj.handle, _p(pa), _p(ea), _p(ta), _p(pb), _p(eb), _p(tb), _p(betas_d), per_frame, n, _p(work),
+                                                  wb, _p(sums), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                   'mc_smplx_vertex_errors')
+        return sums

@@ -126,6 +126,22 @@ __device__ __forceinline__ float group_max(float v, int width) {
     return v;
 }
 
+// fp64 sums in a fixed order (no atomics: the same bits on every run).  wave_sum_f64: lane 0 holds the wave's sum;
+// block_sum_f64: thread 0 of a 256-thread workgroup holds ((w0 + w1) + w2) + w3; `sh` = 4 doubles of LDS, reusable after the call
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ double block_sum_f64(double v, double* sh) {
+    v = wave_sum_f64(v);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const double r = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+    __syncthreads();
+    return r;
+}
+
 // XCD-aware block remap: consecutive remapped ids land on the same XCD (block b runs on XCD b % 8),
 // bijective for any grid size (guide section 5, "XCD swizzle must be bijective").
 __device__ __forceinline__ int xcd_remap(int bid, int nwg) {

@@ -14,6 +14,9 @@
 // [psi | vec(R - I) | beta], the blend shapes are one launch of the fp32 MFMA GEMM (mc_gemm.hip) against the K-contiguous
 // weight [expr_dirs | posedirs | shapedirs] laid out at finalize, and skin_k blends the frame's 55 A_j (LDS) with the
 // per-vertex nonzero skin weights (ELL, in registers across the frames of a workgroup) and stores through LDS in 16-byte pieces.
+// mc_smplx_vertex_errors runs that vertex path for two pose sets chunk by chunk and keeps only the two sums behind the face l2 /
+// lvel errors (tools/s2g_test.py:407-412): vert_err_k leaves one fp64 partial per frame and sum, vert_err_sum_k adds them in one
+// fixed order over the frames, so the sums do not depend on the chunk size either.
 #include "mc_common.h"
 #include "mc_gemm.h"
 #include "mc_options.h"
@@ -223,6 +226,39 @@ __global__ __launch_bounds__(256) void skin_k(const float* __restrict__ vp, long
     }
 }
 
+// face errors of tools/s2g_test.py:409-410, one workgroup per frame f of a chunk: l2[f] = sum (a - b)^2 and, from the second
+// frame of the run on, lvel[f] = sum |(a[f] - b[f-1]) - (b[f] - b[f-1])|; fp32 element operations, fp64 sums in a fixed order.
+// `vb` holds the previous frame's b in its row 0 (row f + 1 = frame f of the chunk); frame f of the chunk is frame f_base + f of the run
+__global__ __launch_bounds__(256) void vert_err_k(const float* __restrict__ va, const float* __restrict__ vb, long E, long f_base,
+                                                  double* __restrict__ l2, double* __restrict__ lvel) {
+    __shared__ double sh[4];
+    const long f = blockIdx.x;
+    const float *a = va + f * E, *b = vb + (f + 1) * E, *bp = vb + f * E;
+    const bool vel = f_base + f > 0;
+    double s2 = 0.0, sv = 0.0;
+    for (long i = threadIdx.x; i < E; i += 256) {
+        const float x = a[i], y = b[i], d = x - y;
+        s2 += (double)(d * d);
+        if (vel) {
+            const float p = bp[i];
+            sv += (double)fabsf((x - p) - (y - p));
+        }
+    }
+    s2 = block_sum_f64(s2, sh);
+    sv = block_sum_f64(sv, sh);
+    if (threadIdx.x == 0) { l2[f_base + f] = s2; lvel[f_base + f] = sv; }
+}
+
+// the per-frame partials in one fixed order over the frames: sums[0] = sum l2, sums[1] = sum lvel
+__global__ __launch_bounds__(256) void vert_err_sum_k(const double* __restrict__ l2, const double* __restrict__ lvel, int n, double* __restrict__ sums) {
+    __shared__ double sh[4];
+    double s2 = 0.0, sv = 0.0;
+    for (int f = threadIdx.x; f < n; f += 256) { s2 += l2[f]; sv += lvel[f]; }
+    s2 = block_sum_f64(s2, sh);
+    sv = block_sum_f64(sv, sh);
+    if (threadIdx.x == 0) { sums[0] = s2; sums[1] = sv; }
+}
+
 int round_up(long a, int m) { return (int)((a + m - 1) / m * m); }
 
 }  // namespace
@@ -269,6 +305,44 @@ int launch_joints(const mc_smplx* m, const double* poses, const double* expr, co
 int check_frames(const mc_smplx* m, const void* poses, const void* betas, int n) {
     MC_REQUIRE(m && poses && betas && n >= 0, "SMPL-X body model: bad argument");
     MC_REQUIRE(m->finalized, "SMPL-X body model not finalized");
+    return MC_OK;
+}
+
+long round_up4(long a) { return (a + 3) / 4 * 4; }
+
+struct VertScratch { float *bias, *feat, *A, *vp; };                     // [N4] (per-call betas), [chunk,Kc], [chunk,JA], [chunk,N4]
+struct FrameOperands { const double *poses, *expr, *trans, *betas; };   // a call's inputs from one frame on
+
+FrameOperands frames_from(const mc_smplx* m, const double* poses, const double* expr, const double* trans, const double* betas, int per_frame, long c0) {
+    return {poses + c0 * NJ3, expr ? expr + c0 * m->ne : nullptr, trans ? trans + c0 * 3 : nullptr, per_frame ? betas + c0 * m->nb : betas};
+}
+
+int launch_shape_bias(const mc_smplx* m, const double* betas, float* bias, hipStream_t s) {
+    hipLaunchKernelGGL(shape_bias_k, dim3(cdiv(m->N4, 256)), dim3(256), 0, s, m->vt4, m->W, (long)m->Kfull, m->Kp, m->nb, betas, m->N4, bias);
+    MC_LAUNCH_CHECK();
+    return MC_OK;
+}
+
+// the vertices of nc frames (one chunk: its scratch fits `w`) -> frames f_base .. f_base + nc of `verts_out` (16-byte aligned base)
+int vertices_chunk(const mc_smplx* m, const McOptions* o, const FrameOperands& x, int per_frame, int nc, const VertScratch& w, float* joints_out,
+                   float* verts_out, long f_base, hipStream_t s) {
+    const int Kc = per_frame ? m->Kfull : m->Kp, N4 = m->N4, V = m->V;
+    int r;
+    if ((r = launch_joints(m, x.poses, x.expr, x.trans, x.betas, per_frame, nc, joints_out, w.A, s))) return r;
+    hipLaunchKernelGGL(feat_k, dim3(nc), dim3(256), 0, s, x.poses, x.expr, per_frame ? x.betas : nullptr, m->ne, m->nb, m->Kp, Kc, w.feat);
+    MC_LAUNCH_CHECK();
+    GemmArgs g;                                  // v_posed = feat W^T + (v_template [+ shapedirs beta])
+    g.A = w.feat; g.lda = Kc; g.W = m->W; g.ldw = m->Kfull; g.bias = per_frame ? m->vt4 : w.bias;
+    g.C = w.vp; g.ldc = N4; g.M = nc; g.N = N4; g.K = Kc;
+    // one kernel whatever the chunk's row count: a chunked call accumulates every element in the same order as an unchunked one
+    g.tune = (int)o->gemm_tune & ~kTuneDma;
+    if ((r = mc_launch_gemm(GM_PLAIN, g, 1, 0, s))) return r;
+    const dim3 grid(cdiv(V, VT), cdiv(nc, SKF));
+    if (m->NZ == 4) hipLaunchKernelGGL(skin_k<4>, grid, dim3(256), 0, s, w.vp, (long)N4, w.A, m->ell_j, m->ell_w, m->NZ, V, nc, f_base, verts_out);
+    else if (m->NZ == 8) hipLaunchKernelGGL(skin_k<8>, grid, dim3(256), 0, s, w.vp, (long)N4, w.A, m->ell_j, m->ell_w, m->NZ, V, nc, f_base, verts_out);
+    else if (m->NZ == 16) hipLaunchKernelGGL(skin_k<16>, grid, dim3(256), 0, s, w.vp, (long)N4, w.A, m->ell_j, m->ell_w, m->NZ, V, nc, f_base, verts_out);
+    else hipLaunchKernelGGL(skin_k<0>, grid, dim3(256), 0, s, w.vp, (long)N4, w.A, m->ell_j, m->ell_w, m->NZ, V, nc, f_base, verts_out);
+    MC_LAUNCH_CHECK();
     return MC_OK;
 }
 
@@ -394,43 +468,76 @@ int mc_smplx_vertices(mc_smplx* m, const double* poses, const double* expr, cons
                "SMPL-X body model: the vertex output and the workspace must be 16-byte aligned device buffers");
     if (n == 0) return MC_OK;
     hipStream_t s = (hipStream_t)stream;
-    const int Kc = betas_per_frame ? m->Kfull : m->Kp, N4 = m->N4, V = m->V;
+    const int Kc = betas_per_frame ? m->Kfull : m->Kp, N4 = m->N4;
     const long one = mc_smplx_work_bytes(m, 1, betas_per_frame), fixed = mc_smplx_work_bytes(m, 0, betas_per_frame);
     MC_REQUIRE(work_bytes >= one, "SMPL-X body model: the workspace holds %ld bytes, one frame needs %ld (mc_smplx_work_bytes)", (long)work_bytes, one);
     const int chunk = (int)std::min<long>((work_bytes - fixed) / (one - fixed), std::min<long>(n, 65535L * SKF));
-    float* bias = (float*)work;
-    float* feat = bias + (betas_per_frame ? 0 : N4);
-    float* A = feat + (long)chunk * Kc;
-    float* vp = A + (long)chunk * JA;
+    VertScratch w;
+    w.bias = (float*)work;
+    w.feat = w.bias + (betas_per_frame ? 0 : N4);
+    w.A = w.feat + (long)chunk * Kc;
+    w.vp = w.A + (long)chunk * JA;
     const McOptions* o = mc_process_options();
     if (!o) return MC_ERR_ARG;
-    if (!betas_per_frame) {
-        hipLaunchKernelGGL(shape_bias_k, dim3(cdiv(N4, 256)), dim3(256), 0, s, m->vt4, m->W, (long)m->Kfull, m->Kp, m->nb, betas, N4, bias);
-        MC_LAUNCH_CHECK();
+    int r;
+    if (!betas_per_frame && (r = launch_shape_bias(m, betas, w.bias, s))) return r;
+    for (int c0 = 0; c0 < n; c0 += chunk) {
+        const FrameOperands x = frames_from(m, poses, expr, trans, betas, betas_per_frame, c0);
+        if ((r = vertices_chunk(m, o, x, betas_per_frame, std::min(chunk, n - c0), w, joints_out ? joints_out + (long)c0 * NJ3 : nullptr, verts_out, c0, s)))
+            return r;
     }
+    return MC_OK;
+}
+
+int64_t mc_smplx_vertex_errors_work_bytes(const mc_smplx* m, int32_t chunk_frames, int32_t n_frames, int32_t betas_per_frame) {
+    if (!m || chunk_frames < 0 || n_frames < 0) return -1;
+    const long E = 3L * m->V, c = chunk_frames;
+    // per-frame partials of the two sums, the vertex path's scratch, a's vertices, b's vertices behind the previous frame's
+    return (int64_t)2 * sizeof(double) * n_frames + mc_smplx_work_bytes(m, chunk_frames, betas_per_frame) +
+           (int64_t)sizeof(float) * (round_up4(c * E) + round_up4((c + 1) * E));
+}
+
+int mc_smplx_vertex_errors(mc_smplx* m, const double* poses_a, const double* expr_a, const double* trans_a, const double* poses_b,
+                           const double* expr_b, const double* trans_b, const double* betas, int32_t betas_per_frame, int32_t n, void* work,
+                           int64_t work_bytes, double* sums_out, void* stream) {
+    if (int r = check_frames(m, poses_a, betas, n)) return r;
+    MC_REQUIRE(poses_b && sums_out && work && ((uintptr_t)work & 15) == 0,
+               "SMPL-X vertex errors: null pose set or output, or a workspace that is not a 16-byte aligned device buffer");
+    hipStream_t s = (hipStream_t)stream;
+    const int Kc = betas_per_frame ? m->Kfull : m->Kp, N4 = m->N4;
+    const long E = 3L * m->V, one = mc_smplx_vertex_errors_work_bytes(m, 1, n, betas_per_frame);
+    MC_REQUIRE(work_bytes >= one, "SMPL-X vertex errors: the workspace holds %ld bytes, %d frames one at a time need %ld (mc_smplx_vertex_errors_work_bytes)",
+               (long)work_bytes, n, one);
+    int chunk = 1, top = (int)std::min<long>(std::max(n, 1), 65535L * SKF);          // the most frames per chunk that fit
+    while (chunk < top) {
+        const int mid = chunk + (top - chunk + 1) / 2;
+        if (mc_smplx_vertex_errors_work_bytes(m, mid, n, betas_per_frame) <= work_bytes) chunk = mid; else top = mid - 1;
+    }
+    double* l2 = (double*)work;
+    double* lvel = l2 + n;
+    VertScratch w;
+    w.bias = (float*)(lvel + n);
+    w.feat = w.bias + (betas_per_frame ? 0 : N4);
+    w.A = w.feat + (long)chunk * Kc;
+    w.vp = w.A + (long)chunk * JA;
+    float* va = w.vp + (long)chunk * N4;
+    float* vb = va + round_up4(chunk * E);
+    const McOptions* o = mc_process_options();
+    if (!o) return MC_ERR_ARG;
+    int r;
+    if (n > 0 && !betas_per_frame && (r = launch_shape_bias(m, betas, w.bias, s))) return r;
     for (int c0 = 0; c0 < n; c0 += chunk) {
         const int nc = std::min(chunk, n - c0);
-        const double* po = poses + (long)c0 * NJ3;
-        const double* ex = expr ? expr + (long)c0 * m->ne : nullptr;
-        const double* tr = trans ? trans + (long)c0 * 3 : nullptr;
-        const double* be = betas_per_frame ? betas + (long)c0 * m->nb : betas;
-        int r;
-        if ((r = launch_joints(m, po, ex, tr, be, betas_per_frame, nc, joints_out ? joints_out + (long)c0 * NJ3 : nullptr, A, s))) return r;
-        hipLaunchKernelGGL(feat_k, dim3(nc), dim3(256), 0, s, po, ex, betas_per_frame ? be : nullptr, m->ne, m->nb, m->Kp, Kc, feat);
+        // both vertex sets of the chunk at frame 0 of their buffers (b behind row 0, the last b frame of the chunk before)
+        if ((r = vertices_chunk(m, o, frames_from(m, poses_a, expr_a, trans_a, betas, betas_per_frame, c0), betas_per_frame, nc, w, nullptr, va, 0, s)) ||
+            (r = vertices_chunk(m, o, frames_from(m, poses_b, expr_b, trans_b, betas, betas_per_frame, c0), betas_per_frame, nc, w, nullptr, vb, 1, s)))
+            return r;
+        hipLaunchKernelGGL(vert_err_k, dim3(nc), dim3(256), 0, s, va, vb, E, (long)c0, l2, lvel);
         MC_LAUNCH_CHECK();
-        GemmArgs g;                                  // v_posed = feat W^T + (v_template [+ shapedirs beta])
-        g.A = feat; g.lda = Kc; g.W = m->W; g.ldw = m->Kfull; g.bias = betas_per_frame ? m->vt4 : bias;
-        g.C = vp; g.ldc = N4; g.M = nc; g.N = N4; g.K = Kc;
-        // one kernel whatever the chunk's row count: a chunked call accumulates every element in the same order as an unchunked one
-        g.tune = (int)o->gemm_tune & ~kTuneDma;
-        if ((r = mc_launch_gemm(GM_PLAIN, g, 1, 0, s))) return r;
-        const dim3 grid(cdiv(V, VT), cdiv(nc, SKF));
-        if (m->NZ == 4) hipLaunchKernelGGL(skin_k<4>, grid, dim3(256), 0, s, vp, (long)N4, A, m->ell_j, m->ell_w, m->NZ, V, nc, (long)c0, verts_out);
-        else if (m->NZ == 8) hipLaunchKernelGGL(skin_k<8>, grid, dim3(256), 0, s, vp, (long)N4, A, m->ell_j, m->ell_w, m->NZ, V, nc, (long)c0, verts_out);
-        else if (m->NZ == 16) hipLaunchKernelGGL(skin_k<16>, grid, dim3(256), 0, s, vp, (long)N4, A, m->ell_j, m->ell_w, m->NZ, V, nc, (long)c0, verts_out);
-        else hipLaunchKernelGGL(skin_k<0>, grid, dim3(256), 0, s, vp, (long)N4, A, m->ell_j, m->ell_w, m->NZ, V, nc, (long)c0, verts_out);
-        MC_LAUNCH_CHECK();
+        if (c0 + nc < n) MC_HIP(hipMemcpyAsync(vb, vb + (long)nc * E, E * sizeof(float), hipMemcpyDeviceToDevice, s));
     }
+    hipLaunchKernelGGL(vert_err_sum_k, dim3(1), dim3(256), 0, s, l2, lvel, n, sums_out);
+    MC_LAUNCH_CHECK();
     return MC_OK;
 }
 

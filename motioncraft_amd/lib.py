@@ -134,6 +134,13 @@ _SIGNATURES = {
     'mc_smplx_joints': (ctypes.c_int, [_P, _P, _P, _P, _P, ctypes.c_int32, ctypes.c_int32, _P, _P]),
     'mc_smplx_work_bytes': (ctypes.c_int64, [_P, ctypes.c_int32, ctypes.c_int32]),
     'mc_smplx_vertices': (ctypes.c_int, [_P, _P, _P, _P, _P, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_int64, _P, _P, _P]),
+    'mc_smplx_vertex_errors_work_bytes': (ctypes.c_int64, [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
+    'mc_smplx_vertex_errors': (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_int64, _P, _P]),
+    'mc_beat_mask': (ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_double,
+                                    ctypes.c_int32, ctypes.c_double, _P, _P]),
+    'mc_beat_align_work_bytes': (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32]),
+    'mc_beat_align': (ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, _P, ctypes.c_int32,
+                                     ctypes.c_double, ctypes.c_double, _P, ctypes.c_int64, _P, _P]),
     'mc_op_renoise': (ctypes.c_int, [_P, _P, ctypes.c_float, ctypes.c_float, _P, ctypes.c_int64, _P]),
     'mc_debug_flop_ledger': (ctypes.c_int, [ctypes.c_int32]),
     'mc_debug_flop_ledger_dump': (ctypes.c_int64, [ctypes.c_char_p, ctypes.c_int64]),

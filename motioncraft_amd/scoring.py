@@ -1,0 +1,306 @@
+"""The scoring half of the speech-to-gesture (S2G) and music-to-dance (M2D) tests: what the reference prints at the end of
+``tools/s2g_test.py`` (``CustomTrainer.test``, lines 262-483) and ``tools/m2d_test.py`` (``finedance_eval``, lines 234-309).
+
+  * ``BeatAlignment``: ``alignment.load_pose`` + ``alignment.calculate_align`` of ``mogen/datasets/EMAGE_2024/utils/metric.py``
+    (lines 78-127, 199-242) on the device (``mc_beat_mask`` / ``mc_beat_align``, ``csrc/mc_metrics.hip``), fed the 55 joints
+    ``SMPLXBodyModel.joints`` leaves there.  Audio onset detection (``load_audio``: librosa) stays with the caller: onset times
+    are an input.
+  * ``face_errors``: the face ``l2`` / ``lvel`` errors of ``s2g_test.py:377-412``; the two vertex sets are reduced to the two
+    sums on the device (``mc_smplx_vertex_errors``) and never leave it.
+  * ``S2GScorer`` / ``M2DScorer``: the accumulation and the printed numbers of the two tools, on the existing ``L1div``, FID and
+    diversity functions of ``evaluation`` and the device embedding model.
+
+Nothing here falls back to the host: the kernels are the only implementation, and a missing library or GPU is an error.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import lib as _lib
+from .body_model import DEFAULT_WORK_BYTES, NUM_JOINTS
+from .evaluation import L1div, calculate_activation_statistics, calculate_diversity, calculate_frechet_distance
+
+UPPER_BODY = (3, 6, 9, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21)           # metric.py:55
+MAX_ORDER = MAX_UPPER = 64                                               # csrc/mc_metrics.hip
+M2D_MAX_FRAMES = 4096                                                    # m2d_test.py:243
+
+
+def _p(t):
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def _stream():
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+class Beats:
+    """What ``load_pose`` returns: the beat mask uint8 [55, t_end - t_start] on the device.  Iterating (or ``lists()``) gives the
+    reference's form, one int64 array of slice-relative beat frames per joint."""
+
+    def __init__(self, mask):
+        self.mask = mask
+
+    def lists(self):
+        m = self.mask.cpu().numpy()
+        return [np.flatnonzero(row).astype(np.int64) for row in m]
+
+    def __iter__(self):
+        return iter(self.lists())
+
+    def __len__(self):
+        return self.mask.shape[0]
+
+
+def _check_onsets(onset_times):
+    on = np.ascontiguousarray(np.asarray(onset_times, dtype=np.float64).reshape(-1))
+    if on.size < 1:
+        raise ValueError('no onset times: the align score is a mean over the onsets')
+    return on
+
+
+class BeatAlignment:
+    """``alignment(sigma, order, mmae, upper_body)`` of metric.py:54-62 with its method names.  ``mean_vel`` [55]: float32 divides
+    the fp32 speeds in fp32, anything else in float64, as numpy would."""
+
+    def __init__(self, sigma, order, mean_vel, upper_body=UPPER_BODY):
+        self.sigma, self.order = float(sigma), int(order)
+        self.upper_body = [int(j) for j in upper_body]
+        self.threshold = 0.3                                             # metric.py:62
+        mv = np.asarray(mean_vel)
+        if mv.shape != (NUM_JOINTS,):
+            raise ValueError(f'mean_vel must be [{NUM_JOINTS}], got {mv.shape}')
+        if not 1 <= self.order <= MAX_ORDER:
+            raise ValueError(f'order={self.order}: 1..{MAX_ORDER}')
+        if not self.sigma > 0:
+            raise ValueError(f'sigma={self.sigma}: must be positive')
+        if not 1 <= len(self.upper_body) <= MAX_UPPER or any(not 0 <= j < NUM_JOINTS for j in self.upper_body):
+            raise ValueError(f'upper_body: 1..{MAX_UPPER} joint indices below {NUM_JOINTS}, got {self.upper_body}')
+        self.mean_vel_fp32 = int(mv.dtype == np.float32)
+        self.mean_vel = np.ascontiguousarray(mv, dtype=np.float64)       # an fp32 value widens exactly
+        self._mv_dev = None
+
+    @staticmethod
+    def _check_pose(joints, t_start, t_end, pose_fps):
+        shape = tuple(joints.shape)
+        if len(shape) != 3 or shape[1:] != (NUM_JOINTS, 3):
+            raise ValueError(f'joints must be [T, {NUM_JOINTS}, 3], got {shape}')
+        t_start, t_end = int(t_start), int(t_end)
+        if t_end - t_start < 1:
+            raise ValueError(f'the slice [{t_start}, {t_end}) holds no frame')
+        if shape[0] < 2 or t_start < 0 or t_end > shape[0]:
+            raise ValueError(f'the slice [{t_start}, {t_end}) must lie within the {shape[0]} frames (at least 2)')
+        if not float(pose_fps) > 0:
+            raise ValueError(f'pose_fps={pose_fps}: must be positive')
+        return t_start, t_end
+
+    def load_pose(self, joints, t_start, t_end, pose_fps):
+        """joints fp32 [T, 55, 3] (device tensor, or anything ``torch.as_tensor`` takes) -> ``Beats`` of the frames
+        ``t_start:t_end`` (metric.py:78-127 with ``without_file=True``)."""
+        t_start, t_end = self._check_pose(joints, t_start, t_end, pose_fps)
+        lib = _lib.load(require_gpu=True)
+        j = torch.as_tensor(joints)
+        j = j.to(device=j.device if j.is_cuda else 'cuda', dtype=torch.float32).contiguous()
+        if self._mv_dev is None or self._mv_dev.device != j.device:
+            self._mv_dev = torch.from_numpy(self.mean_vel).to(j.device)
+        mask = torch.empty(NUM_JOINTS, t_end - t_start, device=j.device, dtype=torch.uint8)
+        _lib.check(lib.mc_beat_mask(_p(j), j.shape[0], NUM_JOINTS, _p(self._mv_dev), self.mean_vel_fp32, t_start, t_end, float(pose_fps),
+                                    self.order, self.threshold, _p(mask), _stream()), 'mc_beat_mask')
+        return Beats(mask)
+
+    def _align(self, onsets, beats, pose_fps):
+        lib = _lib.load(require_gpu=True)
+        mask = beats.mask
+        on = torch.from_numpy(onsets).to(mask.device)
+        nj, n, nu = mask.shape[0], mask.shape[1], len(self.upper_body)
+        wb = int(lib.mc_beat_align_work_bytes(n, nu))
+        work = torch.empty(wb // 8 + 1, device=mask.device, dtype=torch.float64)
+        score = torch.empty(1, device=mask.device, dtype=torch.float64)
+        upper = (ctypes.c_int32 * nu)(*self.upper_body)
+        _lib.check(lib.mc_beat_align(_p(mask), nj, n, upper, nu, _p(on), on.numel(), float(pose_fps), self.sigma, _p(work), work.numel() * 8,
+                                     _p(score), _stream()), 'mc_beat_align')
+        return float(score.item())
+
+    def calculate_align(self, onset_times, beats, pose_fps=30):
+        """onset times in seconds + the ``Beats`` of ``load_pose`` -> the align score (metric.py:228-242)."""
+        onsets = _check_onsets(onset_times)
+        if not isinstance(beats, Beats):
+            raise TypeError('beats: the object load_pose returned')
+        if not float(pose_fps) > 0:
+            raise ValueError(f'pose_fps={pose_fps}: must be positive')
+        return self._align(onsets, beats, pose_fps)
+
+    def score(self, joints, t_start, t_end, pose_fps, onset_times, return_beats=False):
+        """``calculate_align(onset_times, load_pose(joints, t_start, t_end, pose_fps), pose_fps)`` in one call."""
+        onsets = _check_onsets(onset_times)
+        self._check_pose(joints, t_start, t_end, pose_fps)
+        beats = self.load_pose(joints, t_start, t_end, pose_fps)
+        s = self._align(onsets, beats, pose_fps)
+        return (s, beats) if return_beats else s
+
+
+# ---- the channel packings of tools/s2g_test.py ---------------------------------------------------------------------------
+def _rows(x, width, name):
+    x = torch.as_tensor(x)
+    if x.dim() != 2 or x.shape[1] != width:
+        raise ValueError(f'{name} must be [T, {width}], got {tuple(x.shape)}')
+    return x.float()
+
+
+def unpack_rec_motion(rec_motion):
+    """The sampled 322-d motion -> (rec_pose [T,165], rec_exp [T,100], rec_trans [T,3]), s2g_test.py:290-297: body 0:66 stays,
+    the jaw comes from 156:159, the hands (motion 66:156) go to 75:165, the eyes stay zero."""
+    m = _rows(rec_motion, 322, 'rec_motion')
+    pose = m.new_zeros(m.shape[0], 165)
+    pose[:, :66] = m[:, :66]
+    pose[:, 66:69] = m[:, 156:159]
+    pose[:, 75:165] = m[:, 66:156]
+    return pose, m[:, 209:309], m[:, 309:312]
+
+
+def pack_motion(pose, exps, trans):
+    """The inverse for the target (s2g_test.py:306-311): poses / expressions / trans -> the 322-d embedding input; channels
+    159:209 and 312:322 stay zero."""
+    pose, exps, trans = _rows(pose, 165, 'pose'), _rows(exps, 100, 'expressions'), _rows(trans, 3, 'trans')
+    m = pose.new_zeros(pose.shape[0], 322)
+    m[:, :66] = pose[:, :66]
+    m[:, 66:156] = pose[:, 75:165]
+    m[:, 156:159] = pose[:, 66:69]
+    m[:, 209:309] = exps
+    m[:, 309:312] = trans
+    return m
+
+
+def hand_only_motion(pose, trans):
+    """The hand-only embedding input of s2g_test.py:328-342: global orientation, the two hands and the translation; body, jaw
+    and expressions zero."""
+    pose, trans = _rows(pose, 165, 'pose'), _rows(trans, 3, 'trans')
+    m = pose.new_zeros(pose.shape[0], 322)
+    m[:, :3] = pose[:, :3]
+    m[:, 66:156] = pose[:, 75:165]
+    m[:, 309:312] = trans
+    return m
+
+
+def m2d_hand_only_motion(motion):
+    """m2d_test.py:265-268: channels 66:156 only."""
+    motion = _rows(motion, 322, 'motion')
+    m = torch.zeros_like(motion)
+    m[:, 66:156] = motion[:, 66:156]
+    return m
+
+
+def face_errors(model, rec_pose, rec_exp, tar_pose, tar_exp, betas, work_bytes=DEFAULT_WORK_BYTES):
+    """``(l2, lvel)`` of s2g_test.py:377-412: both body-model calls keep the jaw and the expressions only (every other rotation
+    and the translation are subtracted from themselves there), with one beta row per frame; ``model`` adds its mean hand pose to
+    the zeroed hands like the package.  l2 = mean (rec - tar)^2, lvel = mean |(rec[1:] - tar[:-1]) - (tar[1:] - tar[:-1])| over
+    the vertices, reduced on the device."""
+    rec_pose, tar_pose = _rows(rec_pose, 165, 'rec_pose'), _rows(tar_pose, 165, 'tar_pose')
+    n = rec_pose.shape[0]
+    if tar_pose.shape[0] != n:
+        raise ValueError(f'rec_pose holds {n} frames, tar_pose {tar_pose.shape[0]}')
+    if n < 2:
+        raise ValueError('lvel is a mean over frame pairs: at least 2 frames')
+
+    def jaw_only(p):
+        z = torch.zeros_like(p)
+        z[:, 66:69] = p[:, 66:69]
+        return z
+    sums = model.vertex_error_sums(jaw_only(rec_pose), rec_exp, None, jaw_only(tar_pose), tar_exp, None, betas, work_bytes=work_bytes)
+    s2, sv = sums.tolist()
+    per_frame = 3 * model.num_vertices
+    return s2 / (n * per_frame), sv / ((n - 1) * per_frame)
+
+
+def _fid(gt_emb, pred_emb):
+    gt_mu, gt_cov = calculate_activation_statistics(gt_emb, 1.0)
+    pr_mu, pr_cov = calculate_activation_statistics(pred_emb, 1.0)
+    return calculate_frechet_distance(gt_mu, gt_cov, pr_mu, pr_cov)
+
+
+def _embed(evaluator_model, motion):
+    m = motion.float().cuda().unsqueeze(0)
+    length = torch.tensor([m.shape[1]], device=m.device)
+    return evaluator_model.encode_motion(motion=m, motion_length=length, motion_mask=m, device=m.device).detach().cpu().numpy()
+
+
+class S2GScorer:
+    """The accumulators of ``CustomTrainer.test`` (s2g_test.py:262-483): ``add_sequence`` per test sequence, ``summary`` for the
+    six numbers it logs.  ``align_mask`` frames are cut from both ends before the beat alignment (:88, :420)."""
+
+    def __init__(self, body_model, evaluator_model, mean_vel, align_mask=60, sigma=0.3, order=7, pose_fps=30):
+        self.body_model, self.evaluator_model = body_model, evaluator_model
+        self.aligner = BeatAlignment(sigma, order, mean_vel)              # s2g_test.py:87
+        self.align_mask, self.pose_fps = int(align_mask), pose_fps
+        self.l1_calculator = L1div()
+        self.align = self.l2_all = self.lvel = 0.0
+        self.total_length = self.num_sequences = 0
+        self.emb = dict(pred=[], gt=[], hand_pred=[], hand_gt=[])
+
+    def add_sequence(self, rec_motion, tar_pose, tar_exps, tar_trans, tar_beta, onset_times):
+        """rec_motion [T,322] (the sample), tar_pose [T,165], tar_exps [T,100], tar_trans [T,3], tar_beta [T,300] | [300],
+        onset_times [n_on] seconds within the masked window (``load_audio`` of the audio cut like :418-419)."""
+        rec_pose, rec_exp, rec_trans = unpack_rec_motion(rec_motion)
+        tar_pose, tar_exps, tar_trans = _rows(tar_pose, 165, 'tar_pose'), _rows(tar_exps, 100, 'tar_exps'), _rows(tar_trans, 3, 'tar_trans')
+        T = tar_pose.shape[0]
+        if rec_pose.shape[0] != T or tar_exps.shape[0] != T or tar_trans.shape[0] != T:
+            raise ValueError('rec_motion, tar_pose, tar_exps and tar_trans must hold the same number of frames')
+        onsets = _check_onsets(onset_times)
+        if T - 2 * self.align_mask < 1:
+            raise ValueError(f'{T} frames leave nothing between the two masks of {self.align_mask}')
+        ev = self.evaluator_model
+        self.emb['pred'].append(_embed(ev, _rows(rec_motion, 322, 'rec_motion')))                     # :313-325
+        self.emb['gt'].append(_embed(ev, pack_motion(tar_pose, tar_exps, tar_trans)))
+        self.emb['hand_pred'].append(_embed(ev, hand_only_motion(rec_pose, rec_trans)))                # :328-356
+        self.emb['hand_gt'].append(_embed(ev, hand_only_motion(tar_pose, tar_trans)))
+        beta = torch.as_tensor(tar_beta)
+        beta = beta if beta.dim() == 2 else beta.reshape(1, -1).expand(T, -1)
+        joints = self.body_model.joints(rec_pose, None, None, beta)                                    # :364-376, :406
+        l2, lvel = face_errors(self.body_model, rec_pose, rec_exp, tar_pose, tar_exps, beta)           # :377-412
+        self.l2_all += l2 * T
+        self.lvel += lvel * T
+        self.l1_calculator.run(joints.reshape(T, -1))                                                  # :414
+        score = self.aligner.score(joints, self.align_mask, T - self.align_mask, self.pose_fps, onsets)
+        self.align += score * (T - 2 * self.align_mask)                                                # :420-422
+        self.total_length += T
+        self.num_sequences += 1
+        return dict(l2=l2, lvel=lvel, align=score)
+
+    def summary(self):
+        """The numbers of :451-483 under the names the reference logs them with."""
+        if not self.num_sequences:
+            raise ValueError('no sequence was added')
+        cat = {k: np.concatenate(v, axis=0) for k, v in self.emb.items()}
+        return {'l2 loss': self.l2_all / self.total_length,
+                'lvel loss': self.lvel / self.total_length,
+                'align score': self.align / (self.total_length - 2 * self.num_sequences * self.align_mask),
+                'l1div score': self.l1_calculator.avg(),
+                'FID(Whole Body) score': _fid(cat['gt'], cat['pred']),
+                'FID (Hands) score': _fid(cat['hand_gt'], cat['hand_pred'])}
+
+
+class M2DScorer:
+    """``finedance_eval``'s scoring loop (m2d_test.py:234-309): whole-body FID, hands FID (channels 66:156 only) and the
+    diversity of the sampled embeddings with ``diversity_times = N - 1``."""
+
+    def __init__(self, evaluator_model):
+        self.evaluator_model = evaluator_model
+        self.emb = dict(pred=[], gt=[], hand_pred=[], hand_gt=[])
+
+    def add_sequence(self, rec_motion, gt_motion):
+        rec, gt = _rows(rec_motion, 322, 'rec_motion')[:M2D_MAX_FRAMES], _rows(gt_motion, 322, 'gt_motion')     # :243
+        if rec.shape[0] != gt.shape[0]:
+            raise ValueError(f'the sample holds {rec.shape[0]} frames, the ground truth {gt.shape[0]} (m2d_test.py:246)')
+        ev = self.evaluator_model
+        self.emb['pred'].append(_embed(ev, rec))
+        self.emb['gt'].append(_embed(ev, gt))
+        self.emb['hand_pred'].append(_embed(ev, m2d_hand_only_motion(rec)))
+        self.emb['hand_gt'].append(_embed(ev, m2d_hand_only_motion(gt)))
+
+    def summary(self):
+        if len(self.emb['pred']) < 2:
+            raise ValueError('the diversity needs at least two sequences')
+        cat = {k: np.concatenate(v, axis=0) for k, v in self.emb.items()}
+        return {'FID(Whole Body) score': _fid(cat['gt'], cat['pred']),
+                'FID (Hands) score': _fid(cat['hand_gt'], cat['hand_pred']),
+                'Diversity score': calculate_diversity(cat['pred'], diversity_times=cat['pred'].shape[0] - 1, emb_scale=1.0, norm_scale=1.0)}

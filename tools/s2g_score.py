@@ -1,0 +1,65 @@
+#!/usr/bin/env python
+"""Score a speech-to-gesture run from its saved files: the six numbers the reference logs at the end of
+``tools/s2g_test.py`` (``CustomTrainer.test``, lines 451-483), computed on the device by ``motioncraft_amd.scoring``.
+
+    python tools/s2g_score.py RESULTS_DIR --onsets ONSETS_DIR --smplx_model SMPLX_NEUTRAL_2020.npz \
+        --evaluator CHECKPOINT.pth --mean_vel mean_vel.npy
+
+RESULTS_DIR holds the ``res_<id>.npz`` / ``gt_<id>.npz`` pairs the test writes (s2g_test.py:431-448: poses [T,165],
+expressions [T,100], trans [T,3], betas [300]); ONSETS_DIR one ``<id>.npy`` per pair with the audio onset times in seconds,
+i.e. ``alignment.load_audio`` of the audio cut by the align mask on both sides (s2g_test.py:416-419: librosa's onset
+detection stays with the caller).  The sample is re-packed from its saved arrays, so the 322-d channels the ``.npz`` does not
+carry (159:209, 312:322) enter the whole-body embedding as zeros.
+"""
+import argparse
+import glob
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import motioncraft_amd as mc                                    # noqa: E402
+from motioncraft_amd import scoring                             # noqa: E402
+from motioncraft_amd.body_model import SMPLXBodyModel           # noqa: E402
+
+
+def parse_args():
+    p = argparse.ArgumentParser(description='score res_*.npz / gt_*.npz pairs of a speech-to-gesture run')
+    p.add_argument('results', help='directory with the res_<id>.npz / gt_<id>.npz pairs')
+    p.add_argument('--onsets', required=True, metavar='DIR', help='directory with one <id>.npy of onset times (seconds) per pair')
+    p.add_argument('--smplx_model', required=True, metavar='PATH', help='the published SMPL-X model file (.npz)')
+    p.add_argument('--evaluator', required=True, metavar='PATH', help='checkpoint of the T2MContrastiveModel_SMPLX embedding model')
+    p.add_argument('--mean_vel', required=True, metavar='PATH', help='.npy [55]: the mean joint speeds the alignment divides by')
+    p.add_argument('--align_mask', type=int, default=60), p.add_argument('--pose_fps', type=float, default=30)
+    p.add_argument('--latent_dim', type=int, default=256), p.add_argument('--ff_size', type=int, default=1024)
+    p.add_argument('--num_layers', type=int, default=4), p.add_argument('--num_heads', type=int, default=4)
+    return p.parse_args()
+
+
+def main():
+    a = parse_args()
+    ids = sorted(os.path.basename(f)[4:-4] for f in glob.glob(os.path.join(a.results, 'res_*.npz')))
+    if not ids:
+        raise SystemExit(f'{a.results}: no res_*.npz')
+    body = SMPLXBodyModel.from_npz(a.smplx_model)
+    enc = dict(latent_dim=a.latent_dim, ff_size=a.ff_size, num_layers=a.num_layers, num_heads=a.num_heads)
+    evaluator = mc.build_submodule(dict(type='T2MContrastiveModel_SMPLX', motion_encoder=dict(nfeats=322, vae=True, **enc),
+                                        init_cfg=dict(type='Pretrained', checkpoint=a.evaluator)))
+    scorer = scoring.S2GScorer(body, evaluator, np.load(a.mean_vel), align_mask=a.align_mask, pose_fps=a.pose_fps)
+    t = lambda x: torch.from_numpy(np.asarray(x, dtype=np.float32))
+    for i in ids:
+        with np.load(os.path.join(a.results, f'res_{i}.npz')) as res, np.load(os.path.join(a.results, f'gt_{i}.npz')) as gt:
+            rec_motion = scoring.pack_motion(t(res['poses']), t(res['expressions']), t(res['trans']))
+            per_seq = scorer.add_sequence(rec_motion, t(gt['poses']), t(gt['expressions']), t(gt['trans']), t(gt['betas']).reshape(-1)[:300],
+                                          np.load(os.path.join(a.onsets, f'{i}.npy')))
+        print(f'{i}: {rec_motion.shape[0]} frames  l2 {per_seq["l2"]:.6e}  lvel {per_seq["lvel"]:.6e}  align {per_seq["align"]:.6f}', file=sys.stderr)
+    for name, value in scorer.summary().items():
+        print(f'{name}: {value}')
+
+
+if __name__ == '__main__':
+    main()
