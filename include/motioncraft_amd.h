@@ -277,6 +277,32 @@ int mc_op_gemm_tail(const float* h_dev, const float* a_dev, const float* w_dev, 
                     int32_t M, int32_t N, int32_t K, float wc, float wu, int32_t variant, void* stream);
 int mc_op_ln_rows(const float* x_dev, int64_t ldx, const float* gamma_dev, const float* beta_dev,
                   const float* add_dev, int32_t add_mod, float* y_dev, int64_t rows, int32_t L, void* stream);
+/* The two MC-Attn cores as context-free ops (st_attention.py:105-179; the launchers the step calls, no other work).  Layouts, as in the step:
+ *   mf   [2 B * T * H][4 L] motion rows = [body_value | key | value | query], row (b T + t) H + h.  The body op takes the row stride
+ *        ldmf >= L and reads the body_value columns only (the step passes 4 L); the temporal op reads rows of exactly 4 L
+ *   qkv  [frames * H][3 L] = [q | k | v] of the dynamic body topology;  wsm [H][H] = softmax(body_weight, dim 1), as the step passes it
+ *   tf   [2 B][Nt][2 L] text rows = [key | value];  mask [B][T] (sample b of the CFG-doubled batch reads row b % B; samples b >= B are
+ *        the unconditioned half: their text keys carry -1e6 and their text values are 0)
+ *   ys / yt [rows][H * L], row = frame (b T + t)
+ * mc_op_body_attention: ys[f] for the `frames` frames behind the four pointers: static mix + body_value + dynamic linear attention over the H
+ *   parts in 8 heads (H = 8 or 12; L = 32, 64, 128).  split_flag_dev != NULL and *split_flag_dev == 0: frames with frame0 + f >= twin_from
+ *   are the aliased CFG twins and are not produced (their ys rows stay untouched); NULL: no aliasing.
+ * mc_op_temporal_attention: yt rows of samples [b0, b0 + nb) of the 2 B.  twin_flag_dev != NULL and *twin_flag_dev == 0: a sample b >= B
+ *   reads the motion rows of sample b - B (its own were not produced).  skip_text != 0: the unconditioned half skips whole leading blocks
+ *   of its text rows (same bits).  `form` names the kernel; a form that does not exist for the shape is MC_ERR_ARG, never another form:
+ *   LSPLIT needs L >= 64, PAIR L == 64 and even H, the fp16 forms L >= 64. */
+enum { MC_TEMPORAL_STEP = 0,      /* what the fp32 step would launch for nb samples under the process options (temporal_split, chain);
+                                     a reduced-precision context would pick temporal_h_k above temporal_split: ask for F16X3 / F16 */
+       MC_TEMPORAL_WHOLE = 1,     /* temporal_k<L, false>: one workgroup per (sample, part) */
+       MC_TEMPORAL_LSPLIT = 2,    /* temporal_k<L, true>: 32-column slices, query chunks dealt over 2 workgroups while the grid stays <= 256 */
+       MC_TEMPORAL_PAIR = 3,      /* temporal_k<64, false, true>: two parts per workgroup */
+       MC_TEMPORAL_F16X3 = 4,     /* temporal_h_k<L, true>: fp16 MFMA, hi/lo three-product form */
+       MC_TEMPORAL_F16 = 5 };     /* temporal_h_k<L, false>: plain fp16 operands */
+int mc_op_body_attention(const float* mf_dev, int64_t ldmf, const float* qkv_dev, const float* wsm_dev, float* ys_dev, int64_t frames,
+                         int32_t H, int32_t L, int64_t twin_from, const int32_t* split_flag_dev, int64_t frame0, void* stream);
+int mc_op_temporal_attention(const float* mf_dev, const float* tf_dev, const float* mask_dev, float* yt_dev, int32_t b0, int32_t nb,
+                             int32_t B, int32_t T, int32_t Nt, int32_t H, int32_t L, int32_t form, int32_t skip_text,
+                             const int32_t* twin_flag_dev, void* stream);
 int mc_op_sampler_update(const float* x_t_dev, const float* out_text_dev, const float* out_none_dev,
                          const float* noise_dev, float* x_prev_dev, float* x0_dev, int64_t n,
                          const mc_step_coefs* coefs, void* stream);

@@ -887,6 +887,45 @@ int mc_op_ln_rows(const float* x, int64_t ldx, const float* gamma, const float* 
     return mc_launch_ln_rows(x, ldx, 0, gamma, beta, add, add_mod, y, L, rows, L, (hipStream_t)stream);
 }
 
+int mc_op_body_attention(const float* mf, int64_t ldmf, const float* qkv, const float* wsm, float* ys, int64_t frames, int32_t H, int32_t L,
+                         int64_t twin_from, const int32_t* split_flag, int64_t frame0, void* stream) {
+    MC_REQUIRE(mf && qkv && wsm && ys && frames >= 0 && ldmf >= L && twin_from >= 0 && frame0 >= 0, "bad body_attention args");
+    TwinAlias alias;
+    alias.split_flag = split_flag;
+    alias.from = twin_from;
+    return mc_launch_body(mf, ldmf, qkv, wsm, ys, frames, H, L, 8, (hipStream_t)stream, alias, frame0);
+}
+
+int mc_op_temporal_attention(const float* mf, const float* tf, const float* mask, float* yt, int32_t b0, int32_t nb, int32_t B, int32_t T,
+                             int32_t Nt, int32_t H, int32_t L, int32_t form, int32_t skip_text, const int32_t* twin_flag, void* stream) {
+    MC_REQUIRE(mf && tf && mask && yt && B > 0 && T > 0 && Nt > 0 && H > 0 && b0 >= 0 && nb >= 0 && b0 + nb <= 2 * B,
+               "bad temporal_attention args");
+    MC_REQUIRE(L == 32 || L == 64 || L == 128, "temporal_attention: latent_dim=%d unsupported (32, 64, 128)", L);
+    hipStream_t s = (hipStream_t)stream;
+    const bool sk = skip_text != 0;
+    switch (form) {
+    case MC_TEMPORAL_STEP: {         // the fp32 step's own choice
+        const McOptions* o = mc_process_options();
+        if (!o) return MC_ERR_ARG;
+        return mc_launch_temporal(mf, tf, mask, yt, b0, nb, B, T, Nt, H, L, s, twin_flag, o->temporal_split, (o->chain >> kChainTemporalPair) & 1, sk);
+    }
+    case MC_TEMPORAL_WHOLE:
+        return mc_launch_temporal(mf, tf, mask, yt, b0, nb, B, T, Nt, H, L, s, twin_flag, -1, false, sk);
+    case MC_TEMPORAL_LSPLIT:
+        MC_REQUIRE(L >= 64, "temporal_attention form LSPLIT: no column-sliced kernel at latent_dim=%d (64, 128)", L);
+        return mc_launch_temporal(mf, tf, mask, yt, b0, nb, B, T, Nt, H, L, s, twin_flag, (long)nb * H, false, sk);
+    case MC_TEMPORAL_PAIR:
+        MC_REQUIRE(L == 64 && H % 2 == 0, "temporal_attention form PAIR: no two-part kernel at latent_dim=%d, num_parts=%d (64, even)", L, H);
+        return mc_launch_temporal(mf, tf, mask, yt, b0, nb, B, T, Nt, H, L, s, twin_flag, -1, true, sk);
+    case MC_TEMPORAL_F16X3:
+    case MC_TEMPORAL_F16:
+        MC_REQUIRE(L >= 64, "temporal_attention form %s: no fp16 kernel at latent_dim=%d (64, 128)", form == MC_TEMPORAL_F16X3 ? "F16X3" : "F16", L);
+        return mc_launch_temporal_h(mf, tf, mask, yt, b0, nb, B, T, Nt, H, L, form == MC_TEMPORAL_F16X3, s, twin_flag, sk);
+    }
+    mc_set_error("temporal_attention: form %d (0 step, 1 WHOLE, 2 LSPLIT, 3 PAIR, 4 F16X3, 5 F16)", form);
+    return MC_ERR_ARG;
+}
+
 int mc_op_sampler_update(const float* x_t, const float* ot, const float* on, const float* noise, float* x_prev, float* x0,
                          int64_t n, const mc_step_coefs* k, void* stream) {
     MC_REQUIRE(x_t && ot && on && noise && x_prev && k, "null argument");

@@ -14,6 +14,7 @@ LIB_PATH = os.path.join(_HERE, 'libmotioncraft_amd.so')
 
 MC_OK = 0
 ACT_NONE, ACT_GELU, ACT_SILU = 0, 1, 2
+TEMPORAL_FORMS = dict(step=0, whole=1, lsplit=2, pair=3, f16x3=4, f16=5)      # MC_TEMPORAL_* (mc_op_temporal_attention's form)
 
 
 class ModelConfig(ctypes.Structure):
@@ -109,6 +110,10 @@ _SIGNATURES = {
                                        ctypes.c_int32, _P]),
     'mc_op_ln_rows': (ctypes.c_int, [_P, ctypes.c_int64, _P, _P, _P, ctypes.c_int32, _P, ctypes.c_int64,
                                      ctypes.c_int32, _P]),
+    'mc_op_body_attention': (ctypes.c_int, [_P, ctypes.c_int64, _P, _P, _P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
+                                            _P, ctypes.c_int64, _P]),
+    'mc_op_temporal_attention': (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P]),
     'mc_op_sampler_update': (ctypes.c_int, [_P, _P, _P, _P, _P, _P, ctypes.c_int64, ctypes.POINTER(StepCoefs), _P]),
     'mc_postprocess_smplx': (ctypes.c_int, [_P, _P, _P, _P, _P, ctypes.POINTER(ctypes.c_int32 * 4), ctypes.c_int32,
                                             ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P]),
