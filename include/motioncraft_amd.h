@@ -31,6 +31,7 @@
  *   mc_smplx_vertex_errors  the face l2 / lvel sums over the vertices of sample and target   tools/s2g_test.py:377-412
  *   mc_beat_mask, mc_beat_align  alignment.load_pose / calculate_align (beat alignment score)
  *                                                                      mogen/datasets/EMAGE_2024/utils/metric.py:78-127,199-242
+ *   mc_onset_strength, mc_onset_pick  alignment.load_audio (librosa's onset_detect)   metric.py:64-76
  *   mc_op_renoise         GaussianDiffusion._undo (resampling jumps)   gaussian_diffusion.py:429-435, 1113-1118
  *
  * Conventions: plain pointers and sizes only.  `*_dev` pointers are device (HBM) addresses owned
@@ -504,7 +505,7 @@ int mc_smplx_vertex_errors(mc_smplx* m, const double* poses_a_dev, const double*
 
 /* ---- Beat alignment of the speech-to-gesture test (alignment.load_pose + alignment.calculate_align,
  * mogen/datasets/EMAGE_2024/utils/metric.py:78-127,199-242; called at tools/s2g_test.py:418-422 on the 55 joints of
- * mc_smplx_joints).  Audio onset detection (load_audio, librosa) stays with the caller: onset times are an input.
+ * mc_smplx_joints).  The onset times are an input; mc_onset_strength / mc_onset_pick below produce them from the waveform.
  * mc_beat_mask: joints_dev fp32 [n_frames, num_joints, 3] (n_frames >= 2), mean_vel_dev fp64 [num_joints] ->
  * mask_out_dev uint8 [num_joints, t_end - t_start].  speed = |velocity| / mean_vel with forward / central / backward
  * differences in fp32 (dt = 1 / pose_fps rounded to fp32, sqrt((x x + y y) + z z), no fused multiply-add: numpy on fp32 joints),
@@ -523,6 +524,27 @@ int64_t mc_beat_align_work_bytes(int32_t n_slice, int32_t n_upper);
 int mc_beat_align(const uint8_t* mask_dev, int32_t num_joints, int32_t n_slice, const int32_t* upper_body_host, int32_t n_upper,
                   const double* onsets_dev, int32_t n_onsets, double pose_fps, double sigma, void* work_dev, int64_t work_bytes,
                   double* score_out_dev, void* stream);
+
+/* ---- Audio onset detection (alignment.load_audio, metric.py:64-76: librosa 0.10.1's onset.onset_detect with its defaults,
+ * restated in tests/onset_ref.py).  n_fft is 2048; hop a multiple of 4 in 4..512; n_mels 1..128; at most 2^20 frames.
+ * mc_onset_strength: wave_dev fp32 [n_samples] (finite) -> env_out_dev fp32 [F], F = 1 + n_samples / hop, the UN-normalised
+ * onset envelope: frames centred on f hop with zeros outside the clip, power spectrum, mel projection, 10 log10(max(1e-10, .)),
+ * the clamp at (maximum over the whole spectrogram) - 80, then env[j] = mean over the mel rows of max(0, S[j-lag+1] - S[j-lag]),
+ * lag = 1 + n_fft / (2 hop), and env[j] = 0 for j < lag.
+ *   dft_dev fp32 [n_fft, 2 (n_fft/2 + 1)]: column 2b = w[k] cos(2 pi k b / n_fft), column 2b + 1 = -w[k] sin(2 pi k b / n_fft),
+ *           w the analysis window (periodic Hann for librosa's default);
+ *   mel_dev fp32 [n_mels, n_fft/2 + 1]: the mel filter bank, row-major as librosa stores it.
+ * work_dev: 16-byte aligned, work_bytes >= mc_onset_work_bytes(...) (-1: bad argument).  No atomics: two runs give the same bits.
+ * mc_onset_pick: env_dev fp32 [n_frames] -> mask_out_dev uint8 [n_frames] (1 = onset), count_out_dev int32 [1].  With
+ * `normalize` the envelope is first taken to (env - min) / (max - min + DBL_MIN) in fp64, and an all-zero one has no onsets.
+ * Frame n is an onset iff env[n] >= every value of [n - pre_max, n + post_max), env[n] >= the mean of [n - pre_avg, n + post_avg)
+ * + delta, env[n] > 0 and n > the last accepted onset + wait, left to right; the windows are truncated at both ends of the array
+ * (librosa.util.peak_pick; post_max and post_avg count the frame itself, so they are >= 1). */
+int64_t mc_onset_work_bytes(int64_t n_samples, int32_t n_fft, int32_t hop, int32_t n_mels);
+int mc_onset_strength(const float* wave_dev, int64_t n_samples, const float* dft_dev, const float* mel_dev, int32_t n_fft, int32_t hop,
+                      int32_t n_mels, void* work_dev, int64_t work_bytes, float* env_out_dev, void* stream);
+int mc_onset_pick(const float* env_dev, int32_t n_frames, int32_t pre_max, int32_t post_max, int32_t pre_avg, int32_t post_avg, double delta,
+                  int32_t wait, int32_t normalize, uint8_t* mask_out_dev, int32_t* count_out_dev, void* stream);
 
 /* out = a * x + b * noise over n elements (out may alias x) */
 int mc_op_renoise(const float* x_dev, const float* noise_dev, float a, float b, float* out_dev, int64_t n, void* stream);

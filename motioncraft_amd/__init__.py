@@ -8,8 +8,8 @@ from . import models as _models  # registers MotionDiffusion / STMoGenTransforme
 from .models import ControlT2MHalf, wrap_fp16_model
 from .checkpoint import load_checkpoint
 from . import scoring
-from .scoring import BeatAlignment, M2DScorer, S2GScorer, face_errors
+from .scoring import BeatAlignment, M2DScorer, OnsetDetector, S2GScorer, face_errors
 
-__all__ = ['BeatAlignment', 'M2DScorer', 'S2GScorer', 'face_errors', 'scoring','ARCHITECTURES', 'ATTENTIONS', 'LOSSES', 'MODELS', 'SUBMODULES', 'build_architecture',
+__all__ = ['BeatAlignment', 'M2DScorer', 'OnsetDetector', 'S2GScorer', 'face_errors', 'scoring','ARCHITECTURES', 'ATTENTIONS', 'LOSSES', 'MODELS', 'SUBMODULES', 'build_architecture',
            'build_attention', 'build_loss', 'build_submodule', 'Config', 'ConfigDict', 'Registry', 'build_from_cfg', 'ControlT2MHalf',
            'load_checkpoint', 'wrap_fp16_model']

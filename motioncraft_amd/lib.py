@@ -146,6 +146,10 @@ _SIGNATURES = {
     'mc_beat_align_work_bytes': (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32]),
     'mc_beat_align': (ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, _P, ctypes.c_int32,
                                      ctypes.c_double, ctypes.c_double, _P, ctypes.c_int64, _P, _P]),
+    'mc_onset_work_bytes': (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
+    'mc_onset_strength': (ctypes.c_int, [_P, ctypes.c_int64, _P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_int64, _P, _P]),
+    'mc_onset_pick': (ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_double,
+                                     ctypes.c_int32, ctypes.c_int32, _P, _P, _P]),
     'mc_op_renoise': (ctypes.c_int, [_P, _P, ctypes.c_float, ctypes.c_float, _P, ctypes.c_int64, _P]),
     'mc_debug_flop_ledger': (ctypes.c_int, [ctypes.c_int32]),
     'mc_debug_flop_ledger_dump': (ctypes.c_int64, [ctypes.c_char_p, ctypes.c_int64]),

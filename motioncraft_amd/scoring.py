@@ -3,8 +3,13 @@
 
   * ``BeatAlignment``: ``alignment.load_pose`` + ``alignment.calculate_align`` of ``mogen/datasets/EMAGE_2024/utils/metric.py``
     (lines 78-127, 199-242) on the device (``mc_beat_mask`` / ``mc_beat_align``, ``csrc/mc_metrics.hip``), fed the 55 joints
-    ``SMPLXBodyModel.joints`` leaves there.  Audio onset detection (``load_audio``: librosa) stays with the caller: onset times
-    are an input.
+    ``SMPLXBodyModel.joints`` leaves there.
+  * ``OnsetDetector`` / ``BeatAlignment.load_audio``: ``alignment.load_audio`` (metric.py:64-76), i.e. librosa 0.10.1's
+    ``onset.onset_detect(y, sr, hop_length=512, units='time')`` with its defaults, on the device (``mc_onset_strength`` /
+    ``mc_onset_pick``, ``csrc/mc_onset.hip``) from a waveform that is already decoded and at the detector's rate.  librosa is not
+    a dependency: parity is pinned to the float64 restatement ``tests/onset_ref.py``.  Decoding audio files (beyond the PCM wav
+    ``tools/s2g_score.py`` reads) and resampling (the reference's ``librosa.load`` + ``librosa.resample``, soxr) stay with the
+    caller.
   * ``face_errors``: the face ``l2`` / ``lvel`` errors of ``s2g_test.py:377-412``; the two vertex sets are reduced to the two
     sums on the device (``mc_smplx_vertex_errors``) and never leave it.
   * ``S2GScorer`` / ``M2DScorer``: the accumulation and the printed numbers of the two tools, on the existing ``L1div``, FID and
@@ -59,6 +64,117 @@ def _check_onsets(onset_times):
     return on
 
 
+def mel_filter_bank(sr, n_fft, n_mels):
+    """librosa.filters.mel with its defaults (Slaney scale and norm, fmin 0, fmax sr / 2): float32 [n_mels, n_fft // 2 + 1], computed
+    in float64.  The scale is f / (200 / 3) below 1 kHz and logarithmic above, 27 steps per factor 6.4."""
+    step = np.log(6.4) / 27
+    top = sr / 2
+    mel_top = 15.0 + np.log(top / 1000.0) / step if top >= 1000.0 else top / (200.0 / 3)
+    mels = np.linspace(0.0, mel_top, n_mels + 2)
+    edges = np.where(mels >= 15.0, 1000.0 * np.exp(step * (mels - 15.0)), (200.0 / 3) * mels)
+    freqs = np.arange(n_fft // 2 + 1) * (sr / n_fft)
+    lower = (freqs[None, :] - edges[:-2, None]) / (edges[1:-1] - edges[:-2])[:, None]
+    upper = (edges[2:, None] - freqs[None, :]) / (edges[2:] - edges[1:-1])[:, None]
+    return (np.maximum(0.0, np.minimum(lower, upper)) * (2.0 / (edges[2:] - edges[:-2]))[:, None]).astype(np.float32)
+
+
+def dft_table(n_fft):
+    """float32 [n_fft, 2 (n_fft // 2 + 1)], computed in float64: column 2b = w[k] cos(2 pi k b / n_fft), column 2b + 1 =
+    -w[k] sin(2 pi k b / n_fft) with w the periodic Hann window; the angle is reduced as the integer k b mod n_fft first."""
+    k = np.arange(n_fft, dtype=np.int64)
+    ang = (2 * np.pi / n_fft) * ((k[:, None] * np.arange(n_fft // 2 + 1, dtype=np.int64)[None, :]) % n_fft)
+    w = (0.5 - 0.5 * np.cos(2 * np.pi * k / n_fft))[:, None]
+    return np.stack([w * np.cos(ang), -w * np.sin(ang)], axis=-1).reshape(n_fft, -1).astype(np.float32)
+
+
+class OnsetDetector:
+    """``librosa.onset.onset_detect`` of librosa 0.10.1 with its defaults, on the device: log-power mel spectrogram (periodic Hann
+    window, ``center=True`` with zero padding, 128 Slaney mel bands, top_db 80), spectral flux with lag 1 averaged over the bands,
+    min/max normalisation, ``peak_pick`` with pre_max 0.03 s, post_max 0, pre_avg 0.1 s, post_avg 0.1 s, wait 0.03 s, delta 0.07.
+    The waveform is taken as float32 at ``sr``; resampling is the caller's."""
+    DELTA = 0.07
+    N_FFT, MAX_HOP, MAX_MELS = 2048, 512, 128                            # csrc/mc_onset.hip
+
+    def __init__(self, sr=16000, hop_length=512, n_fft=2048, n_mels=128):
+        self.sr, self.hop_length, self.n_fft, self.n_mels = float(sr), int(hop_length), int(n_fft), int(n_mels)
+        if not self.sr > 0:
+            raise ValueError(f'sr={sr}: must be positive')
+        if self.n_fft != self.N_FFT:
+            raise ValueError(f'n_fft={n_fft}: the kernel is written for {self.N_FFT}')
+        if not 4 <= self.hop_length <= self.MAX_HOP or self.hop_length % 4:
+            raise ValueError(f'hop_length={hop_length}: a multiple of 4 in 4..{self.MAX_HOP}')
+        if not 1 <= self.n_mels <= self.MAX_MELS:
+            raise ValueError(f'n_mels={n_mels}: 1..{self.MAX_MELS}')
+        self.mel_basis = mel_filter_bank(self.sr, self.n_fft, self.n_mels)
+        sec = lambda t, extra=0: int(t * self.sr // self.hop_length + extra)      # onset_detect's defaults, in frames
+        self.pre_max, self.post_max, self.pre_avg, self.post_avg, self.wait = sec(0.03), sec(0.00, 1), sec(0.10), sec(0.10, 1), sec(0.03)
+        self._dft = None
+        self._dev = {}
+
+    def num_frames(self, n_samples):
+        return 1 + int(n_samples) // self.hop_length
+
+    @staticmethod
+    def _check_wave(y):
+        t = torch.as_tensor(y)
+        if t.dim() != 1:
+            raise ValueError(f'audio must be 1-D (mono samples), got {tuple(t.shape)}')
+        if t.numel() < 1:
+            raise ValueError('audio holds no sample')
+        if not t.is_floating_point():
+            raise ValueError(f'audio must be floating point, got {t.dtype}')
+        if not bool(torch.isfinite(t).all()):
+            raise ValueError('audio is not finite everywhere')
+        return t
+
+    def _tables(self, device):
+        if device not in self._dev:
+            if self._dft is None:
+                self._dft = dft_table(self.n_fft)
+            self._dev[device] = (torch.from_numpy(self._dft).to(device), torch.from_numpy(self.mel_basis).to(device))
+            torch.cuda.current_stream(device).synchronize()                # the upload is done before any stream reads the cache
+        return self._dev[device]
+
+    def _strength(self, t):
+        lib = _lib.load(require_gpu=True)
+        t = t.to(device=t.device if t.is_cuda else 'cuda', dtype=torch.float32).contiguous()
+        dft, mel = self._tables(t.device)
+        n = t.numel()
+        wb = int(lib.mc_onset_work_bytes(n, self.n_fft, self.hop_length, self.n_mels))
+        if wb < 0:
+            raise ValueError(f'{n} samples at hop {self.hop_length}: more frames than the kernels take')
+        work = torch.empty(wb // 4, device=t.device, dtype=torch.float32)
+        env = torch.empty(self.num_frames(n), device=t.device, dtype=torch.float32)
+        _lib.check(lib.mc_onset_strength(_p(t), n, _p(dft), _p(mel), self.n_fft, self.hop_length, self.n_mels, _p(work), wb, _p(env), _stream()),
+                   'mc_onset_strength')
+        return env
+
+    def strength(self, y):
+        """y [N] (device tensor, or anything ``torch.as_tensor`` takes) -> the un-normalised onset envelope, device fp32
+        [1 + N // hop_length] (``librosa.onset.onset_strength``)."""
+        return self._strength(self._check_wave(y))
+
+    def pick(self, env):
+        """envelope [F] on the device -> (onset mask uint8 [F], count int32 [1]), both on the device."""
+        if not isinstance(env, torch.Tensor) or not env.is_cuda or env.dtype != torch.float32 or env.dim() != 1 or env.numel() < 1:
+            raise ValueError('env must be a float32 device tensor [F] with at least one frame (what strength returns)')
+        env = env.contiguous()
+        lib = _lib.load(require_gpu=True)
+        mask = torch.empty(env.numel(), device=env.device, dtype=torch.uint8)
+        count = torch.empty(1, device=env.device, dtype=torch.int32)
+        _lib.check(lib.mc_onset_pick(_p(env), env.numel(), self.pre_max, self.post_max, self.pre_avg, self.post_avg, self.DELTA, self.wait, 1,
+                                     _p(mask), _p(count), _stream()), 'mc_onset_pick')
+        return mask, count
+
+    def detect(self, y, units='time'):
+        """-> the onsets as float64 seconds (``units='time'``) or int64 frames (``units='frames'``), a numpy array."""
+        if units not in ('time', 'frames'):
+            raise ValueError(f"units={units!r}: 'time' or 'frames'")
+        mask, _ = self.pick(self._strength(self._check_wave(y)))
+        frames = np.flatnonzero(mask.cpu().numpy()).astype(np.int64)
+        return frames if units == 'frames' else (frames * self.hop_length).astype(np.int64) / self.sr
+
+
 class BeatAlignment:
     """``alignment(sigma, order, mmae, upper_body)`` of metric.py:54-62 with its method names.  ``mean_vel`` [55]: float32 divides
     the fp32 speeds in fp32, anything else in float64, as numpy would."""
@@ -79,6 +195,17 @@ class BeatAlignment:
         self.mean_vel_fp32 = int(mv.dtype == np.float32)
         self.mean_vel = np.ascontiguousarray(mv, dtype=np.float64)       # an fp32 value widens exactly
         self._mv_dev = None
+        self._detectors = {}
+
+    def load_audio(self, wave, t_start=None, t_end=None, sr_audio=16000):
+        """metric.py:64-76 with ``without_file=True``: the onset times (float64 seconds, relative to the slice) of
+        ``wave[t_start:t_end]``, or of the whole wave without ``t_start``; hop 512 as there."""
+        if sr_audio not in self._detectors:
+            self._detectors[sr_audio] = OnsetDetector(sr=sr_audio, hop_length=512)
+        wave = torch.as_tensor(wave)
+        if wave.dim() != 1:
+            raise ValueError(f'audio must be 1-D (mono samples), got {tuple(wave.shape)}')
+        return self._detectors[sr_audio].detect(wave if t_start is None else wave[t_start:t_end])
 
     @staticmethod
     def _check_pose(joints, t_start, t_end, pose_fps):
@@ -237,17 +364,30 @@ class S2GScorer:
         self.total_length = self.num_sequences = 0
         self.emb = dict(pred=[], gt=[], hand_pred=[], hand_gt=[])
 
-    def add_sequence(self, rec_motion, tar_pose, tar_exps, tar_trans, tar_beta, onset_times):
-        """rec_motion [T,322] (the sample), tar_pose [T,165], tar_exps [T,100], tar_trans [T,3], tar_beta [T,300] | [300],
-        onset_times [n_on] seconds within the masked window (``load_audio`` of the audio cut like :418-419)."""
+    def add_sequence(self, rec_motion, tar_pose, tar_exps, tar_trans, tar_beta, onset_times=None, audio=None, audio_sr=16000):
+        """rec_motion [T,322] (the sample), tar_pose [T,165], tar_exps [T,100], tar_trans [T,3], tar_beta [T,300] | [300], and
+        exactly one of: onset_times [n_on] seconds within the masked window, or audio [N] at ``audio_sr``, from which they are
+        detected as :416-419 does: the audio cut to int(audio_sr / pose_fps * T) samples, then
+        ``load_audio(cut, a, len(audio) - a)`` with a = int(align_mask * (audio_sr / pose_fps)) -- ``len`` of the UNCUT audio, as
+        there; for audio as long as the motion that drops ``a`` samples on both sides."""
+        if (onset_times is None) == (audio is None):
+            raise ValueError('exactly one of onset_times and audio must be given')
+        if audio is not None:
+            audio = OnsetDetector._check_wave(audio)
+            if not float(audio_sr) > 0:
+                raise ValueError(f'audio_sr={audio_sr}: must be positive')
         rec_pose, rec_exp, rec_trans = unpack_rec_motion(rec_motion)
         tar_pose, tar_exps, tar_trans = _rows(tar_pose, 165, 'tar_pose'), _rows(tar_exps, 100, 'tar_exps'), _rows(tar_trans, 3, 'tar_trans')
         T = tar_pose.shape[0]
         if rec_pose.shape[0] != T or tar_exps.shape[0] != T or tar_trans.shape[0] != T:
             raise ValueError('rec_motion, tar_pose, tar_exps and tar_trans must hold the same number of frames')
-        onsets = _check_onsets(onset_times)
+        onsets = _check_onsets(onset_times) if audio is None else None
         if T - 2 * self.align_mask < 1:
             raise ValueError(f'{T} frames leave nothing between the two masks of {self.align_mask}')
+        if audio is not None:
+            a_offset = int(self.align_mask * (audio_sr / self.pose_fps))
+            cut = audio[:int(audio_sr / self.pose_fps * T)]
+            onsets = _check_onsets(self.aligner.load_audio(cut, a_offset, audio.shape[0] - a_offset, sr_audio=audio_sr))
         ev = self.evaluator_model
         self.emb['pred'].append(_embed(ev, _rows(rec_motion, 322, 'rec_motion')))                     # :313-325
         self.emb['gt'].append(_embed(ev, pack_motion(tar_pose, tar_exps, tar_trans)))

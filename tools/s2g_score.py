@@ -2,19 +2,22 @@
 """Score a speech-to-gesture run from its saved files: the six numbers the reference logs at the end of
 ``tools/s2g_test.py`` (``CustomTrainer.test``, lines 451-483), computed on the device by ``motioncraft_amd.scoring``.
 
-    python tools/s2g_score.py RESULTS_DIR --onsets ONSETS_DIR --smplx_model SMPLX_NEUTRAL_2020.npz \
+    python tools/s2g_score.py RESULTS_DIR (--wav WAV_DIR | --onsets ONSETS_DIR) --smplx_model SMPLX_NEUTRAL_2020.npz \
         --evaluator CHECKPOINT.pth --mean_vel mean_vel.npy
 
 RESULTS_DIR holds the ``res_<id>.npz`` / ``gt_<id>.npz`` pairs the test writes (s2g_test.py:431-448: poses [T,165],
-expressions [T,100], trans [T,3], betas [300]); ONSETS_DIR one ``<id>.npy`` per pair with the audio onset times in seconds,
-i.e. ``alignment.load_audio`` of the audio cut by the align mask on both sides (s2g_test.py:416-419: librosa's onset
-detection stays with the caller).  The sample is re-packed from its saved arrays, so the 322-d channels the ``.npz`` does not
+expressions [T,100], trans [T,3], betas [300]).  WAV_DIR holds one ``<id>.wav`` per pair: 16-bit PCM, mono or the first
+channel, ALREADY at ``--audio_sr`` (the reference's ``librosa.load`` + ``librosa.resample`` of s2g_test.py:416-417 is soxr
+resampling, which this project does not restate: resample first); the onsets are detected on the device from the audio cut
+like s2g_test.py:418-419.  Or ONSETS_DIR holds one ``<id>.npy`` per pair with the onset times in seconds, i.e.
+``alignment.load_audio`` of the audio cut by the align mask on both sides.  The sample is re-packed from its saved arrays, so the 322-d channels the ``.npz`` does not
 carry (159:209, 312:322) enter the whole-body embedding as zeros.
 """
 import argparse
 import glob
 import os
 import sys
+import wave
 
 import numpy as np
 import torch
@@ -30,7 +33,10 @@ from motioncraft_amd.body_model import SMPLXBodyModel           # noqa: E402
 def parse_args():
     p = argparse.ArgumentParser(description='score res_*.npz / gt_*.npz pairs of a speech-to-gesture run')
     p.add_argument('results', help='directory with the res_<id>.npz / gt_<id>.npz pairs')
-    p.add_argument('--onsets', required=True, metavar='DIR', help='directory with one <id>.npy of onset times (seconds) per pair')
+    src = p.add_mutually_exclusive_group(required=True)
+    src.add_argument('--wav', metavar='DIR', help='directory with one <id>.wav per pair: 16-bit PCM at --audio_sr; onsets are detected on the device')
+    src.add_argument('--onsets', metavar='DIR', help='directory with one <id>.npy of onset times (seconds) per pair')
+    p.add_argument('--audio_sr', type=int, default=16000, help='the rate the wav files must already have (the reference\'s audio_sr)')
     p.add_argument('--smplx_model', required=True, metavar='PATH', help='the published SMPL-X model file (.npz)')
     p.add_argument('--evaluator', required=True, metavar='PATH', help='checkpoint of the T2MContrastiveModel_SMPLX embedding model')
     p.add_argument('--mean_vel', required=True, metavar='PATH', help='.npy [55]: the mean joint speeds the alignment divides by')
@@ -38,6 +44,18 @@ def parse_args():
     p.add_argument('--latent_dim', type=int, default=256), p.add_argument('--ff_size', type=int, default=1024)
     p.add_argument('--num_layers', type=int, default=4), p.add_argument('--num_heads', type=int, default=4)
     return p.parse_args()
+
+
+def read_wav(path, sr):
+    """16-bit PCM wav at ``sr`` -> float32 [N] in [-1, 1): the first channel, scaled by 1 / 32768."""
+    with wave.open(path, 'rb') as f:
+        if f.getsampwidth() != 2 or f.getcomptype() != 'NONE':
+            raise SystemExit(f'{path}: {8 * f.getsampwidth()}-bit {f.getcomptype()} samples; this tool reads 16-bit PCM only (decode it first)')
+        if f.getframerate() != sr:
+            raise SystemExit(f'{path}: {f.getframerate()} Hz, but the detector runs at {sr} Hz.  Resampling stays with the caller: the '
+                             f'reference resamples with librosa.resample (soxr), which is not restated here; resample the file to {sr} Hz first')
+        data = np.frombuffer(f.readframes(f.getnframes()), dtype='<i2').reshape(-1, f.getnchannels())
+    return data[:, 0].astype(np.float32) / 32768.0
 
 
 def main():
@@ -54,8 +72,10 @@ def main():
     for i in ids:
         with np.load(os.path.join(a.results, f'res_{i}.npz')) as res, np.load(os.path.join(a.results, f'gt_{i}.npz')) as gt:
             rec_motion = scoring.pack_motion(t(res['poses']), t(res['expressions']), t(res['trans']))
+            source = (dict(audio=read_wav(os.path.join(a.wav, f'{i}.wav'), a.audio_sr), audio_sr=a.audio_sr) if a.wav else
+                      dict(onset_times=np.load(os.path.join(a.onsets, f'{i}.npy'))))
             per_seq = scorer.add_sequence(rec_motion, t(gt['poses']), t(gt['expressions']), t(gt['trans']), t(gt['betas']).reshape(-1)[:300],
-                                          np.load(os.path.join(a.onsets, f'{i}.npy')))
+                                          **source)
         print(f'{i}: {rec_motion.shape[0]} frames  l2 {per_seq["l2"]:.6e}  lvel {per_seq["lvel"]:.6e}  align {per_seq["align"]:.6f}', file=sys.stderr)
     for name, value in scorer.summary().items():
         print(f'{name}: {value}')
