@@ -32,6 +32,7 @@
  *   mc_beat_mask, mc_beat_align  alignment.load_pose / calculate_align (beat alignment score)
  *                                                                      mogen/datasets/EMAGE_2024/utils/metric.py:78-127,199-242
  *   mc_onset_strength, mc_onset_pick  alignment.load_audio (librosa's onset_detect)   metric.py:64-76
+ *   mc_audio_condition    the S2G audio condition `onset+amplitude` [samples, 2]   mogen/datasets/EMAGE_2024/dataloaders/beat_motionx.py:398-412
  *   mc_op_renoise         GaussianDiffusion._undo (resampling jumps)   gaussian_diffusion.py:429-435, 1113-1118
  *
  * Conventions: plain pointers and sizes only.  `*_dev` pointers are device (HBM) addresses owned
@@ -545,6 +546,18 @@ int mc_onset_strength(const float* wave_dev, int64_t n_samples, const float* dft
                       int32_t n_mels, void* work_dev, int64_t work_bytes, float* env_out_dev, void* stream);
 int mc_onset_pick(const float* env_dev, int32_t n_frames, int32_t pre_max, int32_t post_max, int32_t pre_avg, int32_t post_avg, double delta,
                   int32_t wait, int32_t normalize, uint8_t* mask_out_dev, int32_t* count_out_dev, void* stream);
+
+/* ---- The audio condition of the speech-to-gesture configs (audio_rep `onset+amplitude`, beat_motionx.py:398-412; restated in
+ * tests/audio_cond_ref.py): wave_dev fp32 [n_samples] -> out_dev fp32 [n_samples, 2], what mc_wavenc_forward reads with audio_in = 2.
+ *   out[i][0] = max |wave[s .. s + window - 1]|, s = min(i, n_samples - window): the rolling maximum over the full windows; the last
+ *               window's value is repeated over the final window - 1 samples (the reference pads with it), the window never shrinks
+ *   out[i][1] = 1 if i < n_frames and onset_mask_dev[i], else 0: onset_mask_dev uint8 [n_frames] is the mask mc_onset_pick writes, one
+ *               byte per onset FRAME, and the reference writes those frame indices into this sample-indexed column as they are
+ *               (onset_array[audio_onset_f] = 1.0) -- kept.  onset_mask_dev may be NULL: a column of zeros.
+ * window 1..1024 (the reference: 1024) and <= n_samples; n_frames <= n_samples.  One launch, no workspace, no atomics; a maximum
+ * of magnitudes has no rounding, so the result is exact and two runs give the same bits. */
+int mc_audio_condition(const float* wave_dev, int64_t n_samples, int32_t window, const uint8_t* onset_mask_dev, int32_t n_frames,
+                       float* out_dev, void* stream);
 
 /* out = a * x + b * noise over n elements (out may alias x) */
 int mc_op_renoise(const float* x_dev, const float* noise_dev, float a, float b, float* out_dev, int64_t n, void* stream);

@@ -22,11 +22,27 @@ def window_starts(total_frames, motion_length, pre_frames):
     return (total_frames - pre_frames) // stride, stride
 
 
+def _rows_per_frame(r):
+    if int(r) != r or r < 1:
+        raise ValueError(f'c_rows_per_frame={r}: a positive integer')
+    return int(r)
+
+
+def _condition_rows(c, total_frames, r, name='c'):
+    """``c`` as a float32 tensor on the device it is on, holding the rows of ``total_frames`` frames at ``r`` rows per frame"""
+    c = torch.as_tensor(c, dtype=torch.float32)
+    if c.shape[0] < total_frames * r:
+        raise ValueError(f'{name} holds {c.shape[0]} rows, {total_frames} frames at {r} rows per frame need {total_frames * r}')
+    return c
+
+
 def sample_long(model, total_frames, motion_length, pre_frames=30, c=None, text='', repaint=False, overlap_len=30,
                 fix_very_first=True, first_gt=None, mean=None, std=None, gt_space='denormalised', input_dim=322,
-                device=None, condition_kwargs=None, inference_kwargs=None):
+                device=None, condition_kwargs=None, inference_kwargs=None, c_rows_per_frame=1):
     """model: MotionDiffusion mirror (``mc.build_architecture``), opt set on it like the reference tools do.
-    c: per-frame control condition [total_frames, F] (music features) or None.  condition_kwargs: ``xf_out`` /
+    c: control condition [total_frames * c_rows_per_frame, F] or None: one row per frame (music features), or ``c_rows_per_frame``
+    rows per frame (the S2G audio condition: 16000 // 30 = 533 audio samples per frame, s2g_test.py:155); window i reads the rows
+    of its frames, and a ``c`` that is a device tensor is sliced where it is.  condition_kwargs: ``xf_out`` /
     ``clip_feat`` for ONE window ([1, 77, *]).  inference_kwargs: dict or callable(window index) -> dict.
     Returns (stitched de-normalised motion [frames, input_dim] as float32 numpy, list of per-window outputs)."""
     dev = device or torch.device('cuda', torch.cuda.current_device())
@@ -35,8 +51,9 @@ def sample_long(model, total_frames, motion_length, pre_frames=30, c=None, text=
         raise ValueError('sequence shorter than one window')
     mean = np.zeros(input_dim, np.float32) if mean is None else np.asarray(mean)
     std = np.ones(input_dim, np.float32) if std is None else np.asarray(std)
+    r = _rows_per_frame(c_rows_per_frame)
     if c is not None:
-        c = torch.as_tensor(c, dtype=torch.float32)
+        c = _condition_rows(c, total_frames, r)
     pieces_repaint, pieces_plain, windows, outputs = [], [], [], None
     for i in range(n_win):
         lo = i * stride
@@ -45,7 +62,7 @@ def sample_long(model, total_frames, motion_length, pre_frames=30, c=None, text=
                   motion_length=torch.tensor([motion_length], device=dev).long(), num_intervals=1,
                   motion_metas=[{'text': text}])
         if c is not None:
-            kw['c'] = c[lo:lo + motion_length].unsqueeze(0).to(dev)
+            kw['c'] = c[lo * r:(lo + motion_length) * r].unsqueeze(0).to(dev)
         kw.update(condition_kwargs or {})
         inf = inference_kwargs(i) if callable(inference_kwargs) else dict(inference_kwargs or {})
         kw['inference_kwargs'] = inf
@@ -138,11 +155,11 @@ def _gather_ragged(local, lengths, owners, input_dim, device):
 
 def sample_long_batched(model, total_frames, motion_length, pre_frames=30, c=None, text=None, repaint=False, overlap_len=30,
                         fix_very_first=True, first_gt=None, mean=None, std=None, gt_space='denormalised', input_dim=322,
-                        device=None, condition_kwargs=None, inference_kwargs=None, max_batch=160, shard=True):
+                        device=None, condition_kwargs=None, inference_kwargs=None, max_batch=160, shard=True, c_rows_per_frame=1):
     """S sequences x their windows through as few model calls as the mode allows (see the block comment above).
 
-    total_frames: int (every sequence) or a list of S ints.  c: list of S per-frame conditions [total_s, F] (or a tensor
-    [S, total, F]) or None.  text: list of S prompts (or one string).  condition_kwargs: per-SEQUENCE tensors with leading dimension S
+    total_frames: int (every sequence) or a list of S ints.  c: list of S conditions [total_s * c_rows_per_frame, F] (or a tensor
+    [S, total * c_rows_per_frame, F]) or None; ``c_rows_per_frame`` as in ``sample_long``.  text: list of S prompts (or one string).  condition_kwargs: per-SEQUENCE tensors with leading dimension S
     (``xf_out`` [S, 77, *] / ``clip_feat``); every window of sequence s gets row s.  first_gt: [S, >= overlap_len, input_dim] (RePaint,
     fix_very_first).  inference_kwargs: dict, or callable(pairs) -> dict for one model call, ``pairs`` = [(sequence, window), ...] in
     batch order (noise [b, L, C] / step_noise for parity runs).  max_batch: windows per model call (the per-GPU batch; BASELINE
@@ -169,7 +186,8 @@ def sample_long_batched(model, total_frames, motion_length, pre_frames=30, c=Non
     owners = [rank_sequences(S, r, ws) for r in range(ws)]
     mine = owners[rank]
     stride = motion_length - pre_frames
-    cs = None if c is None else [torch.as_tensor(x, dtype=torch.float32) for x in c]
+    r = _rows_per_frame(c_rows_per_frame)
+    cs = None if c is None else [_condition_rows(x, totals[s], r, f'c[{s}]') for s, x in enumerate(c)]
     cond = {k: v for k, v in (condition_kwargs or {}).items()}
     for k, v in cond.items():
         if not torch.is_tensor(v) or v.shape[0] != S:
@@ -182,7 +200,7 @@ def sample_long_batched(model, total_frames, motion_length, pre_frames=30, c=Non
                   motion_length=torch.full((b, 1), motion_length, device=dev).long(), num_intervals=1,
                   motion_metas=[{'text': texts[s]} for s, _ in pairs])
         if cs is not None:
-            kw['c'] = torch.stack([cs[s][w * stride:w * stride + motion_length] for s, w in pairs]).to(dev)
+            kw['c'] = torch.stack([cs[s][w * stride * r:(w * stride + motion_length) * r] for s, w in pairs]).to(dev)
         idx = torch.tensor([s for s, _ in pairs])
         for k, v in cond.items():
             kw[k] = v[idx.to(v.device)]

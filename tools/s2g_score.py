@@ -17,7 +17,6 @@ import argparse
 import glob
 import os
 import sys
-import wave
 
 import numpy as np
 import torch
@@ -26,7 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import motioncraft_amd as mc                                    # noqa: E402
-from motioncraft_amd import scoring                             # noqa: E402
+from motioncraft_amd import scoring, speech                     # noqa: E402
 from motioncraft_amd.body_model import SMPLXBodyModel           # noqa: E402
 
 
@@ -47,15 +46,10 @@ def parse_args():
 
 
 def read_wav(path, sr):
-    """16-bit PCM wav at ``sr`` -> float32 [N] in [-1, 1): the first channel, scaled by 1 / 32768."""
-    with wave.open(path, 'rb') as f:
-        if f.getsampwidth() != 2 or f.getcomptype() != 'NONE':
-            raise SystemExit(f'{path}: {8 * f.getsampwidth()}-bit {f.getcomptype()} samples; this tool reads 16-bit PCM only (decode it first)')
-        if f.getframerate() != sr:
-            raise SystemExit(f'{path}: {f.getframerate()} Hz, but the detector runs at {sr} Hz.  Resampling stays with the caller: the '
-                             f'reference resamples with librosa.resample (soxr), which is not restated here; resample the file to {sr} Hz first')
-        data = np.frombuffer(f.readframes(f.getnframes()), dtype='<i2').reshape(-1, f.getnchannels())
-    return data[:, 0].astype(np.float32) / 32768.0
+    try:
+        return speech.read_wav(path, sr)
+    except ValueError as e:
+        raise SystemExit(str(e))
 
 
 def main():
