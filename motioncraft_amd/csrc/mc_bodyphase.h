@@ -15,6 +15,36 @@
 #include "mc_common.h"
 #include "mc_chain.h"
 
+// per-row LayerNorm of a fragment-distributed row (lane l and lane l ^ 32 hold the two halves; column of x[j][i] = 8 j + 4 hf + i,
+// kq = 4 hf): shared by the fp32 chain kernels (mc_chain.hip) and their fp16 twins (mc_half.hip)
+template <int NJ>
+__device__ __forceinline__ void frag_layernorm(f32x4 (&x)[NJ], const float* __restrict__ gamma,
+                                               const float* __restrict__ beta, int kq) {
+    constexpr int L = 8 * NJ;
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) s += x[j][0] + x[j][1] + x[j][2] + x[j][3];
+    s += __shfl_xor(s, 32, 64);
+    const float mean = s / (float)L;
+    float q = 0.f;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            x[j][i] -= mean;
+            q += x[j][i] * x[j][i];
+        }
+    q += __shfl_xor(q, 32, 64);
+    const float rstd = rsqrtf(q / (float)L + 1e-5f);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const f32x4 g = *reinterpret_cast<const f32x4*>(gamma + 8 * j + kq);
+        const f32x4 b = *reinterpret_cast<const f32x4*>(beta + 8 * j + kq);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) x[j][i] = x[j][i] * rstd * g[i] + b[i];
+    }
+}
+
 // NQ = H: the set produces all H parts of its frames; NQ < H: parts [h0, h0 + NQ) only
 template <int H, int NQ>
 struct BodySet {

@@ -88,35 +88,6 @@ __device__ __forceinline__ f32x16 chunk_mma(const float* Wc, const f32x4 (&xf)[N
     return acc[0];
 }
 
-// per-row LayerNorm of a fragment-distributed row: lane l and lane l^32 hold the two halves
-template <int NJ>
-__device__ __forceinline__ void frag_layernorm(f32x4 (&x)[NJ], const float* __restrict__ gamma,
-                                               const float* __restrict__ beta, int kq) {
-    constexpr int L = 8 * NJ;
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) s += x[j][0] + x[j][1] + x[j][2] + x[j][3];
-    s += __shfl_xor(s, 32, 64);
-    const float mean = s / (float)L;
-    float q = 0.f;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            x[j][i] -= mean;
-            q += x[j][i] * x[j][i];
-        }
-    q += __shfl_xor(q, 32, 64);
-    const float rstd = rsqrtf(q / (float)L + 1e-5f);
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        const f32x4 g = *reinterpret_cast<const f32x4*>(gamma + 8 * j + kq);
-        const f32x4 b = *reinterpret_cast<const f32x4*>(beta + 8 * j + kq);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) x[j][i] = x[j][i] * rstd * g[i] + b[i];
-    }
-}
-
 // =================================================================================================
 // Fused 2-layer MLP (reference: tutel FusedExpertsNetwork; SFFN stmogen.py:596-607)
 // =================================================================================================
@@ -252,12 +223,6 @@ __global__ __launch_bounds__(256, 2) void mlp2_k(MlpArgs g) {
 //            the bank row, (r >> 1) & 7 the slot -- conflict-free for the b128 lane groups {0-3, 12-15, 20-27})
 // Same MFMA order and operands as mlp2_k: the same bits.
 // =================================================================================================
-__device__ __forceinline__ void dma16c(unsigned voff, const float* sbase, unsigned lds_byte) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_byte) : "memory");
-}
-
 template <int L, int MODE>
 __global__ __launch_bounds__(256, 2) void mlp2d_k(MlpArgs g) {
     static_assert(L == 128 || L == 64, "mlp2d_k: L");
@@ -306,8 +271,8 @@ __global__ __launch_bounds__(256, 2) void mlp2d_k(MlpArgs g) {
         const unsigned l2 = l1 + C1 * 4;
 #pragma unroll
         for (int q = 0; q < NP; ++q) {
-            dma16c(vo1[q], W1 + (long)hc * HC * L, l1 + q * 1024);
-            dma16c(vo2[q], W2t + hc * HC, l2 + q * 1024);
+            dma16(vo1[q], W1 + (long)hc * HC * L, l1 + q * 1024);
+            dma16(vo2[q], W2t + hc * HC, l2 + q * 1024);
         }
     };
     const int r = wave * 32 + (lane & 31);

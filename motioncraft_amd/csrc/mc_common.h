@@ -152,3 +152,12 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
     return base + idx;
 }
 
+// LDS-DMA: 16 bytes per lane from sbase + voff (bytes) straight into LDS at lds_byte + 16 lane (M0 form).  Inline asm: the builtin does
+// not survive host-side instantiation inside a kernel TEMPLATE, and the compiler must neither count nor drain it as an ordinary load
+// (the kernels that use it order themselves with their own s_waitcnt vmcnt).
+__device__ __forceinline__ void dma16(unsigned voff, const void* sbase, unsigned lds_byte) {
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_byte) : "memory");
+}
+

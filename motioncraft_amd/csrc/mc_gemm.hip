@@ -415,13 +415,7 @@ __global__ __launch_bounds__(256, 2) void gemm_dma_k(GemmArgs g) {
 // LDS image of a stage: [A rows 0..63 | W rows 0..63][16 floats], 16-byte chunk c of row r at position c ^ ((r >> 2) & 3)
 // (conflict-free ds_read_b128 of any aligned 16-lane group: 4 rows share a 256-byte bank row, rows 4 apart differ in the XOR).
 // ---------------------------------------------------------------------------------------
-constexpr int WBK = 16, WSTAGE = 128 * WBK;     // floats per stage of one wave: (64 + 64) rows x 16
-
-__device__ __forceinline__ void dma16(unsigned voff, const float* sbase, unsigned lds_byte) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_byte) : "memory");
-}
+constexpr int WBK = 16, WSTAGE = 128 * WBK;     // floats per stage of one wave: (64 + 64) rows x 16 (dma16: mc_common.h)
 
 // Persistent form: gridDim.x <= 2 workgroups per CU walk the tile list (tile = blockIdx.x, += gridDim.x); a wave goes from the
 // stores of one tile straight into the first DMAs of the next, and the residual / bias rows of a tile are requested two

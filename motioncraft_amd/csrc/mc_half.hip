@@ -189,14 +189,6 @@ __global__ __launch_bounds__(256, 2) void gemm_h_k(GemmHArgs g) {
 // rows, 16-byte chunk c of row r at position c ^ (r & 7), gemm_dma_k's layout) or 32 (split: 64-byte rows, c ^ ((r >> 2) & 3),
 // gemm_wp_k's layout), double buffered: 2 x 32 KB in either mode, one barrier per k-tile (16 / 24 MFMAs per wave).
 // =================================================================================================
-// 16 bytes per lane from sbase + voff (bytes) straight into LDS at lds_byte + 16 lane (M0 form; asm: the builtin does not survive host-side
-// instantiation inside a kernel TEMPLATE, and the compiler must not count / drain it as an ordinary load anyway -- mc_gemm.hip dma16)
-__device__ __forceinline__ void dma16h(unsigned voff, const mc_half* sbase, unsigned lds_byte) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_byte) : "memory");
-}
-
 template <bool SPLIT, bool PRE = false>
 __global__ __launch_bounds__(256, 2) void gemm_hd_k(GemmHArgs g) {
     constexpr int P = SPLIT ? 2 : 1;
@@ -236,8 +228,8 @@ __global__ __launch_bounds__(256, 2) void gemm_hd_k(GemmHArgs g) {
             const unsigned lw = lds0 + (unsigned)((((buf * 2 + 1) * P + p) * PT + 32 * wave_u * BKH) * 2);
 #pragma unroll
             for (int q = 0; q < NQ; ++q) {
-                dma16h(goa[q], ap, la + q * RPI * BKH * 2);
-                dma16h(gow[q], wp, lw + q * RPI * BKH * 2);
+                dma16(goa[q], ap, la + q * RPI * BKH * 2);
+                dma16(gow[q], wp, lw + q * RPI * BKH * 2);
             }
         }
     };
@@ -364,7 +356,7 @@ __global__ __launch_bounds__(256, 2) void gemm_hf_k(GemmHArgs g) {
             const mc_half* wp = (p ? g.Wl : g.Wh) + s * BKH;
             const unsigned lw = lds0 + (unsigned)((((s % ST) * P + p) * PT + 32 * wave_u * BKH) * 2);
 #pragma unroll
-            for (int q = 0; q < NQ; ++q) dma16h(gow[q], wp, lw + q * RPI * BKH * 2);
+            for (int q = 0; q < NQ; ++q) dma16(gow[q], wp, lw + q * RPI * BKH * 2);
         }
     };
     // this wave's row block of the fragment-major planes (rows past M: the last block -- valid memory, never stored)
@@ -604,7 +596,6 @@ __global__ __launch_bounds__(256, 2) void mlp2_h_k(MlpArgs g, const mc_half* __r
         }
 }
 
-// per-row LayerNorm of a fragment-distributed row (lane l and lane l ^ 32 hold the two halves; column of x[j][i] = 8 j + 4 hf + i)
 // =================================================================================================
 // mlp2hd_k: mlp2_h_k<L, MODE, SPLIT> (L = 128 or 64) with the weight chunks of both layers staged by LDS-DMA (the fp16 twin of mlp2d_k, mc_chain.hip):
 // no staging registers, no ds_write, no padding.  LDS images per plane:
@@ -669,8 +660,8 @@ __global__ __launch_bounds__(256, 2) void mlp2hd_k(MlpArgs g, const mc_half* __r
             const unsigned l2 = lds0 + (unsigned)(((hc & 1) * BUF + P * C1 + p * C2) * 2) + (unsigned)(NP * wave_u) * 1024;
 #pragma unroll
             for (int q = 0; q < NP; ++q) {
-                dma16h(vo1[q], w1p[p] + (long)hc * HC * L, l1 + q * 1024);
-                dma16h(vo2[q], w2p[p] + hc * HC, l2 + q * 1024);
+                dma16(vo1[q], w1p[p] + (long)hc * HC * L, l1 + q * 1024);
+                dma16(vo2[q], w2p[p] + hc * HC, l2 + q * 1024);
             }
         }
     };
@@ -748,33 +739,6 @@ __global__ __launch_bounds__(256, 2) void mlp2hd_k(MlpArgs g, const mc_half* __r
             const f32x4 v = {acc2[t][4 * q] + bb[0], acc2[t][4 * q + 1] + bb[1], acc2[t][4 * q + 2] + bb[2], acc2[t][4 * q + 3] + bb[3]};
             *reinterpret_cast<f32x4*>(yrow + n) = v;
         }
-}
-
-template <int NJ>
-__device__ __forceinline__ void frag_layernorm_h(f32x4 (&x)[NJ], const float* __restrict__ gamma, const float* __restrict__ beta, int kq) {
-    constexpr int L = 8 * NJ;
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) s += x[j][0] + x[j][1] + x[j][2] + x[j][3];
-    s += __shfl_xor(s, 32, 64);
-    const float mean = s / (float)L;
-    float q = 0.f;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            x[j][i] -= mean;
-            q += x[j][i] * x[j][i];
-        }
-    q += __shfl_xor(q, 32, 64);
-    const float rstd = rsqrtf(q / (float)L + 1e-5f);
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        const f32x4 g = *reinterpret_cast<const f32x4*>(gamma + 8 * j + kq);
-        const f32x4 b = *reinterpret_cast<const f32x4*>(beta + 8 * j + kq);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) x[j][i] = x[j][i] * rstd * g[i] + b[i];
-    }
 }
 
 // =================================================================================================
@@ -881,7 +845,7 @@ __global__ __launch_bounds__(256, 2) void projqkv_h_k(RowChainArgs g, const mc_h
 #pragma unroll
     for (int c = 0; c < NKEEP; ++c) MC_PQH_CHUNK(c, xh, xl, orow + c * 32, bvf[4 * c + q] = v;)
     for (int c = NKEEP; c < NC0; ++c) MC_PQH_CHUNK(c, xh, xl, orow + c * 32, )
-    frag_layernorm_h<NJ>(bvf, g.gamma, g.beta, kq);
+    frag_layernorm<NJ>(bvf, g.gamma, g.beta, kq);
 #pragma unroll
     for (int kb = 0; kb < NKB; ++kb) split8(bvf[2 * kb], bvf[2 * kb + 1], bh[kb], bl[kb]);
     for (int c = 0; c < NC1; ++c) MC_PQH_CHUNK(NC0 + c, bh, bl, qrow + c * 32, )
@@ -1002,7 +966,7 @@ __global__ __launch_bounds__(256, 2) void pqbody_h_k(RowChainArgs g, const mc_ha
     for (int c = 0; c < NKEEP; ++c) MC_PBH_CHUNK(c, bvf[4 * c + q] = v;)
     for (int c = NKEEP; c < NC0; ++c) MC_PBH_CHUNK(c, )
 #undef MC_PBH_CHUNK
-    frag_layernorm_h<NJ>(bvf, g.gamma, g.beta, kq);
+    frag_layernorm<NJ>(bvf, g.gamma, g.beta, kq);
 #pragma unroll
     for (int kb = 0; kb < NKB; ++kb) split8(bvf[2 * kb], bvf[2 * kb + 1], bh[kb], bl[kb]);
     auto qkv_chunk = [&](int seq, int bias0, float* sl) {
@@ -1394,17 +1358,15 @@ int mc_launch_gemm_h(const GemmHArgs& g, bool split, hipStream_t s) {
             }();
             MC_REQUIRE(scratch == 0, "gemm_hf_k of this build uses scratch memory (%d bytes; -1 = attributes unreadable): its asynchronous fragment loads are unsafe", scratch);
             MC_LEDGER(split ? "gemm_hf_k<true>" : "gemm_hf_k<false>", grid, 2.0 * g.M * g.N * g.K);
-            if (split) hipLaunchKernelGGL(gemm_hf_k<true>, grid, dim3(256), 0, s, g);
-            else hipLaunchKernelGGL(gemm_hf_k<false>, grid, dim3(256), 0, s, g);
+            mc_dispatch<0, 1>(split, [&](auto S) { hipLaunchKernelGGL(gemm_hf_k<bool(MC_V(S))>, grid, dim3(256), 0, s, g); });
             MC_LAUNCH_CHECK();
             return MC_OK;
         }
-        const bool pre = g.pre && g.R;
-        if (split) {
-            if (pre) hipLaunchKernelGGL((gemm_hd_k<true, true>), grid, dim3(256), 0, s, g);
-            else hipLaunchKernelGGL(gemm_hd_k<true>, grid, dim3(256), 0, s, g);
-        } else if (pre) hipLaunchKernelGGL((gemm_hd_k<false, true>), grid, dim3(256), 0, s, g);
-        else hipLaunchKernelGGL(gemm_hd_k<false>, grid, dim3(256), 0, s, g);
+        mc_dispatch<0, 1>(split, [&](auto S) {
+            mc_dispatch<0, 1>(g.pre && g.R, [&](auto PRE) {
+                hipLaunchKernelGGL((gemm_hd_k<bool(MC_V(S)), bool(MC_V(PRE))>), grid, dim3(256), 0, s, g);
+            });
+        });
         MC_LAUNCH_CHECK();
         return MC_OK;
     }
@@ -1414,8 +1376,7 @@ int mc_launch_gemm_h(const GemmHArgs& g, bool split, hipStream_t s) {
     if (g.M <= 0) return MC_OK;
     dim3 grid(cdiv(g.M, 128) * (g.N / 128));
     MC_LEDGER(split ? "gemm_h_k<true>" : "gemm_h_k<false>", grid, 2.0 * g.M * g.N * g.K);
-    if (split) hipLaunchKernelGGL(gemm_h_k<true>, grid, dim3(256), 0, s, g);
-    else hipLaunchKernelGGL(gemm_h_k<false>, grid, dim3(256), 0, s, g);
+    mc_dispatch<0, 1>(split, [&](auto S) { hipLaunchKernelGGL(gemm_h_k<bool(MC_V(S))>, grid, dim3(256), 0, s, g); });
     MC_LAUNCH_CHECK();
     return MC_OK;
 }
@@ -1519,13 +1480,12 @@ int mc_launch_temporal_h(const float* mf, const float* tf, const float* mask, fl
         snprintf(name, sizeof(name), "temporal_h_k<%d, %s>", L, split ? "true" : "false");
         MC_LEDGER(name, grid, (double)nb * H * (2.0 * (Nt + T) * L * L + 2.0 * T * L * L));
     }
-    if (L == 128) {
-        if (split) hipLaunchKernelGGL((temporal_h_k<128, true>), grid, blk, 0, s, mf, tf, mask, yt, b0, B, T, Nt, H, twin_flag, sk);
-        else hipLaunchKernelGGL((temporal_h_k<128, false>), grid, blk, 0, s, mf, tf, mask, yt, b0, B, T, Nt, H, twin_flag, sk);
-    } else {
-        if (split) hipLaunchKernelGGL((temporal_h_k<64, true>), grid, blk, 0, s, mf, tf, mask, yt, b0, B, T, Nt, H, twin_flag, sk);
-        else hipLaunchKernelGGL((temporal_h_k<64, false>), grid, blk, 0, s, mf, tf, mask, yt, b0, B, T, Nt, H, twin_flag, sk);
-    }
+    const bool known = mc_dispatch<128, 64>(L, [&](auto LL) {
+        mc_dispatch<0, 1>(split, [&](auto S) {
+            hipLaunchKernelGGL((temporal_h_k<MC_V(LL), bool(MC_V(S))>), grid, blk, 0, s, mf, tf, mask, yt, b0, B, T, Nt, H, twin_flag, sk);
+        });
+    });
+    MC_REQUIRE(known, "fp16 temporal attention: latent_dim=%d unsupported", L);
     MC_LAUNCH_CHECK();
     return MC_OK;
 }

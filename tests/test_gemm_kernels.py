@@ -92,6 +92,12 @@ F16_SHAPES = [
     (12544, 128, 192, 0, 1, 0, 0),
     (12544, 384, 256, 1, 0, 1, 0),
     (12544, 1536, 1536, 1, 1, 1, 1),
+    # gemm_hf_k walks three slabs per trip (64 halves of K per slab in the f16 mode, 32 in the split mode); the shapes above leave a
+    # remainder of 0 (f16) and of 0 or 2 (split).  M = 160: five 32-row blocks, so the second tile has one real block and three
+    # waves clamped to it
+    (160, 128, 256, 0, 1, 1, 0),        # f16, 4 slabs: remainder 1
+    (160, 128, 320, 0, 1, 1, 0),        # f16, 5 slabs: remainder 2
+    (160, 128, 320, 1, 1, 1, 0),        # split, 10 slabs: remainder 1
 ]
 
 EVERY_KERNEL = ('gemm_small_k', 'gemm_small16_k<3', 'gemm_small16_k<6', 'gemm_k<0>', 'gemm_dma_k', 'gemm_wp_k',
