@@ -33,6 +33,8 @@
  *                                                                      mogen/datasets/EMAGE_2024/utils/metric.py:78-127,199-242
  *   mc_onset_strength, mc_onset_pick  alignment.load_audio (librosa's onset_detect)   metric.py:64-76
  *   mc_audio_condition    the S2G audio condition `onset+amplitude` [samples, 2]   mogen/datasets/EMAGE_2024/dataloaders/beat_motionx.py:398-412
+ *   mc_pcm_decode, mc_resample_poly  librosa.load + librosa.resample in front of both (res_type='polyphase', not the default soxr_hq)
+ *                                                                      dataloaders/beat_sep_lower.py:392-393; tools/s2g_test.py:416-417
  *   mc_op_renoise         GaussianDiffusion._undo (resampling jumps)   gaussian_diffusion.py:429-435, 1113-1118
  *
  * Conventions: plain pointers and sizes only.  `*_dev` pointers are device (HBM) addresses owned
@@ -558,6 +560,34 @@ int mc_onset_pick(const float* env_dev, int32_t n_frames, int32_t pre_max, int32
  * of magnitudes has no rounding, so the result is exact and two runs give the same bits. */
 int mc_audio_condition(const float* wave_dev, int64_t n_samples, int32_t window, const uint8_t* onset_mask_dev, int32_t n_frames,
                        float* out_dev, void* stream);
+
+/* ---- From a PCM wav file's bytes to the waveform the two blocks above read: what the reference does on the host with librosa.load
+ * (libsndfile decode, librosa.to_mono, resample to 22 050 Hz) + librosa.resample(target_sr = 16000), beat_sep_lower.py:392-393 and
+ * s2g_test.py:416-417.  The resampler is librosa's res_type = 'polyphase', which is scipy.signal.resample_poly(y, up, down) with zero
+ * padding, restated in tests/resample_ref.py and pinned to scipy itself.  It is NOT librosa's default soxr_hq, whose parity stays
+ * unpinned: a condition built this way differs from the reference's above roughly 0.9 of the Nyquist rate.
+ * mc_pcm_decode: pcm_dev = the file's data chunk as uploaded, n_frames * channels * sample_bytes bytes of interleaved little-endian
+ * PCM; sample_bytes 1 (unsigned, offset 128), 2, 3 or 4 (signed).  out_dev fp32 [n_frames]:
+ *   mono != 0  out[i] = fp32((sum over the channels of the integer value, in fp64) / channels / 2^(8 sample_bytes - 1)): the sum and
+ *              the power of two are exact, so the quotient and the conversion are the only roundings, and for 1, 2 and 4 channels
+ *              the conversion alone.  For 16-bit input this equals libsndfile's float32 read followed by librosa.to_mono; for the
+ *              other widths it is this project's definition (libsndfile scales them the same way but was not compared);
+ *   mono == 0  out[i] = fp32(value of channel 0 / 2^(8 sample_bytes - 1)), for 16 bits what speech.read_wav returns.
+ * channels 1..1024; out_dev 4-byte aligned.
+ * mc_resample_out_len: ceil(n_in * up / down), the length scipy and librosa give; -1 for n_in < 0, up < 1, down < 1 or a length
+ * whose indices would leave int64.
+ * mc_resample_poly: x_dev fp32 [n_in] -> y_dev fp32 [n_out], n_out = mc_resample_out_len(n_in, up, down), gcd(up, down) = 1:
+ *   y[m] = fp32(sum over k of x[k] * taps[half + m*down - k*up]),  0 <= k < n_in,  0 <= half + m*down - k*up < n_taps,
+ * taps the fp64 filter ALREADY multiplied by `up`, n_taps odd, half = (n_taps - 1) / 2.  taps_dev holds them phase-major and reversed:
+ * fp64 [up][L], L = ceil(n_taps / up), taps_dev[p * L + i] = taps[p + (L - 1 - i) * up], and 0 where that index is >= n_taps
+ * (audio.phase_major builds it), so that an output walks its inputs and its taps in ascending order.  Products and the sum are fp64,
+ * added in ascending k whatever the tiling, and rounded to fp32 once.  One launch, no workspace, no atomics: two runs give the same
+ * bits.  All sample indices are 64-bit.  A tile of 512 outputs must read at most 16384 inputs ((511 down + n_taps - 1) / up + 2): with
+ * the default filter of 20 max(up, down) + 1 taps that holds for down / up <= 30; resample in two steps beyond. */
+int mc_pcm_decode(const uint8_t* pcm_dev, int64_t n_frames, int32_t channels, int32_t sample_bytes, int32_t mono, float* out_dev, void* stream);
+int64_t mc_resample_out_len(int64_t n_in, int32_t up, int32_t down);
+int mc_resample_poly(const float* x_dev, int64_t n_in, int32_t up, int32_t down, const double* taps_dev, int32_t n_taps, float* y_dev,
+                     int64_t n_out, void* stream);
 
 /* out = a * x + b * noise over n elements (out may alias x) */
 int mc_op_renoise(const float* x_dev, const float* noise_dev, float a, float b, float* out_dev, int64_t n, void* stream);

@@ -9,9 +9,11 @@ from .models import ControlT2MHalf, wrap_fp16_model
 from .checkpoint import load_checkpoint
 from . import scoring
 from .scoring import BeatAlignment, M2DScorer, OnsetDetector, S2GScorer, face_errors
+from . import audio
+from .audio import Resampler, load_wav
 from . import speech
 from .speech import AudioCondition, sample_speech, speech_frames, speech_prompt
 
-__all__ = ['AudioCondition', 'sample_speech', 'speech', 'speech_frames', 'speech_prompt', 'BeatAlignment', 'M2DScorer', 'OnsetDetector', 'S2GScorer', 'face_errors', 'scoring','ARCHITECTURES', 'ATTENTIONS', 'LOSSES', 'MODELS', 'SUBMODULES', 'build_architecture',
+__all__ = ['audio', 'Resampler', 'load_wav', 'AudioCondition', 'sample_speech', 'speech', 'speech_frames', 'speech_prompt', 'BeatAlignment', 'M2DScorer', 'OnsetDetector', 'S2GScorer', 'face_errors', 'scoring','ARCHITECTURES', 'ATTENTIONS', 'LOSSES', 'MODELS', 'SUBMODULES', 'build_architecture',
            'build_attention', 'build_loss', 'build_submodule', 'Config', 'ConfigDict', 'Registry', 'build_from_cfg', 'ControlT2MHalf',
            'load_checkpoint', 'wrap_fp16_model']

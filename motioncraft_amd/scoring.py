@@ -7,9 +7,10 @@
   * ``OnsetDetector`` / ``BeatAlignment.load_audio``: ``alignment.load_audio`` (metric.py:64-76), i.e. librosa 0.10.1's
     ``onset.onset_detect(y, sr, hop_length=512, units='time')`` with its defaults, on the device (``mc_onset_strength`` /
     ``mc_onset_pick``, ``csrc/mc_onset.hip``) from a waveform that is already decoded and at the detector's rate.  librosa is not
-    a dependency: parity is pinned to the float64 restatement ``tests/onset_ref.py``.  Decoding audio files (beyond the PCM wav
-    ``tools/s2g_score.py`` reads) and resampling (the reference's ``librosa.load`` + ``librosa.resample``, soxr) stay with the
-    caller.
+    a dependency: parity is pinned to the float64 restatement ``tests/onset_ref.py``.  Decoding an integer PCM wav and resampling it
+    to the detector's rate is ``motioncraft_amd.audio.load_wav``, also on the device: the reference's ``librosa.load`` +
+    ``librosa.resample`` in librosa's ``polyphase`` mode (``scipy.signal.resample_poly``), not ``soxr_hq``, whose parity stays
+    unpinned.  Compressed and float files stay with the caller.
   * ``face_errors``: the face ``l2`` / ``lvel`` errors of ``s2g_test.py:377-412``; the two vertex sets are reduced to the two
     sums on the device (``mc_smplx_vertex_errors``) and never leave it.
   * ``S2GScorer`` / ``M2DScorer``: the accumulation and the printed numbers of the two tools, on the existing ``L1div``, FID and
@@ -91,7 +92,7 @@ class OnsetDetector:
     """``librosa.onset.onset_detect`` of librosa 0.10.1 with its defaults, on the device: log-power mel spectrogram (periodic Hann
     window, ``center=True`` with zero padding, 128 Slaney mel bands, top_db 80), spectral flux with lag 1 averaged over the bands,
     min/max normalisation, ``peak_pick`` with pre_max 0.03 s, post_max 0, pre_avg 0.1 s, post_avg 0.1 s, wait 0.03 s, delta 0.07.
-    The waveform is taken as float32 at ``sr``; resampling is the caller's."""
+    The waveform is taken as float32 at ``sr``; ``audio.Resampler`` / ``audio.load_wav`` bring one there."""
     DELTA = 0.07
     N_FFT, MAX_HOP, MAX_MELS = 2048, 512, 128                            # csrc/mc_onset.hip
 

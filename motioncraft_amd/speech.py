@@ -7,11 +7,13 @@
     waveform and stays there.  Parity is pinned to the numpy restatement ``tests/audio_cond_ref.py``, bit for bit.
   * ``speech_frames`` / ``speech_prompt`` / ``sample_speech``: the frame count, the text prompt and the window walk of
     ``CustomTrainer._g_test`` (s2g_test.py:120-260) on ``longform.sample_long`` with 533 audio samples per frame.
-  * ``read_wav``: the 16-bit PCM reader of the two S2G tools.
+  * ``read_wav``: the 16-bit PCM reader of the two S2G tools, for a file already at the model's rate.
 
-Decoding other formats and resampling (the reference's ``librosa.load`` + ``librosa.resample``, soxr) stay with the caller, and so
-does the source of the prompt's words (the reference reads them per frame from a TextGrid through its vocabulary).  Nothing here
-falls back to the host: a missing library or GPU is an error.
+Other integer PCM files -- any rate, width and channel count -- are decoded, mixed to mono and resampled on the device by
+``motioncraft_amd.audio.load_wav`` (the two tools' ``--resample``): the reference's ``librosa.load`` + ``librosa.resample`` in
+librosa's ``polyphase`` mode, pinned to scipy; it is not ``soxr_hq``, so a condition built this way differs from the reference's
+above roughly 0.9 of the Nyquist rate.  Compressed and float files stay with the caller, and so does the source of the prompt's
+words (the reference reads them per frame from a TextGrid through its vocabulary).  Nothing here falls back to the host: a missing library or GPU is an error.
 """
 import ctypes
 import wave

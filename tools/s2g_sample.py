@@ -2,15 +2,19 @@
 """Sample a gesture sequence for one speech clip: the front half of the reference's ``tools/s2g_test.py`` (``_g_test``, lines
 120-260, and the ``res_<id>.npz`` of lines 440-448) on the device.
 
-    python tools/s2g_sample.py CONFIG CHECKPOINT --wav CLIP.wav [--words w1 w2 ... | --text "w1 w2 ..."] --out DIR \\
+    python tools/s2g_sample.py CONFIG CHECKPOINT --wav CLIP.wav [--resample [--load_sr 22050]] [--words w1 w2 ... | --text "w1 w2 ..."] --out DIR \\
         [--mean mean.npy --std std.npy] [--repaint --overlap_len N] [--seed S] [--fp16 split|plain] [--graph] [--betas GT.npz] \\
         [--clip_feat feats.npy | --xf_out xf.npy | --random-condition SEED]
 
 CONFIG is an S2G config (``configs/stmogen/S2G_Beats2_*.py``: ``copy_blocks_num``, ``control_cond_feats``,
-``condition_encode_cfg`` with ``condition_pre_encode_type='wav'``); CHECKPOINT may be "synthetic[:SEED]".  CLIP.wav is 16-bit PCM,
-mono or the first channel, ALREADY at 16 kHz: decoding other formats and resampling stay with the caller.  The waveform goes to
-the device once; the ``onset+amplitude`` condition (``motioncraft_amd.speech.AudioCondition``) and the window walk over it stay
-there.  The prompt is 'A person is doing a speech, and the speech content is <words>' for every window; the reference takes each
+``condition_encode_cfg`` with ``condition_pre_encode_type='wav'``); CHECKPOINT may be "synthetic[:SEED]".  Without --resample
+CLIP.wav is 16-bit PCM, mono or the first channel, ALREADY at 16 kHz, and the waveform goes to the device once.  With --resample
+it is integer PCM of any rate, 8 to 32 bits and any channel count: its bytes go to the device once and are decoded, mixed to mono
+and resampled to 16 kHz there (``motioncraft_amd.audio.load_wav``); --load_sr 22050 goes through 22 050 Hz first, as the
+reference's ``librosa.load`` + ``librosa.resample`` do.  The resampler is librosa's ``polyphase`` mode, pinned to
+``scipy.signal.resample_poly``; it is not ``soxr_hq``, the reference's, so the condition differs from the reference's above
+roughly 0.9 of the Nyquist rate.  Compressed and float files stay with the caller.  The ``onset+amplitude`` condition
+(``motioncraft_amd.speech.AudioCondition``) and the window walk over it stay on the device.  The prompt is 'A person is doing a speech, and the speech content is <words>' for every window; the reference takes each
 window's words from a TextGrid, which this tool does not read.  As in ``tools/sample.py``, the prompt reaches the model through
 the CLIP tower only when the ``clip`` package is importable: otherwise give --clip_feat / --xf_out / --random-condition.
 Writes DIR/res_<id>.npz (<id> = the wav's base name) with the keys ``tools/s2g_score.py`` reads.
@@ -26,7 +30,7 @@ ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
 sys.path.insert(0, ROOT)
 
 import motioncraft_amd as mc                                    # noqa: E402
-from motioncraft_amd import scoring, speech, synthetic          # noqa: E402
+from motioncraft_amd import audio, scoring, speech, synthetic   # noqa: E402
 from motioncraft_amd.checkpoint import load_checkpoint          # noqa: E402
 
 AUDIO_SR = 16000                                                # the S2G configs' audio_sr; speech.SAMPLES_PER_FRAME = AUDIO_SR // 30
@@ -36,7 +40,9 @@ def parse_args():
     p = argparse.ArgumentParser(description='speech-to-gesture sampling from a wav file')
     p.add_argument('config')
     p.add_argument('checkpoint')
-    p.add_argument('--wav', required=True, metavar='FILE', help='16-bit PCM at 16 kHz')
+    p.add_argument('--wav', required=True, metavar='FILE', help='16-bit PCM at 16 kHz; with --resample integer PCM of any rate, width and channel count')
+    p.add_argument('--resample', action='store_true', help='decode, mix to mono and resample to 16 kHz on the device (librosa\'s polyphase mode, not soxr_hq)')
+    p.add_argument('--load_sr', type=int, default=None, metavar='N', help='with --resample: go through N Hz first (22050: the reference\'s librosa.load)')
     words = p.add_mutually_exclusive_group()
     words.add_argument('--words', nargs='+', default=None, help='the words of the speech, in order')
     words.add_argument('--text', default=None, help='the same as one string, split at white space')
@@ -59,7 +65,10 @@ def parse_args():
     p.add_argument('--no_repaint', action='store_true')
     p.add_argument('--fp16', choices=['split', 'plain'], default=None, help='fp16-MFMA mode: split = fp32-class hi/lo form')
     p.add_argument('--graph', action='store_true', help='hipGraph replay of the sampler step')
-    return p.parse_args()
+    a = p.parse_args()
+    if a.load_sr is not None and not a.resample:
+        p.error('--load_sr needs --resample')
+    return a
 
 
 def main():
@@ -79,7 +88,11 @@ def main():
         mc.wrap_fp16_model(model, split=(a.fp16 != 'plain'))
     dims = model.model.dims
     try:
-        wav = speech.read_wav(a.wav, AUDIO_SR)
+        if a.resample:
+            print(audio.describe(a.wav, AUDIO_SR, a.load_sr))
+            wav, _ = audio.load_wav(a.wav, sr=AUDIO_SR, load_sr=a.load_sr)
+        else:
+            wav = speech.read_wav(a.wav, AUDIO_SR)
     except ValueError as e:
         raise SystemExit(str(e))
     dev = torch.device('cuda', torch.cuda.current_device())
