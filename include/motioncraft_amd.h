@@ -35,6 +35,8 @@
  *   mc_audio_condition    the S2G audio condition `onset+amplitude` [samples, 2]   mogen/datasets/EMAGE_2024/dataloaders/beat_motionx.py:398-412
  *   mc_pcm_decode, mc_resample_poly  librosa.load + librosa.resample in front of both (res_type='polyphase', not the default soxr_hq)
  *                                                                      dataloaders/beat_sep_lower.py:392-393; tools/s2g_test.py:416-417
+ *   mc_render_*           the frames fast_render.generate_silent_videos* draws (orthographic rasteriser; own shading model)
+ *                                                                      mogen/datasets/EMAGE_2024/utils/fast_render.py:13-81; other_tools.py:695-765
  *   mc_op_renoise         GaussianDiffusion._undo (resampling jumps)   gaussian_diffusion.py:429-435, 1113-1118
  *
  * Conventions: plain pointers and sizes only.  `*_dev` pointers are device (HBM) addresses owned
@@ -588,6 +590,58 @@ int mc_pcm_decode(const uint8_t* pcm_dev, int64_t n_frames, int32_t channels, in
 int64_t mc_resample_out_len(int64_t n_in, int32_t up, int32_t down);
 int mc_resample_poly(const float* x_dev, int64_t n_in, int32_t up, int32_t down, const double* taps_dev, int32_t n_taps, float* y_dev,
                      int64_t n_out, void* stream);
+
+/* ---- Orthographic rasteriser: the vertices mc_smplx_vertices writes -> frames, the last step of the reference's tools
+ * (mogen/datasets/EMAGE_2024/utils/fast_render.py:13-81 builds the scene -- a grey mesh, OrthographicCamera(xmag = ymag = 1), one
+ * DirectionalLight -- and other_tools.py:695-765 feeds it; there pyrender + osmesa draw it in eight host processes).  The geometry below
+ * is restated exactly in tests/raster_ref.py.  The colours are THIS project's shading model: pyrender's were not available to pin.
+ *   project   screen_x = S[0] . (p, 1), screen_y = S[1] . (p, 1) in pixels (row 0 on top), zcam = S[2] . (p, 1), the distance along
+ *             the view direction, S the fp32 3x4 world-to-screen affine, all fp32 fma; snapped to 8 sub-pixel bits,
+ *             X = floor(256 screen_x + 0.5) as int32 (INT32_MIN when that is not finite or beyond the guard band).
+ *             n_v = normalise(sum over the vertex's adjacency list, in list order, of cross(p1 - p0, p2 - p0)): area weighted,
+ *             fp32, no atomics; a vertex without faces has the normal 0.
+ *   raster    per triangle, with P = (256 x + 128, 256 y + 128) the centre of pixel (x, y) and E_ab(P) = (bx - ax)(Py - ay) -
+ *             (by - ay)(Px - ax) in int64: w0 = E_12, w1 = E_20, w2 = E_01, area = w0 + w1 + w2.  area < 0 is counter-clockwise
+ *             with y up = front; area == 0, and area > 0 under cull_backfaces, are dropped, and so is a triangle with a vertex whose
+ *             zcam is not finite or whose snapped coordinate lies outside +-16384 px (every product then fits int64).  A sample is
+ *             covered when the three w have the sign of area or are 0 on a top or left edge (top-left fill rule), over the bounding
+ *             box clamped to the viewport.  b1 = float(w1) / float(area), b2 = float(w2) / float(area),
+ *             z = fmaf(b2, z2 - z0, fmaf(b1, z1 - z0, z0)); a sample with z outside [znear, zfar] is discarded.  The visible face of
+ *             a pixel is the minimum of (bits of z) << 32 | face over its samples, by a 64-bit integer atomic minimum: the nearest
+ *             sample, the lower face id at equal depth, whatever the order of arrival.  A triangle whose clamped box holds more than
+ *             large_threshold pixels is walked by large_slices waves instead of one thread; the result is the same.
+ *   shade     per pixel: background, or b0 = 1 - b1 - b2 and n = normalise(b0 n_0 + b1 n_1 + b2 n_2) (0 when the sum is 0),
+ *             c = min(1, base (ambient + gain max(0, n . light))) per channel, u8 = (int)(255 c + 0.5).  A back face drawn with
+ *             culling off keeps its outward normal.  depth is z of the winning sample (+inf on the background), face its id (-1).
+ * Frames run in chunks of as many as work_dev holds; the result does not depend on the chunk size and two runs give the same bits.
+ * work_dev: 16-byte aligned, at least the bytes mc_render_work_bytes gives for one frame (-1: bad argument).  Its head (a list
+ * counter and the visibility keys of every frame it holds) must be 0 / all-ones when the kernels start; every call leaves it so.  With
+ * work_clean = 0 the call fills it first; a caller that hands back the buffer of an earlier, successful call of the same width and
+ * height, untouched since, may pass work_clean = 1 and skip the fill. */
+typedef struct mc_render mc_render;
+typedef struct mc_render_params {
+    float screen[12];         /* S, row-major 3x4 (render.OrthographicCamera.screen_affine)                                 */
+    float light[3];           /* unit vector towards the light, world space                                                 */
+    float base[3];            /* mesh colour, 0..1                                                                          */
+    float ambient, gain;      /* gain = intensity / pi: a unit-albedo Lambert surface                                       */
+    float znear, zfar;        /* 0 < znear <= zfar                                                                          */
+    int32_t background[3];    /* 0..255                                                                                     */
+    int32_t width, height;    /* 1..16384                                                                                   */
+    int32_t cull_backfaces;
+    int32_t large_threshold;  /* 0 = the default (1024); 1 sends every multi-pixel box to the wave path, INT32_MAX none      */
+    int32_t large_slices;     /* waves that share one triangle of the wave path: 0 = the default (32), at most 1024         */
+} mc_render_params;
+/* faces_host int32 [num_faces,3]; the vertex-to-face adjacency in CSR form, adj_start_host int32 [num_vertices + 1] and
+ * adj_faces_host int32 [adj_start[num_vertices]], the faces of each vertex in ascending order (all three checked here) */
+int mc_render_create(const int32_t* faces_host, int32_t num_faces, int32_t num_vertices, const int32_t* adj_start_host,
+                     const int32_t* adj_faces_host, mc_render** out);
+void mc_render_destroy(mc_render* r);
+int64_t mc_render_work_bytes(const mc_render* r, int32_t n_frames, int32_t width, int32_t height);
+/* verts_dev fp32 [n,V,3] -> rgb_out_dev uint8 [n,H,W,3] (4-byte aligned) and, where not NULL, face_out_dev int32 [n,H,W],
+ * depth_out_dev fp32 [n,H,W], screen_out_dev int32 [n,V,2], zcam_out_dev fp32 [n,V] */
+int mc_render_frames(mc_render* r, const float* verts_dev, int32_t n, const mc_render_params* p, void* work_dev, int64_t work_bytes,
+                     int32_t work_clean, uint8_t* rgb_out_dev, int32_t* face_out_dev, float* depth_out_dev, int32_t* screen_out_dev,
+                     float* zcam_out_dev, void* stream);
 
 /* out = a * x + b * noise over n elements (out may alias x) */
 int mc_op_renoise(const float* x_dev, const float* noise_dev, float a, float b, float* out_dev, int64_t n, void* stream);

@@ -62,6 +62,14 @@ class SMPLXConfig(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ('num_vertices', 'num_joints', 'num_betas', 'num_expr', 'num_pose_feats')]
 
 
+class RenderParams(ctypes.Structure):
+    """mc_render_params (include/motioncraft_amd.h)"""
+    _fields_ = [('screen', ctypes.c_float * 12), ('light', ctypes.c_float * 3), ('base', ctypes.c_float * 3), ('ambient', ctypes.c_float),
+                ('gain', ctypes.c_float), ('znear', ctypes.c_float), ('zfar', ctypes.c_float), ('background', ctypes.c_int32 * 3),
+                ('width', ctypes.c_int32), ('height', ctypes.c_int32), ('cull_backfaces', ctypes.c_int32), ('large_threshold', ctypes.c_int32),
+                ('large_slices', ctypes.c_int32)]
+
+
 class TextEncConfig(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ('clip_dim', 'text_latent_dim', 'num_layers', 'ff_size', 'num_heads', 'max_len',
                                               'clip_layers', 'clip_heads', 'clip_ff', 'vocab')]
@@ -154,6 +162,10 @@ _SIGNATURES = {
     'mc_pcm_decode': (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P]),
     'mc_resample_out_len': (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]),
     'mc_resample_poly': (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_int32, _P, ctypes.c_int64, _P]),
+    'mc_render_create': (ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_int32, _P, _P, ctypes.POINTER(_P)]),
+    'mc_render_destroy': (None, [_P]),
+    'mc_render_work_bytes': (ctypes.c_int64, [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
+    'mc_render_frames': (ctypes.c_int, [_P, _P, ctypes.c_int32, ctypes.POINTER(RenderParams), _P, ctypes.c_int64, ctypes.c_int32, _P, _P, _P, _P, _P, _P]),
     'mc_op_renoise': (ctypes.c_int, [_P, _P, ctypes.c_float, ctypes.c_float, _P, ctypes.c_int64, _P]),
     'mc_debug_flop_ledger': (ctypes.c_int, [ctypes.c_int32]),
     'mc_debug_flop_ledger_dump': (ctypes.c_int64, [ctypes.c_char_p, ctypes.c_int64]),

@@ -145,6 +145,14 @@ def smplx_vertices(post, model, betas=None, return_joints=False):
     return model.vertices(post['poses'], post['expressions'], post['trans'], betas, return_joints=return_joints)
 
 
+def smplx_render(post, body, renderer, betas=None, work_bytes=None):
+    """The frames of ``post`` under ``body`` drawn by ``renderer`` (``render.MeshRenderer`` over ``body.faces``): device uint8
+    [frames, H, W, 3], what the reference's tools hand to ffmpeg (fast_render.py:63-81).  The vertices never leave the device."""
+    verts = smplx_vertices(post, body, betas)
+    verts = verts.reshape(-1, body.num_vertices, 3)
+    return renderer.render(verts) if work_bytes is None else renderer.render(verts, work_bytes=work_bytes)
+
+
 def result_name(text, motion_length):
     """visualize.py:247: 'res_' + caption with '/', ' ' -> '_' and '.' removed + '_<length>'."""
     return 'res_' + text.replace('/', '_').replace(' ', '_').replace('.', '') + f'_{int(motion_length)}'

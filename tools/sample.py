@@ -5,7 +5,7 @@ positions with --pose_npy), everything between the condition features and the fi
 
     python tools/sample.py CONFIG CHECKPOINT --text "a person walks" --motion_length 120 --out ./samples \\
         [--clip_feat feats.npy | --xf_out xf.npy | --random-condition SEED]  [--mean mean.npy --std std.npy]  [--pose_npy joints.npy]
-        [--smplx_model SMPLX_NEUTRAL.npz --joints_npy joints.npy [--verts_npy verts.npy]]
+        [--smplx_model SMPLX_NEUTRAL.npz --joints_npy joints.npy [--verts_npy verts.npy] [--render_dir frames/ [--render_size 960x720]]]
 
 The CLIP tokenizer is not available offline: prompts only name the output file unless the `clip` package is importable
 (then they are tokenized and encoded by the device CLIP tower when the checkpoint carries clip.* weights).
@@ -22,7 +22,7 @@ ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
 sys.path.insert(0, ROOT)
 
 import motioncraft_amd as mc                                    # noqa: E402
-from motioncraft_amd import postprocess, synthetic              # noqa: E402
+from motioncraft_amd import postprocess, render, synthetic             # noqa: E402
 from motioncraft_amd.checkpoint import load_checkpoint          # noqa: E402
 
 
@@ -39,6 +39,11 @@ def parse_args():
     p.add_argument('--joints_npy', default=None, metavar='PATH',
                    help='with --smplx_model: save the 55 SMPL-X joints [frames, 55, 3] of the stitched, filtered motion (tools/s2g_test.py:406)')
     p.add_argument('--verts_npy', default=None, metavar='PATH', help='with --smplx_model: save the skinned vertices [frames, V, 3]')
+    p.add_argument('--render_dir', default=None, metavar='DIR',
+                   help='with --smplx_model: render the stitched, filtered motion on the device and write frame_%%d.bmp there '
+                        '(+ an mp4 when ffmpeg is on PATH); the reference scene of fast_render.py, colours not pinned to pyrender')
+    p.add_argument('--render_size', default='960x720', metavar='WxH', help='frame size of --render_dir (the reference: 960x720)')
+    p.add_argument('--render_fps', type=float, default=30.0, help='frame rate of the mp4 of --render_dir')
     p.add_argument('--clip_feat', help='.npy [n,77,512] CLIP text features (ln_final output)')
     p.add_argument('--xf_out', help='.npy [n,77,text_latent_dim] frozen condition embedding')
     p.add_argument('--random-condition', type=int, default=None, metavar='SEED')
@@ -77,10 +82,14 @@ def main():
     if (a.joints_npy or a.verts_npy or a.smplx_model) and dims.get('dataset', 'motionx') != 'motionx':
         raise ValueError('--smplx_model / --joints_npy / --verts_npy run the SMPL-X body model on a motionx sample; a human_ml3d / '
                          'kit_ml config saves joints with --pose_npy')
-    if (a.joints_npy or a.verts_npy) and not a.smplx_model:
-        raise ValueError('--joints_npy / --verts_npy need the body model file: --smplx_model PATH')
-    if a.smplx_model and not (a.joints_npy or a.verts_npy):
-        raise ValueError('--smplx_model alone writes nothing: name an output with --joints_npy PATH and / or --verts_npy PATH')
+    if (a.joints_npy or a.verts_npy or a.render_dir) and not a.smplx_model:
+        raise ValueError('--joints_npy / --verts_npy / --render_dir need the body model file: --smplx_model PATH')
+    if a.smplx_model and not (a.joints_npy or a.verts_npy or a.render_dir):
+        raise ValueError('--smplx_model alone writes nothing: name an output with --joints_npy PATH, --verts_npy PATH and / or '
+                         '--render_dir DIR')
+    render_size = render.parse_size(a.render_size)
+    if not a.render_fps > 0:
+        raise ValueError(f'--render_fps must be positive, got {a.render_fps}')
     n, T, C = len(a.text), max(a.motion_length), dims['input_feats']
     if not 1 <= T <= dims['max_seq_len']:
         raise ValueError(f'motion_length must be in [1, {dims["max_seq_len"]}]')
@@ -115,6 +124,13 @@ def main():
                 np.save(a.joints_npy, postprocess.smplx_joints(post, body).cpu().numpy())
             if a.verts_npy:
                 np.save(a.verts_npy, postprocess.smplx_vertices(post, body).cpu().numpy())
+            if a.render_dir:
+                if body.faces.shape[0] == 0:
+                    raise ValueError(f'{a.smplx_model} holds no faces (key f): nothing to draw')
+                renderer = render.MeshRenderer(body.faces, body.num_vertices, width=render_size[0], height=render_size[1])
+                paths, mp4 = render.save_frames(postprocess.smplx_render(post, body, renderer), a.render_dir, a.render_fps,
+                                                postprocess.result_name(a.text[0], a.motion_length[0]))
+                print(f'rendered {len(paths)} frames -> {a.render_dir}' + (f', {mp4}' if mp4 else ' (no ffmpeg on PATH: frames only)'))
     else:
         arrs = [o['pred_motion'][:m].numpy() * (std if std is not None else 1.0) + (mean if mean is not None else 0.0)
                 for o, m in zip(out, a.motion_length)]
