@@ -643,6 +643,40 @@ int mc_render_frames(mc_render* r, const float* verts_dev, int32_t n, const mc_r
                      int32_t work_clean, uint8_t* rgb_out_dev, int32_t* face_out_dev, float* depth_out_dev, int32_t* screen_out_dev,
                      float* zcam_out_dev, void* stream);
 
+/* ---- Capsule rasteriser: the joints mc_postprocess_t2m_joints* writes -> the skeleton animation the reference's text-to-motion tool
+ * ends with (plot_3d_motion, mogen/utils/plot_utils.py:107-204: matplotlib's mplot3d on the host).  The scene (ground quad, root
+ * trail, kinematic chains; a pixel's layer is the maximum layer that covers it, there is no depth test), the projection (fp32 fma,
+ * correctly rounded division, 4 sub-pixel bits, a guard band of 8192 px), the exact int64 capsule rule and the triangle rule are
+ * defined in the header comment of csrc/mc_skeleton.hip and restated in tests/skeleton_ref.py.  Not drawn: the title, anti-aliasing
+ * and mplot3d's projecting caps; pixel parity with matplotlib's Agg output is not claimed.
+ * Layers: 0 background, 1 plane, 2 trail, 3 + c chain c.  Frames run in chunks of as many as work_dev holds; the result does not depend
+ * on the chunk size, two runs give the same bits, and there are no atomics. */
+#define MC_SKELETON_MAX_LAYERS 64
+typedef struct mc_skeleton mc_skeleton;
+typedef struct mc_skeleton_params {
+    float screen[16];         /* S, row-major 4x4: world -> (X_num, Y_num, depth, W), pixel = (X_num / W, Y_num / W), row 0 on top
+                                 (skeleton.Mplot3dCamera.screen_projective); row 2 is not read                                */
+    int32_t width, height;    /* 1..4096                                                                                      */
+} mc_skeleton_params;
+/* Chain c is the polyline through chain_joints_host[chain_start_host[c] .. chain_start_host[c + 1]) (int32, at least 2 joints each,
+ * all < num_joints; 1..61 chains) drawn chain_width_px_host[c] pixels wide; the trail is trail_width_px wide.  A width w gives the
+ * radius max(12, floor(8 w + 0.5)) sixteenths of a pixel and must be positive and at most 64.  palette_host uint8 [3 + num_chains][3]:
+ * background, plane (already composited over the background), trail, then the chains. */
+int mc_skeleton_create(const int32_t* chain_joints_host, const int32_t* chain_start_host, int32_t num_chains, int32_t num_joints,
+                       const float* chain_width_px_host, float trail_width_px, const uint8_t* palette_host, mc_skeleton** out);
+void mc_skeleton_destroy(mc_skeleton* h);
+/* bytes that hold n_frames frames of sequences of at most max_trail frames each; -1: bad argument */
+int64_t mc_skeleton_work_bytes(const mc_skeleton* h, int32_t n_frames, int32_t max_trail, int32_t width, int32_t height);
+/* joints_dev fp32 [n,J,3], n = seq_start_host[num_seqs]; sequence s is the rows seq_start_host[s] .. seq_start_host[s + 1] (int32
+ * [num_seqs + 1], ascending from 0, on the host).  work_dev: 16-byte aligned, at least mc_skeleton_work_bytes(h, 1, L, ...) with L the
+ * longest sequence; its contents need not be kept.  -> rgb_out_dev uint8 [n,H,W,3] (4-byte aligned) and, where not NULL,
+ * layer_out_dev uint8 [n,H,W] (4-byte aligned), screen_out_dev int32 [n,J + 4,2] (joints, then the plane's corners; INT32_MIN twice
+ * for an invalid point), trail_screen_out_dev int32 [n,L,2] (frame i of a sequence: its trail points j < i when i >= 2, invalid
+ * elsewhere), stats_out_dev fp32 [num_seqs,6] (MINS, MAXS; an empty sequence's row is not written), traj_out_dev fp32 [n,2]. */
+int mc_skeleton_frames(mc_skeleton* h, const float* joints_dev, const int32_t* seq_start_host, int32_t num_seqs, const mc_skeleton_params* p,
+                       void* work_dev, int64_t work_bytes, uint8_t* rgb_out_dev, uint8_t* layer_out_dev, int32_t* screen_out_dev,
+                       int32_t* trail_screen_out_dev, float* stats_out_dev, float* traj_out_dev, void* stream);
+
 /* out = a * x + b * noise over n elements (out may alias x) */
 int mc_op_renoise(const float* x_dev, const float* noise_dev, float a, float b, float* out_dev, int64_t n, void* stream);
 

@@ -39,6 +39,7 @@ class Inpaint(ctypes.Structure):
 
 
 MAX_TRANSL = 8               # MC_MAX_TRANSL
+SKELETON_MAX_LAYERS = 64     # MC_SKELETON_MAX_LAYERS
 
 
 class Seed(ctypes.Structure):
@@ -68,6 +69,11 @@ class RenderParams(ctypes.Structure):
                 ('gain', ctypes.c_float), ('znear', ctypes.c_float), ('zfar', ctypes.c_float), ('background', ctypes.c_int32 * 3),
                 ('width', ctypes.c_int32), ('height', ctypes.c_int32), ('cull_backfaces', ctypes.c_int32), ('large_threshold', ctypes.c_int32),
                 ('large_slices', ctypes.c_int32)]
+
+
+class SkeletonParams(ctypes.Structure):
+    """mc_skeleton_params (include/motioncraft_amd.h)"""
+    _fields_ = [('screen', ctypes.c_float * 16), ('width', ctypes.c_int32), ('height', ctypes.c_int32)]
 
 
 class TextEncConfig(ctypes.Structure):
@@ -166,6 +172,10 @@ _SIGNATURES = {
     'mc_render_destroy': (None, [_P]),
     'mc_render_work_bytes': (ctypes.c_int64, [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
     'mc_render_frames': (ctypes.c_int, [_P, _P, ctypes.c_int32, ctypes.POINTER(RenderParams), _P, ctypes.c_int64, ctypes.c_int32, _P, _P, _P, _P, _P, _P]),
+    'mc_skeleton_create': (ctypes.c_int, [_P, _P, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_float, _P, ctypes.POINTER(_P)]),
+    'mc_skeleton_destroy': (None, [_P]),
+    'mc_skeleton_work_bytes': (ctypes.c_int64, [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
+    'mc_skeleton_frames': (ctypes.c_int, [_P, _P, _P, ctypes.c_int32, ctypes.POINTER(SkeletonParams), _P, ctypes.c_int64, _P, _P, _P, _P, _P, _P, _P]),
     'mc_op_renoise': (ctypes.c_int, [_P, _P, ctypes.c_float, ctypes.c_float, _P, ctypes.c_int64, _P]),
     'mc_debug_flop_ledger': (ctypes.c_int, [ctypes.c_int32]),
     'mc_debug_flop_ledger_dump': (ctypes.c_int64, [ctypes.c_char_p, ctypes.c_int64]),

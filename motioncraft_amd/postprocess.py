@@ -249,6 +249,14 @@ def recover_joints_stitched(pred_motion, motion_length, mean=None, std=None, joi
     return joints
 
 
+def t2m_render(pred_motion, motion_length, renderer, mean=None, std=None, joints_num=None, sigma=SIGMA_T2M_JOINTS, work_bytes=None):
+    """``plot_t2m`` (tools/visualize.py:46-56) on the device: ``recover_joints_stitched``, then ``renderer``
+    (``skeleton.SkeletonRenderer``) draws ONE animation over the concatenated intervals, as ``plot_3d_motion`` does: device uint8
+    [sum(motion_length), H, W, 3].  The joints never leave the device."""
+    joints = recover_joints_stitched(pred_motion, motion_length, mean, std, joints_num, sigma)
+    return renderer.render(joints) if work_bytes is None else renderer.render(joints, work_bytes=work_bytes)
+
+
 def save_joints_npy(path, pred_motion, motion_length, mean=None, std=None, joints_num=None, sigma=SIGMA_T2M_JOINTS):
     """The --pose_npy file of the reference tool (visualize.py:55-56): stitched, filtered joints [sum(len), J, 3] fp32."""
     joints = recover_joints_stitched(pred_motion, motion_length, mean, std, joints_num, sigma)

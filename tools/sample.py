@@ -5,6 +5,7 @@ positions with --pose_npy), everything between the condition features and the fi
 
     python tools/sample.py CONFIG CHECKPOINT --text "a person walks" --motion_length 120 --out ./samples \\
         [--clip_feat feats.npy | --xf_out xf.npy | --random-condition SEED]  [--mean mean.npy --std std.npy]  [--pose_npy joints.npy]
+        [--anim_dir frames/ [--anim_size 1000x1000] [--anim_fps 20]]
         [--smplx_model SMPLX_NEUTRAL.npz --joints_npy joints.npy [--verts_npy verts.npy] [--render_dir frames/ [--render_size 960x720]]]
 
 The CLIP tokenizer is not available offline: prompts only name the output file unless the `clip` package is importable
@@ -22,7 +23,7 @@ ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
 sys.path.insert(0, ROOT)
 
 import motioncraft_amd as mc                                    # noqa: E402
-from motioncraft_amd import postprocess, render, synthetic             # noqa: E402
+from motioncraft_amd import postprocess, render, skeleton, synthetic   # noqa: E402
 from motioncraft_amd.checkpoint import load_checkpoint          # noqa: E402
 
 
@@ -35,6 +36,11 @@ def parse_args():
     p.add_argument('--out', default='./samples')
     p.add_argument('--pose_npy', default=None, metavar='PATH',
                    help='human_ml3d / kit_ml configs: also save the stitched, filtered joint positions [frames, J, 3] (tools/visualize.py:55-56)')
+    p.add_argument('--anim_dir', default=None, metavar='DIR',
+                   help='human_ml3d / kit_ml configs: draw the stitched, filtered joints as the skeleton animation of plot_3d_motion on the '
+                        'device and write frame_%%d.bmp there (+ an mp4 when ffmpeg is on PATH); no title, no anti-aliasing')
+    p.add_argument('--anim_size', default='1000x1000', metavar='WxH', help='frame size of --anim_dir (the reference: 1000x1000)')
+    p.add_argument('--anim_fps', type=float, default=20.0, help='frame rate of the mp4 of --anim_dir (the reference: 20)')
     p.add_argument('--smplx_model', default=None, metavar='PATH', help='motionx configs: the published SMPL-X model file (.npz)')
     p.add_argument('--joints_npy', default=None, metavar='PATH',
                    help='with --smplx_model: save the 55 SMPL-X joints [frames, 55, 3] of the stitched, filtered motion (tools/s2g_test.py:406)')
@@ -79,6 +85,14 @@ def main():
     if a.pose_npy and dims.get('dataset', 'motionx') == 'motionx':
         raise ValueError('--pose_npy saves joint positions recovered from human_ml3d / kit_ml features; a motionx config '
                          'writes the SMPL-X .npz instead')
+    if a.anim_dir and dims.get('dataset', 'motionx') == 'motionx':
+        raise ValueError('--anim_dir draws the skeleton of a human_ml3d / kit_ml sample; a motionx config renders the mesh with '
+                         '--smplx_model PATH --render_dir DIR')
+    anim_size = render.parse_size(a.anim_size, '--anim_size')
+    if max(anim_size) > skeleton.MAX_SIZE:
+        raise ValueError(f'--anim_size: at most {skeleton.MAX_SIZE} pixels a side, got {a.anim_size!r}')
+    if not a.anim_fps > 0:
+        raise ValueError(f'--anim_fps must be positive, got {a.anim_fps}')
     if (a.joints_npy or a.verts_npy or a.smplx_model) and dims.get('dataset', 'motionx') != 'motionx':
         raise ValueError('--smplx_model / --joints_npy / --verts_npy run the SMPL-X body model on a motionx sample; a human_ml3d / '
                          'kit_ml config saves joints with --pose_npy')
@@ -136,9 +150,16 @@ def main():
                 for o, m in zip(out, a.motion_length)]
         path = os.path.join(a.out, postprocess.result_name(a.text[0], a.motion_length[0]) + '.npy')
         np.save(path, np.concatenate(arrs, axis=0))
-        if a.pose_npy:
+        if a.pose_npy or a.anim_dir:
             pred = torch.stack([o['pred_motion'] for o in out]).to(dev).contiguous()
+        if a.pose_npy:
             postprocess.save_joints_npy(a.pose_npy, pred, a.motion_length, mean, std)
+        if a.anim_dir:
+            chains = skeleton.KIT_CHAINS if dims['input_feats'] == 251 else skeleton.T2M_CHAINS
+            renderer = skeleton.SkeletonRenderer(chains, width=anim_size[0], height=anim_size[1])
+            paths, mp4 = render.save_frames(postprocess.t2m_render(pred, a.motion_length, renderer, mean, std), a.anim_dir, a.anim_fps,
+                                            postprocess.result_name(a.text[0], a.motion_length[0]))
+            print(f'drew {len(paths)} frames -> {a.anim_dir}' + (f', {mp4}' if mp4 else ' (no ffmpeg on PATH: frames only)'))
     print(f'pred_motion: {n} x {T} x {C} -> {path}')
 
 
