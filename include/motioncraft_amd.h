@@ -309,6 +309,49 @@ int mc_op_body_attention(const float* mf_dev, int64_t ldmf, const float* qkv_dev
 int mc_op_temporal_attention(const float* mf_dev, const float* tf_dev, const float* mask_dev, float* yt_dev, int32_t b0, int32_t nb,
                              int32_t B, int32_t T, int32_t Nt, int32_t H, int32_t L, int32_t form, int32_t skip_text,
                              const int32_t* twin_flag_dev, void* stream);
+/* The kernels of the step-invariant encoders as context-free ops (text, evaluation, BiGRU and wav encoders): each calls the launcher
+ * its encoder calls, no other work.
+ * mc_op_enc_ln: y = LayerNorm_L(x) gamma + beta over `rows` rows of L floats (L % 4 == 0, L <= 4096), relu != 0: max(., 0) on the way
+ *   out; y == x is allowed.
+ * mc_op_enc_embed_tokens: x[r][:] = emb[clamp(ids[r], 0, vocab - 1)][:] + pos[r % S][:], d % 4 == 0.
+ * mc_op_enc_attention: softmax((q / 8) k^T) v per (sample, head) over qkv [B*S][3 d] = [q | k | v], head_dim 64 (d = 64 heads) -> out
+ *   [B*S][d].  valid: uint8 [B][S], 0 = the key is not attended (NULL: all are); causal != 0: key j > query i is not attended either.
+ *   A query left with no key gives a zero row.  `form` names the kernel; a form that does not exist for the arguments is MC_ERR_ARG,
+ *   never another form: SMALL needs valid == NULL and S <= 128. */
+enum { MC_ENC_ATTN_LAYER = 0,     /* what an encoder layer launches: SMALL where it exists, else STREAM */
+       MC_ENC_ATTN_SMALL = 1,     /* mha_small_k: one workgroup per (sample, head), all keys in LDS */
+       MC_ENC_ATTN_STREAM = 2 };  /* mha_masked_k: 16-query blocks, keys streamed 64 at a time with the running-max softmax */
+int mc_op_enc_ln(const float* x_dev, const float* gamma_dev, const float* beta_dev, float* y_dev, int64_t rows, int32_t L, float eps,
+                 int32_t relu, void* stream);
+int mc_op_enc_embed_tokens(const int32_t* ids_dev, const float* emb_dev, const float* pos_dev, float* x_dev, int64_t rows, int32_t S,
+                           int32_t d, int32_t vocab, void* stream);
+int mc_op_enc_attention(const float* qkv_dev, const uint8_t* valid_dev, float* out_dev, int32_t B, int32_t S, int32_t d, int32_t heads,
+                        int32_t causal, int32_t form, void* stream);
+/* The grouped / strided forms of the fp32 MFMA GEMM, mode 0 (plain) or 4 (encoder: rows of any alignment, table, duplicate rows):
+ *   C[g c_gstride + r ldc + n] = act(sum_k A[g a_gstride + r lda + k] W[g w_gstride + n ldw + k] + bias[g b_gstride + n]) + add[(r % add_mod)
+ *   ld_add + n] + R[g r_gstride + r ldr + n]   (act_after_res != 0: R inside the activation), r < M, n < N, k < K, g < groups;
+ * dup_rows != 0: row r + dup_rows of C receives the same values.  W rows are zero padded from K to the next multiple of 4 (ldw % 4 == 0);
+ * mode 0 needs K, lda % 4 == 0; add / dup_rows are mode 4 only and need 16-byte aligned output rows.  r_gstride < 0: c_gstride. */
+typedef struct mc_gemm_strided {
+    const float* a_dev; int64_t lda, a_gstride;
+    const float* w_dev; int64_t ldw, w_gstride;
+    const float* bias_dev; int64_t b_gstride;
+    float* c_dev; int64_t ldc, c_gstride;
+    const float* res_dev; int64_t ldr, r_gstride;
+    const float* add_dev; int64_t ld_add, dup_rows;
+    int32_t add_mod, act, act_after_res, M, N, K;
+} mc_gemm_strided;
+int mc_op_gemm_strided(int32_t mode, int32_t groups, const mc_gemm_strided* args, void* stream);
+/* recurrence steps [s0, s0 + steps) of a bidirectional GRU on h [B][2][H] in place (direction 1 visits t = len - 1 - s): gi [2][B*S][3H]
+ * = input products + b_ih (gate order r | z | n), whh [2][3H][H], bhh [2][3H]; sample b is updated at steps s < min(lens[b] / len_div, S).
+ * H % 4 == 0; scratch is allocated here; synchronises */
+int mc_op_bigru_steps(const float* gi_dev, const float* whh_dev, const float* bhh_dev, float* h_dev, const int32_t* lens_dev,
+                      int32_t len_div, int32_t B, int32_t S, int32_t H, int32_t s0, int32_t steps, void* stream);
+/* Conv1d(kernel 4, stride 2, padding 1) + LeakyReLU(slope) over channels-last frames x [B*T] rows of ldx floats (C used):
+ * w_tapmajor [O][4][Cp] (element (o, tap, c) = weight[o][c][tap], zero for c >= C; Cp % 4 == 0), y_padded [B][T1 + 2][O] with
+ * T1 = (T - 2) / 2 + 1 and rows 0 and T1 + 1 of every sample zero (the padded input of a next convolution); synchronises */
+int mc_op_conv1d_k4s2(const float* x_dev, int64_t ldx, const float* w_tapmajor_dev, const float* bias_dev, float* y_padded_dev, int32_t B,
+                      int32_t T, int32_t C, int32_t Cp, int32_t O, float slope, void* stream);
 int mc_op_sampler_update(const float* x_t_dev, const float* out_text_dev, const float* out_none_dev,
                          const float* noise_dev, float* x_prev_dev, float* x0_dev, int64_t n,
                          const mc_step_coefs* coefs, void* stream);

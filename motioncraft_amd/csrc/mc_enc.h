@@ -25,6 +25,11 @@ int mc_enc_ln(const float* X, const float* g, const float* b, float* Y, long row
 // X[r][:] = emb[ids[r]][:] + pos[r % S][:]
 int mc_enc_embed_tokens(const int* ids, const float* emb, const float* pos, float* X, long rows, int S, int d, int vocab,
                         hipStream_t s);
+// multi-head attention over qkv [B*S][3d] (q | k | v, head_dim 64) -> att [B*S][d]; valid: uint8 [B][S] key mask or nullptr.
+// form (MC_ENC_ATTN_*): LAYER = mha_small_k when there is no key mask and S <= 128, else the streaming mha_masked_k; SMALL / STREAM
+// name the kernel, and a form that does not exist for the arguments is MC_ERR_ARG.  A query with no usable key gives a zero row.
+int mc_enc_attention(const float* qkv, const uint8_t* valid, float* att, int B, int S, int d, int heads, int causal, int form,
+                     hipStream_t s);
 // one encoder layer over x [rows = B*S][d] in place; scratch: qkv [rows][3d], att [rows][d], y [rows][d], hid [rows][ff]
 //   post-LN (nn.TransformerEncoderLayer norm_first=False, DistilBERT): x = LN1(x + SA(x)); x = LN2(x + FF(x))
 //   pre-LN  (CLIP ResidualAttentionBlock):                              x = x + SA(LN1(x)); x = x + MLP(LN2(x))

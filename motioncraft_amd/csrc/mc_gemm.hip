@@ -1202,6 +1202,11 @@ int mc_launch_gemm(int mode, const GemmArgs& g0, int groups, int max_tiles, hipS
     int ntm = (mode == GM_EXP1 || mode == GM_EXP2) ? max_tiles : cdiv(g.M, BM);
     if (ntm <= 0 || ntn <= 0) return MC_OK;
     if (mode != GM_ENC) MC_REQUIRE(g.K % 4 == 0 && g.lda % 4 == 0 && g.ldw % 4 == 0, "gemm: K/lda/ldw must be multiples of 4");
+    // the row-periodic table and the duplicate rows exist in the vector epilogue only (gemm_k's `vec` condition)
+    if (mode == GM_ENC && (g.add || g.dup_rows))
+        MC_REQUIRE(g.N % 4 == 0 && g.ldc % 4 == 0 && g.c_col % 4 == 0 && g.c_gstride % 4 == 0 && (!g.add || g.ld_add % 4 == 0) &&
+                       (!g.R || (g.ldr % 4 == 0 && (g.r_gstride < 0 || g.r_gstride % 4 == 0))),
+                   "gemm: an add table or duplicate rows need 16-byte aligned output rows (N=%d ldc=%ld)", g.N, g.ldc);
     dim3 grid(ntm * ntn, groups > 0 ? groups : 1, 1);
     const bool vec_out = (g.ldc % 4 == 0) && (g.c_col % 4 == 0) && (!g.R || g.ldr % 4 == 0);
     // (GM_ENC with aligned operands -- the padded pose rows of the large-batch encoder -- is a plain GEMM + row-periodic table + duplicate

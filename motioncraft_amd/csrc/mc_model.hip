@@ -830,6 +830,23 @@ int mc_op_gemm(const float* a, const float* w, const float* bias, const float* r
     return dense(nullptr, a, K, w, ldw, bias, res, N, cdev, N, M, N, K, act, (hipStream_t)stream);
 }
 
+int mc_op_gemm_strided(int32_t mode, int32_t groups, const mc_gemm_strided* a, void* stream) {
+    MC_REQUIRE(a && (mode == GM_PLAIN || mode == GM_ENC) && groups >= 1, "gemm_strided: mode %d (0 plain, 4 encoder), groups %d", mode, groups);
+    MC_REQUIRE(a->a_dev && a->w_dev && a->c_dev && a->M > 0 && a->N > 0 && a->K > 0 && a->lda > 0 && a->ldc >= a->N && a->ldw >= a->K &&
+                   a->ldw % 4 == 0 && a->add_mod >= 1 && a->dup_rows >= 0 && (!a->res_dev || a->ldr >= a->N) && (!a->add_dev || a->ld_add >= a->N),
+               "bad gemm_strided args");
+    GemmArgs g;
+    g.A = a->a_dev; g.lda = a->lda; g.a_gstride = a->a_gstride;
+    g.W = a->w_dev; g.ldw = a->ldw; g.w_gstride = a->w_gstride;
+    g.bias = a->bias_dev; g.b_gstride = a->b_gstride;
+    g.C = a->c_dev; g.ldc = a->ldc; g.c_gstride = a->c_gstride;
+    g.R = a->res_dev; g.ldr = a->ldr; g.r_gstride = a->r_gstride;
+    g.act = a->act; g.act_after_res = a->act_after_res;
+    g.add = a->add_dev; g.add_mod = a->add_mod; g.ld_add = a->ld_add; g.dup_rows = a->dup_rows;
+    g.M = a->M; g.N = a->N; g.K = a->K;
+    return mc_launch_gemm(mode, g, groups, 0, (hipStream_t)stream);
+}
+
 // the two fp16 GEMM ops: `g` holds the A operand (fp32 rows or fp16 planes); the fp32 weight is split into temporary planes here
 static int gemm_f16_op(GemmHArgs g, const float* w, const float* bias, const float* res, float* cdev, int M, int N, int K, bool split, hipStream_t s) {
     mc_half* planes = nullptr;

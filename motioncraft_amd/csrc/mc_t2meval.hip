@@ -109,6 +109,22 @@ int bind_head(ParamStore& ps, const std::string& pre, int din, int hid, int dout
     return MC_OK;
 }
 
+// recurrence steps [s0, s0 + steps) of both directions on h [B][2][H] in place: per step one grouped [B, H] x [H, 3H] GEMM into the
+// scratch gh [B][2][3H] and the gate kernel.  whh [2][3H][H], bhh [2][3H]
+int bigru_steps(const float* gi, const float* whh, const float* bhh, float* h, float* gh, const int* lens, int len_div, int B, int S,
+                int H, int s0, int steps, hipStream_t s) {
+    int r;
+    GemmArgs q;                                        // gh[b][d] = h[b][d] W_hh[d]^T + b_hh[d]
+    q.A = h; q.lda = 2 * H; q.a_gstride = H; q.W = whh; q.ldw = H; q.w_gstride = (long)3 * H * H; q.bias = bhh; q.b_gstride = 3 * H;
+    q.C = gh; q.ldc = 6 * H; q.c_gstride = 3 * H; q.M = B; q.N = 3 * H; q.K = H;
+    for (int st = s0; st < s0 + steps; ++st) {
+        if ((r = mc_launch_gemm(GM_PLAIN, q, 2, 0, s))) return r;
+        hipLaunchKernelGGL(gru_gate_k, dim3(grid_for((long)B * 2 * H)), dim3(256), 0, s, gi, gh, h, lens, len_div, st, B, S, H);
+        MC_LAUNCH_CHECK();
+    }
+    return MC_OK;
+}
+
 // x [B*S][din] -> out [B][dout];  buf: emb [B*S][H] | gi [2][B*S][3H] | h [B][2H] | gh [B][6H] | y [B][H]
 int run_head(const Head& p, const float* x, const int* lens, int len_div, int B, int S, float* buf, float* out, hipStream_t s) {
     const int H = p.hid;
@@ -126,19 +142,34 @@ int run_head(const Head& p, const float* x, const int* lens, int len_div, int B,
     if ((r = mc_launch_gemm(GM_PLAIN, g, 2, 0, s))) return r;
     hipLaunchKernelGGL(gru_init_k, dim3(grid_for((long)B * 2 * H)), dim3(256), 0, s, p.hidden, h, B, H);
     MC_LAUNCH_CHECK();
-    GemmArgs q;                                        // gh[b][d] = h[b][d] W_hh[d]^T + b_hh[d]
-    q.A = h; q.lda = 2 * H; q.a_gstride = H; q.W = p.whh; q.ldw = H; q.w_gstride = (long)3 * H * H; q.bias = p.bhh; q.b_gstride = 3 * H;
-    q.C = gh; q.ldc = 6 * H; q.c_gstride = 3 * H; q.M = B; q.N = 3 * H; q.K = H;
-    for (int st = 0; st < S; ++st) {
-        if ((r = mc_launch_gemm(GM_PLAIN, q, 2, 0, s))) return r;
-        hipLaunchKernelGGL(gru_gate_k, dim3(grid_for((long)B * 2 * H)), dim3(256), 0, s, gi, gh, h, lens, len_div, st, B, S, H);
-        MC_LAUNCH_CHECK();
-    }
+    if ((r = bigru_steps(gi, p.whh, p.bhh, h, gh, lens, len_div, B, S, H, 0, S, s))) return r;
     if ((r = mc_enc_dense(h, 2 * H, p.o0_w, 2 * H, p.o0_b, nullptr, 0, y, H, B, H, 2 * H, ACT_NONE, s))) return r;
     if ((r = mc_enc_ln(y, p.ln_g, p.ln_b, y, B, H, 1e-5f, 0, s))) return r;
     hipLaunchKernelGGL(lrelu_k, dim3(grid_for((long)B * H)), dim3(256), 0, s, y, (long)B * H, 0.2f);
     MC_LAUNCH_CHECK();
     return mc_enc_dense(y, H, p.o3_w, H, p.o3_b, nullptr, 0, out, p.dout, B, p.dout, H, ACT_NONE, s);
+}
+
+// Conv1d(k = 4, s = 2, p = 1) + LeakyReLU(slope) over channels-last frames, T1 = (T - 2) / 2 + 1 outputs per sample.  xp != nullptr:
+// x [B*T] rows of ldx floats, of which C are copied into the zero-padded xp [B][T + 2][Cp] first; xp == nullptr: x is that padded
+// buffer already.  w tap-major [O][4][Cp].  pad_out: y is the padded input of a next convolution, [B][T1 + 2][O] with zero rows 0 and
+// T1 + 1 (LeakyReLU keeps zeros: it runs over the whole buffer); else y [B][T1][O].
+int conv_k4s2(const float* x, int ldx, int C, float* xp, const float* w, const float* bias, float* y, bool pad_out, int B, int T, int Cp,
+              int O, float slope, hipStream_t s) {
+    const int T1 = (T + 2 - 4) / 2 + 1;
+    if (xp) {
+        hipLaunchKernelGGL(pad_time_k, dim3(grid_for((long)B * (T + 2) * Cp)), dim3(256), 0, s, x, xp, B, T, C, ldx, Cp);
+        MC_LAUNCH_CHECK();
+    }
+    const long yrows = pad_out ? T1 + 2 : T1, n_y = (long)B * yrows * O;
+    if (pad_out) MC_HIP(hipMemsetAsync(y, 0, (size_t)n_y * sizeof(float), s));
+    GemmArgs g;
+    g.A = xp ? xp : x; g.lda = 2 * Cp; g.a_gstride = (long)(T + 2) * Cp; g.W = w; g.ldw = 4 * Cp; g.bias = bias;
+    g.C = pad_out ? y + O : y; g.ldc = O; g.c_gstride = yrows * O; g.M = T1; g.N = O; g.K = 4 * Cp;
+    if (int r = mc_launch_gemm(GM_PLAIN, g, B, 0, s)) return r;
+    hipLaunchKernelGGL(lrelu_k, dim3(grid_for(n_y)), dim3(256), 0, s, y, n_y, slope);
+    MC_LAUNCH_CHECK();
+    return MC_OK;
 }
 
 size_t head_floats(const Head& p, int B, int S) {
@@ -174,6 +205,33 @@ int mc_t2meval_create(const mc_t2meval_config* cfg, mc_t2meval** out) {
 }
 
 void mc_t2meval_destroy(mc_t2meval* e) { delete e; }
+
+int mc_op_bigru_steps(const float* gi, const float* whh, const float* bhh, float* h, const int32_t* lens, int32_t len_div, int32_t B,
+                      int32_t S, int32_t H, int32_t s0, int32_t steps, void* stream) {
+    MC_REQUIRE(gi && whh && bhh && h && lens && len_div >= 1 && B >= 1 && S >= 1 && H >= 4 && H % 4 == 0 && s0 >= 0 && steps >= 0,
+               "bad bigru_steps args");
+    hipStream_t s = (hipStream_t)stream;
+    float* gh = nullptr;
+    MC_HIP(hipMalloc((void**)&gh, sizeof(float) * (size_t)B * 6 * H));
+    const int r = bigru_steps(gi, whh, bhh, h, gh, lens, len_div, B, S, H, s0, steps, s);
+    (void)hipStreamSynchronize(s);
+    (void)hipFree(gh);
+    return r;
+}
+
+int mc_op_conv1d_k4s2(const float* x, int64_t ldx, const float* w_tapmajor, const float* bias, float* y_padded, int32_t B, int32_t T,
+                      int32_t C, int32_t Cp, int32_t O, float slope, void* stream) {
+    MC_REQUIRE(x && w_tapmajor && bias && y_padded && B >= 1 && T >= 2 && C >= 1 && ldx >= C && Cp >= C && Cp % 4 == 0 && O >= 4 &&
+                   O % 4 == 0,
+               "bad conv1d_k4s2 args");
+    hipStream_t s = (hipStream_t)stream;
+    float* xp = nullptr;
+    MC_HIP(hipMalloc((void**)&xp, sizeof(float) * (size_t)B * (T + 2) * Cp));
+    const int r = conv_k4s2(x, (int)ldx, C, xp, w_tapmajor, bias, y_padded, true, B, T, Cp, O, slope, s);
+    (void)hipStreamSynchronize(s);
+    (void)hipFree(xp);
+    return r;
+}
 
 int mc_t2meval_set_param(mc_t2meval* e, const char* name, const float* host, int64_t numel) {
     MC_REQUIRE(e && name && host && numel > 0, "bad argument");
@@ -242,22 +300,9 @@ int mc_t2meval_encode_motion(mc_t2meval* e, const float* motion, const int32_t* 
     float* c2 = pad2 + n_pad2;
     float* mov = c2 + n_c2;
     float* buf = mov + n_c2;
-    hipLaunchKernelGGL(pad_time_k, dim3(grid_for((long)B * (T + 2) * Cp)), dim3(256), 0, s, motion, pad1, B, T, C, c.input_size, Cp);
-    MC_LAUNCH_CHECK();
-    MC_HIP(hipMemsetAsync(pad2, 0, n_pad2 * sizeof(float), s));
-    GemmArgs g;                                        // conv 1 -> rows 1 .. T1 of the padded buffer of conv 2
-    g.A = pad1; g.lda = 2 * Cp; g.a_gstride = (long)(T + 2) * Cp; g.W = e->c1_w; g.ldw = 4 * Cp; g.bias = e->c1_b;
-    g.C = pad2 + Hm; g.ldc = Hm; g.c_gstride = (long)(T1 + 2) * Hm; g.M = T1; g.N = Hm; g.K = 4 * Cp;
-    if ((r = mc_launch_gemm(GM_PLAIN, g, B, 0, s))) return r;
-    // LeakyReLU(0.2) keeps zeros: applying it to the whole padded buffer leaves the pad rows zero
-    hipLaunchKernelGGL(lrelu_k, dim3(grid_for((long)n_pad2)), dim3(256), 0, s, pad2, (long)B * (T1 + 2) * Hm, 0.2f);
-    MC_LAUNCH_CHECK();
-    GemmArgs q;                                        // conv 2
-    q.A = pad2; q.lda = 2 * Hm; q.a_gstride = (long)(T1 + 2) * Hm; q.W = e->c2_w; q.ldw = 4 * Hm; q.bias = e->c2_b;
-    q.C = c2; q.ldc = Lm; q.c_gstride = (long)T2 * Lm; q.M = T2; q.N = Lm; q.K = 4 * Hm;
-    if ((r = mc_launch_gemm(GM_PLAIN, q, B, 0, s))) return r;
-    hipLaunchKernelGGL(lrelu_k, dim3(grid_for((long)n_c2)), dim3(256), 0, s, c2, (long)n_c2, 0.2f);
-    MC_LAUNCH_CHECK();
+    // conv 1 -> rows 1 .. T1 of the padded buffer of conv 2; conv 2 -> c2
+    if ((r = conv_k4s2(motion, c.input_size, C, pad1, e->c1_w, e->c1_b, pad2, true, B, T, Cp, Hm, 0.2f, s))) return r;
+    if ((r = conv_k4s2(pad2, Hm, Hm, nullptr, e->c2_w, e->c2_b, c2, false, B, T1, Hm, Lm, 0.2f, s))) return r;
     if ((r = mc_enc_dense(c2, Lm, e->mo_w, Lm, e->mo_b, nullptr, 0, mov, Lm, (long)B * T2, Lm, Lm, ACT_NONE, s))) return r;
     return run_head(e->motion, mov, lengths, 4, B, T2, buf, out, s);
 }

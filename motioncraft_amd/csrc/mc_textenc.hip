@@ -19,9 +19,9 @@
 namespace {
 
 // LayerNorm over rows of L floats (L % 4 == 0, L <= 4096): one wavefront per row, two-pass variance.
-__global__ __launch_bounds__(256) void ln_wide_k(const float* __restrict__ X, const float* __restrict__ gamma,
-                                                 const float* __restrict__ beta, float* __restrict__ Y, long rows, int L,
-                                                 float eps, int relu) {
+// X == Y is allowed (a wave reads its whole row before it writes it): neither is __restrict__.
+__global__ __launch_bounds__(256) void ln_wide_k(const float* X, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                 float* Y, long rows, int L, float eps, int relu) {
     const int lane = threadIdx.x & 63;
     const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= rows) return;
@@ -205,6 +205,29 @@ int mc_enc_embed_tokens(const int* ids, const float* emb, const float* pos, floa
     return MC_OK;
 }
 
+int mc_enc_attention(const float* qkv, const uint8_t* valid, float* att, int B, int S, int d, int heads, int causal, int form,
+                     hipStream_t s) {
+    MC_REQUIRE(B >= 1 && S >= 1 && heads >= 1 && d == heads * MHA_HD, "encoder attention: B=%d S=%d width %d with %d heads (head_dim must be %d)",
+               B, S, d, heads, MHA_HD);
+    MC_REQUIRE(form == MC_ENC_ATTN_LAYER || form == MC_ENC_ATTN_SMALL || form == MC_ENC_ATTN_STREAM,
+               "encoder attention: form %d (0 the layer's rule, 1 SMALL, 2 STREAM)", form);
+    const bool small_ok = valid == nullptr && S <= MHA_S;
+    MC_REQUIRE(form != MC_ENC_ATTN_SMALL || small_ok, "encoder attention form SMALL: no key mask and S <= %d (S=%d%s)", MHA_S, S,
+               valid ? ", key mask" : "");
+    const double flops = 4.0 * S * S * MHA_HD * B * heads * (causal ? 0.5 : 1.0);
+    if (form == MC_ENC_ATTN_SMALL || (form == MC_ENC_ATTN_LAYER && small_ok)) {
+        const dim3 grid(B * heads);
+        MC_LEDGER("mha_small_k", grid, flops);
+        hipLaunchKernelGGL(mha_small_k, grid, dim3(256), 0, s, qkv, att, S, d, heads, causal);
+    } else {
+        const dim3 grid(B * heads, cdiv(S, MHA_QB));
+        MC_LEDGER("mha_masked_k", grid, flops);
+        hipLaunchKernelGGL(mha_masked_k, grid, dim3(256), 0, s, qkv, valid, att, S, d, heads, causal);
+    }
+    MC_LAUNCH_CHECK();
+    return MC_OK;
+}
+
 int mc_enc_layer(const EncLayer& p, float* x, float* qkv, float* att, float* y, float* hid, long rows, int B, int S, int d,
                  int heads, int ff, bool pre_ln, int act, int causal, const uint8_t* valid, float eps, hipStream_t s) {
     MC_REQUIRE(d == heads * MHA_HD, "encoder layer: width %d with %d heads (head_dim must be %d)", d, heads, MHA_HD);
@@ -215,11 +238,7 @@ int mc_enc_layer(const EncLayer& p, float* x, float* qkv, float* att, float* y, 
         src = y;
     }
     if ((r = mc_enc_dense(src, d, p.in_w, d, p.in_b, nullptr, 0, qkv, 3 * d, rows, 3 * d, d, ACT_NONE, s))) return r;
-    if (valid == nullptr && S <= MHA_S)
-        hipLaunchKernelGGL(mha_small_k, dim3(B * heads), dim3(256), 0, s, qkv, att, S, d, heads, causal);
-    else
-        hipLaunchKernelGGL(mha_masked_k, dim3(B * heads, cdiv(S, MHA_QB)), dim3(256), 0, s, qkv, valid, att, S, d, heads, causal);
-    MC_LAUNCH_CHECK();
+    if ((r = mc_enc_attention(qkv, valid, att, B, S, d, heads, causal, MC_ENC_ATTN_LAYER, s))) return r;
     if (pre_ln) {
         if ((r = mc_enc_dense(att, d, p.out_w, d, p.out_b, x, d, x, d, rows, d, d, ACT_NONE, s))) return r;   // x += out_proj(att)
         if ((r = mc_enc_ln(x, p.n2_g, p.n2_b, y, rows, d, eps, 0, s))) return r;
@@ -297,6 +316,24 @@ int mc_textenc_create(const mc_textenc_config* cfg, mc_textenc** out) {
 }
 
 void mc_textenc_destroy(mc_textenc* e) { delete e; }
+
+int mc_op_enc_ln(const float* x, const float* gamma, const float* beta, float* y, int64_t rows, int32_t L, float eps, int32_t relu,
+                 void* stream) {
+    MC_REQUIRE(x && gamma && beta && y && rows >= 1 && L >= 4 && L <= 4096, "bad enc_ln args");
+    return mc_enc_ln(x, gamma, beta, y, rows, L, eps, relu, (hipStream_t)stream);
+}
+
+int mc_op_enc_embed_tokens(const int32_t* ids, const float* emb, const float* pos, float* x, int64_t rows, int32_t S, int32_t d,
+                           int32_t vocab, void* stream) {
+    MC_REQUIRE(ids && emb && pos && x && rows >= 1 && S >= 1 && d >= 4 && vocab >= 1, "bad enc_embed_tokens args");
+    return mc_enc_embed_tokens(ids, emb, pos, x, rows, S, d, vocab, (hipStream_t)stream);
+}
+
+int mc_op_enc_attention(const float* qkv, const uint8_t* valid, float* out, int32_t B, int32_t S, int32_t d, int32_t heads,
+                        int32_t causal, int32_t form, void* stream) {
+    MC_REQUIRE(qkv && out, "bad enc_attention args");
+    return mc_enc_attention(qkv, valid, out, B, S, d, heads, causal != 0, form, (hipStream_t)stream);
+}
 
 int mc_textenc_set_param(mc_textenc* e, const char* name, const float* host, int64_t numel) {
     MC_REQUIRE(e && name && host && numel > 0, "bad argument");

@@ -32,6 +32,21 @@ class StepCoefs(ctypes.Structure):
 
 
 _P = ctypes.c_void_p
+ENC_ATTN_FORMS = dict(layer=0, small=1, stream=2)       # MC_ENC_ATTN_* (mc_op_enc_attention's form)
+GM_PLAIN, GM_ENC = 0, 4                                 # mc_op_gemm_strided's mode
+
+
+class GemmStrided(ctypes.Structure):
+    """mc_gemm_strided (include/motioncraft_amd.h): operands, strides and epilogue of one grouped GEMM launch."""
+    _fields_ = [('a_dev', _P), ('lda', ctypes.c_int64), ('a_gstride', ctypes.c_int64),
+                ('w_dev', _P), ('ldw', ctypes.c_int64), ('w_gstride', ctypes.c_int64),
+                ('bias_dev', _P), ('b_gstride', ctypes.c_int64),
+                ('c_dev', _P), ('ldc', ctypes.c_int64), ('c_gstride', ctypes.c_int64),
+                ('res_dev', _P), ('ldr', ctypes.c_int64), ('r_gstride', ctypes.c_int64),
+                ('add_dev', _P), ('ld_add', ctypes.c_int64), ('dup_rows', ctypes.c_int64)] + [
+        (n, ctypes.c_int32) for n in ('add_mod', 'act', 'act_after_res', 'M', 'N', 'K')]
+
+
 class Inpaint(ctypes.Structure):
     """mc_inpaint (include/motioncraft_amd.h): model_kwargs['y'] operands of one RePaint step."""
     _fields_ = [('gt_dev', ctypes.c_void_p), ('keep_dev', ctypes.c_void_p), ('gt_noise_dev', ctypes.c_void_p),
@@ -128,6 +143,15 @@ _SIGNATURES = {
                                             _P, ctypes.c_int64, _P]),
     'mc_op_temporal_attention': (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                                 ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P]),
+    'mc_op_enc_ln': (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_int64, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, _P]),
+    'mc_op_enc_embed_tokens': (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P]),
+    'mc_op_enc_attention': (ctypes.c_int, [_P, _P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                           ctypes.c_int32, _P]),
+    'mc_op_gemm_strided': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(GemmStrided), _P]),
+    'mc_op_bigru_steps': (ctypes.c_int, [_P, _P, _P, _P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                         ctypes.c_int32, _P]),
+    'mc_op_conv1d_k4s2': (ctypes.c_int, [_P, ctypes.c_int64, _P, _P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                         ctypes.c_int32, ctypes.c_float, _P]),
     'mc_op_sampler_update': (ctypes.c_int, [_P, _P, _P, _P, _P, _P, ctypes.c_int64, ctypes.POINTER(StepCoefs), _P]),
     'mc_postprocess_smplx': (ctypes.c_int, [_P, _P, _P, _P, _P, ctypes.POINTER(ctypes.c_int32 * 4), ctypes.c_int32,
                                             ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P]),
