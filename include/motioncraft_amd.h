@@ -37,6 +37,8 @@
  *                                                                      dataloaders/beat_sep_lower.py:392-393; tools/s2g_test.py:416-417
  *   mc_render_*           the frames fast_render.generate_silent_videos* draws (orthographic rasteriser; own shading model)
  *                                                                      mogen/datasets/EMAGE_2024/utils/fast_render.py:13-81; other_tools.py:695-765
+ *   mc_mjpeg_*            convert_img_to_mp4 / add_audio_to_video: frames -> one video file (baseline JPEG on the device, for a Motion-JPEG AVI)
+ *                                                                      mogen/datasets/EMAGE_2024/utils/media.py:4-33
  *   mc_op_renoise         GaussianDiffusion._undo (resampling jumps)   gaussian_diffusion.py:429-435, 1113-1118
  *
  * Conventions: plain pointers and sizes only.  `*_dev` pointers are device (HBM) addresses owned
@@ -719,6 +721,30 @@ int64_t mc_skeleton_work_bytes(const mc_skeleton* h, int32_t n_frames, int32_t m
 int mc_skeleton_frames(mc_skeleton* h, const float* joints_dev, const int32_t* seq_start_host, int32_t num_seqs, const mc_skeleton_params* p,
                        void* work_dev, int64_t work_bytes, uint8_t* rgb_out_dev, uint8_t* layer_out_dev, int32_t* screen_out_dev,
                        int32_t* trail_screen_out_dev, float* stats_out_dev, float* traj_out_dev, void* stream);
+
+/* ---- Baseline JPEG encoder: the uint8 RGB frames the two rasterisers write -> one complete JFIF file per frame, back to back in a
+ * device byte buffer, for a Motion-JPEG AVI (video.AviWriter) in place of the reference's ffmpeg child processes
+ * (mogen/datasets/EMAGE_2024/utils/media.py:4-33).  SOF0, 8 bit, Y / Cb / Cr, 4:2:0 or 4:4:4, the Annex K quantisation tables under the
+ * IJG quality rule, the Annex K Huffman tables in every frame, one restart interval per MCU row (DRI; RST(row mod 8) between rows), edges
+ * replicated up to the MCU.  The arithmetic is integer only and defined in the header comment of csrc/mc_mjpeg.hip (fixed-point JFIF
+ * colour matrix, 2x2 chroma mean, a two-pass integer DCT, round-half-away quantisation), restated in tests/jpeg_ref.py: the byte stream
+ * is a definition.  Frames run in chunks of as many as work_dev holds; the result does not depend on the chunk size. */
+#define MC_MJPEG_420 0
+#define MC_MJPEG_444 1
+typedef struct mc_mjpeg mc_mjpeg;
+/* width, height 1..16384; quality 1..100 */
+int mc_mjpeg_create(int32_t width, int32_t height, int32_t quality, int32_t subsampling, mc_mjpeg** out);
+void mc_mjpeg_destroy(mc_mjpeg* h);
+/* scratch that holds `frames` frames at once; -1: bad argument */
+int64_t mc_mjpeg_work_bytes(const mc_mjpeg* h, int32_t frames);
+/* a true upper bound of the bytes `frames` frames encode to, whatever their content: per frame the header and, per restart interval,
+ * 2 * 208 bytes per block (1660 bits at most, every byte stuffed) and its 2-byte marker; -1: bad argument */
+int64_t mc_mjpeg_max_bytes(const mc_mjpeg* h, int32_t frames);
+/* rgb_dev uint8 [n,H,W,3] -> out_dev: frame i is the bytes offsets_dev[i] .. offsets_dev[i + 1] (int64 [n + 1], offsets_dev[0] = 0).
+ * work_dev: 256-byte aligned, at least mc_mjpeg_work_bytes(h, 1); its contents need not be kept.  Returns an error and launches nothing
+ * when work_bytes is below that, or when out_capacity is below mc_mjpeg_max_bytes(h, n): nothing is sized by a typical ratio. */
+int mc_mjpeg_encode(mc_mjpeg* h, const uint8_t* rgb_dev, int32_t n, void* work_dev, int64_t work_bytes, uint8_t* out_dev, int64_t out_capacity,
+                    int64_t* offsets_dev, void* stream);
 
 /* out = a * x + b * noise over n elements (out may alias x) */
 int mc_op_renoise(const float* x_dev, const float* noise_dev, float a, float b, float* out_dev, int64_t n, void* stream);

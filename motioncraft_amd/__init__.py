@@ -15,9 +15,11 @@ from . import render
 from .render import DirectionalLight, MeshRenderer, OrthographicCamera
 from . import skeleton
 from .skeleton import KIT_CHAINS, T2M_CHAINS, Mplot3dCamera, SkeletonRenderer
+from . import video
+from .video import AviWriter, JpegEncoder, save_avi
 from . import speech
 from .speech import AudioCondition, sample_speech, speech_frames, speech_prompt
 
-__all__ = ['skeleton', 'KIT_CHAINS', 'T2M_CHAINS', 'Mplot3dCamera', 'SkeletonRenderer', 'render', 'DirectionalLight', 'MeshRenderer', 'OrthographicCamera', 'audio', 'Resampler', 'load_wav', 'AudioCondition', 'sample_speech', 'speech', 'speech_frames', 'speech_prompt', 'BeatAlignment', 'M2DScorer', 'OnsetDetector', 'S2GScorer', 'face_errors', 'scoring','ARCHITECTURES', 'ATTENTIONS', 'LOSSES', 'MODELS', 'SUBMODULES', 'build_architecture',
+__all__ = ['video', 'AviWriter', 'JpegEncoder', 'save_avi', 'skeleton', 'KIT_CHAINS', 'T2M_CHAINS', 'Mplot3dCamera', 'SkeletonRenderer', 'render', 'DirectionalLight', 'MeshRenderer', 'OrthographicCamera', 'audio', 'Resampler', 'load_wav', 'AudioCondition', 'sample_speech', 'speech', 'speech_frames', 'speech_prompt', 'BeatAlignment', 'M2DScorer', 'OnsetDetector', 'S2GScorer', 'face_errors', 'scoring','ARCHITECTURES', 'ATTENTIONS', 'LOSSES', 'MODELS', 'SUBMODULES', 'build_architecture',
            'build_attention', 'build_loss', 'build_submodule', 'Config', 'ConfigDict', 'Registry', 'build_from_cfg', 'ControlT2MHalf',
            'load_checkpoint', 'wrap_fp16_model']

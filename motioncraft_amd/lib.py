@@ -200,6 +200,11 @@ _SIGNATURES = {
     'mc_skeleton_destroy': (None, [_P]),
     'mc_skeleton_work_bytes': (ctypes.c_int64, [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
     'mc_skeleton_frames': (ctypes.c_int, [_P, _P, _P, ctypes.c_int32, ctypes.POINTER(SkeletonParams), _P, ctypes.c_int64, _P, _P, _P, _P, _P, _P, _P]),
+    'mc_mjpeg_create': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_P)]),
+    'mc_mjpeg_destroy': (None, [_P]),
+    'mc_mjpeg_work_bytes': (ctypes.c_int64, [_P, ctypes.c_int32]),
+    'mc_mjpeg_max_bytes': (ctypes.c_int64, [_P, ctypes.c_int32]),
+    'mc_mjpeg_encode': (ctypes.c_int, [_P, _P, ctypes.c_int32, _P, ctypes.c_int64, _P, ctypes.c_int64, _P, _P]),
     'mc_op_renoise': (ctypes.c_int, [_P, _P, ctypes.c_float, ctypes.c_float, _P, ctypes.c_int64, _P]),
     'mc_debug_flop_ledger': (ctypes.c_int, [ctypes.c_int32]),
     'mc_debug_flop_ledger_dump': (ctypes.c_int64, [ctypes.c_char_p, ctypes.c_int64]),

@@ -5,8 +5,9 @@ positions with --pose_npy), everything between the condition features and the fi
 
     python tools/sample.py CONFIG CHECKPOINT --text "a person walks" --motion_length 120 --out ./samples \\
         [--clip_feat feats.npy | --xf_out xf.npy | --random-condition SEED]  [--mean mean.npy --std std.npy]  [--pose_npy joints.npy]
-        [--anim_dir frames/ [--anim_size 1000x1000] [--anim_fps 20]]
-        [--smplx_model SMPLX_NEUTRAL.npz --joints_npy joints.npy [--verts_npy verts.npy] [--render_dir frames/ [--render_size 960x720]]]
+        [--anim_dir frames/ | --anim_avi clip.avi [--anim_size 1000x1000] [--anim_fps 20]]
+        [--smplx_model SMPLX_NEUTRAL.npz --joints_npy joints.npy [--verts_npy verts.npy] [--render_dir frames/ | --render_avi clip.avi [--render_size 960x720]]]
+        [--avi_quality 90]
 
 The CLIP tokenizer is not available offline: prompts only name the output file unless the `clip` package is importable
 (then they are tokenized and encoded by the device CLIP tower when the checkpoint carries clip.* weights).
@@ -23,7 +24,7 @@ ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
 sys.path.insert(0, ROOT)
 
 import motioncraft_amd as mc                                    # noqa: E402
-from motioncraft_amd import postprocess, render, skeleton, synthetic   # noqa: E402
+from motioncraft_amd import postprocess, render, skeleton, synthetic, video   # noqa: E402
 from motioncraft_amd.checkpoint import load_checkpoint          # noqa: E402
 
 
@@ -50,6 +51,11 @@ def parse_args():
                         '(+ an mp4 when ffmpeg is on PATH); the reference scene of fast_render.py, colours not pinned to pyrender')
     p.add_argument('--render_size', default='960x720', metavar='WxH', help='frame size of --render_dir (the reference: 960x720)')
     p.add_argument('--render_fps', type=float, default=30.0, help='frame rate of the mp4 of --render_dir')
+    p.add_argument('--render_avi', default=None, metavar='FILE',
+                   help='with --smplx_model: encode the rendered frames on the device into one Motion-JPEG AVI (no --render_dir needed)')
+    p.add_argument('--anim_avi', default=None, metavar='FILE',
+                   help='human_ml3d / kit_ml configs: encode the skeleton animation on the device into one Motion-JPEG AVI (no --anim_dir needed)')
+    p.add_argument('--avi_quality', type=int, default=90, metavar='N', help='JPEG quality of --render_avi / --anim_avi, 1..100')
     p.add_argument('--clip_feat', help='.npy [n,77,512] CLIP text features (ln_final output)')
     p.add_argument('--xf_out', help='.npy [n,77,text_latent_dim] frozen condition embedding')
     p.add_argument('--random-condition', type=int, default=None, metavar='SEED')
@@ -85,8 +91,8 @@ def main():
     if a.pose_npy and dims.get('dataset', 'motionx') == 'motionx':
         raise ValueError('--pose_npy saves joint positions recovered from human_ml3d / kit_ml features; a motionx config '
                          'writes the SMPL-X .npz instead')
-    if a.anim_dir and dims.get('dataset', 'motionx') == 'motionx':
-        raise ValueError('--anim_dir draws the skeleton of a human_ml3d / kit_ml sample; a motionx config renders the mesh with '
+    if (a.anim_dir or a.anim_avi) and dims.get('dataset', 'motionx') == 'motionx':
+        raise ValueError('--anim_dir / --anim_avi draw the skeleton of a human_ml3d / kit_ml sample; a motionx config renders the mesh with '
                          '--smplx_model PATH --render_dir DIR')
     anim_size = render.parse_size(a.anim_size, '--anim_size')
     if max(anim_size) > skeleton.MAX_SIZE:
@@ -96,11 +102,13 @@ def main():
     if (a.joints_npy or a.verts_npy or a.smplx_model) and dims.get('dataset', 'motionx') != 'motionx':
         raise ValueError('--smplx_model / --joints_npy / --verts_npy run the SMPL-X body model on a motionx sample; a human_ml3d / '
                          'kit_ml config saves joints with --pose_npy')
-    if (a.joints_npy or a.verts_npy or a.render_dir) and not a.smplx_model:
-        raise ValueError('--joints_npy / --verts_npy / --render_dir need the body model file: --smplx_model PATH')
-    if a.smplx_model and not (a.joints_npy or a.verts_npy or a.render_dir):
-        raise ValueError('--smplx_model alone writes nothing: name an output with --joints_npy PATH, --verts_npy PATH and / or '
-                         '--render_dir DIR')
+    if (a.joints_npy or a.verts_npy or a.render_dir or a.render_avi) and not a.smplx_model:
+        raise ValueError('--joints_npy / --verts_npy / --render_dir / --render_avi need the body model file: --smplx_model PATH')
+    if a.smplx_model and not (a.joints_npy or a.verts_npy or a.render_dir or a.render_avi):
+        raise ValueError('--smplx_model alone writes nothing: name an output with --joints_npy PATH, --verts_npy PATH, '
+                         '--render_dir DIR and / or --render_avi FILE')
+    if not 1 <= a.avi_quality <= 100:
+        raise ValueError(f'--avi_quality must be in 1..100, got {a.avi_quality}')
     render_size = render.parse_size(a.render_size)
     if not a.render_fps > 0:
         raise ValueError(f'--render_fps must be positive, got {a.render_fps}')
@@ -138,28 +146,36 @@ def main():
                 np.save(a.joints_npy, postprocess.smplx_joints(post, body).cpu().numpy())
             if a.verts_npy:
                 np.save(a.verts_npy, postprocess.smplx_vertices(post, body).cpu().numpy())
-            if a.render_dir:
+            if a.render_dir or a.render_avi:
                 if body.faces.shape[0] == 0:
                     raise ValueError(f'{a.smplx_model} holds no faces (key f): nothing to draw')
                 renderer = render.MeshRenderer(body.faces, body.num_vertices, width=render_size[0], height=render_size[1])
-                paths, mp4 = render.save_frames(postprocess.smplx_render(post, body, renderer), a.render_dir, a.render_fps,
-                                                postprocess.result_name(a.text[0], a.motion_length[0]))
-                print(f'rendered {len(paths)} frames -> {a.render_dir}' + (f', {mp4}' if mp4 else ' (no ffmpeg on PATH: frames only)'))
+                frames = postprocess.smplx_render(post, body, renderer)
+                if a.render_dir:
+                    paths, mp4 = render.save_frames(frames, a.render_dir, a.render_fps, postprocess.result_name(a.text[0], a.motion_length[0]))
+                    print(f'rendered {len(paths)} frames -> {a.render_dir}' + (f', {mp4}' if mp4 else ' (no ffmpeg on PATH: frames only)'))
+                if a.render_avi:
+                    size = video.save_avi(frames, a.render_avi, a.render_fps, quality=a.avi_quality)
+                    print(f'rendered {frames.shape[0]} frames -> {a.render_avi} ({size} bytes)')
     else:
         arrs = [o['pred_motion'][:m].numpy() * (std if std is not None else 1.0) + (mean if mean is not None else 0.0)
                 for o, m in zip(out, a.motion_length)]
         path = os.path.join(a.out, postprocess.result_name(a.text[0], a.motion_length[0]) + '.npy')
         np.save(path, np.concatenate(arrs, axis=0))
-        if a.pose_npy or a.anim_dir:
+        if a.pose_npy or a.anim_dir or a.anim_avi:
             pred = torch.stack([o['pred_motion'] for o in out]).to(dev).contiguous()
         if a.pose_npy:
             postprocess.save_joints_npy(a.pose_npy, pred, a.motion_length, mean, std)
-        if a.anim_dir:
+        if a.anim_dir or a.anim_avi:
             chains = skeleton.KIT_CHAINS if dims['input_feats'] == 251 else skeleton.T2M_CHAINS
             renderer = skeleton.SkeletonRenderer(chains, width=anim_size[0], height=anim_size[1])
-            paths, mp4 = render.save_frames(postprocess.t2m_render(pred, a.motion_length, renderer, mean, std), a.anim_dir, a.anim_fps,
-                                            postprocess.result_name(a.text[0], a.motion_length[0]))
-            print(f'drew {len(paths)} frames -> {a.anim_dir}' + (f', {mp4}' if mp4 else ' (no ffmpeg on PATH: frames only)'))
+            frames = postprocess.t2m_render(pred, a.motion_length, renderer, mean, std)
+            if a.anim_dir:
+                paths, mp4 = render.save_frames(frames, a.anim_dir, a.anim_fps, postprocess.result_name(a.text[0], a.motion_length[0]))
+                print(f'drew {len(paths)} frames -> {a.anim_dir}' + (f', {mp4}' if mp4 else ' (no ffmpeg on PATH: frames only)'))
+            if a.anim_avi:
+                size = video.save_avi(frames, a.anim_avi, a.anim_fps, quality=a.avi_quality)
+                print(f'drew {frames.shape[0]} frames -> {a.anim_avi} ({size} bytes)')
     print(f'pred_motion: {n} x {T} x {C} -> {path}')
 
 
