@@ -264,6 +264,8 @@ int mc_debug_flop_ledger(int32_t enable);
 int64_t mc_debug_flop_ledger_dump(char* buf, int64_t cap);
 
 /* op-level entry points (kernel parity tests call these through the same ABI) */
+/* the activation an `act` argument or field names; LRELU: nn.LeakyReLU() slope 0.01; QUICKGELU: x sigmoid(1.702 x) (CLIP) */
+enum { MC_ACT_NONE = 0, MC_ACT_GELU = 1, MC_ACT_SILU = 2, MC_ACT_LRELU = 3, MC_ACT_QUICKGELU = 4 };
 int mc_op_gemm(const float* a_dev, const float* w_dev, const float* bias_dev, const float* res_dev,
                float* c_dev, int32_t M, int32_t N, int32_t K, int32_t ldw, int32_t act, void* stream);
 /* C = A W^T + bias + res on the fp16 MFMA (split != 0: hi/lo three-product form); N % 128 == 0, K % 32 == 0; synchronises */
@@ -329,11 +331,12 @@ int mc_op_enc_embed_tokens(const int32_t* ids_dev, const float* emb_dev, const f
                            int32_t d, int32_t vocab, void* stream);
 int mc_op_enc_attention(const float* qkv_dev, const uint8_t* valid_dev, float* out_dev, int32_t B, int32_t S, int32_t d, int32_t heads,
                         int32_t causal, int32_t form, void* stream);
-/* The grouped / strided forms of the fp32 MFMA GEMM, mode 0 (plain) or 4 (encoder: rows of any alignment, table, duplicate rows):
+/* The grouped / strided forms of the fp32 MFMA GEMM, mode MC_GM_PLAIN or MC_GM_ENC (encoder: rows of any alignment, table, duplicate rows):
  *   C[g c_gstride + r ldc + n] = act(sum_k A[g a_gstride + r lda + k] W[g w_gstride + n ldw + k] + bias[g b_gstride + n]) + add[(r % add_mod)
  *   ld_add + n] + R[g r_gstride + r ldr + n]   (act_after_res != 0: R inside the activation), r < M, n < N, k < K, g < groups;
  * dup_rows != 0: row r + dup_rows of C receives the same values.  W rows are zero padded from K to the next multiple of 4 (ldw % 4 == 0);
- * mode 0 needs K, lda % 4 == 0; add / dup_rows are mode 4 only and need 16-byte aligned output rows.  r_gstride < 0: c_gstride. */
+ * MC_GM_PLAIN needs K, lda % 4 == 0; add / dup_rows are MC_GM_ENC only and need 16-byte aligned output rows.  r_gstride < 0: c_gstride. */
+enum { MC_GM_PLAIN = 0, MC_GM_ENC = 4 };
 typedef struct mc_gemm_strided {
     const float* a_dev; int64_t lda, a_gstride;
     const float* w_dev; int64_t ldw, w_gstride;
@@ -560,14 +563,16 @@ int mc_smplx_vertex_errors(mc_smplx* m, const double* poses_a_dev, const double*
  * mask_out_dev uint8 [num_joints, t_end - t_start].  speed = |velocity| / mean_vel with forward / central / backward
  * differences in fp32 (dt = 1 / pose_fps rounded to fp32, sqrt((x x + y y) + z z), no fused multiply-add: numpy on fp32 joints),
  * the division in fp32 when mean_vel_fp32 is set (the values are then fp32 numbers held as doubles) and in fp64 otherwise.
- * Over s = speed[t_start:t_end, j], index i is a beat iff s[i] < s[clip(i +- k, 0, n - 1)] for every k = 1..order (1..64;
+ * Over s = speed[t_start:t_end, j], index i is a beat iff s[i] < s[clip(i +- k, 0, n - 1)] for every k = 1..order (1..MC_BEAT_MAX_ORDER;
  * scipy.signal.argrelextrema(np.less, mode='clip')) and speed[i, j] > threshold, where i is slice-relative but looked up in the
  * unsliced array, like metric.py:113-123. */
+#define MC_BEAT_MAX_ORDER 64
+#define MC_BEAT_MAX_UPPER 64
 int mc_beat_mask(const float* joints_dev, int32_t n_frames, int32_t num_joints, const double* mean_vel_dev, int32_t mean_vel_fp32,
                  int32_t t_start, int32_t t_end, double pose_fps, int32_t order, double threshold, uint8_t* mask_out_dev, void* stream);
 /* bytes of workspace of mc_beat_align (-1: bad argument) */
 int64_t mc_beat_align_work_bytes(int32_t n_slice, int32_t n_upper);
-/* mask_dev [num_joints, n_slice] as written by mc_beat_mask, upper_body_host: n_upper (1..64) joint indices in HOST memory,
+/* mask_dev [num_joints, n_slice] as written by mc_beat_mask, upper_body_host: n_upper (1..MC_BEAT_MAX_UPPER) joint indices in HOST memory,
  * onsets_dev fp64 [n_onsets] seconds (n_onsets >= 1) -> score_out_dev fp64 [1]: the mean over the upper-body joints of the mean
  * over onsets of exp(-d^2 / (2 sigma^2)), d = |onset - nearest beat time i / pose_fps| (GAHR, metric.py:204-216); a joint
  * without beats contributes 0.  Fixed-order fp64 sums, no atomics: two runs give the same bits.  work_dev 8-byte aligned. */
@@ -576,7 +581,8 @@ int mc_beat_align(const uint8_t* mask_dev, int32_t num_joints, int32_t n_slice, 
                   double* score_out_dev, void* stream);
 
 /* ---- Audio onset detection (alignment.load_audio, metric.py:64-76: librosa 0.10.1's onset.onset_detect with its defaults,
- * restated in tests/onset_ref.py).  n_fft is 2048; hop a multiple of 4 in 4..512; n_mels 1..128; at most 2^20 frames.
+ * restated in tests/onset_ref.py).  n_fft is MC_ONSET_N_FFT; hop a multiple of 4 in 4..MC_ONSET_MAX_HOP; n_mels 1..MC_ONSET_MAX_MELS; at most
+ * 2^20 frames.
  * mc_onset_strength: wave_dev fp32 [n_samples] (finite) -> env_out_dev fp32 [F], F = 1 + n_samples / hop, the UN-normalised
  * onset envelope: frames centred on f hop with zeros outside the clip, power spectrum, mel projection, 10 log10(max(1e-10, .)),
  * the clamp at (maximum over the whole spectrogram) - 80, then env[j] = mean over the mel rows of max(0, S[j-lag+1] - S[j-lag]),
@@ -590,6 +596,9 @@ int mc_beat_align(const uint8_t* mask_dev, int32_t num_joints, int32_t n_slice, 
  * Frame n is an onset iff env[n] >= every value of [n - pre_max, n + post_max), env[n] >= the mean of [n - pre_avg, n + post_avg)
  * + delta, env[n] > 0 and n > the last accepted onset + wait, left to right; the windows are truncated at both ends of the array
  * (librosa.util.peak_pick; post_max and post_avg count the frame itself, so they are >= 1). */
+#define MC_ONSET_N_FFT 2048
+#define MC_ONSET_MAX_HOP 512
+#define MC_ONSET_MAX_MELS 128
 int64_t mc_onset_work_bytes(int64_t n_samples, int32_t n_fft, int32_t hop, int32_t n_mels);
 int mc_onset_strength(const float* wave_dev, int64_t n_samples, const float* dft_dev, const float* mel_dev, int32_t n_fft, int32_t hop,
                       int32_t n_mels, void* work_dev, int64_t work_bytes, float* env_out_dev, void* stream);
@@ -603,8 +612,11 @@ int mc_onset_pick(const float* env_dev, int32_t n_frames, int32_t pre_max, int32
  *   out[i][1] = 1 if i < n_frames and onset_mask_dev[i], else 0: onset_mask_dev uint8 [n_frames] is the mask mc_onset_pick writes, one
  *               byte per onset FRAME, and the reference writes those frame indices into this sample-indexed column as they are
  *               (onset_array[audio_onset_f] = 1.0) -- kept.  onset_mask_dev may be NULL: a column of zeros.
- * window 1..1024 (the reference: 1024) and <= n_samples; n_frames <= n_samples.  One launch, no workspace, no atomics; a maximum
- * of magnitudes has no rounding, so the result is exact and two runs give the same bits. */
+ * window 1..MC_AUDIO_COND_MAX_WINDOW (the reference: 1024) and <= n_samples; n_frames <= n_samples.  One launch, a workgroup per
+ * MC_AUDIO_COND_TILE output samples, no workspace, no atomics; a maximum of magnitudes has no rounding, so the result is exact and two runs
+ * give the same bits. */
+#define MC_AUDIO_COND_MAX_WINDOW 1024
+#define MC_AUDIO_COND_TILE 4096
 int mc_audio_condition(const float* wave_dev, int64_t n_samples, int32_t window, const uint8_t* onset_mask_dev, int32_t n_frames,
                        float* out_dev, void* stream);
 
@@ -629,8 +641,9 @@ int mc_audio_condition(const float* wave_dev, int64_t n_samples, int32_t window,
  * fp64 [up][L], L = ceil(n_taps / up), taps_dev[p * L + i] = taps[p + (L - 1 - i) * up], and 0 where that index is >= n_taps
  * (audio.phase_major builds it), so that an output walks its inputs and its taps in ascending order.  Products and the sum are fp64,
  * added in ascending k whatever the tiling, and rounded to fp32 once.  One launch, no workspace, no atomics: two runs give the same
- * bits.  All sample indices are 64-bit.  A tile of 512 outputs must read at most 16384 inputs ((511 down + n_taps - 1) / up + 2): with
+ * bits.  All sample indices are 64-bit.  A tile of MC_RESAMPLE_TILE outputs must read at most 16384 inputs ((511 down + n_taps - 1) / up + 2): with
  * the default filter of 20 max(up, down) + 1 taps that holds for down / up <= 30; resample in two steps beyond. */
+#define MC_RESAMPLE_TILE 512
 int mc_pcm_decode(const uint8_t* pcm_dev, int64_t n_frames, int32_t channels, int32_t sample_bytes, int32_t mono, float* out_dev, void* stream);
 int64_t mc_resample_out_len(int64_t n_in, int32_t up, int32_t down);
 int mc_resample_poly(const float* x_dev, int64_t n_in, int32_t up, int32_t down, const double* taps_dev, int32_t n_taps, float* y_dev,
@@ -648,7 +661,7 @@ int mc_resample_poly(const float* x_dev, int64_t n_in, int32_t up, int32_t down,
  *   raster    per triangle, with P = (256 x + 128, 256 y + 128) the centre of pixel (x, y) and E_ab(P) = (bx - ax)(Py - ay) -
  *             (by - ay)(Px - ax) in int64: w0 = E_12, w1 = E_20, w2 = E_01, area = w0 + w1 + w2.  area < 0 is counter-clockwise
  *             with y up = front; area == 0, and area > 0 under cull_backfaces, are dropped, and so is a triangle with a vertex whose
- *             zcam is not finite or whose snapped coordinate lies outside +-16384 px (every product then fits int64).  A sample is
+ *             zcam is not finite or whose snapped coordinate lies outside +-MC_RENDER_MAX_SIZE px (every product then fits int64).  A sample is
  *             covered when the three w have the sign of area or are 0 on a top or left edge (top-left fill rule), over the bounding
  *             box clamped to the viewport.  b1 = float(w1) / float(area), b2 = float(w2) / float(area),
  *             z = fmaf(b2, z2 - z0, fmaf(b1, z1 - z0, z0)); a sample with z outside [znear, zfar] is discarded.  The visible face of
@@ -663,6 +676,8 @@ int mc_resample_poly(const float* x_dev, int64_t n_in, int32_t up, int32_t down,
  * counter and the visibility keys of every frame it holds) must be 0 / all-ones when the kernels start; every call leaves it so.  With
  * work_clean = 0 the call fills it first; a caller that hands back the buffer of an earlier, successful call of the same width and
  * height, untouched since, may pass work_clean = 1 and skip the fill. */
+#define MC_RENDER_MAX_SIZE 16384
+#define MC_RENDER_MAX_SLICES 1024
 typedef struct mc_render mc_render;
 typedef struct mc_render_params {
     float screen[12];         /* S, row-major 3x4 (render.OrthographicCamera.screen_affine)                                 */
@@ -671,10 +686,10 @@ typedef struct mc_render_params {
     float ambient, gain;      /* gain = intensity / pi: a unit-albedo Lambert surface                                       */
     float znear, zfar;        /* 0 < znear <= zfar                                                                          */
     int32_t background[3];    /* 0..255                                                                                     */
-    int32_t width, height;    /* 1..16384                                                                                   */
+    int32_t width, height;    /* 1..MC_RENDER_MAX_SIZE                                                                      */
     int32_t cull_backfaces;
     int32_t large_threshold;  /* 0 = the default (1024); 1 sends every multi-pixel box to the wave path, INT32_MAX none      */
-    int32_t large_slices;     /* waves that share one triangle of the wave path: 0 = the default (32), at most 1024         */
+    int32_t large_slices;     /* waves that share one triangle of the wave path: 0 = the default (32), at most MC_RENDER_MAX_SLICES */
 } mc_render_params;
 /* faces_host int32 [num_faces,3]; the vertex-to-face adjacency in CSR form, adj_start_host int32 [num_vertices + 1] and
  * adj_faces_host int32 [adj_start[num_vertices]], the faces of each vertex in ascending order (all three checked here) */
@@ -697,15 +712,18 @@ int mc_render_frames(mc_render* r, const float* verts_dev, int32_t n, const mc_r
  * Layers: 0 background, 1 plane, 2 trail, 3 + c chain c.  Frames run in chunks of as many as work_dev holds; the result does not depend
  * on the chunk size, two runs give the same bits, and there are no atomics. */
 #define MC_SKELETON_MAX_LAYERS 64
+#define MC_SKELETON_MAX_SIZE 4096
+#define MC_SKELETON_MIN_RADIUS 12
+#define MC_SKELETON_MAX_RADIUS 512
 typedef struct mc_skeleton mc_skeleton;
 typedef struct mc_skeleton_params {
     float screen[16];         /* S, row-major 4x4: world -> (X_num, Y_num, depth, W), pixel = (X_num / W, Y_num / W), row 0 on top
                                  (skeleton.Mplot3dCamera.screen_projective); row 2 is not read                                */
-    int32_t width, height;    /* 1..4096                                                                                      */
+    int32_t width, height;    /* 1..MC_SKELETON_MAX_SIZE                                                                      */
 } mc_skeleton_params;
 /* Chain c is the polyline through chain_joints_host[chain_start_host[c] .. chain_start_host[c + 1]) (int32, at least 2 joints each,
  * all < num_joints; 1..61 chains) drawn chain_width_px_host[c] pixels wide; the trail is trail_width_px wide.  A width w gives the
- * radius max(12, floor(8 w + 0.5)) sixteenths of a pixel and must be positive and at most 64.  palette_host uint8 [3 + num_chains][3]:
+ * radius max(MC_SKELETON_MIN_RADIUS, floor(8 w + 0.5)) sixteenths of a pixel, at most MC_SKELETON_MAX_RADIUS: w must be positive and at most 64.  palette_host uint8 [3 + num_chains][3]:
  * background, plane (already composited over the background), trail, then the chains. */
 int mc_skeleton_create(const int32_t* chain_joints_host, const int32_t* chain_start_host, int32_t num_chains, int32_t num_joints,
                        const float* chain_width_px_host, float trail_width_px, const uint8_t* palette_host, mc_skeleton** out);
@@ -731,8 +749,9 @@ int mc_skeleton_frames(mc_skeleton* h, const float* joints_dev, const int32_t* s
  * is a definition.  Frames run in chunks of as many as work_dev holds; the result does not depend on the chunk size. */
 #define MC_MJPEG_420 0
 #define MC_MJPEG_444 1
+#define MC_MJPEG_MAX_SIZE 16384
 typedef struct mc_mjpeg mc_mjpeg;
-/* width, height 1..16384; quality 1..100 */
+/* width, height 1..MC_MJPEG_MAX_SIZE; quality 1..100 */
 int mc_mjpeg_create(int32_t width, int32_t height, int32_t quality, int32_t subsampling, mc_mjpeg** out);
 void mc_mjpeg_destroy(mc_mjpeg* h);
 /* scratch that holds `frames` frames at once; -1: bad argument */

@@ -15,7 +15,6 @@ orig // gcd)``; it is pinned to scipy itself (``tests/test_resample_host.py``, `
 and a condition built this way differs from the reference's above roughly 0.9 of the Nyquist rate, where the two filters' transition
 bands differ.  Nothing here falls back to the host: a missing library or GPU is an error.
 """
-import ctypes
 import functools
 import math
 import wave
@@ -24,17 +23,10 @@ import numpy as np
 import torch
 
 from . import lib as _lib
+from .lib import ptr as _p, stream as _stream
 
-RESAMPLE_TILE = 512                                                      # csrc/mc_resample.hip: outputs per workgroup
+RESAMPLE_TILE = _lib.MC_RESAMPLE_TILE                                    # outputs per workgroup
 LIBROSA_LOAD_SR = 22050                                                  # librosa.load's default rate, the reference's detour
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr())
-
-
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 def resample_filter(up, down, window=('kaiser', 5.0)):

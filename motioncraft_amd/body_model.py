@@ -14,13 +14,10 @@ import numpy as np
 import torch
 
 from . import lib as _lib
+from .lib import ptr as _p, stream as _stream
 
 NUM_JOINTS, POSE_FEATS, MAX_BETAS, MAX_EXPR = 55, 486, 300, 100
 DEFAULT_WORK_BYTES = 256 << 20
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
 class SMPLXBodyModel:
@@ -156,7 +153,7 @@ class SMPLXBodyModel:
         dev, lead, n, poses, expr, trans, betas, per_frame = self._operands(poses, expressions, trans, betas)
         out = torch.empty(n, NUM_JOINTS, 3, device=dev, dtype=torch.float32)
         _lib.check(obj.lib.mc_smplx_joints(obj.handle, _p(poses), _p(expr), _p(trans), _p(betas), per_frame, n, _p(out),
-                                           ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), 'mc_smplx_joints')
+                                           _stream()), 'mc_smplx_joints')
         return out.reshape(lead + (NUM_JOINTS, 3))
 
     def vertices(self, poses, expressions=None, trans=None, betas=None, return_joints=False, work_bytes=DEFAULT_WORK_BYTES):
@@ -170,7 +167,7 @@ class SMPLXBodyModel:
         verts = torch.empty(n, self.num_vertices, 3, device=dev, dtype=torch.float32)
         jout = torch.empty(n, NUM_JOINTS, 3, device=dev, dtype=torch.float32) if return_joints else None
         _lib.check(obj.lib.mc_smplx_vertices(obj.handle, _p(poses), _p(expr), _p(trans), _p(betas), per_frame, n, _p(work), wb,
-                                             _p(verts), _p(jout), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                                             _p(verts), _p(jout), _stream()),
                    'mc_smplx_vertices')
         verts = verts.reshape(lead + (self.num_vertices, 3))
         return (verts, jout.reshape(lead + (NUM_JOINTS, 3))) if return_joints else verts
@@ -190,6 +187,6 @@ class SMPLXBodyModel:
         work = torch.empty(wb, device=dev, dtype=torch.uint8)
         sums = torch.empty(2, device=dev, dtype=torch.float64)
         _lib.check(obj.lib.mc_smplx_vertex_errors(obj.handle, _p(pa), _p(ea), _p(ta), _p(pb), _p(eb), _p(tb), _p(betas_d), per_frame, n, _p(work),
-                                                  wb, _p(sums), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                                                  wb, _p(sums), _stream()),
                    'mc_smplx_vertex_errors')
         return sums

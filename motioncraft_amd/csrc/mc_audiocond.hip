@@ -19,8 +19,8 @@
 
 namespace {
 
-constexpr int TILE = 4096;                   // output samples per workgroup (speech.AUDIO_COND_TILE)
-constexpr int MAX_WINDOW = 1024;
+constexpr int TILE = MC_AUDIO_COND_TILE;     // output samples per workgroup
+constexpr int MAX_WINDOW = MC_AUDIO_COND_MAX_WINDOW;
 constexpr int SPAN = TILE + MAX_WINDOW - 1;  // staged samples at most
 // a level is written four entries at a time up to the next multiple of 4 and reads up to 8 entries past the one it starts at; both
 // buffers are defined over that whole range (zeros behind the samples, and zeros in the second buffer until a level writes it), so

@@ -5,14 +5,10 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <utility>
+#include "../../include/motioncraft_amd.h"     // the C-ABI: every translation unit sees the declarations of what it defines
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-#define MC_OK 0
-#define MC_ERR_ARG 1
-#define MC_ERR_HIP 2
-#define MC_ERR_STATE 3
 
 #define MC_HIP(expr)                                                                        \
     do {                                                                                    \
@@ -71,7 +67,7 @@ __device__ __forceinline__ float gelu_exact(float x) {
 __device__ __forceinline__ float silu_f(float x) { return x / (1.0f + expf(-x)); }
 
 // activation codes shared by host + device
-enum { ACT_NONE = 0, ACT_GELU = 1, ACT_SILU = 2, ACT_LRELU = 3, ACT_QUICKGELU = 4 };   // LRELU: nn.LeakyReLU() slope 0.01; QUICKGELU: x sigmoid(1.702 x) (CLIP)
+enum { ACT_NONE = MC_ACT_NONE, ACT_GELU = MC_ACT_GELU, ACT_SILU = MC_ACT_SILU, ACT_LRELU = MC_ACT_LRELU, ACT_QUICKGELU = MC_ACT_QUICKGELU };   // LRELU: nn.LeakyReLU() slope 0.01; QUICKGELU: x sigmoid(1.702 x) (CLIP)
 __device__ __forceinline__ float apply_act(float v, int act) {
     if (act == ACT_GELU) return gelu_exact(v);
     if (act == ACT_SILU) return silu_f(v);

@@ -1,6 +1,7 @@
 // Last-error string of the C-ABI (thread-local).
 #include <stdarg.h>
 #include <stdio.h>
+#include "../../include/motioncraft_amd.h"
 static thread_local char g_err[1024] = "";
 void mc_set_error(const char* fmt, ...) {
     va_list ap;
@@ -29,14 +30,14 @@ void mc_ledger_add_(const char* kernel, long grid_threads, double flops) {
     r.flops += flops;
     r.calls += 1;
 }
-extern "C" int mc_debug_flop_ledger(int enable) {          // enable != 0: clear and start recording; 0: stop
+extern "C" int mc_debug_flop_ledger(int32_t enable) {          // enable != 0: clear and start recording; 0: stop
     std::lock_guard<std::mutex> lk(g_ledger_mu);
     if (enable) g_ledger.clear();
     mc_ledger_on = enable != 0;
     return 0;
 }
 // text dump "kernel\tcalls\tflops\n" per row into buf (NUL-terminated, truncated at cap); returns the bytes the whole dump needs
-extern "C" long mc_debug_flop_ledger_dump(char* buf, long cap) {
+extern "C" int64_t mc_debug_flop_ledger_dump(char* buf, int64_t cap) {
     std::lock_guard<std::mutex> lk(g_ledger_mu);
     std::string out;
     char line[256];

@@ -2,8 +2,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "mc_options.h"
+#include "../../include/motioncraft_amd.h"
 
-enum { GM_PLAIN = 0, GM_EXP1 = 1, GM_EXP2 = 2, GM_COMB = 3, GM_ENC = 4 };
+enum { GM_PLAIN = MC_GM_PLAIN, GM_EXP1 = 1, GM_EXP2 = 2, GM_COMB = 3, GM_ENC = MC_GM_ENC };     // the two public modes, and the MoE kernels' own
 
 // bits of GemmArgs::tune / TailArgs::tune (McOptions::gemm_tune)
 enum : int {

@@ -19,7 +19,7 @@
 namespace {
 
 constexpr int TF = 256;                      // slice frames per workgroup of beat_mask_k
-constexpr int MAX_ORDER = 64, MAX_UPPER = 64;
+constexpr int MAX_ORDER = MC_BEAT_MAX_ORDER, MAX_UPPER = MC_BEAT_MAX_UPPER;
 
 struct SpeedArgs {
     const float* joints;                     // [T, nj, 3]

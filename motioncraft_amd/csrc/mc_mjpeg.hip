@@ -50,7 +50,6 @@
 
 namespace {
 
-constexpr int MAX_SIZE = 16384;
 constexpr int BLOCK_WORDS = 52;                // 1660 bits
 constexpr int BLOCK_BYTES = 4 * BLOCK_WORDS;   // of bit buffer per block; twice that after stuffing
 constexpr int TILE = 256;                      // blocks of an interval in LDS at a time: one per thread
@@ -390,7 +389,7 @@ struct mc_mjpeg {
 
 extern "C" int mc_mjpeg_create(int32_t width, int32_t height, int32_t quality, int32_t subsampling, mc_mjpeg** out) {
     MC_REQUIRE(out, "mjpeg: null argument");
-    MC_REQUIRE(width >= 1 && height >= 1 && width <= MAX_SIZE && height <= MAX_SIZE, "mjpeg: width=%d height=%d (1..%d each)", width, height, MAX_SIZE);
+    MC_REQUIRE(width >= 1 && height >= 1 && width <= MC_MJPEG_MAX_SIZE && height <= MC_MJPEG_MAX_SIZE, "mjpeg: width=%d height=%d (1..%d each)", width, height, MC_MJPEG_MAX_SIZE);
     MC_REQUIRE(quality >= 1 && quality <= 100, "mjpeg: quality=%d (1..100)", quality);
     MC_REQUIRE(subsampling == MC_MJPEG_420 || subsampling == MC_MJPEG_444, "mjpeg: subsampling=%d (MC_MJPEG_420 or MC_MJPEG_444)", subsampling);
     mc_mjpeg* h = new (std::nothrow) mc_mjpeg;

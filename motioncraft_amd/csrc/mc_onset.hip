@@ -28,10 +28,10 @@
 
 namespace {
 
-constexpr int NFFT = 2048, NBIN = NFFT / 2 + 1, NCOL = 2 * NBIN;
+constexpr int NFFT = MC_ONSET_N_FFT, NBIN = NFFT / 2 + 1, NCOL = 2 * NBIN;
 constexpr int FT = 32;                       // frames per workgroup of onset_melpow_k (the row tile)
 constexpr int CT = 128;                      // table columns per workgroup: one 32-wide MFMA tile per wave
-constexpr int MAX_HOP = 512, MAX_MELS = 128, MAX_FRAMES = 1 << 20, MAX_WINDOW = 1 << 16;
+constexpr int MAX_HOP = MC_ONSET_MAX_HOP, MAX_MELS = MC_ONSET_MAX_MELS, MAX_FRAMES = 1 << 20, MAX_WINDOW = 1 << 16;
 constexpr int SPAN = (FT - 1) * MAX_HOP + NFFT;
 __host__ __device__ constexpr int lds_at(int p) { return p + 4 * (p >> 9); }
 constexpr int SPAN_LDS = lds_at(SPAN - 1) + 1;

@@ -30,13 +30,12 @@
 
 namespace {
 
-constexpr int GUARD = 16384 * 256;             // |snapped coordinate| <= 16384 px: differences < 2^24, products < 2^48
+constexpr int GUARD = MC_RENDER_MAX_SIZE * 256;   // |snapped coordinate| <= 16384 px: differences < 2^24, products < 2^48
 constexpr int OUTSIDE = INT_MIN;               // what project_k stores for a coordinate that is not finite or beyond the guard band
 constexpr unsigned long long EMPTY = ~0ull;    // background key
 constexpr int DEFAULT_LARGE = 1024;            // bounding-box pixels above which a triangle takes the wave path (the sweep)
 constexpr int LARGE_BLOCKS = 1024;             // raster_large_k's fixed grid: 4096 waves stride the list
 constexpr int DEFAULT_SLICES = 32;             // waves that share one listed triangle (the sweep)
-constexpr int MAX_SLICES = 1024;
 
 struct Layout {                                // byte offsets into work_dev for a chunk capacity of c frames
     long counter, keys, list, screen, zcam, normal, total;
@@ -353,7 +352,7 @@ extern "C" int mc_render_create(const int32_t* faces_host, int32_t num_faces, in
 
 extern "C" void mc_render_destroy(mc_render* r) { delete r; }
 
-static bool size_ok(int32_t width, int32_t height) { return width >= 1 && height >= 1 && width <= 16384 && height <= 16384; }
+static bool size_ok(int32_t width, int32_t height) { return width >= 1 && height >= 1 && width <= MC_RENDER_MAX_SIZE && height <= MC_RENDER_MAX_SIZE; }
 
 extern "C" int64_t mc_render_work_bytes(const mc_render* r, int32_t n_frames, int32_t width, int32_t height) {
     if (!r || n_frames < 1 || !size_ok(width, height)) return -1;
@@ -365,14 +364,14 @@ extern "C" int mc_render_frames(mc_render* r, const float* verts_dev, int32_t n,
                                 float* zcam_out_dev, void* stream) {
     MC_REQUIRE(r && p && rgb_out_dev && work_dev && (verts_dev || n == 0), "render: null argument");
     MC_REQUIRE(n >= 0, "render: n=%d", n);
-    MC_REQUIRE(size_ok(p->width, p->height), "render: width=%d height=%d (1..16384 each, the guard band)", p->width, p->height);
+    MC_REQUIRE(size_ok(p->width, p->height), "render: width=%d height=%d (1..%d each, the guard band)", p->width, p->height, MC_RENDER_MAX_SIZE);
     MC_REQUIRE(p->znear > 0.f && p->zfar >= p->znear && isfinite(p->zfar), "render: znear=%g zfar=%g (0 < znear <= zfar < inf: depth keys order as "
                "integers only for positive floats)", (double)p->znear, (double)p->zfar);
     for (int c = 0; c < 3; ++c)
         MC_REQUIRE(p->background[c] >= 0 && p->background[c] <= 255 && p->base[c] >= 0.f && p->base[c] <= 1.f,
                    "render: background must be 0..255 and base 0..1 per channel");
     MC_REQUIRE(p->large_threshold >= 0, "render: large_threshold=%d (0 = default)", p->large_threshold);
-    MC_REQUIRE(p->large_slices >= 0 && p->large_slices <= MAX_SLICES, "render: large_slices=%d (0 = default, at most %d)", p->large_slices, MAX_SLICES);
+    MC_REQUIRE(p->large_slices >= 0 && p->large_slices <= MC_RENDER_MAX_SLICES, "render: large_slices=%d (0 = default, at most %d)", p->large_slices, MC_RENDER_MAX_SLICES);
     MC_REQUIRE(((uintptr_t)work_dev & 15) == 0 && ((uintptr_t)rgb_out_dev & 3) == 0 && ((uintptr_t)verts_dev & 3) == 0,
                "render: work must be 16-byte, rgb_out and verts 4-byte aligned");
     const long W = p->width, H = p->height, V = r->V, F = r->F;

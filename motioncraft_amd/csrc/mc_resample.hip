@@ -20,7 +20,7 @@
 
 namespace {
 
-constexpr int TILE = 512;                    // outputs per workgroup (audio.RESAMPLE_TILE)
+constexpr int TILE = MC_RESAMPLE_TILE;       // outputs per workgroup
 constexpr long MAX_SPAN_BYTES = 64 << 10;    // the dynamic LDS a launch gets without asking for more
 
 __global__ __launch_bounds__(256) void resample_poly_k(const float* __restrict__ x, long n_in, long up, long down, const double* __restrict__ table,

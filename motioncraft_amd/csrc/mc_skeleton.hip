@@ -58,8 +58,8 @@ namespace {
 
 constexpr int GUARD = 1 << 17;                 // |snapped coordinate| <= 8192 px
 constexpr int INVALID = INT_MIN;
-constexpr int MIN_R = 12, MAX_R = 512;
-constexpr int MAX_SIZE = 4096;
+constexpr int MIN_R = MC_SKELETON_MIN_RADIUS, MAX_R = MC_SKELETON_MAX_RADIUS;
+constexpr int MAX_SIZE = MC_SKELETON_MAX_SIZE;
 constexpr int TILE_W = 64, TILE_H = 16;        // 256 threads x 4 pixels in a row; 8.3 KB of LDS, so LDS never bounds the occupancy
 constexpr int STAGE = 256;                     // primitives staged per pass: one per thread
 

@@ -10,15 +10,11 @@ import numpy as np
 import torch
 
 from . import lib as _lib
+from .lib import ptr as _ptr, stream as _stream
 from .weights import control_info, pack_state_dict
 
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+PRECISIONS = _lib.named('MC_PREC_')               # 'f32', 'f16', 'f16x3' -> mc_ctx_set_precision's code
+TIE_POLICIES = _lib.named('MC_TIE_')              # 'stable', 'reverse' -> mc_ctx_set_tie_policy's code
 
 
 def _dev_f32(t, name):
@@ -87,7 +83,8 @@ class NativeContext:
     def effective_precision(self):
         """'f32' / 'f16' / 'f16x3' the per-step kernels really run in (a reduced-precision mode falls back to the fp32 small-batch
         kernels up to 512 residual rows, i.e. B = 1 at 196 frames)."""
-        return {0: 'f32', 1: 'f16', 2: 'f16x3'}[int(self.lib.mc_ctx_effective_precision(self.handle))]
+        code = int(self.lib.mc_ctx_effective_precision(self.handle))
+        return next(name for name, c in PRECISIONS.items() if c == code)
 
     @property
     def uses_coop_routing(self):
@@ -106,7 +103,7 @@ class NativeContext:
     def set_precision(self, precision):
         """'f32' (default, exact fp32 MFMA), 'f16' (fp16 operands, fp32 accumulate) or 'f16x3' (fp16 hi/lo split, three
         products: fp32-class) for the per-step GEMM-shaped kernels; gate / routing / normalisations stay fp32."""
-        code = {'f32': 0, 'f16': 1, 'f16x3': 2}[precision]
+        code = PRECISIONS[precision]
         self._drop_graph()
         _lib.check(self.lib.mc_ctx_set_precision(self.handle, code), 'mc_ctx_set_precision')
         self.precision = precision
@@ -129,7 +126,7 @@ class NativeContext:
     def set_tie_policy(self, policy):
         """'stable' (default) or 'reverse': order of equal-importance tokens at a capacity cut (tutel boundary, a16).
         Call before set_condition."""
-        code = {'stable': 0, 'reverse': 1}[policy]
+        code = TIE_POLICIES[policy]
         self._drop_graph()             # a captured graph has the tie key and the twin-mode launch sequence baked in
         self._keep = []                # the library forgets the condition: set_condition must follow
         _lib.check(self.lib.mc_ctx_set_tie_policy(self.handle, code), 'mc_ctx_set_tie_policy')

@@ -63,7 +63,7 @@ class NativeEvalEncoder(_lib.NativeObject):
         out = torch.empty(m.shape[0], self.cfg.latent_dim, device=m.device, dtype=torch.float32)
         _lib.check(self.lib.mc_evalenc_encode_motion(self.handle, ctypes.c_void_p(m.data_ptr()), ctypes.c_void_p(n.data_ptr()),
                                                      m.shape[0], m.shape[1], ctypes.c_void_p(out.data_ptr()),
-                                                     ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                                                     _lib.stream()),
                    'mc_evalenc_encode_motion')
         return out
 
@@ -78,7 +78,7 @@ class NativeEvalEncoder(_lib.NativeObject):
         out = torch.empty(ids.shape[0], self.cfg.latent_dim, device=ids.device, dtype=torch.float32)
         _lib.check(self.lib.mc_evalenc_encode_text(self.handle, ctypes.c_void_p(ids.data_ptr()), ctypes.c_void_p(mask.data_ptr()),
                                                    ids.shape[0], ids.shape[1], ctypes.c_void_p(out.data_ptr()),
-                                                   ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                                                   _lib.stream()),
                    'mc_evalenc_encode_text')
         return out
 
@@ -461,7 +461,7 @@ class NativeT2MEvaluator(_lib.NativeObject):
         out = torch.empty(m.shape[0], self.cfg.motion_latent, device=m.device, dtype=torch.float32)
         _lib.check(self.lib.mc_t2meval_encode_motion(self.handle, ctypes.c_void_p(m.data_ptr()), ctypes.c_void_p(n.data_ptr()),
                                                      m.shape[0], m.shape[1], ctypes.c_void_p(out.data_ptr()),
-                                                     ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                                                     _lib.stream()),
                    'mc_t2meval_encode_motion')
         return out
 
@@ -479,7 +479,7 @@ class NativeT2MEvaluator(_lib.NativeObject):
         out = torch.empty(w.shape[0], self.cfg.text_out, device=w.device, dtype=torch.float32)
         _lib.check(self.lib.mc_t2meval_encode_text(self.handle, ctypes.c_void_p(w.data_ptr()), ctypes.c_void_p(p.data_ptr()),
                                                    ctypes.c_void_p(n.data_ptr()), w.shape[0], w.shape[1], ctypes.c_void_p(out.data_ptr()),
-                                                   ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                                                   _lib.stream()),
                    'mc_t2meval_encode_text')
         return out
 

@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from . import lib as _lib
+from .lib import ptr as _p, stream as _stream
 
 # per-tool filter widths: (body + jaw, hands, trans, expressions); None = unfiltered
 SIGMAS_T2M = (3.5, 3.5, 3.0, 2.0)      # tools/visualize.py:244-246 (whole poses array at 3.5)
@@ -69,7 +70,6 @@ def _check_pred(x):
         raise ValueError(f'SMPL-X post-processing expects the 322-d motionx layout, got {x.shape[2]}')
 
 
-_p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
 def postprocess_smplx(pred_motion, motion_length=None, mean=None, std=None, sigmas=SIGMAS_T2M):
@@ -92,7 +92,7 @@ def postprocess_smplx(pred_motion, motion_length=None, mean=None, std=None, sigm
     trans = torch.empty(B, T, 3, device=dev, dtype=torch.float64)
     _lib.check(lib.mc_postprocess_smplx(_p(x), _p(len_d), _p(mean_d), _p(std_d), _p(taps_d), ctypes.byref(radius), stats_f32,
                                         B, T, C, _p(poses), _p(expr), _p(trans),
-                                        ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                                        _stream()),
                'mc_postprocess_smplx')
     return dict(poses=poses, expressions=expr, trans=trans, stats_f32=bool(stats_f32))
 
@@ -120,7 +120,7 @@ def postprocess_smplx_stitched(pred_motion, motion_length, mean=None, std=None, 
     if n:
         _lib.check(lib.mc_postprocess_smplx_stitched(_p(x), _p(rows_d), n, _p(mean_d), _p(std_d), _p(taps_d),
                                                      ctypes.byref(radius), stats_f32, C, _p(poses), _p(expr), _p(trans),
-                                                     ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                                                     _stream()),
                    'mc_postprocess_smplx_stitched')
     return dict(poses=poses, expressions=expr, trans=trans, stats_f32=bool(stats_f32))
 
@@ -219,7 +219,7 @@ def recover_joints(pred_motion, motion_length=None, mean=None, std=None, joints_
     len_d = None if lens is None else torch.tensor(lens, dtype=torch.int32, device=dev)
     joints = torch.empty(B, T, J, 3, device=dev, dtype=torch.float32)
     _lib.check(lib.mc_postprocess_t2m_joints(_p(x), _p(len_d), _p(mean_d), _p(std_d), _p(taps_d), radius, stats_f32, B, T, C, J,
-                                             _p(joints), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                                             _p(joints), _stream()),
                'mc_postprocess_t2m_joints')
     return joints
 
@@ -244,7 +244,7 @@ def recover_joints_stitched(pred_motion, motion_length, mean=None, std=None, joi
         work = torch.empty(n, 4, device=dev, dtype=torch.float64)
         _lib.check(lib.mc_postprocess_t2m_joints_stitched(_p(x), _p(rows_d), n, _p(mean_d), _p(std_d), _p(taps_d), radius, stats_f32,
                                                           C, J, _p(work), _p(joints),
-                                                          ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                                                          _stream()),
                    'mc_postprocess_t2m_joints_stitched')
     return joints
 

@@ -21,9 +21,10 @@ import numpy as np
 import torch
 
 from . import lib as _lib
+from .lib import ptr as _p
 
 DEFAULT_WORK_BYTES = 256 << 20
-MAX_SIZE = 16384                                   # the rasteriser's guard band, in pixels
+MAX_SIZE = _lib.MC_RENDER_MAX_SIZE                 # the rasteriser's guard band, in pixels
 
 
 def _rot_x_pose(angle_deg, ty, tz):
@@ -110,10 +111,6 @@ def _colour(c, what):
     if a.shape != (3,) or not np.all((a >= 0) & (a <= 255) & (a == np.round(a))):
         raise ValueError(f'{what} must be three integers in 0..255, got {c!r}')
     return [int(v) for v in a]
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
 class MeshRenderer:

@@ -24,20 +24,13 @@ import numpy as np
 import torch
 
 from . import lib as _lib
+from .lib import ptr as _p, stream as _stream
 from .body_model import DEFAULT_WORK_BYTES, NUM_JOINTS
 from .evaluation import L1div, calculate_activation_statistics, calculate_diversity, calculate_frechet_distance
 
 UPPER_BODY = (3, 6, 9, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21)           # metric.py:55
-MAX_ORDER = MAX_UPPER = 64                                               # csrc/mc_metrics.hip
+MAX_ORDER, MAX_UPPER = _lib.MC_BEAT_MAX_ORDER, _lib.MC_BEAT_MAX_UPPER
 M2D_MAX_FRAMES = 4096                                                    # m2d_test.py:243
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 class Beats:
@@ -94,7 +87,7 @@ class OnsetDetector:
     min/max normalisation, ``peak_pick`` with pre_max 0.03 s, post_max 0, pre_avg 0.1 s, post_avg 0.1 s, wait 0.03 s, delta 0.07.
     The waveform is taken as float32 at ``sr``; ``audio.Resampler`` / ``audio.load_wav`` bring one there."""
     DELTA = 0.07
-    N_FFT, MAX_HOP, MAX_MELS = 2048, 512, 128                            # csrc/mc_onset.hip
+    N_FFT, MAX_HOP, MAX_MELS = _lib.MC_ONSET_N_FFT, _lib.MC_ONSET_MAX_HOP, _lib.MC_ONSET_MAX_MELS
 
     def __init__(self, sr=16000, hop_length=512, n_fft=2048, n_mels=128):
         self.sr, self.hop_length, self.n_fft, self.n_mels = float(sr), int(hop_length), int(n_fft), int(n_mels)

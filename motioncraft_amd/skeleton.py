@@ -17,11 +17,12 @@ import numpy as np
 import torch
 
 from . import lib as _lib
+from .lib import ptr as _p, stream as _stream
 
 DEFAULT_WORK_BYTES = 64 << 20
-MAX_SIZE = 4096                                    # the rasteriser's viewport limit, in pixels
+MAX_SIZE = _lib.MC_SKELETON_MAX_SIZE               # the rasteriser's viewport limit, in pixels
 MAX_CHAINS = _lib.SKELETON_MAX_LAYERS - 3
-MIN_RADIUS, MAX_RADIUS = 12, 512                   # of a capsule, in sixteenths of a pixel
+MIN_RADIUS, MAX_RADIUS = _lib.MC_SKELETON_MIN_RADIUS, _lib.MC_SKELETON_MAX_RADIUS       # of a capsule, in sixteenths of a pixel
 INVALID = -2 ** 31                                 # both coordinates of a point that was dropped
 
 # matplotlib's named colours, as RGB
@@ -166,10 +167,6 @@ def _colour(c, what):
     return tuple(int(v) for v in a)
 
 
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
 class SkeletonRenderer:
     """``SkeletonRenderer(chains)``; ``.render(joints)`` -> uint8 [n, H, W, 3] on the joints' device and current stream.
 
@@ -284,5 +281,5 @@ class SkeletonRenderer:
                 _lib.check(obj.lib.mc_skeleton_frames(obj.handle, _p(x), seq_start.ctypes.data_as(ctypes.c_void_p), len(lens), ctypes.byref(p),
                                                       _p(work), wb, _p(rgb), _p(out.get('layer')), _p(out.get('screen')),
                                                       _p(out.get('trail_screen')), _p(out.get('stats')), _p(out.get('traj')),
-                                                      ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), 'mc_skeleton_frames')
+                                                      _stream(dev)), 'mc_skeleton_frames')
         return out if return_buffers else rgb

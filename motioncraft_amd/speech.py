@@ -15,24 +15,20 @@ librosa's ``polyphase`` mode, pinned to scipy; it is not ``soxr_hq``, so a condi
 above roughly 0.9 of the Nyquist rate.  Compressed and float files stay with the caller, and so does the source of the prompt's
 words (the reference reads them per frame from a TextGrid through its vocabulary).  Nothing here falls back to the host: a missing library or GPU is an error.
 """
-import ctypes
 import wave
 
 import numpy as np
 import torch
 
 from . import lib as _lib
+from .lib import ptr as _p, stream as _stream
 from . import longform
 from .scoring import OnsetDetector
 
-AUDIO_COND_TILE = 4096                                                   # csrc/mc_audiocond.hip: output samples per workgroup
-MAX_WINDOW = 1024                                                        # csrc/mc_audiocond.hip
+AUDIO_COND_TILE = _lib.MC_AUDIO_COND_TILE                                # output samples per workgroup
+MAX_WINDOW = _lib.MC_AUDIO_COND_MAX_WINDOW
 SAMPLES_PER_FRAME = 16000 // 30                                          # s2g_test.py:155: audio rows per motion frame
 PROMPT = 'A person is doing a speech, and the speech content is '        # s2g_test.py:175
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr())
 
 
 def read_wav(path, sr):
@@ -70,7 +66,7 @@ class AudioCondition:
         lib = _lib.load(require_gpu=True)
         out = torch.empty(t.numel(), 2, device=t.device, dtype=torch.float32)
         _lib.check(lib.mc_audio_condition(_p(t), t.numel(), window, _p(mask) if mask is not None else None, 0 if mask is None else mask.numel(),
-                                          _p(out), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), 'mc_audio_condition')
+                                          _p(out), _stream()), 'mc_audio_condition')
         return out
 
     def __call__(self, y):

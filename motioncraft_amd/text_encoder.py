@@ -82,7 +82,7 @@ class NativeTextEncoder(_lib.NativeObject):
         out = self._out(f.shape[0], f.device)
         _lib.check(self.lib.mc_textenc_forward_feat(self.handle, ctypes.c_void_p(f.data_ptr()), f.shape[0],
                                                     ctypes.c_void_p(out.data_ptr()),
-                                                    ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                                                    _lib.stream()),
                    'mc_textenc_forward_feat')
         return out
 
@@ -96,7 +96,7 @@ class NativeTextEncoder(_lib.NativeObject):
         _lib.check(self.lib.mc_textenc_forward_tokens(self.handle, ctypes.c_void_p(t.data_ptr()), t.shape[0],
                                                       ctypes.c_void_p(feat.data_ptr()) if feat is not None else None,
                                                       ctypes.c_void_p(out.data_ptr()),
-                                                      ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                                                      _lib.stream()),
                    'mc_textenc_forward_tokens')
         return (out, feat) if return_clip_feat else out
 

@@ -8,7 +8,6 @@ wraps them with the standard library alone.  Every player reads the result, and 
 (``ffmpeg -i clip.avi -c copy clip.mp4`` for the video; PCM audio wants ``-c:a aac``).  No inter-frame codec, no OpenDML: a file ends
 below 2^31 bytes.
 """
-import ctypes
 import fractions
 import os
 import struct
@@ -17,16 +16,13 @@ import numpy as np
 import torch
 
 from . import lib as _lib
-from .render import MAX_SIZE
+from .lib import ptr as _p, stream as _stream
 
 DEFAULT_WORK_BYTES = 256 << 20
 OUT_BYTES = 256 << 20                              # device bytes of encoded output per call: frames go through in groups whose BOUND fits
-SUBSAMPLINGS = {'4:2:0': 0, '4:4:4': 1}            # MC_MJPEG_420, MC_MJPEG_444
+MAX_SIZE = _lib.MC_MJPEG_MAX_SIZE
+SUBSAMPLINGS = {'4:2:0': _lib.MC_MJPEG_420, '4:4:4': _lib.MC_MJPEG_444}
 RIFF_LIMIT = 2 ** 31 - 1
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr())
 
 
 def _size(width, height):
@@ -96,7 +92,7 @@ class JpegEncoder:
         work = self._work[1]
         for f0 in range(0, n, group):
             with torch.cuda.device(dev):
-                stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+                stream = _stream(dev)
                 k = min(group, n - f0)
                 cap = self.max_bytes(k)
                 out = torch.empty(cap, device=dev, dtype=torch.uint8)

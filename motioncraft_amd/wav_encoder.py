@@ -88,7 +88,7 @@ class NativeWavEncoder(_lib.NativeObject):
         out = torch.empty(B, T, self.out_dim, device=wav.device, dtype=torch.float32)
         _lib.check(self.lib.mc_wavenc_forward(self.handle, ctypes.c_void_p(wav.data_ptr()), B, S,
                                               ctypes.c_void_p(out.data_ptr()),
-                                              ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), 'mc_wavenc_forward')
+                                              _lib.stream()), 'mc_wavenc_forward')
         return out
 
     forward = __call__
