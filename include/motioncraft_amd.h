@@ -39,6 +39,8 @@
  *                                                                      mogen/datasets/EMAGE_2024/utils/fast_render.py:13-81; other_tools.py:695-765
  *   mc_mjpeg_*            convert_img_to_mp4 / add_audio_to_video: frames -> one video file (baseline JPEG on the device, for a Motion-JPEG AVI)
  *                                                                      mogen/datasets/EMAGE_2024/utils/media.py:4-33
+ *   mc_emb_frechet, mc_emb_statistics, mc_emb_zscore, mc_emb_retrieval, mc_emb_pair_distance  the metric functions over embedding tables
+ *                         (Frechet distance, R precision, matching score, diversity, multimodality)   mogen/core/evaluation/utils.py:12-140
  *   mc_op_renoise         GaussianDiffusion._undo (resampling jumps)   gaussian_diffusion.py:429-435, 1113-1118
  *
  * Conventions: plain pointers and sizes only.  `*_dev` pointers are device (HBM) addresses owned
@@ -46,7 +48,8 @@
  * are fp32, contiguous, row-major.  Every function returns 0 on success or an MC_ERR_* code;
  * mc_last_error() returns a thread-local description.  A handle is re-entrant across handles but
  * not thread-safe per handle.  No call synchronises the device except mc_model_set_param
- * (synchronous H2D upload) and the *_create/_destroy functions.
+ * (synchronous H2D upload), the *_create/_destroy functions and mc_emb_frechet (it waits for `stream` once per
+ * Jacobi sweep to read the count of rotated pairs, so it cannot be captured into a graph).
  */
 #ifndef MOTIONCRAFT_AMD_H
 #define MOTIONCRAFT_AMD_H
@@ -60,6 +63,7 @@ extern "C" {
 #define MC_ERR_ARG 1
 #define MC_ERR_HIP 2
 #define MC_ERR_STATE 3
+#define MC_ERR_NOCONV 4   /* an iteration reached its cap without converging (mc_emb_frechet) */
 
 typedef struct mc_model mc_model;
 typedef struct mc_ctx mc_ctx;
@@ -764,6 +768,49 @@ int64_t mc_mjpeg_max_bytes(const mc_mjpeg* h, int32_t frames);
  * when work_bytes is below that, or when out_capacity is below mc_mjpeg_max_bytes(h, n): nothing is sized by a typical ratio. */
 int mc_mjpeg_encode(mc_mjpeg* h, const uint8_t* rgb_dev, int32_t n, void* work_dev, int64_t work_bytes, uint8_t* out_dev, int64_t out_capacity,
                     int64_t* offsets_dev, void* stream);
+
+/* ---- The quality metrics over embedding tables (mogen/core/evaluation/utils.py:12-140), reduced on the device in fp64.
+ * A table is [rows, d] row-major in DEVICE memory, fp32 or (table_fp64 != 0) fp64; 2..MC_EMB_MAX_ROWS rows (1.. where stated),
+ * d in 1..MC_EMB_MAX_DIM.  Every `_dev` pointer is checked to be a device address: a host pointer is MC_ERR_ARG.  Results are fp64; every
+ * sum runs in a fixed order (strided per-thread sums, then a fixed tree; the one atomic is an integer counter), so two runs give the
+ * same bits.  Error codes: MC_ERR_ARG (null, ill-sized or host argument; workspace too small or not 8-byte aligned), MC_ERR_HIP,
+ * and from mc_emb_frechet MC_ERR_NOCONV when a decomposition still rotated column pairs in its last allowed sweep.
+ *
+ * mc_emb_frechet: gt_dev [n, d], pred_dev [m, d] -> fid_out_dev fp64 [1] = |mu1 - mu2|^2 + Tr C1 + Tr C2 - 2 Tr sqrt(C1 C2) of the tables
+ * times emb_scale, with Tr sqrt(C1 C2) = (sum of the singular values of A_c B_c^T) / sqrt((n - 1)(m - 1)) over the column-centred tables:
+ * no covariance and no matrix root is formed, and the value is the exact one for positive semi-definite covariances, also when
+ * n - 1 < d.  Three one-sided Jacobi decompositions (each table over min(rows, d) columns, then the small product), one launch per
+ * round of disjoint column pairs.  After each sweep the call synchronises `stream` to read the count of rotated pairs; a
+ * decomposition takes at most max_sweeps sweeps (0: MC_EMB_MAX_SWEEPS; 1..MC_EMB_MAX_SWEEPS).  work_dev: 8-byte aligned,
+ * mc_emb_frechet_work_bytes(n, m, d) bytes (-1: bad argument), contents need not be kept.  info_host (HOST memory, may be NULL):
+ * int32 [6] = sweeps and round launches of the decompositions of gt, pred and the product.
+ * mc_emb_statistics: -> mean_out_dev fp64 [d], cov_out_dev fp64 [d, d]: np.mean / np.cov(rowvar=False) of table * emb_scale
+ * (calculate_activation_statistics); work_dev as above with mc_emb_statistics_work_bytes(n, d).
+ * mc_emb_zscore: table [n >= 1, d] -> out_dev fp64 [n, d] = (x - column mean) / population standard deviation, a deviation of
+ * exactly zero replaced by 1e-8 (evaluation._zscore).
+ * mc_emb_retrieval: text_dev, motion_dev [n >= 1, d] cut into batches of `batch` (1..MC_EMB_MAX_BATCH) rows, the last one ragged; within a
+ * batch dist(t_i, m_j) = sqrt(sum (t_i - m_j)^2) from direct differences and rank_i = #{j : dist(t_i, m_j) < dist(t_i, m_i)} +
+ * #{j < i : dist(t_i, m_j) = dist(t_i, m_i)} -> counts_out_dev int32 [ceil(n / batch), top_k]: per batch the rows with rank_i < k for
+ * k = 1..top_k (1..MC_EMB_MAX_TOPK), and (may be NULL) match_sum_out_dev fp64 [ceil(n / batch)]: the sum over the batch of dist(t_i, m_i).
+ * mc_emb_pair_distance: table [groups, rows, d] (groups * rows <= MC_EMB_MAX_ROWS), first_dev / second_dev int32 [n_pairs] row indices
+ * in 0..rows - 1 (an index outside is clamped into the table) -> mean_out_dev fp64 [1]: the mean over groups and pairs of
+ * |(a[g, first] * emb_scale - a[g, second] * emb_scale) * norm_scale| (calculate_diversity with groups = 1, calculate_multimodality). */
+#define MC_EMB_MAX_DIM 512
+#define MC_EMB_MAX_ROWS 1048576
+#define MC_EMB_MAX_BATCH 64
+#define MC_EMB_MAX_TOPK 64
+#define MC_EMB_MAX_SWEEPS 30
+int64_t mc_emb_frechet_work_bytes(int32_t n, int32_t m, int32_t d);
+int mc_emb_frechet(const void* gt_dev, int32_t n, const void* pred_dev, int32_t m, int32_t d, int32_t table_fp64, double emb_scale, int32_t max_sweeps,
+                   void* work_dev, int64_t work_bytes, double* fid_out_dev, int32_t* info_host, void* stream);
+int64_t mc_emb_statistics_work_bytes(int32_t n, int32_t d);
+int mc_emb_statistics(const void* table_dev, int32_t n, int32_t d, int32_t table_fp64, double emb_scale, void* work_dev, int64_t work_bytes,
+                      double* mean_out_dev, double* cov_out_dev, void* stream);
+int mc_emb_zscore(const void* table_dev, int32_t n, int32_t d, int32_t table_fp64, double* out_dev, void* stream);
+int mc_emb_retrieval(const void* text_dev, const void* motion_dev, int32_t n, int32_t d, int32_t table_fp64, int32_t batch, int32_t top_k,
+                     int32_t* counts_out_dev, double* match_sum_out_dev, void* stream);
+int mc_emb_pair_distance(const void* table_dev, int32_t groups, int32_t rows, int32_t d, int32_t table_fp64, const int32_t* first_dev,
+                         const int32_t* second_dev, int32_t n_pairs, double emb_scale, double norm_scale, double* mean_out_dev, void* stream);
 
 /* out = a * x + b * noise over n elements (out may alias x) */
 int mc_op_renoise(const float* x_dev, const float* noise_dev, float a, float b, float* out_dev, int64_t n, void* stream);

@@ -17,9 +17,10 @@ from . import skeleton
 from .skeleton import KIT_CHAINS, T2M_CHAINS, Mplot3dCamera, SkeletonRenderer
 from . import video
 from .video import AviWriter, JpegEncoder, save_avi
+from . import embmetrics
 from . import speech
 from .speech import AudioCondition, sample_speech, speech_frames, speech_prompt
 
-__all__ = ['video', 'AviWriter', 'JpegEncoder', 'save_avi', 'skeleton', 'KIT_CHAINS', 'T2M_CHAINS', 'Mplot3dCamera', 'SkeletonRenderer', 'render', 'DirectionalLight', 'MeshRenderer', 'OrthographicCamera', 'audio', 'Resampler', 'load_wav', 'AudioCondition', 'sample_speech', 'speech', 'speech_frames', 'speech_prompt', 'BeatAlignment', 'M2DScorer', 'OnsetDetector', 'S2GScorer', 'face_errors', 'scoring','ARCHITECTURES', 'ATTENTIONS', 'LOSSES', 'MODELS', 'SUBMODULES', 'build_architecture',
+__all__ = ['embmetrics', 'video', 'AviWriter', 'JpegEncoder', 'save_avi', 'skeleton', 'KIT_CHAINS', 'T2M_CHAINS', 'Mplot3dCamera', 'SkeletonRenderer', 'render', 'DirectionalLight', 'MeshRenderer', 'OrthographicCamera', 'audio', 'Resampler', 'load_wav', 'AudioCondition', 'sample_speech', 'speech', 'speech_frames', 'speech_prompt', 'BeatAlignment', 'M2DScorer', 'OnsetDetector', 'S2GScorer', 'face_errors', 'scoring','ARCHITECTURES', 'ATTENTIONS', 'LOSSES', 'MODELS', 'SUBMODULES', 'build_architecture',
            'build_attention', 'build_loss', 'build_submodule', 'Config', 'ConfigDict', 'Registry', 'build_from_cfg', 'ControlT2MHalf',
            'load_checkpoint', 'wrap_fp16_model']

@@ -7,7 +7,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libmotioncraft_amd.so')
-SOURCES = ['mc_error.cpp', 'mc_gemm.hip', 'mc_kernels.hip', 'mc_route.hip', 'mc_attn.hip', 'mc_chain.hip', 'mc_half.hip', 'mc_post.hip', 'mc_wavenc.hip', 'mc_textenc.hip', 'mc_evalenc.hip', 'mc_t2meval.hip', 'mc_smplx.hip', 'mc_metrics.hip', 'mc_onset.hip', 'mc_audiocond.hip', 'mc_resample.hip', 'mc_render.hip', 'mc_skeleton.hip', 'mc_mjpeg.hip', 'mc_step.hip', 'mc_model.hip']
+SOURCES = ['mc_error.cpp', 'mc_gemm.hip', 'mc_kernels.hip', 'mc_route.hip', 'mc_attn.hip', 'mc_chain.hip', 'mc_half.hip', 'mc_post.hip', 'mc_wavenc.hip', 'mc_textenc.hip', 'mc_evalenc.hip', 'mc_t2meval.hip', 'mc_smplx.hip', 'mc_metrics.hip', 'mc_embmetrics.hip', 'mc_onset.hip', 'mc_audiocond.hip', 'mc_resample.hip', 'mc_render.hip', 'mc_skeleton.hip', 'mc_mjpeg.hip', 'mc_step.hip', 'mc_model.hip']
 
 
 def _hipcc():

@@ -7,7 +7,9 @@
   * the metric functions and the five evaluators of ``mogen/core/evaluation/`` (``EVALUATORS`` registry with the
     reference's metric names 'R Precision', 'Matching Score', 'FID', 'Diversity', 'MultiModality'; ``build_evaluator``).
     Like the reference they are host numpy over the [N, 256] embedding tables (the reference calls
-    ``.cpu().detach().numpy()`` before every metric; ``scipy.linalg.sqrtm`` for the Frechet distance).
+    ``.cpu().detach().numpy()`` before every metric; ``scipy.linalg.sqrtm`` for the Frechet distance).  With
+    ``on_device=True`` (a key of ``eval_cfg``) the tables stay on the device and every evaluator reduces them there
+    (``motioncraft_amd.embmetrics``); the index draws of diversity and multimodality stay on the host generator.
 """
 import copy
 import ctypes
@@ -16,7 +18,7 @@ import os
 import numpy as np
 import torch
 
-from . import lib as _lib
+from . import embmetrics, lib as _lib
 from .builder import SUBMODULES
 from .registry import Registry
 from .synthetic import sinusoid_table
@@ -222,12 +224,13 @@ class BaseEvaluator:
     ENC_BATCH = 32
 
     def __init__(self, batch_size=None, drop_last=False, replication_times=1, replication_reduction='statistics',
-                 eval_begin_idx=None, eval_end_idx=None, evaluator_model=None):
+                 eval_begin_idx=None, eval_end_idx=None, evaluator_model=None, on_device=False):
         assert replication_reduction in ('statistics', 'mean', 'concat')
         self.batch_size, self.drop_last = batch_size, drop_last
         self.replication_times, self.replication_reduction = replication_times, replication_reduction
         self.eval_begin_idx, self.eval_end_idx = eval_begin_idx, eval_end_idx
         self.evaluator_model = evaluator_model
+        self.on_device = bool(on_device)              # True: the embedding tables never leave the device (embmetrics)
         self.append_indexes = None
 
     def evaluate(self, results):
@@ -267,15 +270,15 @@ class BaseEvaluator:
         for i in range(0, motion.shape[0], self.ENC_BATCH):
             sl = slice(i, i + self.ENC_BATCH)
             embs.append(self.evaluator_model.encode_motion(motion=motion[sl].to(device), motion_length=motion_length[sl].to(device),
-                                                           motion_mask=motion_mask[sl].to(device), device=device).cpu())
-        return torch.cat(embs, dim=0)
+                                                           motion_mask=motion_mask[sl].to(device), device=device))
+        return torch.cat(embs if self.on_device else [e.cpu() for e in embs], dim=0)
 
     def encode_text(self, text, token, device):
         embs = []
         for i in range(0, len(text), self.ENC_BATCH):
             sl = slice(i, i + self.ENC_BATCH)
-            embs.append(self.evaluator_model.encode_text(text=text[sl], token=None if token is None else token[sl], device=device).cpu())
-        return torch.cat(embs, dim=0)
+            embs.append(self.evaluator_model.encode_text(text=text[sl], token=None if token is None else token[sl], device=device))
+        return torch.cat(embs if self.on_device else [e.cpu() for e in embs], dim=0)
 
     def _device(self):
         # the embedding model decides where it runs; T2MContrastiveModel_SMPLX is device-only
@@ -283,20 +286,26 @@ class BaseEvaluator:
 
     def _motion_emb(self, res, prefix='pred_'):
         dev = self._device()
-        return self.encode_motion(res[prefix + 'motion'], res[prefix + 'motion_length'], res[prefix + 'motion_mask'], dev).numpy()
+        emb = self.encode_motion(res[prefix + 'motion'], res[prefix + 'motion_length'], res[prefix + 'motion_mask'], dev)
+        return emb.detach() if self.on_device else emb.numpy()
 
     def _text_emb(self, res):
-        return self.encode_text(res['text'], res['token'] or None, self._device()).numpy()
+        emb = self.encode_text(res['text'], res['token'] or None, self._device())
+        return emb.detach() if self.on_device else emb.numpy()
 
 
 class PrecisionEvaluator(BaseEvaluator):
     def __init__(self, data_len=0, evaluator_model=None, top_k=3, batch_size=32, drop_last=False, replication_times=1,
                  replication_reduction='statistics', **kwargs):
-        super().__init__(batch_size, drop_last, replication_times, replication_reduction, 0, data_len, evaluator_model)
+        super().__init__(batch_size, drop_last, replication_times, replication_reduction, 0, data_len, evaluator_model,
+                         on_device=kwargs.get('on_device', False))
         self.top_k = top_k
 
     def single_evaluate(self, results):
         res = self.prepare_results(results)
+        if self.on_device:
+            text = self._text_emb(res)
+            return embmetrics.r_precision_counts(text, self._motion_emb(res), self.top_k).cpu().numpy()[0], text.shape[0]
         order = np.argsort(euclidean_distance_matrix(self._text_emb(res), self._motion_emb(res)), axis=1)
         return calculate_top_k(order, top_k=self.top_k).sum(axis=0), order.shape[0]
 
@@ -314,10 +323,14 @@ class PrecisionEvaluator(BaseEvaluator):
 class MatchingScoreEvaluator(BaseEvaluator):
     def __init__(self, data_len=0, evaluator_model=None, batch_size=32, drop_last=False, replication_times=1,
                  replication_reduction='statistics', **kwargs):
-        super().__init__(batch_size, drop_last, replication_times, replication_reduction, 0, data_len, evaluator_model)
+        super().__init__(batch_size, drop_last, replication_times, replication_reduction, 0, data_len, evaluator_model,
+                         on_device=kwargs.get('on_device', False))
 
     def single_evaluate(self, results):
         res = self.prepare_results(results)
+        if self.on_device:
+            text, motion = embmetrics.zscore(self._text_emb(res)), embmetrics.zscore(self._motion_emb(res))
+            return float(embmetrics.matching_score_sum(text, motion).item()), text.shape[0]
         text, motion = _zscore(self._text_emb(res)), _zscore(self._motion_emb(res))
         return euclidean_distance_matrix(text, motion).trace(), text.shape[0]
 
@@ -331,11 +344,15 @@ class MatchingScoreEvaluator(BaseEvaluator):
 class FIDEvaluator(BaseEvaluator):
     def __init__(self, data_len=0, evaluator_model=None, batch_size=None, drop_last=False, replication_times=1, emb_scale=1,
                  replication_reduction='statistics', **kwargs):
-        super().__init__(batch_size, drop_last, replication_times, replication_reduction, 0, data_len, evaluator_model)
+        super().__init__(batch_size, drop_last, replication_times, replication_reduction, 0, data_len, evaluator_model,
+                         on_device=kwargs.get('on_device', False))
         self.emb_scale = emb_scale
 
     def single_evaluate(self, results):
         res = self.prepare_results(results)
+        if self.on_device:
+            pred, gt = embmetrics.zscore(self._motion_emb(res)), embmetrics.zscore(self._motion_emb(res, prefix=''))
+            return float(embmetrics.frechet_distance(gt, pred, self.emb_scale).item())
         pred, gt = _zscore(self._motion_emb(res)), _zscore(self._motion_emb(res, prefix=''))
         gt_mu, gt_cov = calculate_activation_statistics(gt, self.emb_scale)
         pr_mu, pr_cov = calculate_activation_statistics(pred, self.emb_scale)
@@ -348,10 +365,13 @@ class FIDEvaluator(BaseEvaluator):
 class DiversityEvaluator(BaseEvaluator):
     def __init__(self, data_len=0, evaluator_model=None, num_samples=300, batch_size=None, drop_last=False, replication_times=1,
                  replication_reduction='statistics', emb_scale=1, norm_scale=1, **kwargs):
-        super().__init__(batch_size, drop_last, replication_times, replication_reduction, 0, data_len, evaluator_model)
+        super().__init__(batch_size, drop_last, replication_times, replication_reduction, 0, data_len, evaluator_model,
+                         on_device=kwargs.get('on_device', False))
         self.num_samples, self.emb_scale, self.norm_scale = num_samples, emb_scale, norm_scale
 
     def single_evaluate(self, results):
+        if self.on_device:
+            return float(embmetrics.diversity(self._motion_emb(self.prepare_results(results)), self.num_samples, self.emb_scale, self.norm_scale).item())
         return calculate_diversity(self._motion_emb(self.prepare_results(results)), self.num_samples, self.emb_scale, self.norm_scale)
 
     def parse_values(self, values):
@@ -362,12 +382,14 @@ class MultiModalityEvaluator(BaseEvaluator):
     def __init__(self, data_len=0, evaluator_model=None, num_samples=100, num_repeats=30, num_picks=10, batch_size=None,
                  drop_last=False, replication_times=1, replication_reduction='statistics', **kwargs):
         super().__init__(batch_size, drop_last, replication_times, replication_reduction, data_len,
-                         data_len + num_samples * num_repeats, evaluator_model)
+                         data_len + num_samples * num_repeats, evaluator_model, on_device=kwargs.get('on_device', False))
         self.num_samples, self.num_repeats, self.num_picks = num_samples, num_repeats, num_picks
         self.append_indexes = [np.repeat(np.random.choice(data_len, num_samples), num_repeats) for _ in range(replication_times)]
 
     def single_evaluate(self, results):
         emb = self._motion_emb(self.prepare_results(results))
+        if self.on_device:
+            return float(embmetrics.multimodality(emb.reshape(self.num_samples, self.num_repeats, -1), self.num_picks).item())
         return calculate_multimodality(emb.reshape(self.num_samples, self.num_repeats, -1), self.num_picks)
 
     def parse_values(self, values):

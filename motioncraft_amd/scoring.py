@@ -23,7 +23,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import lib as _lib
+from . import embmetrics, lib as _lib
 from .lib import ptr as _p, stream as _stream
 from .body_model import DEFAULT_WORK_BYTES, NUM_JOINTS
 from .evaluation import L1div, calculate_activation_statistics, calculate_diversity, calculate_frechet_distance
@@ -339,18 +339,30 @@ def _fid(gt_emb, pred_emb):
     return calculate_frechet_distance(gt_mu, gt_cov, pr_mu, pr_cov)
 
 
-def _embed(evaluator_model, motion):
+def _embed_device(evaluator_model, motion):
     m = motion.float().cuda().unsqueeze(0)
     length = torch.tensor([m.shape[1]], device=m.device)
-    return evaluator_model.encode_motion(motion=m, motion_length=length, motion_mask=m, device=m.device).detach().cpu().numpy()
+    return evaluator_model.encode_motion(motion=m, motion_length=length, motion_mask=m, device=m.device).detach()
+
+
+def _embed(evaluator_model, motion):
+    return _embed_device(evaluator_model, motion).cpu().numpy()
+
+
+def _tables(emb, on_device):
+    """the per-sequence embeddings of a scorer as one table per key; ``fid`` reduces a (gt, pred) pair of them"""
+    if on_device:
+        return {k: torch.cat(v, dim=0) for k, v in emb.items()}, lambda gt, pred: float(embmetrics.frechet_distance(gt, pred).item())
+    return {k: np.concatenate(v, axis=0) for k, v in emb.items()}, _fid
 
 
 class S2GScorer:
     """The accumulators of ``CustomTrainer.test`` (s2g_test.py:262-483): ``add_sequence`` per test sequence, ``summary`` for the
-    six numbers it logs.  ``align_mask`` frames are cut from both ends before the beat alignment (:88, :420)."""
+    six numbers it logs.  ``align_mask`` frames are cut from both ends before the beat alignment (:88, :420).  ``on_device``: the
+    embeddings stay on the device and the two FIDs are reduced there (``embmetrics.frechet_distance``)."""
 
-    def __init__(self, body_model, evaluator_model, mean_vel, align_mask=60, sigma=0.3, order=7, pose_fps=30):
-        self.body_model, self.evaluator_model = body_model, evaluator_model
+    def __init__(self, body_model, evaluator_model, mean_vel, align_mask=60, sigma=0.3, order=7, pose_fps=30, on_device=False):
+        self.body_model, self.evaluator_model, self.on_device = body_model, evaluator_model, bool(on_device)
         self.aligner = BeatAlignment(sigma, order, mean_vel)              # s2g_test.py:87
         self.align_mask, self.pose_fps = int(align_mask), pose_fps
         self.l1_calculator = L1div()
@@ -382,11 +394,11 @@ class S2GScorer:
             a_offset = int(self.align_mask * (audio_sr / self.pose_fps))
             cut = audio[:int(audio_sr / self.pose_fps * T)]
             onsets = _check_onsets(self.aligner.load_audio(cut, a_offset, audio.shape[0] - a_offset, sr_audio=audio_sr))
-        ev = self.evaluator_model
-        self.emb['pred'].append(_embed(ev, _rows(rec_motion, 322, 'rec_motion')))                     # :313-325
-        self.emb['gt'].append(_embed(ev, pack_motion(tar_pose, tar_exps, tar_trans)))
-        self.emb['hand_pred'].append(_embed(ev, hand_only_motion(rec_pose, rec_trans)))                # :328-356
-        self.emb['hand_gt'].append(_embed(ev, hand_only_motion(tar_pose, tar_trans)))
+        ev, embed = self.evaluator_model, _embed_device if self.on_device else _embed
+        self.emb['pred'].append(embed(ev, _rows(rec_motion, 322, 'rec_motion')))                      # :313-325
+        self.emb['gt'].append(embed(ev, pack_motion(tar_pose, tar_exps, tar_trans)))
+        self.emb['hand_pred'].append(embed(ev, hand_only_motion(rec_pose, rec_trans)))                 # :328-356
+        self.emb['hand_gt'].append(embed(ev, hand_only_motion(tar_pose, tar_trans)))
         beta = torch.as_tensor(tar_beta)
         beta = beta if beta.dim() == 2 else beta.reshape(1, -1).expand(T, -1)
         joints = self.body_model.joints(rec_pose, None, None, beta)                                    # :364-376, :406
@@ -404,37 +416,39 @@ class S2GScorer:
         """The numbers of :451-483 under the names the reference logs them with."""
         if not self.num_sequences:
             raise ValueError('no sequence was added')
-        cat = {k: np.concatenate(v, axis=0) for k, v in self.emb.items()}
+        cat, fid = _tables(self.emb, self.on_device)
         return {'l2 loss': self.l2_all / self.total_length,
                 'lvel loss': self.lvel / self.total_length,
                 'align score': self.align / (self.total_length - 2 * self.num_sequences * self.align_mask),
                 'l1div score': self.l1_calculator.avg(),
-                'FID(Whole Body) score': _fid(cat['gt'], cat['pred']),
-                'FID (Hands) score': _fid(cat['hand_gt'], cat['hand_pred'])}
+                'FID(Whole Body) score': fid(cat['gt'], cat['pred']),
+                'FID (Hands) score': fid(cat['hand_gt'], cat['hand_pred'])}
 
 
 class M2DScorer:
     """``finedance_eval``'s scoring loop (m2d_test.py:234-309): whole-body FID, hands FID (channels 66:156 only) and the
-    diversity of the sampled embeddings with ``diversity_times = N - 1``."""
+    diversity of the sampled embeddings with ``diversity_times = N - 1``.  ``on_device``: as for ``S2GScorer``, the diversity included."""
 
-    def __init__(self, evaluator_model):
-        self.evaluator_model = evaluator_model
+    def __init__(self, evaluator_model, on_device=False):
+        self.evaluator_model, self.on_device = evaluator_model, bool(on_device)
         self.emb = dict(pred=[], gt=[], hand_pred=[], hand_gt=[])
 
     def add_sequence(self, rec_motion, gt_motion):
         rec, gt = _rows(rec_motion, 322, 'rec_motion')[:M2D_MAX_FRAMES], _rows(gt_motion, 322, 'gt_motion')     # :243
         if rec.shape[0] != gt.shape[0]:
             raise ValueError(f'the sample holds {rec.shape[0]} frames, the ground truth {gt.shape[0]} (m2d_test.py:246)')
-        ev = self.evaluator_model
-        self.emb['pred'].append(_embed(ev, rec))
-        self.emb['gt'].append(_embed(ev, gt))
-        self.emb['hand_pred'].append(_embed(ev, m2d_hand_only_motion(rec)))
-        self.emb['hand_gt'].append(_embed(ev, m2d_hand_only_motion(gt)))
+        ev, embed = self.evaluator_model, _embed_device if self.on_device else _embed
+        self.emb['pred'].append(embed(ev, rec))
+        self.emb['gt'].append(embed(ev, gt))
+        self.emb['hand_pred'].append(embed(ev, m2d_hand_only_motion(rec)))
+        self.emb['hand_gt'].append(embed(ev, m2d_hand_only_motion(gt)))
 
     def summary(self):
         if len(self.emb['pred']) < 2:
             raise ValueError('the diversity needs at least two sequences')
-        cat = {k: np.concatenate(v, axis=0) for k, v in self.emb.items()}
-        return {'FID(Whole Body) score': _fid(cat['gt'], cat['pred']),
-                'FID (Hands) score': _fid(cat['hand_gt'], cat['hand_pred']),
-                'Diversity score': calculate_diversity(cat['pred'], diversity_times=cat['pred'].shape[0] - 1, emb_scale=1.0, norm_scale=1.0)}
+        cat, fid = _tables(self.emb, self.on_device)
+        times = cat['pred'].shape[0] - 1
+        return {'FID(Whole Body) score': fid(cat['gt'], cat['pred']),
+                'FID (Hands) score': fid(cat['hand_gt'], cat['hand_pred']),
+                'Diversity score': (float(embmetrics.diversity(cat['pred'], times).item()) if self.on_device else
+                                    calculate_diversity(cat['pred'], diversity_times=times, emb_scale=1.0, norm_scale=1.0))}

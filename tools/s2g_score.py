@@ -3,7 +3,7 @@
 ``tools/s2g_test.py`` (``CustomTrainer.test``, lines 451-483), computed on the device by ``motioncraft_amd.scoring``.
 
     python tools/s2g_score.py RESULTS_DIR (--wav WAV_DIR [--resample [--load_sr 22050]] | --onsets ONSETS_DIR) --smplx_model SMPLX_NEUTRAL_2020.npz \
-        --evaluator CHECKPOINT.pth --mean_vel mean_vel.npy
+        --evaluator CHECKPOINT.pth --mean_vel mean_vel.npy [--device_metrics]
 
 RESULTS_DIR holds the ``res_<id>.npz`` / ``gt_<id>.npz`` pairs the test writes (s2g_test.py:431-448: poses [T,165],
 expressions [T,100], trans [T,3], betas [300]).  WAV_DIR holds one ``<id>.wav`` per pair.  Without --resample it is 16-bit PCM,
@@ -14,7 +14,9 @@ librosa's ``polyphase`` mode, pinned to ``scipy.signal.resample_poly``; it is no
 unpinned, so the audio differs from the reference's above roughly 0.9 of the Nyquist rate.  The onsets are detected on the device
 from the audio cut like s2g_test.py:418-419.  Or ONSETS_DIR holds one ``<id>.npy`` per pair with the onset times in seconds, i.e.
 ``alignment.load_audio`` of the audio cut by the align mask on both sides.  The sample is re-packed from its saved arrays, so the 322-d channels the ``.npz`` does not
-carry (159:209, 312:322) enter the whole-body embedding as zeros.
+carry (159:209, 312:322) enter the whole-body embedding as zeros.  With --device_metrics the embeddings never leave the device and
+the two FIDs are the nuclear-norm form of ``motioncraft_amd.embmetrics``: exact for the singular covariances of a few sequences,
+where ``scipy.linalg.sqrtm`` carries a rounding band of its own (about 1e-7 relative).
 """
 import argparse
 import glob
@@ -44,6 +46,7 @@ def parse_args():
     p.add_argument('--smplx_model', required=True, metavar='PATH', help='the published SMPL-X model file (.npz)')
     p.add_argument('--evaluator', required=True, metavar='PATH', help='checkpoint of the T2MContrastiveModel_SMPLX embedding model')
     p.add_argument('--mean_vel', required=True, metavar='PATH', help='.npy [55]: the mean joint speeds the alignment divides by')
+    p.add_argument('--device_metrics', action='store_true', help='keep the embeddings on the device and reduce the two FIDs there (embmetrics.frechet_distance)')
     p.add_argument('--align_mask', type=int, default=60), p.add_argument('--pose_fps', type=float, default=30)
     p.add_argument('--latent_dim', type=int, default=256), p.add_argument('--ff_size', type=int, default=1024)
     p.add_argument('--num_layers', type=int, default=4), p.add_argument('--num_heads', type=int, default=4)
@@ -74,7 +77,7 @@ def main():
     enc = dict(latent_dim=a.latent_dim, ff_size=a.ff_size, num_layers=a.num_layers, num_heads=a.num_heads)
     evaluator = mc.build_submodule(dict(type='T2MContrastiveModel_SMPLX', motion_encoder=dict(nfeats=322, vae=True, **enc),
                                         init_cfg=dict(type='Pretrained', checkpoint=a.evaluator)))
-    scorer = scoring.S2GScorer(body, evaluator, np.load(a.mean_vel), align_mask=a.align_mask, pose_fps=a.pose_fps)
+    scorer = scoring.S2GScorer(body, evaluator, np.load(a.mean_vel), align_mask=a.align_mask, pose_fps=a.pose_fps, on_device=a.device_metrics)
     t = lambda x: torch.from_numpy(np.asarray(x, dtype=np.float32))
     for i in ids:
         with np.load(os.path.join(a.results, f'res_{i}.npz')) as res, np.load(os.path.join(a.results, f'gt_{i}.npz')) as gt:
