@@ -92,8 +92,17 @@ typedef struct mc_model_config {
 
 /* per-step scalars of the sampler, fp64 schedule tables cast to fp32 like _extract_into_tensor
  * (gaussian_diffusion.py:1330-1343) */
+#define MC_SAMPLER_DDPM 0
+#define MC_SAMPLER_DDIM 1
+#define MC_SAMPLER_MULTISTEP 2
+/* mode MC_SAMPLER_MULTISTEP (DPM-Solver++ 2M on the data prediction; the reference has no counterpart): the update is
+ *   x_prev = c2 x + c1 x0 + eta x0_prev
+ * c1 = coefficient of x0 and c2 = coefficient of x (their roles in mode 0), eta = k1, the coefficient of the x0 of the step taken
+ * before this one (kept by the context, buffer "x0_hist"; never read when eta == 0).  text_coef / none_coef as in every mode; all
+ * other fields are ignored, no noise is drawn.  The host computes the three scalars for a whole walk
+ * (GaussianDiffusion.multistep_coefs). */
 typedef struct mc_step_coefs {
-    int32_t mode;             /* 0 = DDPM p_sample, 1 = DDIM ddim_sample           */
+    int32_t mode;             /* MC_SAMPLER_*: 0 = DDPM p_sample, 1 = DDIM ddim_sample, 2 = multistep (above) */
     float text_coef;          /* w = 1 + scale * t_orig / 1000 (stmogen.py:655-659) */
     float none_coef;          /* 1 - w                                             */
     float c1, c2;             /* posterior_mean_coef1/2[i]                          */
@@ -215,7 +224,14 @@ int mc_ctx_set_control(mc_ctx* c, const float* c_feat_dev, int32_t Tc, void* str
  * decoder (tests read intermediates through mc_ctx_get_buffer). */
 int mc_denoise(mc_ctx* c, const float* x_t_dev, int32_t step_index, float* out2_dev,
                int32_t stop_after_layers, void* stream);
-/* denoise + CFG combine + sampler update in one call; x0_dev may be NULL; x_prev_dev may alias x_t_dev */
+/* denoise + CFG combine + sampler update in one call; x0_dev may be NULL; x_prev_dev may alias x_t_dev.
+ * Mode 2 (MC_SAMPLER_MULTISTEP) in mc_sample_step, mc_sample_loop, mc_ctx_graph_capture / _step: noise_dev may be NULL, seed and
+ * noise_draw0 are ignored.  The context owns the history buffer "x0_hist" [B,T,C] (allocated on the first mode-2 call, or by
+ * mc_ctx_graph_capture of a mode-2 table: contexts that never use the mode keep their workspace size) and a "history valid" flag:
+ * a mode-2 step sets it; mc_ctx_set_condition, mc_ctx_set_control and mc_ctx_set_timesteps clear it; a mode-2 step with eta != 0
+ * while it is clear is MC_ERR_STATE.  A graph is captured for one table: a table that mixes mode 2 with other modes is MC_ERR_ARG
+ * (and a replay checks the flag on the host against the table entry of the step it is asked for).
+ * mc_sample_step_inpaint and mc_sample_step_seeded return MC_ERR_ARG for mode 2. */
 int mc_sample_step(mc_ctx* c, const float* x_t_dev, int32_t step_index, const mc_step_coefs* coefs,
                    const float* noise_dev, float* x_prev_dev, float* x0_dev, void* stream);
 
@@ -258,6 +274,7 @@ int mc_sample_step_inpaint(mc_ctx* c, const float* x_t_dev, int32_t step_index, 
 /* named context buffers: "h","z","proj","mf","qkv","ys","yt","a" (fp32 rows; refused while a reduced-precision context keeps fp16
  * planes there),"a_tail" (the deferred last FiLM block's fp32 rows),"z2","out2","emb","ss","tf",
  * "idx","gate","comb_w","key","cap_idx","cap_w" (layer selects tf / ss / cap slices),
+ * "x0_hist" (the multistep sampler's previous x0 [B,T,C]; MC_ERR_STATE before the context's first mode-2 call),
  * "route_split" (one int: the last routing call's twin-split flag, nonzero if a capacity cut separated a token from its CFG twin) */
 int mc_ctx_get_buffer(mc_ctx* c, const char* name, int32_t layer, void** dev_ptr, int64_t* numel);
 
@@ -364,6 +381,11 @@ int mc_op_conv1d_k4s2(const float* x_dev, int64_t ldx, const float* w_tapmajor_d
 int mc_op_sampler_update(const float* x_t_dev, const float* out_text_dev, const float* out_none_dev,
                          const float* noise_dev, float* x_prev_dev, float* x0_dev, int64_t n,
                          const mc_step_coefs* coefs, void* stream);
+/* the mode-2 update without a context: x0 = text_coef out_text + none_coef out_none;  x_prev = c2 x_t + c1 x0 + eta x0_hist;
+ * x0_hist <- x0 (IN-OUT [n]; read only when eta != 0, so it may be uninitialised on a first step).  x_prev_dev may alias x_t_dev,
+ * x0_dev may be NULL.  coefs->mode must be MC_SAMPLER_MULTISTEP. */
+int mc_op_sampler_multistep(const float* x_t_dev, const float* out_text_dev, const float* out_none_dev, float* x0_hist_dev,
+                            float* x_prev_dev, float* x0_dev, int64_t n, const mc_step_coefs* coefs, void* stream);
 
 /* Result post-processing of the 322-d motion.  pred_dev [B,T,322] normalised; lengths_dev [B]
  * int32 valid frames (NULL = T); mean/std_dev [322] fp64; taps_dev [4][MC_POST_MAXTAP] fp64 = normalised Gaussian

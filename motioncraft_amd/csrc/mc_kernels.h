@@ -36,7 +36,7 @@ int mc_launch_add_rows(float* out, const float* a, const float* b, const float* 
 int mc_launch_softmax_rows_small(const float* W, float* out, int rows, int cols, hipStream_t s);
 
 struct SamplerCoefs {
-    int mode;          // 0 ddpm, 1 ddim
+    int mode;          // 0 ddpm, 1 ddim, 2 multistep (reads c1 = k0, c2 = kx, eta = k1: sampler_multistep_k)
     float text_coef, none_coef;
     float c1, c2;      // ddpm: posterior_mean_coef1/2
     float log_var;     // ddpm: model_log_variance (FIXED_LARGE)
@@ -54,6 +54,11 @@ int mc_launch_sampler_update(const float* x_t, const float* out_text, const floa
                              const float* noise, float* x_prev, float* x0_out, long n,
                              SamplerCoefs c, hipStream_t s, const SamplerCoefs* table = nullptr, const int* step_ptr = nullptr,
                              const RngArgs* rng = nullptr, const PadOut* pad = nullptr);
+// mode 2 (multistep): x_prev = c.c2 x_t + c.c1 x0 + c.eta x0_hist;  x0_hist <- x0 (in-out [n], read only when c.eta != 0); no noise.
+// table / step_ptr / pad as above
+int mc_launch_sampler_multistep(const float* x_t, const float* out_text, const float* out_none, float* x0_hist, float* x_prev,
+                                float* x0_out, long n, SamplerCoefs c, hipStream_t s, const SamplerCoefs* table = nullptr,
+                                const int* step_ptr = nullptr, const PadOut* pad = nullptr);
 // out[n] = the normals / bits[n] = the raw 32-bit words of draw `rng` (either may be null)
 int mc_launch_philox_fill(float* out, uint32_t* bits, long n, RngArgs rng, hipStream_t s);
 // out = table[*step].text_coef * x + table[*step].none_coef * y   (CFG combine of the two halves under graph replay)

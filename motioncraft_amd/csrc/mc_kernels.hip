@@ -327,6 +327,69 @@ __global__ __launch_bounds__(256) void sampler_update_k(const float* x_t, const 
     }
 }
 
+// Multistep update (mode 2: DPM-Solver++ 2M on the data prediction; coefficients from GaussianDiffusion.multistep_coefs):
+//   x0 = cfg_elem(o_text, o_none);   x_prev = k1 x0_prev + (kx x + k0 x0);   hist <- x0      with kx = c2, k0 = c1, k1 = eta
+// A kernel of its own: sampler_elem / sampler_update_k keep the rounding sequence their goldens were recorded against.  Same operand
+// forms as sampler_update_k (x_prev may alias x_t; VEC = every operand 16-byte aligned; table / step_ptr under graph replay; PadOut).
+// `hist` is in-out: every thread reads its own elements before it writes them, and only when k1 != 0 (kernel-uniform) -- a first step
+// meets an uninitialised buffer, and 0 x NaN would be NaN.  The products are spelled out so the bits do not depend on contraction.
+__device__ __forceinline__ float multistep_elem(float x, float x0, float x0_prev, float kx, float k0, float k1) {
+    return fmaf(k1, x0_prev, fmaf(kx, x, __fmul_rn(k0, x0)));
+}
+template <bool VEC>
+__global__ __launch_bounds__(256) void sampler_multistep_k(const float* x_t, const float* __restrict__ o_text,
+                                                           const float* __restrict__ o_none, float* __restrict__ hist,
+                                                           float* x_prev, float* __restrict__ x0_out, long n, SamplerCoefs c,
+                                                           const SamplerCoefs* __restrict__ table,
+                                                           const int* __restrict__ step_ptr, PadOut po) {
+    if (table) {          // graph replay: this step's schedule coefficients from the device table
+        const float tc = c.text_coef, nc = c.none_coef;
+        c = table[*step_ptr];
+        c.text_coef = tc;
+        c.none_coef = nc;
+    }
+    const float kx = c.c2, k0 = c.c1, k1 = c.eta;
+    const bool use_hist = k1 != 0.f;
+    const long ngroups = (n + 3) >> 2;
+    for (long gi = (long)blockIdx.x * blockDim.x + threadIdx.x; gi < ngroups; gi += (long)gridDim.x * blockDim.x) {
+        const long i = gi * 4;
+        if (VEC && i + 4 <= n) {
+            const f32x4 x = *reinterpret_cast<const f32x4*>(x_t + i);
+            const f32x4 a = *reinterpret_cast<const f32x4*>(o_text + i), b = *reinterpret_cast<const f32x4*>(o_none + i);
+            f32x4 hp = {0.f, 0.f, 0.f, 0.f};
+            if (use_hist) hp = *reinterpret_cast<const f32x4*>(hist + i);
+            f32x4 out, x0v;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                x0v[j] = cfg_elem(a[j], b[j], c);
+                out[j] = multistep_elem(x[j], x0v[j], hp[j], kx, k0, k1);
+            }
+            *reinterpret_cast<f32x4*>(x_prev + i) = out;
+            *reinterpret_cast<f32x4*>(hist + i) = x0v;
+            if (x0_out) *reinterpret_cast<f32x4*>(x0_out + i) = x0v;
+            if (po.xpad) {        // the next step's pose-encoder operand: the same rows at the padded stride (pad columns stay zero)
+                long row = i / po.C;
+                int col = (int)(i - row * po.C);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    po.xpad[row * po.Cp + col] = out[j];
+                    if (++col == po.C) { col = 0; ++row; }
+                }
+            }
+        } else {
+            for (int j = 0; j < 4 && i + j < n; ++j) {
+                const float x0 = cfg_elem(o_text[i + j], o_none[i + j], c);
+                const float hp = use_hist ? hist[i + j] : 0.f;
+                const float o = multistep_elem(x_t[i + j], x0, hp, kx, k0, k1);
+                x_prev[i + j] = o;
+                hist[i + j] = x0;
+                if (x0_out) x0_out[i + j] = x0;
+                if (po.xpad) po.xpad[(i + j) / po.C * po.Cp + (i + j) % po.C] = o;
+            }
+        }
+    }
+}
+
 // the same draws written to memory (tests; callers that want the loop's noise stream)
 __global__ __launch_bounds__(256) void philox_fill_k(float* __restrict__ out, uint32_t* __restrict__ bits, long n, RngArgs rng) {
     const long ngroups = (n + 3) >> 2;
@@ -556,6 +619,24 @@ int mc_launch_sampler_update(const float* x_t, const float* out_text, const floa
     if (dev_rng) { if (vec) MC_SU(true, true); else MC_SU(true, false); }
     else { if (vec) MC_SU(false, true); else MC_SU(false, false); }
 #undef MC_SU
+    MC_LAUNCH_CHECK();
+    return MC_OK;
+}
+
+int mc_launch_sampler_multistep(const float* x_t, const float* out_text, const float* out_none, float* x0_hist, float* x_prev, float* x0_out, long n,
+                                SamplerCoefs c, hipStream_t s, const SamplerCoefs* table, const int* step_ptr, const PadOut* pad) {
+    MC_REQUIRE(x_t && out_text && out_none && x0_hist && x_prev && n >= 0, "multistep update: null operand");
+    MC_REQUIRE(table || c.mode == 2, "multistep update: coefficients of mode %d", c.mode);
+    MC_REQUIRE(x0_hist != x_t && x0_hist != x_prev && x0_hist != x0_out && x0_hist != out_text && x0_hist != out_none,
+               "multistep update: the history buffer aliases another operand");
+    if (n == 0) return MC_OK;
+    const bool vec = ((uintptr_t)x_t | (uintptr_t)out_text | (uintptr_t)out_none | (uintptr_t)x_prev | (uintptr_t)x0_out | (uintptr_t)x0_hist) % 16 == 0;
+    int blocks = cdiv((n + 3) / 4, 256);
+    if (blocks > 2048) blocks = 2048;
+    const PadOut po = pad ? *pad : PadOut();
+    MC_REQUIRE(!po.xpad || (po.C > 0 && po.Cp >= po.C), "multistep update: bad padded-copy shape");
+    if (vec) hipLaunchKernelGGL((sampler_multistep_k<true>), dim3(blocks), dim3(256), 0, s, x_t, out_text, out_none, x0_hist, x_prev, x0_out, n, c, table, step_ptr, po);
+    else hipLaunchKernelGGL((sampler_multistep_k<false>), dim3(blocks), dim3(256), 0, s, x_t, out_text, out_none, x0_hist, x_prev, x0_out, n, c, table, step_ptr, po);
     MC_LAUNCH_CHECK();
     return MC_OK;
 }

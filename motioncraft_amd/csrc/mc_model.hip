@@ -400,6 +400,8 @@ static void graph_release(mc_ctx* c) {       // the captured sampler step (mc_ct
     if (c->graph_exec) { (void)hipGraphExecDestroy(c->graph_exec); c->graph_exec = nullptr; }
     if (c->graph) { (void)hipGraphDestroy(c->graph); c->graph = nullptr; }
     c->graph_steps = 0;
+    c->graph_multistep = false;
+    c->graph_k1.clear();
 }
 static void prof_clear(mc_ctx* c) {
     for (auto& p : c->prof) { if (p.e0) (void)hipEventDestroy(p.e0); if (p.e1) (void)hipEventDestroy(p.e1); }
@@ -519,6 +521,7 @@ int mc_ctx_enable_capture(mc_ctx* c) {
 int mc_ctx_set_timesteps(mc_ctx* c, const int32_t* t_orig_host, int32_t S, void* stream) {
     MC_REQUIRE(c && t_orig_host, "null argument");
     MC_REQUIRE(S >= 1 && S <= c->maxS, "num_steps=%d exceeds context max_steps=%d", S, c->maxS);
+    c->hist_valid = false;       // (multistep sampler: the previous x0 belongs to the old schedule)
     hipStream_t s = (hipStream_t)stream;
     const mc_model_config& g = c->m->cfg;
     const int D = g.latent_dim * g.num_parts, Te = g.time_embed_dim;
@@ -544,6 +547,7 @@ int mc_ctx_set_timesteps(mc_ctx* c, const int32_t* t_orig_host, int32_t S, void*
 // condition batch (the MoE capacity couples both halves, so both are routed together).
 int mc_ctx_set_condition(mc_ctx* c, const float* xf_out_dev, const float* mask_dev, void* stream) {
     MC_REQUIRE(c && xf_out_dev && mask_dev, "null argument");
+    c->hist_valid = false;       // (multistep sampler: the previous x0 belongs to the old condition)
     hipStream_t s = (hipStream_t)stream;
     const mc_model_config& g = c->m->cfg;
     const int L = g.latent_dim, Dt = g.text_latent_dim, Nt = g.max_text_len;
@@ -566,6 +570,7 @@ int mc_ctx_set_condition(mc_ctx* c, const float* xf_out_dev, const float* mask_d
 // step-invariant, evaluated once per condition batch.
 int mc_ctx_set_control(mc_ctx* c, const float* c_feat_dev, int32_t Tc, void* stream) {
     MC_REQUIRE(c, "null context");
+    c->hist_valid = false;       // (multistep sampler: the previous x0 belongs to the old control condition)
     const mc_model_config& g = c->m->cfg;
     if (!c_feat_dev) { c->have_ctrl = false; return MC_OK; }
     MC_REQUIRE(g.num_ctrl_layers > 0, "the model has no control branch");
@@ -602,14 +607,42 @@ int mc_denoise(mc_ctx* c, const float* x_t, int32_t step, float* out2_dev, int32
 }
 
 
+// ---- multistep sampler (mode 2): the context's history buffer and its "history valid" flag ----
+static bool is_multistep(const mc_step_coefs* k) { return k->mode == MC_SAMPLER_MULTISTEP; }
+static int check_mode(const mc_step_coefs* k) {
+    MC_REQUIRE(k->mode == MC_SAMPLER_DDPM || k->mode == MC_SAMPLER_DDIM || k->mode == MC_SAMPLER_MULTISTEP, "unknown sampler mode %d", k->mode);
+    return MC_OK;
+}
+// allocated by the first mode-2 call: contexts that never use the mode keep their workspace size
+static int hist_alloc(mc_ctx* c) {
+    return c->x0_hist ? MC_OK : ws_alloc(c, &c->x0_hist, (size_t)c->B * c->T * c->m->cfg.input_feats);
+}
+// before a mode-2 step with coefficient k1 of the previous x0
+static int hist_require(const mc_ctx* c, float k1, int32_t step) {
+    if (k1 != 0.f && !c->hist_valid) {
+        mc_set_error("multistep step at schedule index %d reads the previous x0 (k1 = %g), but the context holds none: no multistep step ran since "
+                     "the condition / control / timesteps were set", step, (double)k1);
+        return MC_ERR_STATE;
+    }
+    return MC_OK;
+}
+
 int mc_sample_step(mc_ctx* c, const float* x_t, int32_t step, const mc_step_coefs* k, const float* noise,
                    float* x_prev, float* x0, void* stream) {
-    MC_REQUIRE(c && x_t && k && noise && x_prev, "null argument");
+    MC_REQUIRE(c && x_t && k && x_prev, "null argument");
+    int r;
+    if ((r = check_mode(k))) return r;
+    const bool ms = c->graph_mode ? c->graph_multistep : is_multistep(k);
+    MC_REQUIRE(noise || ms, "null argument (noise_dev may be NULL in mode 2 only)");
+    if (ms && !c->graph_mode) {
+        if ((r = hist_require(c, k->eta, step))) return r;
+        if ((r = hist_alloc(c))) return r;
+    }
     X0Parts p;
-    if (int r = denoise_combined(c, x_t, step, k, stream, &p)) return r;
-    const long n = (long)c->B * c->T * c->m->cfg.input_feats;
-    return mc_launch_sampler_update(x_t, p.a, p.second(), noise, x_prev, x0, n, p.coefs(k), (hipStream_t)stream,
-                                    c->graph_mode ? c->gcoefs : nullptr, c->graph_mode ? c->gstep : nullptr);
+    if ((r = denoise_combined(c, x_t, step, k, stream, &p))) return r;
+    if ((r = sampler_update(c, x_t, p, k, noise, x_prev, x0, (hipStream_t)stream))) return r;
+    if (ms && !c->graph_mode) c->hist_valid = true;
+    return MC_OK;
 }
 
 static RngArgs rng_args(uint64_t seed, uint64_t draw) {
@@ -635,15 +668,23 @@ int mc_sample_loop(mc_ctx* c, float* x, const int32_t* step_indices, const mc_st
     const bool fold_pad = chain_on(c, kChainPadX) && c->xpad;
     c->xpad_ready = false;
     for (int k = 0; k < num_steps; ++k) {
+        int r = check_mode(&coefs[k]);
+        if (r == MC_OK && is_multistep(&coefs[k])) r = hist_alloc(c);
+        if (r != MC_OK) return r;
+    }
+    for (int k = 0; k < num_steps; ++k) {
+        const bool ms = is_multistep(&coefs[k]);
+        int r = ms ? hist_require(c, coefs[k].eta, step_indices[k]) : MC_OK;
+        if (r != MC_OK) { c->xpad_ready = false; return r; }
         X0Parts p;
-        int r = denoise_combined(c, x, step_indices[k], &coefs[k], stream, &p);
+        r = denoise_combined(c, x, step_indices[k], &coefs[k], stream, &p);
         if (r != MC_OK) { c->xpad_ready = false; return r; }
         const RngArgs rng = rng_args(seed, noise_draw0 + (uint64_t)k);
         const bool more = fold_pad && k + 1 < num_steps;
-        r = mc_launch_sampler_update(x, p.a, p.second(), noise ? noise + (long)k * n : nullptr, x, k + 1 == num_steps ? x0_last : nullptr, n,
-                                     p.coefs(&coefs[k]), (hipStream_t)stream, nullptr, nullptr, noise ? nullptr : &rng,
-                                     more ? &po : nullptr);
+        r = sampler_update(c, x, p, &coefs[k], noise ? noise + (long)k * n : nullptr, x, k + 1 == num_steps ? x0_last : nullptr, (hipStream_t)stream,
+                           noise ? nullptr : &rng, more ? &po : nullptr);
         if (r != MC_OK) { c->xpad_ready = false; return r; }
+        if (ms) c->hist_valid = true;
         c->xpad_ready = more;
     }
     c->xpad_ready = false;
@@ -658,14 +699,26 @@ int mc_op_philox_normal(float* out, uint32_t* bits, int64_t n, uint64_t seed, ui
 // ---- hipGraph replay of mc_sample_step -------------------------------------------------------------------------------
 int mc_ctx_graph_capture(mc_ctx* c, float* x_dev, const float* noise_dev, const mc_step_coefs* coefs_host, int32_t num_steps,
                          void* stream) {
-    MC_REQUIRE(c && x_dev && noise_dev && coefs_host, "null argument");
+    MC_REQUIRE(c && x_dev && coefs_host, "null argument");
     MC_REQUIRE(c->have_cond, "mc_ctx_set_condition not called");
     MC_REQUIRE(num_steps >= 1 && num_steps == c->S, "num_steps=%d must equal the schedule set by mc_ctx_set_timesteps (%d)", num_steps, c->S);
     MC_REQUIRE(!c->cap_idx, "routing capture (tests) and graph replay are mutually exclusive");
     hipStream_t s = (hipStream_t)stream;
     MC_REQUIRE(s != nullptr, "graph capture needs a non-default stream");
-    graph_release(c);
     int r;
+    // the update kernel is baked into the graph and the mode comes from the device table: one graph per table, all of it mode 2 or none of it
+    int n_ms = 0;
+    for (int i = 0; i < num_steps; ++i) {
+        if ((r = check_mode(&coefs_host[i]))) return r;
+        n_ms += is_multistep(&coefs_host[i]) ? 1 : 0;
+    }
+    MC_REQUIRE(n_ms == 0 || n_ms == num_steps, "the table mixes mode 2 (%d entries) with other modes (%d): capture one graph per table", n_ms, num_steps - n_ms);
+    MC_REQUIRE(noise_dev || n_ms, "null argument (noise_dev may be NULL for a mode-2 table only)");
+    graph_release(c);
+    if (n_ms && (r = hist_alloc(c))) return r;
+    c->graph_multistep = n_ms != 0;
+    c->graph_k1.assign(num_steps, 0.f);
+    for (int i = 0; i < num_steps; ++i) c->graph_k1[i] = n_ms ? coefs_host[i].eta : 0.f;
     if (!c->gstep && (r = ws_alloc(c, &c->gstep, 1)) != MC_OK) return r;
     if (!c->gcoefs && (r = ws_alloc(c, &c->gcoefs, (size_t)c->maxS)) != MC_OK) return r;
     std::vector<SamplerCoefs> tab(num_steps);
@@ -694,9 +747,11 @@ int mc_ctx_graph_step(mc_ctx* c, int32_t step, void* stream) {
     MC_REQUIRE(c && c->graph_exec, "no captured graph (mc_ctx_graph_capture)");
     MC_REQUIRE(step >= 0 && step < c->graph_steps, "step_index %d outside the %d captured steps", step, c->graph_steps);
     hipStream_t s = (hipStream_t)stream;
-    int r = mc_launch_set_int(c->gstep, step, s);
-    if (r != MC_OK) return r;
+    int r;
+    if (c->graph_multistep && (r = hist_require(c, c->graph_k1[step], step))) return r;
+    if ((r = mc_launch_set_int(c->gstep, step, s))) return r;
     MC_HIP(hipGraphLaunch(c->graph_exec, s));
+    if (c->graph_multistep) c->hist_valid = true;
     return MC_OK;
 }
 
@@ -709,6 +764,7 @@ int mc_ctx_graph_release(mc_ctx* c) {
 int mc_sample_step_seeded(mc_ctx* c, float* x_t, int32_t step, const mc_step_coefs* k, const float* noise,
                           const mc_seed* sd, float* x_prev, float* x0, void* stream) {
     MC_REQUIRE(c && x_t && k && noise && x_prev && sd, "null argument");
+    MC_REQUIRE(!is_multistep(k), "mc_sample_step_seeded: the multistep sampler (mode 2) has no pre_seq / transl_req seeding");
     MC_REQUIRE(sd->pre_len >= 0 && sd->pre_len <= c->T, "pre_seq has %d frames, the window %d", sd->pre_len, c->T);
     MC_REQUIRE(sd->num_transl >= 0 && sd->num_transl <= MC_MAX_TRANSL, "num_transl=%d outside [0, %d]", sd->num_transl, MC_MAX_TRANSL);
     MC_REQUIRE(sd->num_transl == 0 || c->T >= 2, "transl_req seeds frames 0 and 1: the window has %d", c->T);
@@ -730,6 +786,7 @@ int mc_sample_step_seeded(mc_ctx* c, float* x_t, int32_t step, const mc_step_coe
 int mc_sample_step_inpaint(mc_ctx* c, const float* x_t, int32_t step, const mc_step_coefs* k, const float* noise,
                            const mc_inpaint* ip, float* x_prev, float* x0, void* stream) {
     MC_REQUIRE(c && x_t && k && noise && x_prev && ip, "null argument");
+    MC_REQUIRE(!is_multistep(k), "mc_sample_step_inpaint: the multistep sampler (mode 2) has no outpainting (RePaint) form");
     X0Parts p;
     if (int r = denoise_combined(c, x_t, step, k, stream, &p)) return r;
     const int C = c->m->cfg.input_feats;
@@ -817,6 +874,10 @@ int mc_ctx_get_buffer(mc_ctx* c, const char* name, int32_t layer, void** dev_ptr
     else if (n == "cb" && c->cb) { p = c->cb; cnt = c->rows * D; }
     else if (n == "cap_idx" && c->cap_idx) { p = c->cap_idx + (long)layer * 2 * c->N; cnt = 2 * c->N; }
     else if (n == "cap_w" && c->cap_w) { p = c->cap_w + (long)layer * 2 * c->N; cnt = 2 * c->N; }
+    else if (n == "x0_hist") {
+        if (!c->x0_hist) { mc_set_error("buffer 'x0_hist' does not exist before the context's first multistep (mode 2) call"); return MC_ERR_STATE; }
+        p = c->x0_hist; cnt = (int64_t)c->B * c->T * g.input_feats;
+    }
     else if (n == "route_split") { p = const_cast<int*>(mc_route_split_flag_ptr(c->rb)); cnt = 1; }
     else { mc_set_error("unknown buffer '%s'", name); return MC_ERR_ARG; }
     *dev_ptr = p;
@@ -947,6 +1008,13 @@ int mc_op_sampler_update(const float* x_t, const float* ot, const float* on, con
                          int64_t n, const mc_step_coefs* k, void* stream) {
     MC_REQUIRE(x_t && ot && on && noise && x_prev && k, "null argument");
     return mc_launch_sampler_update(x_t, ot, on, noise, x_prev, x0, n, to_coefs(k), (hipStream_t)stream);
+}
+
+int mc_op_sampler_multistep(const float* x_t, const float* ot, const float* on, float* x0_hist, float* x_prev, float* x0, int64_t n,
+                            const mc_step_coefs* k, void* stream) {
+    MC_REQUIRE(x_t && ot && on && x0_hist && x_prev && k && n >= 0, "bad argument");
+    MC_REQUIRE(is_multistep(k), "mc_op_sampler_multistep: coefficients of mode %d (MC_SAMPLER_MULTISTEP = 2 expected)", k->mode);
+    return mc_launch_sampler_multistep(x_t, ot, on, x0_hist, x_prev, x0, n, to_coefs(k), (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -745,3 +745,17 @@ int denoise_combined(mc_ctx* c, const float* x_t, int32_t step, const mc_step_co
     }
     return dense(c, c->z2, D, c->dec_w, D, c->dec_b, nullptr, 0, c->out2, C, BT, C, D, ACT_NONE, s);
 }
+
+// The sampler update behind denoise_combined: ONE place picks the kernel by mode for the per-step entry, the fused loop and the captured
+// step.  Under capture the coefficients (the mode among them) come from the device table at replay, so the kernel is picked from what
+// mc_ctx_graph_capture found in the table (all mode 2 or none of it), not from the step-0 entry `k`.
+int sampler_update(mc_ctx* c, const float* x_t, const X0Parts& x0p, const mc_step_coefs* k, const float* noise, float* x_prev, float* x0,
+                   hipStream_t s, const RngArgs* rng, const PadOut* pad) {
+    const long n = (long)c->B * c->T * c->m->cfg.input_feats;
+    const SamplerCoefs* table = c->graph_mode ? c->gcoefs : nullptr;
+    const int* step_ptr = c->graph_mode ? c->gstep : nullptr;
+    const bool multistep = c->graph_mode ? c->graph_multistep : k->mode == MC_SAMPLER_MULTISTEP;
+    if (!multistep) return mc_launch_sampler_update(x_t, x0p.a, x0p.second(), noise, x_prev, x0, n, x0p.coefs(k), s, table, step_ptr, rng, pad);
+    MC_REQUIRE(c->x0_hist, "multistep update without a history buffer");
+    return mc_launch_sampler_multistep(x_t, x0p.a, x0p.second(), c->x0_hist, x_prev, x0, n, x0p.coefs(k), s, table, step_ptr, pad);
+}

@@ -6,7 +6,8 @@ Mirrors the sampling half of the reference's ``mogen/models/utils/gaussian_diffu
 so callers written against it keep working; the per-step arithmetic itself (network, CFG combine,
 posterior / DDIM update) runs in libmotioncraft_amd.so.  The RePaint / outpainting mode of the DDIM loop
 (``y = {gt, outpainting_mask}``: :492-501, :855-877, the resampling ``harmonize`` loop :1050-1118 and its jump
-schedule ``mogen/models/utils/scheduler.py:178-208``) is covered too.  Training losses, learned variances and
+schedule ``mogen/models/utils/scheduler.py:178-208``) is covered too.  ``dpm_solver_sample_loop`` (DPM-Solver++ 2M, ``multistep_coefs``,
+``logsnr_timesteps``) is this project's own: the reference has no second-order sampler.  Training losses, learned variances and
 cond_fn guidance are outside this path and raise loudly.
 """
 import enum
@@ -50,8 +51,11 @@ def get_named_beta_schedule(schedule_name, num_diffusion_timesteps):
 
 
 def space_timesteps(num_timesteps, section_counts):
-    """Retained original timesteps for a respacing spec ('15,15,8,6,6', [..] or 'ddimN')."""
+    """Retained original timesteps for a respacing spec ('15,15,8,6,6', [..], 'ddimN', or 'logsnrN': the linear schedule's
+    ``logsnr_timesteps``; ``build_diffusion`` passes the configured schedule's betas itself)."""
     if isinstance(section_counts, str):
+        if section_counts.startswith('logsnr'):
+            return logsnr_timesteps(num_timesteps, int(section_counts[6:]))
         if section_counts.startswith('ddim'):
             want = int(section_counts[4:])
             for stride in range(1, num_timesteps):
@@ -72,6 +76,31 @@ def space_timesteps(num_timesteps, section_counts):
             pos += stride
         start += size
     return set(kept)
+
+
+def logsnr_timesteps(num_timesteps_or_betas, S):
+    """Original timesteps for ``SpacedDiffusion(use_timesteps=...)`` spaced uniformly in the log-SNR half
+    ``lambda(t) = log(sqrt(ab_t) / sqrt(1 - ab_t))``: ``S`` points between ``lambda(T-1)`` and ``lambda(0)``, each snapped to the
+    integer timestep whose ``lambda`` is nearest.  ``T-1`` and ``0`` are always in the set.  Neighbouring points can snap to the same
+    timestep (the schedule is flat in ``lambda`` where it is steep in ``t``), so the set may hold FEWER than ``S`` values.  An
+    integer argument means the linear schedule of that many steps; otherwise it is the ``betas`` array."""
+    if np.ndim(num_timesteps_or_betas) == 0:
+        betas = get_named_beta_schedule('linear', int(num_timesteps_or_betas))
+    else:
+        betas = np.asarray(num_timesteps_or_betas, dtype=np.float64)
+    S, T = int(S), len(betas)
+    if S < 2 or T < 2:
+        raise ValueError(f'logsnr_timesteps: S={S} points of a {T}-step schedule (both must be at least 2)')
+    ac = np.cumprod(1.0 - betas)
+    lam = 0.5 * (np.log(ac) - np.log1p(-ac))                   # decreasing in t
+    kept = {0, T - 1}
+    for v in np.linspace(lam[T - 1], lam[0], S):
+        j = int(np.searchsorted(-lam, -v))                      # first t with lam[t] <= v
+        j = min(max(j, 0), T - 1)
+        if j > 0 and abs(lam[j - 1] - v) <= abs(lam[j] - v):
+            j -= 1
+        kept.add(j)
+    return kept
 
 
 class GaussianDiffusion:
@@ -146,6 +175,45 @@ class GaussianDiffusion:
         c.ab, c.ab_prev, c.eta = self.alphas_cumprod[i], self.alphas_cumprod_prev[i], eta
         c.nonzero = 0.0 if i == 0 else 1.0
         return c
+
+    def multistep_coefs(self, indices, scale, order=2):
+        """DPM-Solver++ (2M) on the data prediction: the ``StepCoefs`` (mode 2) of a whole walk through the schedule indices
+        ``indices``.  Every update is ``x_prev = kx x + k0 x0 + k1 x0_prev`` (``c2``, ``c1`` and ``eta`` of the struct), computed in fp64
+        and cast to fp32 like ``step_coefs`` casts its tables.  With ``alpha = sqrt(ab)``, ``sigma = sqrt(1 - ab)``, ``lambda =
+        log(alpha / sigma)``, s = index i and t = the level below it, ``h = lambda_t - lambda_s``:
+
+          order 1:  kx = sigma_t / sigma_s,  k0 = -alpha_t expm1(-h),  k1 = 0          (DDIM with eta = 0)
+          order 2:  r = h_prev / h,  k0 = -alpha_t expm1(-h) (1 + 1 / (2 r)),  k1 = alpha_t expm1(-h) / (2 r)
+
+        ``k1`` weighs the x0 of the step taken just before, so the coefficients belong to the sequence, not to an index.  First-order
+        are: the first step of the walk (no history), the step at i == 1 (the last one with a finite h: the lower-order final step,
+        always on) and the step at i == 0, which has sigma_t = 0 and is emitted as exactly (0, 1, 0): x_prev = x0."""
+        if order not in (1, 2):
+            raise ValueError(f'order={order!r}: the multistep solver is implemented for order 1 and 2')
+        out, h_prev = [], None
+        for i in indices:
+            i = int(i)
+            t_orig = self.timestep_map[i]
+            w = (1 - (1000 - int(t_orig)) / 1000) * scale + 1
+            c = _lib.StepCoefs()
+            c.mode = _lib.MC_SAMPLER_MULTISTEP
+            c.text_coef, c.none_coef = w, 1 - w
+            ab_s, ab_t = float(self.alphas_cumprod[i]), float(self.alphas_cumprod_prev[i])
+            if ab_t >= 1.0:
+                kx, k0, k1, h = 0.0, 1.0, 0.0, None
+            else:
+                a_s, s_s, a_t, s_t = math.sqrt(ab_s), math.sqrt(1 - ab_s), math.sqrt(ab_t), math.sqrt(1 - ab_t)
+                h = math.log(a_t / s_t) - math.log(a_s / s_s)
+                kx, k0, k1 = s_t / s_s, -a_t * math.expm1(-h), 0.0
+                if order == 2 and h_prev is not None and i != 1:
+                    r = h_prev / h
+                    k0, k1 = k0 * (1 + 1 / (2 * r)), -k0 / (2 * r)
+            c.c2, c.c1, c.eta = kx, k0, k1
+            c.ab, c.ab_prev = ab_s, ab_t            # (informative: mode 2 reads c1, c2, eta and the two CFG weights only)
+            c.nonzero = 0.0 if i == 0 else 1.0
+            out.append(c)
+            h_prev = h
+        return out
 
     def _loop(self, mode, model, shape, noise, model_kwargs, device, progress, eta, step_noise, generator,
               num_steps=None, trajectory=None, pre_seq=None, transl_req=None, graph=False, fused=True):
@@ -346,6 +414,83 @@ class GaussianDiffusion:
                           generator, num_steps, trajectory, pre_seq=pre_seq, graph=graph, fused=fused)
 
 
+    def dpm_solver_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
+                               model_kwargs=None, device=None, progress=False, order=2, generator=None, num_steps=None,
+                               trajectory=None, graph=False, fused=True, pre_seq=None, transl_req=None):
+        """DPM-Solver++ (2M) on the model's x0 prediction: a second-order multistep walk down the (spaced) schedule, one denoiser call
+        per step like DDIM, meant for 10-20 steps (``respace='ddimN'`` or ``'logsnrN'``).  The reference has no such sampler; the
+        coefficients are ``multistep_coefs`` (first-order first and last finite step, ``x = x0`` at index 0), ``order=1`` is DDIM with
+        eta = 0.  Deterministic given ``noise``: no per-step draw exists, ``generator`` only draws x_T when ``noise`` is None.
+        ``num_steps`` / ``trajectory`` / ``graph`` / ``fused`` as in the other two loops.  No outpainting (RePaint) and no
+        pre_seq / transl_req seeding: those raise."""
+        self._check_supported(clip_denoised, denoised_fn, cond_fn, model_kwargs, pre_seq, transl_req)
+        if order not in (1, 2):
+            raise ValueError(f'order={order!r}: the multistep solver is implemented for order 1 and 2')
+        if model_kwargs is None:
+            model_kwargs = {}
+        keep = ((model_kwargs.get('y', {}) or {}).get('outpainting_mask', None))
+        if keep is not None and bool(keep.any()):
+            raise NotImplementedError('dpm_solver_sample_loop with an outpainting mask (RePaint): not implemented for the '
+                                      'multistep sampler, use ddim_sample_loop')
+        if pre_seq is not None:
+            raise NotImplementedError('dpm_solver_sample_loop with pre_seq seeding: not implemented for the multistep sampler')
+        if transl_req:
+            raise NotImplementedError('dpm_solver_sample_loop with transl_req seeding: not implemented for the multistep sampler')
+        if not isinstance(shape, (tuple, list)):
+            raise AssertionError('shape must be a tuple or list')
+        B, T, C = shape
+        if device is None:
+            device = torch.device('cuda', torch.cuda.current_device())
+        ctx = model.sampling_context(B, T, self.timestep_map, model_kwargs, device)
+        if noise is not None:
+            img = noise.to(device=device, dtype=torch.float32).contiguous().clone()
+        else:
+            img = torch.randn(*shape, device=device, generator=generator)
+        indices = list(range(self.num_timesteps))[::-1]
+        # k1 of a step belongs to the walk: the coefficients of the whole descent; a truncated run is a prefix of it
+        coefs = self.multistep_coefs(indices, model.cfg_scale, order)
+        if num_steps is not None:
+            indices, coefs = indices[:num_steps], coefs[:num_steps]
+        if graph:
+            if trajectory is not None:
+                raise ValueError('graph replay covers the plain step (no trajectory)')
+            key = ('dpmpp', int(order), float(model.cfg_scale), tuple(int(t) for t in self.timestep_map))
+            st = getattr(ctx, '_graph_state', None)
+            if st is None or st['key'] != key:
+                side = torch.cuda.Stream(device=device)
+                side.wait_stream(torch.cuda.current_stream(device))
+                with torch.cuda.stream(side):
+                    gx = torch.empty_like(img)
+                    table = self.multistep_coefs(list(range(self.num_timesteps))[::-1], model.cfg_scale, order)[::-1]
+                    ctx.graph_capture(gx, None, table)            # table[i]: schedule index i of the descent
+                st = ctx._graph_state = dict(key=key, stream=side, x=gx, noise=None)
+            side = st['stream']
+            side.wait_stream(torch.cuda.current_stream(device))
+            with torch.cuda.stream(side):
+                st['x'].copy_(img)
+                for i in indices:
+                    ctx.graph_step(i)
+                img.copy_(st['x'])
+            torch.cuda.current_stream(device).wait_stream(side)
+        elif fused and trajectory is None and not progress:
+            ctx.sample_loop(img, indices, coefs, noise=None)
+        else:
+            plan = list(zip(indices, coefs))
+            if progress:
+                from tqdm.auto import tqdm
+                plan = tqdm(plan)
+            nxt = torch.empty_like(img)
+            x0 = torch.empty_like(img) if trajectory is not None else None
+            for i, c in plan:
+                ctx.sample_step(img, i, c, None, x_prev=nxt, x0=x0)
+                img, nxt = nxt, img
+                if trajectory is not None:
+                    trajectory.append((i, img.clone(), x0.clone()))
+        if getattr(ctx, 'uses_coop_routing', False):
+            ctx.check()
+        return img
+
+
 def get_schedule_jump_cjm_ddim(time_respacing=25, jump_length=1, jump_n_sample=1):
     """Visit order of the resampling ("harmonize") DDIM loop, mirrors mogen/models/utils/scheduler.py:178-208:
     start 60 % into the schedule (step 15 of 25), walk down to 0, and the first jump_n_sample-1 times a multiple
@@ -392,6 +537,11 @@ def build_diffusion(cfg, opt=None):
     var_type = {'learned': ModelVarType.LEARNED, 'fixed_small': ModelVarType.FIXED_SMALL,
                 'fixed_large': ModelVarType.FIXED_LARGE, 'learned_range': ModelVarType.LEARNED_RANGE}[cfg['model_var_type']]
     if cfg.get('respace', None) is not None:
-        return SpacedDiffusion(use_timesteps=space_timesteps(cfg['diffusion_steps'], cfg['respace']), betas=betas,
+        respace = cfg['respace']
+        if isinstance(respace, str) and respace.startswith('logsnr'):
+            use = logsnr_timesteps(betas, int(respace[6:]))
+        else:
+            use = space_timesteps(cfg['diffusion_steps'], respace)
+        return SpacedDiffusion(use_timesteps=use, betas=betas,
                                model_mean_type=mean_type, model_var_type=var_type, loss_type=LossType.MSE, opt=opt)
     return GaussianDiffusion(betas=betas, model_mean_type=mean_type, model_var_type=var_type, loss_type=LossType.MSE)

@@ -180,8 +180,10 @@ class NativeContext:
         return out2
 
     def sample_step(self, x_t, step_index, coefs, noise, x_prev=None, x0=None):
+        """One step (mc_sample_step).  ``noise`` may be None for multistep coefficients (mode 2) only: that mode draws nothing and
+        keeps the previous x0 in the context instead."""
         x = _dev_f32(x_t, 'x_t')
-        n = _dev_f32(noise, 'noise')
+        n = _dev_f32(noise, 'noise') if noise is not None else None
         if x_prev is None:
             x_prev = torch.empty_like(x)
         _lib.check(self.lib.mc_sample_step(self.handle, _ptr(x), int(step_index), ctypes.byref(coefs), _ptr(n),
@@ -212,9 +214,9 @@ class NativeContext:
         """Capture mc_sample_step into ONE hipGraph for the whole schedule.  ``x`` [B,T,C] is updated in place by every
         ``graph_step``, ``noise`` [B,T,C] is read by every replay (refill it in place between steps); both tensors must stay
         alive and keep their addresses.  ``coefs``: list of StepCoefs for every schedule index.  Call on a non-default
-        torch stream (``with torch.cuda.stream(s):``)."""
-        x, noise = _dev_f32(x, 'x'), _dev_f32(noise, 'noise')
-        if tuple(x.shape) != (self.B, self.T, self.C) or noise.shape != x.shape:
+        torch stream (``with torch.cuda.stream(s):``).  A table of multistep coefficients (mode 2, all entries) takes ``noise=None``."""
+        x, noise = _dev_f32(x, 'x'), (_dev_f32(noise, 'noise') if noise is not None else None)
+        if tuple(x.shape) != (self.B, self.T, self.C) or (noise is not None and noise.shape != x.shape):
             raise ValueError(f'x / noise shape {tuple(x.shape)} != {(self.B, self.T, self.C)}')
         arr = (_lib.StepCoefs * len(coefs))(*coefs)
         self._graph_keep = (x, noise)

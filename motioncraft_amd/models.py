@@ -418,6 +418,11 @@ class MotionDiffusion:
             output = self.diffusion_test.ddim_sample_loop(self.model, (B, T, dim_pose), clip_denoised=False,
                                                           progress=False, model_kwargs=model_kwargs, eta=0,
                                                           **inference_kwargs)
+        elif self.inference_type == 'dpmpp':
+            # DPM-Solver++ (2M), no counterpart in the reference; `order` (1 or 2, default 2) may come with inference_kwargs
+            output = self.diffusion_test.dpm_solver_sample_loop(self.model, (B, T, dim_pose), clip_denoised=False,
+                                                                progress=False, model_kwargs=model_kwargs,
+                                                                **inference_kwargs)
         elif self.inference_type == 'gt':
             output = motion
         else:

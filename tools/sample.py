@@ -7,7 +7,7 @@ positions with --pose_npy), everything between the condition features and the fi
         [--clip_feat feats.npy | --xf_out xf.npy | --random-condition SEED]  [--mean mean.npy --std std.npy]  [--pose_npy joints.npy]
         [--anim_dir frames/ | --anim_avi clip.avi [--anim_size 1000x1000] [--anim_fps 20]]
         [--smplx_model SMPLX_NEUTRAL.npz --joints_npy joints.npy [--verts_npy verts.npy] [--render_dir frames/ | --render_avi clip.avi [--render_size 960x720]]]
-        [--avi_quality 90]
+        [--avi_quality 90]  [--sampler ddpm|ddim|dpmpp [--steps N [--spacing time|logsnr]]]
 
 The CLIP tokenizer is not available offline: prompts only name the output file unless the `clip` package is importable
 (then they are tokenized and encoded by the device CLIP tower when the checkpoint carries clip.* weights).
@@ -70,7 +70,36 @@ def parse_args():
     # MI355X options: fp16 MFMA (also switched on by a top-level `fp16 = dict(...)` in the config, tools/test.py:95-97), replay
     p.add_argument('--fp16', choices=['split', 'plain'], default=None, help='fp16-MFMA mode: split = fp32-class hi/lo form')
     p.add_argument('--graph', action='store_true', help='hipGraph replay of the sampler step')
+    # the sampler: default = the config's inference_type; dpmpp = DPM-Solver++ (2M), a second-order multistep walk for 10-20 steps (no
+    # counterpart in the reference; sample quality with trained weights at those step counts is unmeasured)
+    p.add_argument('--sampler', choices=['ddpm', 'ddim', 'dpmpp'], default=None, help="default: the config's inference_type")
+    p.add_argument('--steps', type=int, default=None, metavar='N', help='with --sampler dpmpp: respace the test schedule to N steps')
+    p.add_argument('--spacing', choices=['time', 'logsnr'], default=None,
+                   help='with --sampler dpmpp --steps N: uniform in the timestep (ddimN, default) or in the log-SNR (logsnrN)')
     return p.parse_args()
+
+
+def apply_sampler(cfg, a):
+    """--sampler / --steps / --spacing -> cfg.model (inference_type, diffusion_test.respace)"""
+    if a.sampler != 'dpmpp':
+        if a.steps is not None or a.spacing is not None:
+            raise SystemExit('--steps / --spacing belong to --sampler dpmpp (the other samplers take the schedule of the config / '
+                             '--timestep_respacing)')
+        if a.sampler is not None:
+            cfg.model['inference_type'] = a.sampler
+        return
+    if a.repaint:
+        raise SystemExit('--sampler dpmpp has no outpainting (RePaint) form: use --sampler ddim with --repaint')
+    cfg.model['inference_type'] = 'dpmpp'
+    if a.steps is None:
+        if a.spacing is not None:
+            raise SystemExit('--spacing needs --steps N')
+        return
+    if a.steps < 2:
+        raise SystemExit(f'--steps must be at least 2, got {a.steps}')
+    test = dict(cfg.model['diffusion_test'])
+    test['respace'] = ('logsnr' if a.spacing == 'logsnr' else 'ddim') + str(a.steps)
+    cfg.model['diffusion_test'] = test
 
 
 def main():
@@ -78,6 +107,7 @@ def main():
     assert len(a.text) == len(a.motion_length)
     cfg = mc.Config.fromfile(a.config)
     cfg.model['opt'] = a
+    apply_sampler(cfg, a)
     model = mc.build_architecture(cfg.model)
     if a.checkpoint.startswith('synthetic'):
         seed = int(a.checkpoint.split(':')[1]) if ':' in a.checkpoint else 0
