@@ -205,6 +205,9 @@ int mc_ctx_set_tie_policy(mc_ctx* c, int32_t policy);
  *   "half_min_rows" (MC_HALF_MIN_ROWS, 512), "gate_small" (MC_GATE_SMALL, 12000), "split_expert" (MC_SPLIT_EXPERT, 0),
  *   "split_sffn" (MC_SPLIT_SFFN, 0), "route_reg" (MC_ROUTE_REG, 1), "route_coop" (MC_ROUTE_COOP, 1),
  *   "route_small" (MC_ROUTE_SMALL_CTX, else MC_ROUTE_SMALL, 20480: 0 .. 131072), "route_per" (none, 0: 0, 10 or 16),
+ *   "route_early" (MC_ROUTE_EARLY, 1: 0 or 1; two-stream schedule: each sample group's experts start behind its own gate, 0 joins
+ *   the groups in front of the routing; same bits either way; a context of a latent_dim = 64 model starts at 0 unless the variable
+ *   is set: measured slower there),
  *   "dbg_delay_us" (none, 0: -100000 .. 100000; tests: holds one sample group's stream that long in front of every layer tail,
  *   so the two-stream schedule runs far out of phase; results must not change).
  * Results never depend on them beyond fp32 summation order where DESIGN.md says so.  An unknown key or a value outside the
@@ -274,6 +277,8 @@ int mc_sample_step_inpaint(mc_ctx* c, const float* x_t_dev, int32_t step_index, 
 /* named context buffers: "h","z","proj","mf","qkv","ys","yt","a" (fp32 rows; refused while a reduced-precision context keeps fp16
  * planes there),"a_tail" (the deferred last FiLM block's fp32 rows),"z2","out2","emb","ss","tf",
  * "idx","gate","comb_w","key","cap_idx","cap_w" (layer selects tf / ss / cap slices),
+ * "src_row","dst_row" (ints, [2N]: expert slot -> token / -> 2 token + choice), "tile_group","tile_row0","tile_nrows" (ints,
+ * [2][max_tiles]: the 128-row tile map of either slot group), "num_tiles" (2 ints: tiles of either slot group) -- of the last routing,
  * "x0_hist" (the multistep sampler's previous x0 [B,T,C]; MC_ERR_STATE before the context's first mode-2 call),
  * "route_split" (one int: the last routing call's twin-split flag, nonzero if a capacity cut separated a token from its CFG twin) */
 int mc_ctx_get_buffer(mc_ctx* c, const char* name, int32_t layer, void** dev_ptr, int64_t* numel);

@@ -98,6 +98,10 @@ struct mc_ctx {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     hipEvent_t ev_side = nullptr;      // the side stream's work so far (recorded on it for a join / cross-join)
     hipEvent_t ev_stag = nullptr;      // chain bit 26: the first group's first FiLM row kernel is done (the second group's tail starts behind it)
+    // early routing (option route_early, run_layer): the second group's gate and slot fill are done / the whole-batch selection is done /
+    // the twin layer's second CFG half has read the first half's expert rows (the next layer's experts overwrite them)
+    hipEvent_t ev_gate1 = nullptr, ev_sel = nullptr, ev_front = nullptr;
+    bool early_clean = false;   // both groups' counts and fill cursors are known to be zero on the stream (the selection-only routing cleans up after itself)
     bool no_alias = false;          // introspection runs (stop_after_layers < num_layers): every intermediate row is materialised
     bool defer_last_gemm = false;   // sampler entry points: the last FiLM GEMM runs on the CFG-combined rows (see denoise_combined)
     // Two HIP streams only overlap when the runtime maps them to different HARDWARE queues (GPU_MAX_HW_QUEUES, default 4, handed out round-robin as streams

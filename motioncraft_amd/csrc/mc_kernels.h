@@ -144,7 +144,16 @@ int mc_launch_gate_finish(const float* proj, const float* sim_n, const float* lo
                           RouteBufs rb, hipStream_t s);
 // capacity/BPR drop decision + slot compaction + tile map (tile rows = 128)
 // Nsrc = N, or N/2 (twin mode); tokens >= gsplit get their own slot group (tile map at [max_tiles, 2 max_tiles))
-int mc_launch_route(long N, long Nsrc, long gsplit, int E, int capacity, RouteBufs rb, const McOptions& o, hipStream_t s);
+// select_only: the capacity cut alone (comb_w, twin-split flag, kept counts) from the sum of the two groups' counts, by the barrier-free
+// launch sequence; no slot plan, no fill -- safe beside running expert kernels (early routing, run_layer)
+int mc_launch_route(long N, long Nsrc, long gsplit, int E, int capacity, RouteBufs rb, const McOptions& o, hipStream_t s, bool select_only = false);
+// early routing: sample group `group` (0 / 1) counts its (choice, expert) pairs in its own block ...
+int* mc_route_group_counts(const RouteBufs& rb, int group);
+// ... and gets its slot plan from them alone: tile map of the group + src_row / dst_row for ALL pairs of tokens [tok0, tok0 + ntok), kept
+// or not, in slots [2 tok0, 2 (tok0 + ntok)).  Needs the group's fill cursors zero: the selection-only routing leaves them so, else
+// mc_route_early_reset (both groups' counts and cursors)
+int mc_launch_route_fill_group(int group, long tok0, long ntok, int E, RouteBufs rb, hipStream_t s);
+int mc_route_early_reset(const RouteBufs& rb, hipStream_t s);
 const int* mc_route_num_tiles_ptr(const RouteBufs& rb, int group = 0);
 // twin mode: 1 after routing iff some second-half token was kept/dropped differently from its first-half twin
 const int* mc_route_split_flag_ptr(const RouteBufs& rb);

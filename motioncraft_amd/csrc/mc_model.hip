@@ -220,6 +220,11 @@ const OptionDef kOptions[] = {
     // the register kernels (beyond: route_coop_k; B=3: 97.5 -> 90.4 ms vs the streaming form).  The tests set MC_ROUTE_SMALL_CTX
     {"route_small", "MC_ROUTE_SMALL_CTX", "MC_ROUTE_SMALL", &McOptions::route_small, 20480,
      [](long v) -> std::string { return v >= 0 && v <= 131072 ? "" : "route_small: 0 .. 131072 pairs (the one-workgroup kernels hold at most 131072)"; }},
+    // two-stream schedule: each sample group's experts start behind its own gate, the whole-batch capacity cut runs beside them
+    // (run_layer); 0: the groups join in front of the routing.  Inert in the one-stream schedules.  Applied where it helps, as
+    // kChainStagger is: a context of an L = 64 model (M2D loses 0.45 ms per step with it) starts at 0 unless the variable says otherwise
+    {"route_early", "MC_ROUTE_EARLY", nullptr, &McOptions::route_early, 1,
+     [](long v) -> std::string { return v == 0 || v == 1 ? "" : "route_early: 0 or 1"; }},
     {"route_per", nullptr, nullptr, &McOptions::route_per, 0,                              // route_coop_k pairs per thread (0: 10 up to 256 workgroups, 16 beyond)
      [](long v) -> std::string { return v == 0 || v == 10 || v == 16 ? "" : "route_per: 0 (default), 10 or 16"; }},
     {"dbg_delay_us", nullptr, nullptr, &McOptions::dbg_delay_us, 0,                        // tests: hold the second (> 0) or first (< 0) group's stream
@@ -313,6 +318,7 @@ int mc_ctx_create(mc_model* m, int32_t batch, int32_t frames, int32_t max_steps,
     const mc_model_config& g = m->cfg;
     mc_ctx* c = new mc_ctx();
     if (int r = seed_options(c->opt)) { mc_ctx_destroy(c); return r; }
+    if (m->cfg.latent_dim == 64 && !getenv("MC_ROUTE_EARLY")) c->opt.route_early = 0;      // (measured per width: see kOptions)
     c->m = m;
     c->B = batch;
     c->T = frames;
@@ -328,7 +334,7 @@ int mc_ctx_create(mc_model* m, int32_t batch, int32_t frames, int32_t max_steps,
     bool cand_ok = true;
     for (int k = 0; k < mc_ctx::SIDE_CAND; ++k) cand_ok = cand_ok && hipStreamCreateWithFlags(&c->side_cand[k], hipStreamNonBlocking) == hipSuccess;
     c->side = c->side_cand[0];
-    for (hipEvent_t* e : {&c->ev_fork, &c->ev_join, &c->ev_side, &c->ev_stag}) cand_ok = cand_ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
+    for (hipEvent_t* e : {&c->ev_fork, &c->ev_join, &c->ev_side, &c->ev_stag, &c->ev_gate1, &c->ev_sel, &c->ev_front}) cand_ok = cand_ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
     if (!cand_ok) {
         mc_set_error("could not create the side stream / events");
         mc_ctx_destroy(c);
@@ -415,7 +421,7 @@ void mc_ctx_destroy(mc_ctx* c) {
     prof_clear(c);
     for (int k = 0; k < mc_ctx::SIDE_CAND; ++k)
         if (c->side_cand[k]) { (void)hipStreamSynchronize(c->side_cand[k]); (void)hipStreamDestroy(c->side_cand[k]); }
-    for (hipEvent_t e : {c->ev_fork, c->ev_join, c->ev_side, c->ev_stag})
+    for (hipEvent_t e : {c->ev_fork, c->ev_join, c->ev_side, c->ev_stag, c->ev_gate1, c->ev_sel, c->ev_front})
         if (e) (void)hipEventDestroy(e);
     for (void* p : c->allocs) (void)hipFree(p);
     delete c;
@@ -878,6 +884,12 @@ int mc_ctx_get_buffer(mc_ctx* c, const char* name, int32_t layer, void** dev_ptr
         if (!c->x0_hist) { mc_set_error("buffer 'x0_hist' does not exist before the context's first multistep (mode 2) call"); return MC_ERR_STATE; }
         p = c->x0_hist; cnt = (int64_t)c->B * c->T * g.input_feats;
     }
+    else if (n == "src_row") { p = c->rb.src_row; cnt = 2 * c->N; }
+    else if (n == "dst_row") { p = c->rb.dst_row; cnt = 2 * c->N; }
+    else if (n == "tile_group") { p = c->rb.tile_group; cnt = 2L * c->rb.max_tiles; }
+    else if (n == "tile_row0") { p = c->rb.tile_row0; cnt = 2L * c->rb.max_tiles; }
+    else if (n == "tile_nrows") { p = c->rb.tile_nrows; cnt = 2L * c->rb.max_tiles; }
+    else if (n == "num_tiles") { p = const_cast<int*>(mc_route_num_tiles_ptr(c->rb, 0)); cnt = 2; }
     else if (n == "route_split") { p = const_cast<int*>(mc_route_split_flag_ptr(c->rb)); cnt = 1; }
     else { mc_set_error("unknown buffer '%s'", name); return MC_ERR_ARG; }
     *dev_ptr = p;

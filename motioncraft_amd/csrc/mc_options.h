@@ -40,7 +40,7 @@ static_assert(kChainDefault == 763363319, "the default chain mask is public ABI"
 struct McOptions {
     long chain, small_gemm_rows, split_rows_expert, split_rows_sffn, temporal_split, big_tokens, rowchain_split;
     long gemm_tune, small_tile_n, gemm_wp_grid, half_min_rows, gate_small, split_expert, split_sffn;
-    long route_reg, route_coop, route_small, route_per, dbg_delay_us;
+    long route_reg, route_coop, route_small, route_early, route_per, dbg_delay_us;
 };
 
 // The options of context-free launches (mc_op_*, the text / eval / wav encoders): one snapshot of the environment through the same

@@ -40,7 +40,10 @@ enum {
     ST_SPLIT = ST_DONE + 1,
     ST_PREFIX = ST_DONE + 2,    // [MAXP][2]   (hi, lo) of the selected prefix / final threshold
     ST_HIST = ST_PREFIX + 2 * MAXP,  // [MAXP][256]
-    ST_BAR = (ST_HIST + MAXP * 256 + 31) / 32 * 32,   // grid barrier words of route_coop_k (17 x 32 ints, zeroed once at context creation)
+    // early routing (mc_launch_route_fill_group / select_only): the second sample group's gate counts its (choice, expert) pairs here,
+    // the first one's in ST_CNT; the whole-batch selection reads their sum.  The per-group slot fill uses ST_FILL as its cursors.
+    ST_CNT1 = ST_HIST + MAXP * 256,  // [2][MAXE]
+    ST_BAR = (ST_CNT1 + MAXP + 31) / 32 * 32,   // grid barrier words of route_coop_k (17 x 32 ints, zeroed once at context creation)
     ST_TOTAL = ST_BAR + 17 * 32
 };
 
@@ -107,7 +110,8 @@ __global__ __launch_bounds__(256) void gate_finish_k(const float* __restrict__ p
 }
 
 // problem setup: limit per (choice, expert); active when the expert overflows.
-__global__ void route_init_k(int* __restrict__ state, int E, int capacity, int cnt_mul) {
+// early: the counts are the sum of the two sample groups' blocks (ST_CNT, ST_CNT1), and both are handed back zeroed
+__global__ void route_init_k(int* __restrict__ state, int E, int capacity, int cnt_mul, int early) {
     const int p = threadIdx.x;  // 0..MAXP-1
     __shared__ int any;
     if (p == 0) any = 0;
@@ -116,8 +120,8 @@ __global__ void route_init_k(int* __restrict__ state, int E, int capacity, int c
         const int choice = p / MAXE, e = p % MAXE;
         int act = 0, rank = 0;
         if (e < E) {
-            const int c0 = state[ST_CNT + e] * cnt_mul;
-            const int cnt = state[ST_CNT + p] * cnt_mul;
+            const int c0 = (state[ST_CNT + e] + (early ? state[ST_CNT1 + e] : 0)) * cnt_mul;
+            const int cnt = (state[ST_CNT + p] + (early ? state[ST_CNT1 + p] : 0)) * cnt_mul;
             const int limit = choice == 0 ? capacity : capacity - c0;   // second choices start at count_0[e]
             if (limit <= 0) act = cnt > 0 ? -1 : 0;
             else if (cnt > limit) { act = 1; rank = limit; }
@@ -133,6 +137,7 @@ __global__ void route_init_k(int* __restrict__ state, int E, int capacity, int c
     if (threadIdx.x < 2) state[ST_DONE + threadIdx.x] = 0;
     __syncthreads();
     if (p == 0) state[ST_ANY] = any;
+    if (early && p < MAXP) { state[ST_CNT + p] = 0; state[ST_CNT1 + p] = 0; }
 }
 
 // one radix pass (byte `pass` from the top of the 64-bit composite key)
@@ -311,6 +316,70 @@ __global__ __launch_bounds__(256) void route_fill_k(const int* __restrict__ idx,
             src_row[slot] = (int)(a >> 1);
             dst_row[slot] = (int)a;
         }
+    }
+}
+
+// Early routing: the slot plan of ONE sample group from its own gate output.  EVERY (token, choice) pair of the group's source tokens
+// [tok0, tok0 + ntok) gets a slot, kept or not (the capacity cut only shows in comb_w, which the projection behind the experts reads:
+// an expert row is computed whether its pair is kept or not), so nothing here depends on the other group.  The group's slot range is
+// [2 tok0, 2 (tok0 + ntok)): experts packed consecutively, a partial last tile per expert, as route_plan_k lays them out.  Every
+// workgroup derives the offsets from the group's (choice, expert) counts `cnt`; workgroup 0 writes the tile map; pairs are placed with
+// LDS cursors and one global reservation per (workgroup, expert) in `cursor` (zero on entry).
+__global__ __launch_bounds__(256) void route_fill_group_k(const int* __restrict__ idx, const int* __restrict__ cnt, long tok0, long ntok, int E,
+                                                          int* __restrict__ cursor, int* __restrict__ num_tiles, int* __restrict__ tile_group,
+                                                          int* __restrict__ tile_row0, int* __restrict__ tile_nrows, int max_tiles,
+                                                          int* __restrict__ src_row, int* __restrict__ dst_row) {
+    constexpr int PER = 8;  // pairs per thread
+    __shared__ int s_off[MAXE + 1], s_t0[MAXE + 1], s_cnt[MAXE], s_base[MAXE];
+    const long a_begin = 2 * tok0, a_end = 2 * (tok0 + ntok);
+    if (threadIdx.x < MAXE) s_cnt[threadIdx.x] = 0;
+    if (threadIdx.x == 0) {
+        long off = a_begin;
+        int nt = 0;
+        for (int e = 0; e < MAXE; ++e) {
+            s_off[e] = (int)off;
+            s_t0[e] = nt;
+            const int c = e < E ? cnt[e] + cnt[MAXE + e] : 0;
+            off += c;
+            nt += (c + TILE_ROWS - 1) / TILE_ROWS;
+        }
+        s_off[MAXE] = (int)off;
+        s_t0[MAXE] = nt;
+        if (blockIdx.x == 0) *num_tiles = min(nt, max_tiles);
+    }
+    __syncthreads();
+    if (blockIdx.x == 0)
+        for (int e = 0; e < E; ++e) {
+            const int t1 = min(s_t0[e + 1], max_tiles);
+            for (int t = s_t0[e] + threadIdx.x; t < t1; t += blockDim.x) {
+                const int r = (t - s_t0[e]) * TILE_ROWS;
+                tile_group[t] = e;
+                tile_row0[t] = s_off[e] + r;
+                tile_nrows[t] = min(TILE_ROWS, s_off[e + 1] - s_off[e] - r);
+            }
+        }
+    const long a0 = a_begin + ((long)blockIdx.x * 256 + threadIdx.x) * PER;
+    int le[PER], lp[PER];
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+        const long a = a0 + i;
+        le[i] = -1;
+        if (a < a_end) {
+            const int e = idx[a];
+            if (e >= 0 && e < E) { le[i] = e; lp[i] = atomicAdd(&s_cnt[e], 1); }
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < MAXE && s_cnt[threadIdx.x]) s_base[threadIdx.x] = s_off[threadIdx.x] + atomicAdd(&cursor[threadIdx.x], s_cnt[threadIdx.x]);
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+        if (le[i] < 0) continue;
+        const long a = a0 + i;
+        const long slot = (long)s_base[le[i]] + lp[i];
+        if (slot < a_begin || slot >= a_end) continue;            // (counts and idx of one gate launch agree: never taken; keeps a stale count inside the group's range)
+        src_row[slot] = (int)(a >> 1);
+        dst_row[slot] = (int)a;
     }
 }
 
@@ -986,6 +1055,25 @@ void mc_route_coop_release(int dev, int nwg) {      // dev = the device the rese
     if (nwg > 0 && dev >= 0 && dev < 64) g_coop_reserved[dev].fetch_sub(nwg);
 }
 const int* mc_route_num_tiles_ptr(const RouteBufs& rb, int group) { return rb.state + ST_NTILES + group; }
+int* mc_route_group_counts(const RouteBufs& rb, int group) { return rb.state + (group ? ST_CNT1 : ST_CNT); }
+
+int mc_route_early_reset(const RouteBufs& rb, hipStream_t s) {
+    MC_HIP(hipMemsetAsync(rb.state, 0, sizeof(int) * ST_OFF, s));                  // ST_CNT, ST_KEPT, ST_FILL
+    MC_HIP(hipMemsetAsync(rb.state + ST_CNT1, 0, sizeof(int) * MAXP, s));
+    return MC_OK;
+}
+
+int mc_launch_route_fill_group(int group, long tok0, long ntok, int E, RouteBufs rb, hipStream_t s) {
+    MC_REQUIRE(group == 0 || group == 1, "route fill: group %d", group);
+    MC_REQUIRE(E >= 2 && E <= MAXE && tok0 >= 0 && ntok >= 0 && 2 * (tok0 + ntok) < (1L << 31), "route fill: bad range (%ld, %ld)", tok0, ntok);
+    const long to = (long)group * rb.max_tiles;
+    const int blocks = ntok > 0 ? (int)cdiv(2 * ntok, 256L * 8) : 1;
+    hipLaunchKernelGGL(route_fill_group_k, dim3(blocks), dim3(256), 0, s, rb.idx, mc_route_group_counts(rb, group), tok0, ntok, E,
+                       rb.state + ST_FILL + group * MAXE, rb.state + ST_NTILES + group, rb.tile_group + to, rb.tile_row0 + to,
+                       rb.tile_nrows + to, rb.max_tiles, rb.src_row, rb.dst_row);
+    MC_LAUNCH_CHECK();
+    return MC_OK;
+}
 const int* mc_route_split_flag_ptr(const RouteBufs& rb) { return rb.state + ST_SPLIT; }
 
 int mc_launch_gate_finish(const float* proj, const float* sim_n, const float* logit_scale, long N, int E,
@@ -1005,9 +1093,14 @@ int mc_launch_gate_finish(const float* proj, const float* sim_n, const float* lo
 // the capacity test still ranks all N tokens (a twin ranks right behind its original: same score, larger index, so
 // "twin kept => original kept"), combine weights are produced for all N, expert slots only for the first half.
 // gsplit: tokens >= gsplit form slot group 1 (own slot ranges and tile map at [max_tiles, 2 max_tiles)); >= N: one group.
-int mc_launch_route(long N, long Nsrc, long gsplit, int E, int capacity, RouteBufs rb, const McOptions& o, hipStream_t s) {
+// select_only (early routing): the capacity cut alone -- comb_w for all N pairs, the twin-split flag, the kept counts -- from the summed
+// per-group counts, which it hands back zeroed together with the fill cursors; no plan, no fill (the groups' slot plans exist already and
+// their expert kernels may be running: mc_launch_route_fill_group).  Always the barrier-free launch sequence: route_coop_k spins on a
+// grid barrier and must not share the chip with another kernel of the context.
+int mc_launch_route(long N, long Nsrc, long gsplit, int E, int capacity, RouteBufs rb, const McOptions& o, hipStream_t s, bool select_only) {
     MC_REQUIRE(Nsrc == N || 2 * Nsrc == N, "route: Nsrc=%ld must be N or N/2 (N=%ld)", Nsrc, N);
     MC_REQUIRE(Nsrc == N || rb.tie_xor == 0xFFFFFFFFu, "route: the twin mode needs the stable tie order (a twin must rank right behind its original)");
+    MC_REQUIRE(!select_only || !mc_route_is_small(o, N), "route: the selection-only mode is not for the one-workgroup sizes");
     if (mc_route_is_small(o, N)) {
 #define MC_ROUTE_SMALL(KERNEL)                                                                                                       \
     hipLaunchKernelGGL(KERNEL, dim3(1), dim3(SMALL_THREADS), 0, s, rb.idx, rb.gate, rb.key, N, Nsrc, gsplit, E, capacity,   \
@@ -1020,7 +1113,7 @@ int mc_launch_route(long N, long Nsrc, long gsplit, int E, int capacity, RouteBu
         MC_LAUNCH_CHECK();
         return MC_OK;
     }
-    if (o.route_coop && 2 * N <= COOP_MAX_WG * 256 * COOP_PER) {
+    if (!select_only && o.route_coop && 2 * N <= COOP_MAX_WG * 256 * COOP_PER) {
         // pairs per thread: 10 while that is at most one workgroup per CU (<= 256; B=64 at 196 frames: 236 workgroups, 45 us either way --
         // the ~6 grid barriers set the time), 16 beyond (M2D at 160 windows per GPU: 360 -> 225 workgroups, 88 -> 80 us per routing)
         const int per = o.route_per ? (int)o.route_per : (cdiv(2 * N, 256L * COOP_PER) > 256 ? 16 : 10);
@@ -1034,7 +1127,7 @@ int mc_launch_route(long N, long Nsrc, long gsplit, int E, int capacity, RouteBu
         MC_LAUNCH_CHECK();
         return MC_OK;
     }
-    hipLaunchKernelGGL(route_init_k, dim3(1), dim3(256), 0, s, rb.state, E, capacity, (int)(N / Nsrc));
+    hipLaunchKernelGGL(route_init_k, dim3(1), dim3(256), 0, s, rb.state, E, capacity, (int)(N / Nsrc), select_only ? 1 : 0);
     int blocks = cdiv(2 * N, 256 * 8);
     if (blocks > 1024) blocks = 1024;
     if (blocks < 1) blocks = 1;
@@ -1042,6 +1135,7 @@ int mc_launch_route(long N, long Nsrc, long gsplit, int E, int capacity, RouteBu
         hipLaunchKernelGGL(route_hist_k, dim3(blocks), dim3(256), 0, s, rb.idx, rb.key, N, Nsrc, rb.state, pass, rb.tie_xor);
     }
     hipLaunchKernelGGL(route_keep_k, dim3(blocks), dim3(256), 0, s, rb.idx, rb.gate, rb.key, N, Nsrc, gsplit, rb.comb_w, rb.state, rb.tie_xor);
+    if (select_only) { MC_LAUNCH_CHECK(); return MC_OK; }
     // (planning inside the keep kernel's last workgroup was measured slower: 39 us vs 10 + 14 for the two launches)
     hipLaunchKernelGGL(route_plan_k, dim3(1), dim3(256), 0, s, rb.state, E, rb.tile_group, rb.tile_row0, rb.tile_nrows,
                        rb.max_tiles);

@@ -157,6 +157,11 @@ static int moe_proj(const mc_ctx* c, const MoeW& w, float* Y, long ldy, long tok
     return mc_launch_gemm(GM_COMB, p, 1, 0, s);
 }
 
+static int moe_capacity(const mc_model_config& g, long Ntok) {      // tutel extract_critical
+    const int E = g.num_experts;
+    return g.topk * (int)((double)g.capacity_factor * (double)((Ntok + E - 1) / E));
+}
+
 // One tutel MoE layer + GELU + proj (class MOE, st_attention.py:49-56) over Ntok tokens whose
 // gate/expert input `z` ([Ntok, din], embedding already added) is in HBM.
 // `gated`: idx/gate/key/counts were already produced (fused gate_k); otherwise run projector + gate finish here.
@@ -171,8 +176,9 @@ int run_moe(mc_ctx* c, const MoeW& w, const float* z, long Ntok, float* out, lon
         if ((r = dense(c, z, din, w.gate_w, din, w.gate_b, nullptr, 0, c->proj, 256, Ntok, 256, din, ACT_NONE, s))) return r;
         if ((r = mc_launch_gate_finish(c->proj, w.sim_n, w.scale, Ntok, E, c->rb, s))) return r;
     }
-    const int capacity = g.topk * (int)((double)g.capacity_factor * (double)((Ntok + E - 1) / E));  // tutel extract_critical
+    const int capacity = moe_capacity(g, Ntok);
     c->cnt_clean = false;
+    c->early_clean = false;      // (the fill of this routing uses the cursors)
     c->led_nsrc = twin ? Ntok / 2 : Ntok;
     c->led_gsplit = gsplit;
     if ((r = mc_launch_route(Ntok, twin ? Ntok / 2 : Ntok, gsplit, E, capacity, c->rb, c->opt, s))) return r;
@@ -501,13 +507,54 @@ static int run_layer(mc_ctx* c, int i, float* hs, int step, bool twin_ok, int sp
     const long half = (long)c->B * c->T;                    // rows of one CFG half (= one sample group of the two-stream schedule)
     const long sub_rows = ((long)c->B / 2) * c->T;          // rows of the first sub-group (whole samples)
     const bool twin_split = twin && split == 2 && chain_on(c, kChainGroupExperts) && chain_on(c, kChainTwinAlias) && chain_on(c, kChainTwinSplit) && !c->no_alias && sub_rows > 0;
+    // two slot groups when the two sample groups run on two streams: each group's expert MLP joins its own chain
+    const bool grouped = split == 2 && chain_on(c, kChainGroupExperts);
+    const long gsplit = twin_split ? sub_rows * H : grouped ? half * H : c->N;
+    // Early routing (option route_early): what couples the tokens of the batch is the capacity cut alone, and its results (comb_w, the
+    // twin-split flag) are first read by the projection BEHIND the expert MLP, whose rows are independent of their slots.  So each group's
+    // experts start behind its own gate, over a slot plan of ALL the group's pairs (mc_launch_route_fill_group), and the whole-batch
+    // selection runs beside them:
+    //   s:     gate 0 -> fill 0 -> experts 0 -> wait(ev_gate1) -> selection -> ev_sel -> projection of group 0 ...
+    //   side:  gate 1 -> fill 1 -> ev_gate1 -> experts 1 -> wait(ev_sel) -> projection of group 1 ...
+    // (ev_gate1 sits behind fill 1, not in front of it: the selection hands the counts and cursors back zeroed, which fill 1 must have
+    // read by then; the few microseconds of fill 1 are long over when experts 0 end.)  The twin layer without its sub-group split (gate on
+    // one stream) runs the same thing with one group.  The one-workgroup routing sizes keep the joined form.
+    // (Measured, B=64 fp32: the selection on the side stream in front of experts 1 instead -- so that it never runs alone -- gains 0.17 ms
+    // per step where this order gains 0.29: profiles/route_early_ab.txt.)
+    const bool early = fused_gate && grouped && c->opt.route_early != 0 && !mc_route_is_small(c->opt, c->N);
     if (fused_gate) {
         GateArgs ga;
         ga.X = hs; ga.ldx = L; ga.gamma = w.norm_g; ga.beta = w.norm_b; ga.emb = w.mm.emb; ga.emb_mod = c->T * H;
         ga.Z = c->z; ga.Wp = w.mm.gate_w; ga.bp = w.mm.gate_b; ga.sim_nT = w.mm.sim_nT; ga.logit_scale = w.mm.scale;
         ga.E = g.num_experts; ga.L = L; ga.small_tokens = c->opt.gate_small;
         ga.idx = c->rb.idx; ga.gate = c->rb.gate; ga.key = c->rb.key; ga.cnt = c->rb.state;
-        if (split == 2 && (!twin || twin_split)) {
+        if (early) {
+            const bool two = !twin || twin_split;                  // both streams (else: the twin layer's one gate launch on `s`)
+            const long nsrc = twin ? c->N / 2 : c->N;              // source tokens: group 0 = [0, gsplit), group 1 = [gsplit, nsrc)
+            const int E = g.num_experts;
+            if (!(c->cnt_clean && c->early_clean) && (r = mc_route_early_reset(c->rb, s))) return r;
+            c->cnt_clean = c->early_clean = false;
+            c->led_nsrc = nsrc;
+            c->led_gsplit = gsplit;
+            if (two && (r = side_fork(c, s))) return r;
+            ga.zero_cnt = 0;
+            ga.tok0 = 0; ga.N = gsplit; ga.cnt = mc_route_group_counts(c->rb, 0);
+            if ((r = mc_launch_gate(ga, s))) return r;
+            if ((r = mc_launch_route_fill_group(0, 0, gsplit, E, c->rb, s))) return r;
+            if ((r = moe_experts(c, w.mm, c->z, c->N, 0, s, &w.h_fc1, &w.h_fc2))) return r;
+            if (two) {
+                ga.tok0 = gsplit; ga.N = nsrc; ga.cnt = mc_route_group_counts(c->rb, 1);
+                if ((r = mc_launch_gate(ga, c->side))) return r;
+                if ((r = mc_launch_route_fill_group(1, gsplit, nsrc - gsplit, E, c->rb, c->side))) return r;
+                MC_HIP(hipEventRecord(c->ev_gate1, c->side));
+                if ((r = moe_experts(c, w.mm, c->z, c->N, 1, c->side, &w.h_fc1, &w.h_fc2))) return r;
+                MC_HIP(hipStreamWaitEvent(s, c->ev_gate1, 0));     // the cut ranks the whole batch: both gates must have arrived
+            } else if ((r = mc_launch_route_fill_group(1, gsplit, 0, E, c->rb, s))) return r;      // (an empty second group: no tiles)
+            if ((r = mc_launch_route(c->N, nsrc, gsplit, E, moe_capacity(g, c->N), c->rb, c->opt, s, true))) return r;
+            c->cnt_clean = c->early_clean = true;
+            MC_HIP(hipEventRecord(c->ev_sel, s));
+            if (two) MC_HIP(hipStreamWaitEvent(c->side, c->ev_sel, 0));      // group 1's projection reads comb_w and the twin-split flag
+        } else if (split == 2 && (!twin || twin_split)) {
             if (!c->cnt_clean) MC_HIP(hipMemsetAsync(ga.cnt, 0, sizeof(int) * 32, s));
             c->cnt_clean = false;
             if ((r = side_fork(c, s))) return r;
@@ -524,14 +571,11 @@ static int run_layer(mc_ctx* c, int i, float* hs, int step, bool twin_ok, int sp
             c->cnt_clean = false;
             if ((r = mc_launch_gate(ga, s))) return r;
         }
-        if (split == 2 && (r = side_join(c, s))) return r;       // routing ranks the whole batch: both groups must have arrived
+        if (split == 2 && !early && (r = side_join(c, s))) return r;       // routing ranks the whole batch: both groups must have arrived
     } else {
         if ((r = mc_launch_ln_rows(hs, L, 0, w.norm_g, w.norm_b, w.mm.emb, c->T * H, c->z, L, c->N, L, s))) return r;
     }
-    // two slot groups when the two sample groups run on two streams: each group's expert MLP joins its own chain
-    const bool grouped = split == 2 && chain_on(c, kChainGroupExperts);
-    const long gsplit = twin_split ? sub_rows * H : grouped ? half * H : c->N;
-    if ((r = run_moe(c, w.mm, c->z, c->N, nullptr, 0, fused_gate, twin, gsplit, s, &w.h_fc1, &w.h_fc2))) return r;   // routing (+ experts if one group)
+    if (!early && (r = run_moe(c, w.mm, c->z, c->N, nullptr, 0, fused_gate, twin, gsplit, s, &w.h_fc1, &w.h_fc2))) return r;   // routing (+ experts if one group)
     if (c->cap_idx) {
         if (twin) {     // expert ids exist for the first half only: the twins have the same ones
             MC_HIP(hipMemcpyAsync(c->cap_idx + (long)i * 2 * c->N, c->rb.idx, sizeof(int) * c->N, hipMemcpyDeviceToDevice, s));
@@ -550,9 +594,11 @@ static int run_layer(mc_ctx* c, int i, float* hs, int step, bool twin_ok, int sp
         // workgroups at B=64, so ~8 % of every launch is a tail on a partly idle chip; with two independent chains in
         // flight the next kernel of one half starts inside the tail of the other (same effect as two batches in flight).
         if (twin_split) {
-            if ((r = side_fork(c, s))) return r;
-            if ((r = moe_experts(c, w.mm, c->z, c->N, 0, s, &w.h_fc1, &w.h_fc2))) return r;
-            if ((r = moe_experts(c, w.mm, c->z, c->N, 1, c->side, &w.h_fc1, &w.h_fc2))) return r;
+            if (!early) {
+                if ((r = side_fork(c, s))) return r;
+                if ((r = moe_experts(c, w.mm, c->z, c->N, 0, s, &w.h_fc1, &w.h_fc2))) return r;
+                if ((r = moe_experts(c, w.mm, c->z, c->N, 1, c->side, &w.h_fc1, &w.h_fc2))) return r;
+            }
             auto front = [&](long row0, long nrows, hipStream_t sk) {       // projection + body branch of a row range on one stream
                 const int e = layer_proj(c, i, twin, row0, nrows, sk);
                 return e ? e : layer_body(c, i, twin, row0, nrows, sk);
@@ -566,13 +612,15 @@ static int run_layer(mc_ctx* c, int i, float* hs, int step, bool twin_ok, int sp
             MC_HIP(hipStreamWaitEvent(s, c->ev_side, 0));
             // the second CFG half's own front: exits at once while no twin pair was split by a capacity cut (the usual case)
             if ((r = front(half, half, c->side))) return r;
-            if ((r = layer_temporal(c, i, twin, 0, half, s))) return r;
+            if (early) MC_HIP(hipEventRecord(c->ev_front, c->side));      // (it read the first half's expert rows, which the next layer's
+            if ((r = layer_temporal(c, i, twin, 0, half, s))) return r;   //  experts on `s` overwrite with no join in front of them)
+            if (early) MC_HIP(hipStreamWaitEvent(s, c->ev_front, 0));
             if ((r = layer_temporal(c, i, twin, half, half, c->side))) return r;
         } else {
             if (grouped && twin) {         // group 1 combines group 0's expert rows (its own tokens have no slots): fork after them
-                if ((r = moe_experts(c, w.mm, c->z, c->N, 0, s, &w.h_fc1, &w.h_fc2))) return r;
+                if (!early && (r = moe_experts(c, w.mm, c->z, c->N, 0, s, &w.h_fc1, &w.h_fc2))) return r;
                 if ((r = side_fork(c, s))) return r;
-            } else {
+            } else if (!early) {           // (early: the side stream forked in front of its gate and waits for the selection)
                 if ((r = side_fork(c, s))) return r;
                 if (grouped) {
                     if ((r = moe_experts(c, w.mm, c->z, c->N, 0, s, &w.h_fc1, &w.h_fc2))) return r;
@@ -586,6 +634,10 @@ static int run_layer(mc_ctx* c, int i, float* hs, int step, bool twin_ok, int sp
                 MC_HIP(hipStreamWaitEvent(c->side, c->ev_join, 0));
             }
             if ((r = layer_rows(c, i, twin, half, half, c->side, c->side))) return r;
+            if (early && twin) {           // as above: group 1 read the first half's expert rows
+                MC_HIP(hipEventRecord(c->ev_front, c->side));
+                MC_HIP(hipStreamWaitEvent(s, c->ev_front, 0));
+            }
         }
         if ((r = dbg_hold(c, c->side, s))) return r;      // (tests) hold one sample group's stream in front of its tail: > 0 the second group, < 0 the first
         if ((r = layer_rows_tail(c, i, hs, step, twin, 0, half, s, evstag ? c->ev_stag : nullptr, nullptr))) return r;

@@ -119,6 +119,7 @@ class NativeContext:
         'gate_small' (MC_GATE_SMALL, 12000), 'split_expert' (MC_SPLIT_EXPERT, 0), 'split_sffn' (MC_SPLIT_SFFN, 0),
         'route_reg' (MC_ROUTE_REG, 1), 'route_coop' (MC_ROUTE_COOP, 1),
         'route_small' (MC_ROUTE_SMALL_CTX, else MC_ROUTE_SMALL, 20480; 0 .. 131072), 'route_per' (no variable, 0; 0, 10 or 16),
+        'route_early' (MC_ROUTE_EARLY, 1 -- 0 for an L = 64 model; 0 or 1),
         'dbg_delay_us' (no variable, 0; -100000 .. 100000).  An unknown key or an invalid value raises."""
         self._drop_graph()
         _lib.check(self.lib.mc_ctx_set_option(self.handle, str(key).encode(), int(value)), 'mc_ctx_set_option')
