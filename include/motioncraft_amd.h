@@ -197,7 +197,7 @@ int mc_ctx_set_tie_policy(mc_ctx* c, int32_t policy);
  * measurement and for the tests that pin alternative kernels to each other).  The MC_* environment variable of a key only seeds
  * the default of contexts created afterwards (and of context-free calls such as mc_op_gemm, read once per process); two contexts
  * of one process may differ.  Key (variable, default):
- *   "chain" (MC_CHAIN, 763363319: bit mask; the retired bits 3, 23, 25, 28 and bits >= 30 are rejected),
+ *   "chain" (MC_CHAIN, 762806311: bit mask; the retired bits 3, 4, 6 - 14, 19, 23, 25, 28 and bits >= 30 are rejected),
  *   "small_gemm_rows" (MC_SMALL_GEMM_ROWS, 5600), "split_rows_expert" (MC_SPLIT_ROWS_EXPERT, 2048),
  *   "split_rows_sffn" (MC_SPLIT_ROWS_SFFN, 8192), "temporal_split" (MC_TEMPORAL_SPLIT, 96), "big_tokens" (MC_BIG_TOKENS, 65536),
  *   "rowchain_split" (MC_ROWCHAIN_SPLIT, 20480), "gemm_tune" (MC_GEMM_TUNE, 1841: bits 0, 4, 5, 6, 8, 9, 10 only),

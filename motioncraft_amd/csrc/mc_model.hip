@@ -668,10 +668,10 @@ int mc_sample_loop(mc_ctx* c, float* x, const int32_t* step_indices, const mc_st
     MC_REQUIRE(num_steps >= 0, "num_steps < 0");
     const long n = (long)c->B * c->T * c->m->cfg.input_feats;
     // the sampler update of step k also writes x_{t-1} at the padded row stride the pose-encoder GEMM of step k + 1 stages from
-    // (chain bit 19: no pad_rows_k launch between the steps; the first step of a loop pads, which also zeroes the pad columns)
+    // (no pad_rows_k launch between the steps; the first step of a loop pads, which also zeroes the pad columns)
     PadOut po;
     po.xpad = c->xpad; po.C = c->m->cfg.input_feats; po.Cp = c->m->Cp;
-    const bool fold_pad = chain_on(c, kChainPadX) && c->xpad;
+    const bool fold_pad = c->xpad != nullptr;
     c->xpad_ready = false;
     for (int k = 0; k < num_steps; ++k) {
         int r = check_mode(&coefs[k]);

@@ -12,7 +12,7 @@ static const HalfW* half_planes(const mc_ctx* c, const HalfW* hw) { return hw &&
 static bool split3(const mc_ctx* c) { return c->prec == MC_PREC_F16X3; }      // the three-product hi / lo form
 
 // twin layer: rows of the second CFG half whose routing equals their twin's are aliased, not recomputed ...
-static bool twin_aliased(const mc_ctx* c, bool twin) { return twin && chain_on(c, kChainTwinAlias) && !c->no_alias; }
+static bool twin_aliased(const mc_ctx* c, bool twin) { return twin && !c->no_alias; }
 // ... and the kernels' argument for it, counted in tokens or in frames (the empty value when nothing is aliased)
 static TwinAlias twin_alias(const mc_ctx* c, bool twin, bool tokens) {
     return twin_aliased(c, twin) ? TwinAlias{mc_route_split_flag_ptr(c->rb), (tokens ? c->N : c->rows) / 2} : TwinAlias();
@@ -110,7 +110,7 @@ static int moe_experts(mc_ctx* c, const MoeW& w, const float* z, long Ntok, int 
             c->hbuf_floats >= (size_t)S * 2 * Ntok * din) {
             m.Y = c->hbuf; m.nsplit = S; m.y_sstride = 2 * Ntok * din;
             // B = 1 sizes (the estimated tile count straddles 256 / 3): 3 or 4 ways decided on the device from the real count
-            const bool dyn = S == 4 && c->opt.split_expert == 0 && (2 * Ntok / 128 + E / 2) * 3 <= 300 && chain_on(c, kChainDynSlices);
+            const bool dyn = S == 4 && c->opt.split_expert == 0 && (2 * Ntok / 128 + E / 2) * 3 <= 300;
             m.dyn_split = dyn ? 1 : 0;
             if ((r = mc_launch_mlp(MLP_EXPERT, m, 1, max_tiles, s))) return r;
             return mc_launch_splitk_reduce(c->hbuf, S, 2 * Ntok, din, nullptr, nullptr, c->y2, s,
@@ -267,7 +267,7 @@ static int film_block(mc_ctx* c, float* hs, const float* y1, const float* y2, co
 // stream right after the projection) ...
 static bool pq_fused(const mc_ctx* c) {
     const int L = c->m->cfg.latent_dim;
-    return chain_on(c, kChainRowchain) && chain_on(c, kChainProjQkv) && c->N > c->opt.big_tokens && mc_mlp_supported(L, 32) && (4 * L) % 32 == 0;
+    return chain_on(c, kChainRowchain) && c->N > c->opt.big_tokens && mc_mlp_supported(L, 32) && (4 * L) % 32 == 0;
 }
 // ... and the body-topology attention too (pqbody_k: frame-aligned tiles, q/k/v never leave the chip): L = 128 / 64, 12 parts
 static bool body_fused(const mc_ctx* c) {
@@ -343,7 +343,7 @@ static int layer_rows(mc_ctx* c, int i, bool twin, long row0, long nrows, hipStr
     if (st != s) {
         MC_HIP(hipEventRecord(c->ev_fork, s));
         MC_HIP(hipStreamWaitEvent(st, c->ev_fork, 0));
-        if (chain_on(c, kChainSideBody) && c->rows <= 1200) sb = st; else stt = st;      // (B <= 3 at 196 frames: -1.5 .. -3 %; B = 4: +1 %)
+        if (c->rows <= 1200) sb = st; else stt = st;      // (B <= 3 at 196 frames: -1.5 .. -3 %; B = 4: +1 %)
         if ((r = dbg_hold(c, st, s))) return r;        // (tests) hold the side stream (> 0) or the main stream (< 0) behind the fork
     }
     if ((r = layer_body(c, i, twin, row0, nrows, sb))) return r;
@@ -392,8 +392,7 @@ static int layer_rows_tail(mc_ctx* c, int i, float* hs, int step, bool twin, lon
         } else if (nrows <= c->opt.split_rows_sffn && nrows == c->rows && S > 1 && F / 32 >= S && c->hbuf_floats >= (size_t)S * nrows * D) {     // small batches: see moe_experts
             m.Y = c->hbuf; m.nsplit = S; m.y_sstride = nrows * D;
             if ((r = mc_launch_mlp(MLP_PARTS, m, H, 0, s))) return r;
-            if (chain_on(c, kChainSffnPartials)) z2_parts = S;          // the FiLM row kernel adds the partial planes up itself
-            else if ((r = mc_launch_splitk_reduce(c->hbuf, S, nrows, D, nullptr, nullptr, c->z2 + o, s))) return r;
+            z2_parts = S;          // the FiLM row kernel adds the partial planes up itself
         } else if ((r = mc_launch_mlp(MLP_PARTS, m, H, 0, s))) return r;
     } else {
         GemmArgs f1;
@@ -483,171 +482,198 @@ static int side_join(mc_ctx* c, hipStream_t s) {
     return MC_OK;
 }
 
-// One DecoderLayer (STMA + SFFN, stmogen.py:610-623) in place on the residual stream `hs` [rows, D];
-// `i` selects the layer slot (weights, text K/V, FiLM tables): base layers first, control copies after.
-// `split`: 0 = one stream; 1 = CFG halves on two streams, joined at the end of the layer; 2 = same, but the halves
-// stay apart across layers (the caller joins after the last one) and the gate is split too -- the streams only meet at
-// the routing step, the one place where tokens of the whole batch are ranked against each other.
-static int run_layer(mc_ctx* c, int i, float* hs, int step, bool twin_ok, int split, hipStream_t s) {
+// The schedule of one DecoderLayer has two shapes: one stream, or the two sample groups on two streams (`two_groups`, decided once per call
+// by denoise_impl; the groups stay apart across layers and only meet where tokens of the whole batch are ranked against each other).
+// Its decisions, taken once per layer and read by the phases of run_layer:
+struct LayerPlan {
+    bool two_groups, fused_gate, twin, twin_split, early, stagger;
+    long half, sub_rows;   // rows of one CFG half (= one sample group); rows of the twin layer's first sub-group (whole samples)
+    long nsrc, gsplit;     // routed source tokens; slot group 0 = tokens [0, gsplit), group 1 = [gsplit, nsrc)  (gsplit = N: one slot group)
+};
+static LayerPlan layer_plan(const mc_ctx* c, bool twin_ok, bool two_groups) {
+    const int L = c->m->cfg.latent_dim, H = c->m->cfg.num_parts;
+    LayerPlan p;
+    p.two_groups = two_groups;
+    // gate_k (two_groups implies it); else ln_rows and, inside run_moe, the projector GEMM + gate finish
+    p.fused_gate = chain_on(c, kChainGate) && mc_mlp_supported(L, 32);
+    // The two CFG halves enter base layer 0 with the same residual stream (the pose encoder output is written to both,
+    // stmogen.py:736-740), so gate scores and expert outputs of token i + N/2 equal those of token i: gate and experts run on the
+    // first half only, routing still ranks all N tokens ("twin" mode, mc_route.hip).
+    p.twin = twin_ok && p.fused_gate && chain_on(c, kChainRowchain) && c->N % 2 == 0 &&
+             c->rb.tie_xor == 0xFFFFFFFFu;   // (the dedupe relies on a twin ranking right behind its original: stable tie order)
+    p.half = (long)c->B * c->T; p.sub_rows = ((long)c->B / 2) * c->T;
+    // Twin layer of the two-group schedule: gate, experts and the front kernels exist for the FIRST CFG half only (the second one aliases
+    // it), so the half is cut into two sample sub-groups that go down the two streams (otherwise one stream idles for the first ~1.75 ms
+    // of every step at B=64); the streams cross-join behind the front (the temporal kernel of either CFG half reads mf rows of the whole
+    // first half) and continue per CFG half as in every other layer.
+    p.twin_split = p.twin && two_groups && chain_on(c, kChainTwinSplit) && !c->no_alias && p.sub_rows > 0;
+    // option route_early: each group's experts start behind its own gate (moe_front, form c); the one-workgroup routing sizes stay joined
+    p.early = p.fused_gate && two_groups && c->opt.route_early != 0 && !mc_route_is_small(c->opt, c->N);
+    // the second group's first FiLM block starts behind the first group's FiLM row kernel (measured per shape, same-box A/B: helps the exact-fp32
+    // L = 128 step; the fp16 modes lose 0.1 - 0.2 ms and the L = 64 models (M2D) 0.35 ms with it, batch 32 is neutral: applied where it helps)
+    p.stagger = two_groups && chain_on(c, kChainStagger) && !use_half(c) && L == 128;
+    p.nsrc = p.twin ? c->N / 2 : c->N;
+    p.gsplit = p.twin_split ? p.sub_rows * H : two_groups ? p.half * H : c->N;
+    return p;
+}
+
+// (tests) cap_idx: the routing's expert ids and combine weights of layer `i`, copied on `s` behind the routing
+static int capture_routing(mc_ctx* c, int i, bool twin, hipStream_t s) {
+    if (!c->cap_idx) return MC_OK;
+    int* const ids = c->cap_idx + (long)i * 2 * c->N;      // (twin: expert ids exist for the first half only, the twins have the same ones)
+    MC_HIP(hipMemcpyAsync(ids, c->rb.idx, sizeof(int) * (twin ? 1 : 2) * c->N, hipMemcpyDeviceToDevice, s));
+    if (twin) MC_HIP(hipMemcpyAsync(ids + c->N, c->rb.idx, sizeof(int) * c->N, hipMemcpyDeviceToDevice, s));
+    MC_HIP(hipMemcpyAsync(c->cap_w + (long)i * 2 * c->N, c->rb.comb_w, sizeof(float) * 2 * c->N, hipMemcpyDeviceToDevice, s));
+    return MC_OK;
+}
+
+// Phase 1 of a layer, the MoE front: gate + routing + experts (the only part that couples tokens across the batch), up to "the expert rows
+// are in flight".  ON RETURN every stream that will run row kernels is ordered behind the selection results (comb_w, the twin-split flag)
+// and behind the expert rows its first row kernel reads; with two groups the side stream is forked.  Each form also leaves the next routing
+// what it relies on (cnt_clean, early_clean, led_nsrc, led_gsplit): forms a and b through run_moe, form c in its own block.
+static int moe_front(mc_ctx* c, int i, float* hs, const LayerPlan& p, hipStream_t s) {
     const mc_model_config& g = c->m->cfg;
-    const int L = g.latent_dim, H = g.num_parts;
+    const int L = g.latent_dim, H = g.num_parts, E = g.num_experts;
     const LayerW& w = c->lw[i];
     int r;
-    // ---- STMA: gate + routing + experts (the only part that couples tokens across the batch) ----
-    const bool fused_gate = chain_on(c, kChainGate) && mc_mlp_supported(L, 32);
-    // The two CFG halves enter base layer 0 with the same residual stream (the pose encoder output is written to
-    // both, stmogen.py:736-740), so gate scores and expert outputs of token i + N/2 equal those of token i:
-    // gate and experts run on the first half only, routing still ranks all N tokens ("twin" mode, mc_route.hip).
-    const bool twin = twin_ok && fused_gate && chain_on(c, kChainRowchain) && chain_on(c, kChainTwin) && (c->N % 2 == 0) &&
-                      c->rb.tie_xor == 0xFFFFFFFFu;   // (the dedupe relies on a twin ranking right behind its original: stable tie order)
-    // Twin layer of the large-batch schedule: gate, experts and the front kernels exist for the FIRST CFG half only (the second one
-    // aliases it), so the half is cut into two sample sub-groups that go down the two streams (otherwise one stream idles for the
-    // first ~1.75 ms of every step at B=64); the streams cross-join behind the front (the temporal kernel of either CFG half reads
-    // mf rows of the whole first half) and continue per CFG half as in every other layer.
-    const long half = (long)c->B * c->T;                    // rows of one CFG half (= one sample group of the two-stream schedule)
-    const long sub_rows = ((long)c->B / 2) * c->T;          // rows of the first sub-group (whole samples)
-    const bool twin_split = twin && split == 2 && chain_on(c, kChainGroupExperts) && chain_on(c, kChainTwinAlias) && chain_on(c, kChainTwinSplit) && !c->no_alias && sub_rows > 0;
-    // two slot groups when the two sample groups run on two streams: each group's expert MLP joins its own chain
-    const bool grouped = split == 2 && chain_on(c, kChainGroupExperts);
-    const long gsplit = twin_split ? sub_rows * H : grouped ? half * H : c->N;
-    // Early routing (option route_early): what couples the tokens of the batch is the capacity cut alone, and its results (comb_w, the
-    // twin-split flag) are first read by the projection BEHIND the expert MLP, whose rows are independent of their slots.  So each group's
-    // experts start behind its own gate, over a slot plan of ALL the group's pairs (mc_launch_route_fill_group), and the whole-batch
-    // selection runs beside them:
-    //   s:     gate 0 -> fill 0 -> experts 0 -> wait(ev_gate1) -> selection -> ev_sel -> projection of group 0 ...
-    //   side:  gate 1 -> fill 1 -> ev_gate1 -> experts 1 -> wait(ev_sel) -> projection of group 1 ...
-    // (ev_gate1 sits behind fill 1, not in front of it: the selection hands the counts and cursors back zeroed, which fill 1 must have
-    // read by then; the few microseconds of fill 1 are long over when experts 0 end.)  The twin layer without its sub-group split (gate on
-    // one stream) runs the same thing with one group.  The one-workgroup routing sizes keep the joined form.
-    // (Measured, B=64 fp32: the selection on the side stream in front of experts 1 instead -- so that it never runs alone -- gains 0.17 ms
-    // per step where this order gains 0.29: profiles/route_early_ab.txt.)
-    const bool early = fused_gate && grouped && c->opt.route_early != 0 && !mc_route_is_small(c->opt, c->N);
-    if (fused_gate) {
-        GateArgs ga;
-        ga.X = hs; ga.ldx = L; ga.gamma = w.norm_g; ga.beta = w.norm_b; ga.emb = w.mm.emb; ga.emb_mod = c->T * H;
-        ga.Z = c->z; ga.Wp = w.mm.gate_w; ga.bp = w.mm.gate_b; ga.sim_nT = w.mm.sim_nT; ga.logit_scale = w.mm.scale;
-        ga.E = g.num_experts; ga.L = L; ga.small_tokens = c->opt.gate_small;
-        ga.idx = c->rb.idx; ga.gate = c->rb.gate; ga.key = c->rb.key; ga.cnt = c->rb.state;
-        if (early) {
-            const bool two = !twin || twin_split;                  // both streams (else: the twin layer's one gate launch on `s`)
-            const long nsrc = twin ? c->N / 2 : c->N;              // source tokens: group 0 = [0, gsplit), group 1 = [gsplit, nsrc)
-            const int E = g.num_experts;
-            if (!(c->cnt_clean && c->early_clean) && (r = mc_route_early_reset(c->rb, s))) return r;
-            c->cnt_clean = c->early_clean = false;
-            c->led_nsrc = nsrc;
-            c->led_gsplit = gsplit;
-            if (two && (r = side_fork(c, s))) return r;
-            ga.zero_cnt = 0;
-            ga.tok0 = 0; ga.N = gsplit; ga.cnt = mc_route_group_counts(c->rb, 0);
-            if ((r = mc_launch_gate(ga, s))) return r;
-            if ((r = mc_launch_route_fill_group(0, 0, gsplit, E, c->rb, s))) return r;
-            if ((r = moe_experts(c, w.mm, c->z, c->N, 0, s, &w.h_fc1, &w.h_fc2))) return r;
-            if (two) {
-                ga.tok0 = gsplit; ga.N = nsrc; ga.cnt = mc_route_group_counts(c->rb, 1);
-                if ((r = mc_launch_gate(ga, c->side))) return r;
-                if ((r = mc_launch_route_fill_group(1, gsplit, nsrc - gsplit, E, c->rb, c->side))) return r;
-                MC_HIP(hipEventRecord(c->ev_gate1, c->side));
-                if ((r = moe_experts(c, w.mm, c->z, c->N, 1, c->side, &w.h_fc1, &w.h_fc2))) return r;
-                MC_HIP(hipStreamWaitEvent(s, c->ev_gate1, 0));     // the cut ranks the whole batch: both gates must have arrived
-            } else if ((r = mc_launch_route_fill_group(1, gsplit, 0, E, c->rb, s))) return r;      // (an empty second group: no tiles)
-            if ((r = mc_launch_route(c->N, nsrc, gsplit, E, moe_capacity(g, c->N), c->rb, c->opt, s, true))) return r;
-            c->cnt_clean = c->early_clean = true;
-            MC_HIP(hipEventRecord(c->ev_sel, s));
-            if (two) MC_HIP(hipStreamWaitEvent(c->side, c->ev_sel, 0));      // group 1's projection reads comb_w and the twin-split flag
-        } else if (split == 2 && (!twin || twin_split)) {
+    GateArgs ga;
+    ga.X = hs; ga.ldx = L; ga.gamma = w.norm_g; ga.beta = w.norm_b; ga.emb = w.mm.emb; ga.emb_mod = c->T * H;
+    ga.Z = c->z; ga.Wp = w.mm.gate_w; ga.bp = w.mm.gate_b; ga.sim_nT = w.mm.sim_nT; ga.logit_scale = w.mm.scale;
+    ga.E = E; ga.L = L; ga.small_tokens = c->opt.gate_small;
+    ga.idx = c->rb.idx; ga.gate = c->rb.gate; ga.key = c->rb.key; ga.cnt = c->rb.state;
+    auto gate_whole = [&]() {      // one launch over all source tokens on `s`
+        ga.N = p.nsrc;
+        ga.zero_cnt = c->cnt_clean ? 0 : 1;      // small batches: the previous layer's routing kernel left the counts zeroed
+        c->cnt_clean = false;
+        return mc_launch_gate(ga, s);
+    };
+    auto gate_group = [&](int group, hipStream_t sk, int* cnt) {      // group 0 = tokens [0, gsplit), group 1 = [gsplit, nsrc); the counts were zeroed
+        ga.zero_cnt = 0; ga.cnt = cnt;
+        ga.tok0 = group ? p.gsplit : 0; ga.N = group ? p.nsrc : p.gsplit;
+        return mc_launch_gate(ga, sk);
+    };
+    auto experts = [&](int group, hipStream_t sk) { return moe_experts(c, w.mm, c->z, c->N, group, sk, &w.h_fc1, &w.h_fc2); };
+    // two groups: do both streams carry a gate and an expert launch?  (else: the twin layer without its sub-group split -- one gate launch and
+    // one slot group on `s`; group 1 combines group 0's expert rows, so the side stream forks behind them)
+    const bool both = !p.twin || p.twin_split;
+
+    // ---- (a) one stream: gate (or ln_rows + the unfused gate inside run_moe), routing, experts ----
+    if (!p.two_groups) {
+        if (p.fused_gate) { if ((r = gate_whole())) return r; }
+        else if ((r = mc_launch_ln_rows(hs, L, 0, w.norm_g, w.norm_b, w.mm.emb, c->T * H, c->z, L, c->N, L, s))) return r;
+        if ((r = run_moe(c, w.mm, c->z, c->N, nullptr, 0, p.fused_gate, p.twin, p.gsplit, s, &w.h_fc1, &w.h_fc2))) return r;
+        return capture_routing(c, i, p.twin, s);
+    }
+
+    // ---- (b) two groups, joined: gate per group, join, routing (it ranks the whole batch: both groups must have arrived), fork, experts per group ----
+    if (!p.early) {
+        if (both) {
             if (!c->cnt_clean) MC_HIP(hipMemsetAsync(ga.cnt, 0, sizeof(int) * 32, s));
             c->cnt_clean = false;
             if ((r = side_fork(c, s))) return r;
-            ga.zero_cnt = 0;
-            // group 0 on `s`, group 1 on the side stream (twin layer: the two sub-groups of the first CFG half)
-            const long cut = twin_split ? sub_rows * H : half * H;
-            ga.tok0 = 0; ga.N = cut;
-            if ((r = mc_launch_gate(ga, s))) return r;
-            ga.tok0 = cut; ga.N = twin_split ? half * H : c->N;
-            if ((r = mc_launch_gate(ga, c->side))) return r;
-        } else {
-            ga.N = twin ? c->N / 2 : c->N;
-            ga.zero_cnt = c->cnt_clean ? 0 : 1;      // small batches: the previous layer's routing kernel left the counts zeroed
-            c->cnt_clean = false;
-            if ((r = mc_launch_gate(ga, s))) return r;
-        }
-        if (split == 2 && !early && (r = side_join(c, s))) return r;       // routing ranks the whole batch: both groups must have arrived
+            if ((r = gate_group(0, s, ga.cnt))) return r;
+            if ((r = gate_group(1, c->side, ga.cnt))) return r;
+        } else if ((r = gate_whole())) return r;
+        if ((r = side_join(c, s))) return r;
+        if ((r = run_moe(c, w.mm, c->z, c->N, nullptr, 0, true, p.twin, p.gsplit, s, &w.h_fc1, &w.h_fc2))) return r;      // (gsplit < N: the routing alone)
+        if ((r = capture_routing(c, i, p.twin, s))) return r;
+        if (both && (r = side_fork(c, s))) return r;
+        if ((r = experts(0, s))) return r;
+        return both ? experts(1, c->side) : side_fork(c, s);      // (one gate: group 1 combines group 0's expert rows, so it forks behind them)
+    }
+
+    // ---- (c) two groups, early ----
+    // What couples the tokens of the batch is the capacity cut alone, and its results are first read by the projection BEHIND the expert MLP,
+    // whose rows are independent of their slots.  So each group's experts start behind its own gate, over a slot plan of ALL the group's pairs
+    // (mc_launch_route_fill_group), and the whole-batch selection runs beside them:
+    //   s:     gate 0 -> fill 0 -> experts 0 -> wait(ev_gate1) -> selection -> ev_sel -> projection of group 0 ...
+    //   side:  gate 1 -> fill 1 -> ev_gate1 -> experts 1 -> wait(ev_sel) -> projection of group 1 ...
+    // (ev_gate1 sits behind fill 1, not in front of it: the selection hands the counts and cursors back zeroed, which fill 1 must have
+    // read by then; the few microseconds of fill 1 are long over when experts 0 end.)
+    // (Measured, B=64 fp32: the selection on the side stream in front of experts 1 instead -- so that it never runs alone -- gains 0.17 ms
+    // per step where this order gains 0.29: profiles/route_early_ab.txt.)
+    if (!(c->cnt_clean && c->early_clean) && (r = mc_route_early_reset(c->rb, s))) return r;
+    c->cnt_clean = c->early_clean = false;
+    c->led_nsrc = p.nsrc; c->led_gsplit = p.gsplit;
+    if (both && (r = side_fork(c, s))) return r;
+    if ((r = gate_group(0, s, mc_route_group_counts(c->rb, 0)))) return r;
+    if ((r = mc_launch_route_fill_group(0, 0, p.gsplit, E, c->rb, s))) return r;
+    if ((r = experts(0, s))) return r;
+    if (both) {
+        if ((r = gate_group(1, c->side, mc_route_group_counts(c->rb, 1)))) return r;
+        if ((r = mc_launch_route_fill_group(1, p.gsplit, p.nsrc - p.gsplit, E, c->rb, c->side))) return r;
+        MC_HIP(hipEventRecord(c->ev_gate1, c->side));
+        if ((r = experts(1, c->side))) return r;
+        MC_HIP(hipStreamWaitEvent(s, c->ev_gate1, 0));     // the cut ranks the whole batch: both gates must have arrived
+    } else if ((r = mc_launch_route_fill_group(1, p.gsplit, 0, E, c->rb, s))) return r;      // (an empty second group: no tiles)
+    if ((r = mc_launch_route(c->N, p.nsrc, p.gsplit, E, moe_capacity(g, c->N), c->rb, c->opt, s, true))) return r;
+    c->cnt_clean = c->early_clean = true;
+    MC_HIP(hipEventRecord(c->ev_sel, s));
+    if (both) MC_HIP(hipStreamWaitEvent(c->side, c->ev_sel, 0));      // group 1's projection reads comb_w and the twin-split flag
+    if ((r = capture_routing(c, i, p.twin, s))) return r;
+    return both ? MC_OK : side_fork(c, s);
+}
+
+// The one hazard early routing adds to the row phase of a twin layer: group 1's front reads the FIRST half's expert rows, which the next
+// layer's experts on the caller's stream overwrite with no join in front of them.  kFrontRead: recorded on the side stream behind that
+// front; kFrontWait: the caller's stream waits for it.  (The joined form meets in front of the next routing: nothing is enqueued.)
+enum { kFrontRead = 1, kFrontWait = 2 };
+static int expert_rows_guard(mc_ctx* c, const LayerPlan& p, int what, hipStream_t s) {
+    if (!(p.early && p.twin)) return MC_OK;
+    if (what & kFrontRead) MC_HIP(hipEventRecord(c->ev_front, c->side));
+    if (what & kFrontWait) MC_HIP(hipStreamWaitEvent(s, c->ev_front, 0));
+    return MC_OK;
+}
+
+// One DecoderLayer (STMA + SFFN, stmogen.py:610-623) in place on the residual stream `hs` [rows, D];
+// `i` selects the layer slot (weights, text K/V, FiLM tables): base layers first, control copies after.
+static int run_layer(mc_ctx* c, int i, float* hs, int step, bool twin_ok, bool two_groups, hipStream_t s) {
+    const LayerPlan p = layer_plan(c, twin_ok, two_groups);
+    const bool twin = p.twin;
+    const long half = p.half;
+    int r;
+    if ((r = moe_front(c, i, hs, p, s))) return r;
+    // ---- phase 2: the row-independent rest of the layer ----
+    if (!two_groups) {
+        // Small batches: the temporal branch runs on the side stream beside LN + qkv + body (measured +2.4 % at B=8).
+        const bool side_temporal = c->side && c->N <= c->opt.big_tokens;
+        if ((r = layer_rows(c, i, twin, 0, 2 * half, s, side_temporal ? c->side : s))) return r;
+        return layer_rows_tail(c, i, hs, step, twin, 0, 2 * half, s);
+    }
+    // Large batches: the two CFG halves go down two streams.  Each kernel of the chain fills 4.59 "waves" of
+    // workgroups at B=64, so ~8 % of every launch is a tail on a partly idle chip; with two independent chains in
+    // flight the next kernel of one half starts inside the tail of the other (same effect as two batches in flight).
+    if (p.twin_split) {
+        auto front = [&](long row0, long nrows, hipStream_t sk) {       // projection + body branch of a row range on one stream
+            const int e = layer_proj(c, i, twin, row0, nrows, sk);
+            return e ? e : layer_body(c, i, twin, row0, nrows, sk);
+        };
+        if ((r = front(0, p.sub_rows, s))) return r;
+        if ((r = front(p.sub_rows, half - p.sub_rows, c->side))) return r;
+        // cross-join: each stream waits for the other's front
+        MC_HIP(hipEventRecord(c->ev_join, s));
+        MC_HIP(hipEventRecord(c->ev_side, c->side));
+        MC_HIP(hipStreamWaitEvent(c->side, c->ev_join, 0));
+        MC_HIP(hipStreamWaitEvent(s, c->ev_side, 0));
+        // the second CFG half's own front: exits at once while no twin pair was split by a capacity cut (the usual case)
+        if ((r = front(half, half, c->side))) return r;
+        if ((r = expert_rows_guard(c, p, kFrontRead, s))) return r;
+        if ((r = layer_temporal(c, i, twin, 0, half, s))) return r;
+        if ((r = expert_rows_guard(c, p, kFrontWait, s))) return r;
+        if ((r = layer_temporal(c, i, twin, half, half, c->side))) return r;
     } else {
-        if ((r = mc_launch_ln_rows(hs, L, 0, w.norm_g, w.norm_b, w.mm.emb, c->T * H, c->z, L, c->N, L, s))) return r;
-    }
-    if (!early && (r = run_moe(c, w.mm, c->z, c->N, nullptr, 0, fused_gate, twin, gsplit, s, &w.h_fc1, &w.h_fc2))) return r;   // routing (+ experts if one group)
-    if (c->cap_idx) {
-        if (twin) {     // expert ids exist for the first half only: the twins have the same ones
-            MC_HIP(hipMemcpyAsync(c->cap_idx + (long)i * 2 * c->N, c->rb.idx, sizeof(int) * c->N, hipMemcpyDeviceToDevice, s));
-            MC_HIP(hipMemcpyAsync(c->cap_idx + (long)i * 2 * c->N + c->N, c->rb.idx, sizeof(int) * c->N, hipMemcpyDeviceToDevice, s));
-        } else {
-            MC_HIP(hipMemcpyAsync(c->cap_idx + (long)i * 2 * c->N, c->rb.idx, sizeof(int) * 2 * c->N, hipMemcpyDeviceToDevice, s));
-        }
-        MC_HIP(hipMemcpyAsync(c->cap_w + (long)i * 2 * c->N, c->rb.comb_w, sizeof(float) * 2 * c->N, hipMemcpyDeviceToDevice, s));
-    }
-    // ---- the row-independent rest of the layer ----
-    // (measured per shape, same-box A/B: helps the exact-fp32 L = 128 step; the fp16 modes -- whose GEMMs are a small part of the chain -- lose 0.1 - 0.2 ms and the
-    //  L = 64 models (M2D) 0.35 ms with it, batch 32 is neutral: applied where it helps)
-    const bool evstag = split == 2 && chain_on(c, kChainStagger) && !use_half(c) && L == 128;
-    if (split) {
-        // Large batches: the two CFG halves go down two streams.  Each kernel of the chain fills 4.59 "waves" of
-        // workgroups at B=64, so ~8 % of every launch is a tail on a partly idle chip; with two independent chains in
-        // flight the next kernel of one half starts inside the tail of the other (same effect as two batches in flight).
-        if (twin_split) {
-            if (!early) {
-                if ((r = side_fork(c, s))) return r;
-                if ((r = moe_experts(c, w.mm, c->z, c->N, 0, s, &w.h_fc1, &w.h_fc2))) return r;
-                if ((r = moe_experts(c, w.mm, c->z, c->N, 1, c->side, &w.h_fc1, &w.h_fc2))) return r;
-            }
-            auto front = [&](long row0, long nrows, hipStream_t sk) {       // projection + body branch of a row range on one stream
-                const int e = layer_proj(c, i, twin, row0, nrows, sk);
-                return e ? e : layer_body(c, i, twin, row0, nrows, sk);
-            };
-            if ((r = front(0, sub_rows, s))) return r;
-            if ((r = front(sub_rows, half - sub_rows, c->side))) return r;
-            // cross-join: each stream waits for the other's front
+        if ((r = layer_rows(c, i, twin, 0, half, s, s))) return r;
+        if (twin_aliased(c, twin)) {
+            // twin aliasing: group 1 reads group 0's mf / ys instead of producing its own
             MC_HIP(hipEventRecord(c->ev_join, s));
-            MC_HIP(hipEventRecord(c->ev_side, c->side));
             MC_HIP(hipStreamWaitEvent(c->side, c->ev_join, 0));
-            MC_HIP(hipStreamWaitEvent(s, c->ev_side, 0));
-            // the second CFG half's own front: exits at once while no twin pair was split by a capacity cut (the usual case)
-            if ((r = front(half, half, c->side))) return r;
-            if (early) MC_HIP(hipEventRecord(c->ev_front, c->side));      // (it read the first half's expert rows, which the next layer's
-            if ((r = layer_temporal(c, i, twin, 0, half, s))) return r;   //  experts on `s` overwrite with no join in front of them)
-            if (early) MC_HIP(hipStreamWaitEvent(s, c->ev_front, 0));
-            if ((r = layer_temporal(c, i, twin, half, half, c->side))) return r;
-        } else {
-            if (grouped && twin) {         // group 1 combines group 0's expert rows (its own tokens have no slots): fork after them
-                if (!early && (r = moe_experts(c, w.mm, c->z, c->N, 0, s, &w.h_fc1, &w.h_fc2))) return r;
-                if ((r = side_fork(c, s))) return r;
-            } else if (!early) {           // (early: the side stream forked in front of its gate and waits for the selection)
-                if ((r = side_fork(c, s))) return r;
-                if (grouped) {
-                    if ((r = moe_experts(c, w.mm, c->z, c->N, 0, s, &w.h_fc1, &w.h_fc2))) return r;
-                    if ((r = moe_experts(c, w.mm, c->z, c->N, 1, c->side, &w.h_fc1, &w.h_fc2))) return r;
-                }
-            }
-            if ((r = layer_rows(c, i, twin, 0, half, s, s))) return r;
-            if (twin_aliased(c, twin)) {
-                // twin aliasing: group 1 reads group 0's mf / ys instead of producing its own
-                MC_HIP(hipEventRecord(c->ev_join, s));
-                MC_HIP(hipStreamWaitEvent(c->side, c->ev_join, 0));
-            }
-            if ((r = layer_rows(c, i, twin, half, half, c->side, c->side))) return r;
-            if (early && twin) {           // as above: group 1 read the first half's expert rows
-                MC_HIP(hipEventRecord(c->ev_front, c->side));
-                MC_HIP(hipStreamWaitEvent(s, c->ev_front, 0));
-            }
         }
-        if ((r = dbg_hold(c, c->side, s))) return r;      // (tests) hold one sample group's stream in front of its tail: > 0 the second group, < 0 the first
-        if ((r = layer_rows_tail(c, i, hs, step, twin, 0, half, s, evstag ? c->ev_stag : nullptr, nullptr))) return r;
-        if ((r = layer_rows_tail(c, i, hs, step, twin, half, half, c->side, nullptr, evstag ? c->ev_stag : nullptr))) return r;
-        return split == 1 ? side_join(c, s) : MC_OK;
+        if ((r = layer_rows(c, i, twin, half, half, c->side, c->side))) return r;
+        if ((r = expert_rows_guard(c, p, kFrontRead | kFrontWait, s))) return r;
     }
-    // Small batches: the temporal branch runs on the side stream beside LN + qkv + body (measured +2.4 % at B=8).
-    const bool side_temporal = c->side && c->N <= c->opt.big_tokens;
-    if ((r = layer_rows(c, i, twin, 0, 2 * half, s, side_temporal ? c->side : s))) return r;
-    return layer_rows_tail(c, i, hs, step, twin, 0, 2 * half, s);
+    if ((r = dbg_hold(c, c->side, s))) return r;      // (tests) hold one sample group's stream in front of its tail: > 0 the second group, < 0 the first
+    if ((r = layer_rows_tail(c, i, hs, step, twin, 0, half, s, p.stagger ? c->ev_stag : nullptr, nullptr))) return r;
+    return layer_rows_tail(c, i, hs, step, twin, half, half, c->side, nullptr, p.stagger ? c->ev_stag : nullptr);
 }
 
 // `seed` != nullptr: x_t is overwritten in place on its first frames before the network reads it (mc_sample_step_seeded)
@@ -682,13 +708,13 @@ int denoise_impl(mc_ctx* c, const float* x_t, int32_t step, float* out2_dev, int
     const int nl = stop_after >= 0 ? (stop_after < g.num_layers ? stop_after : g.num_layers) : g.num_layers;
     c->no_alias = stop_after >= 0 && stop_after < g.num_layers;
     const int NC = c->have_ctrl ? g.num_ctrl_layers : 0;
-    // large batches: the CFG halves run on two streams (see run_layer); with a control branch the extra whole-batch
-    // ops between layers need both halves, so the halves re-join after every layer
+    // large batches: the CFG halves run on two streams (see run_layer) and stay there across the layers, the control branch's row-wise
+    // ops between them included
     const bool fused = chain_on(c, kChainGate) && chain_on(c, kChainRowchain) && mc_mlp_supported(L, 32);
-    const int split = (c->side && chain_on(c, kChainTwoStreams) && c->N > c->opt.big_tokens && fused) ? ((NC > 0 && !chain_on(c, kChainCtrlGroups)) ? 1 : 2) : 0;
-    // row-wise op between layers, on the stream of the sample group that owns the rows (one launch when not split)
+    const bool two_groups = c->side && chain_on(c, kChainTwoStreams) && c->N > c->opt.big_tokens && fused;
+    // row-wise op between layers, on the stream of the sample group that owns the rows (one launch on one stream)
     auto by_group = [&](auto&& fn) -> int {
-        if (split != 2) return fn(0L, c->rows, s);
+        if (!two_groups) return fn(0L, c->rows, s);
         if (int e = fn(0L, BT, s)) return e;
         return fn(BT, BT, c->side);
     };
@@ -702,7 +728,7 @@ int denoise_impl(mc_ctx* c, const float* x_t, int32_t step, float* out2_dev, int
                          return mc_launch_add_rows(c->hc + r0 * D, c->h + r0 * D, c->cb + r0 * D, nullptr, n, D, sk); })))
                     return r;
             }
-            if ((r = run_layer(c, slot, c->hc, step, false, split, s))) return r;                       // copied_block
+            if ((r = run_layer(c, slot, c->hc, step, false, two_groups, s))) return r;                       // copied_block
             const LayerW& cw = c->lw[slot];
             if ((r = by_group([&](long r0, long n, hipStream_t sk) {                                   // h += after_proj(c)
                      if (const HalfW* hp = half_planes(c, &cw.h_after))
@@ -710,9 +736,9 @@ int denoise_impl(mc_ctx* c, const float* x_t, int32_t step, float* out2_dev, int
                      return dense(c, c->hc + r0 * D, D, cw.after_w, D, cw.after_b, c->h + r0 * D, D, c->h + r0 * D, D, n, D, D, ACT_NONE, sk); })))
                 return r;
         }
-        if ((r = run_layer(c, i, c->h, step, i == 0, split, s))) return r;
+        if ((r = run_layer(c, i, c->h, step, i == 0, two_groups, s))) return r;
     }
-    if (split == 2 && (r = side_join(c, s))) return r;       // the groups meet again before the pose decoder
+    if (two_groups && (r = side_join(c, s))) return r;       // the groups meet again before the pose decoder
     if (stop_after >= 0) return MC_OK;
     // PoseDecoder as one dense [D -> C] GEMM (stmogen.py:505-544), /2 folded into the packed weight
     float* o = out2_dev ? out2_dev : c->out2;
@@ -734,9 +760,8 @@ SamplerCoefs to_coefs(const mc_step_coefs* k) {
 int denoise_combined(mc_ctx* c, const float* x_t, int32_t step, const mc_step_coefs* k, void* stream, X0Parts* x0, const SeedArgs* seed) {
     const mc_model_config& g = c->m->cfg;
     // ... and so is the Linear of the very last StylizationBlock (h += a W^T + b): it, too, runs once on the combined
-    // rows  h_c = comb(h) + comb(a) W^T + b  instead of on both halves.
-    const bool defer = chain_on(c, kChainDeferTail);
-    c->defer_last_gemm = defer;
+    // rows  h_c = comb(h) + comb(a) W^T + b  instead of on both halves (defer_last_gemm: the layers leave that GEMM out).
+    c->defer_last_gemm = true;
     int r = denoise_impl(c, x_t, step, nullptr, g.num_layers, stream, seed);   // all layers (minus that GEMM), no decoder
     c->defer_last_gemm = false;
     if (r != MC_OK) return r;
@@ -749,8 +774,8 @@ int denoise_combined(mc_ctx* c, const float* x_t, int32_t step, const mc_step_co
         if (c->graph_mode) return mc_launch_cfg_combine_tab(x, y, c->gcoefs, c->gstep, out, BT * D, s);
         return mc_launch_axpby(x, y, k->text_coef, k->none_coef, out, BT * D, s);
     };
-    const bool grouped = defer && c->dec_cat_w && chain_on(c, kChainTailGrouped);      // the folded tail as ONE grouped GEMM (dec_cat_w)
-    if (grouped && chain_on(c, kChainTailOnePass) && BT > c->opt.small_gemm_rows && D % 32 == 0) {
+    const bool folded = c->dec_cat_w != nullptr;      // the Linear composed with the decoder at pack time (a model with dec.wf / dec.bf bound)
+    if (folded && chain_on(c, kChainTailOnePass) && BT > c->opt.small_gemm_rows && D % 32 == 0) {
         // large batches: CFG combination, both K groups and the biases in ONE GEMM pass (gemm_tail_k): no axpby_pair_k, no partial outputs
         TailArgs t;
         t.H = c->h; t.Af = deferred_a(c); t.half = BT * D; t.lda = D;
@@ -769,7 +794,7 @@ int denoise_combined(mc_ctx* c, const float* x_t, int32_t step, const mc_step_co
         if (mc_gemm_tail_two_outputs(t)) x0->b = t.C2;      // gemm_tail2_k: x0 = C + C2, added by the sampler-update kernel
         return MC_OK;
     }
-    if (grouped) {
+    if (folded) {
         // h_c and a_c in one launch
         if ((r = mc_launch_axpby_pair(c->h, c->h + BT * D, c->z2, deferred_a(c), deferred_a(c) + BT * D, c->z2 + BT * D, k->text_coef, k->none_coef,
                                       c->graph_mode ? c->gcoefs : nullptr, c->graph_mode ? c->gstep : nullptr, BT * D, s))) return r;
@@ -785,16 +810,11 @@ int denoise_combined(mc_ctx* c, const float* x_t, int32_t step, const mc_step_co
         x0->b = c->out2 + BT * C;
         return D % 32 == 0 ? mc_launch_gemm_small(t, s, 2) : mc_launch_gemm(GM_PLAIN, t, 2, 0, s);
     }
+    // no folded weight: both combinations, the Linear on the combined rows, then the decoder
+    float* const ad = deferred_a(c);
     if ((r = combine(c->h, c->h + BT * D, c->z2))) return r;     // h_c
-    if (defer) {
-        float* const ad = deferred_a(c);
-        if ((r = combine(ad, ad + BT * D, ad))) return r;      // a_c
-        if (c->dec_wf) {
-            if ((r = dense(c, c->z2, D, c->dec_w, D, c->dec_bf, nullptr, 0, c->out2, C, BT, C, D, ACT_NONE, s))) return r;
-            return dense(c, ad, D, c->dec_wf, D, nullptr, c->out2, C, c->out2, C, BT, C, D, ACT_NONE, s);
-        }
-        if ((r = dense(c, ad, D, w.ffn_out_w, D, w.ffn_out_b, c->z2, D, c->z2, D, BT, D, D, ACT_NONE, s))) return r;  // h_c += a_c W^T + b
-    }
+    if ((r = combine(ad, ad + BT * D, ad))) return r;            // a_c
+    if ((r = dense(c, ad, D, w.ffn_out_w, D, w.ffn_out_b, c->z2, D, c->z2, D, BT, D, D, ACT_NONE, s))) return r;  // h_c += a_c W^T + b
     return dense(c, c->z2, D, c->dec_w, D, c->dec_b, nullptr, 0, c->out2, C, BT, C, D, ACT_NONE, s);
 }
 

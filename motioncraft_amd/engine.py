@@ -111,7 +111,7 @@ class NativeContext:
     def set_option(self, key, value):
         """Kernel-selection switch of THIS context (mc_ctx_set_option); the MC_* variable of a key only seeds the default of
         contexts created afterwards.  Key (variable, default):
-        'chain' (MC_CHAIN, 763363319; retired bits 3, 23, 25, 28 and bits >= 30 raise), 'small_gemm_rows' (MC_SMALL_GEMM_ROWS, 5600),
+        'chain' (MC_CHAIN, 762806311; retired bits 3, 4, 6 - 14, 19, 23, 25, 28 and bits >= 30 raise), 'small_gemm_rows' (MC_SMALL_GEMM_ROWS, 5600),
         'split_rows_expert' (MC_SPLIT_ROWS_EXPERT, 2048), 'split_rows_sffn' (MC_SPLIT_ROWS_SFFN, 8192),
         'temporal_split' (MC_TEMPORAL_SPLIT, 96), 'big_tokens' (MC_BIG_TOKENS, 65536), 'rowchain_split' (MC_ROWCHAIN_SPLIT, 20480),
         'gemm_tune' (MC_GEMM_TUNE, 1841; bits 0, 4, 5, 6, 8, 9, 10), 'small_tile_n' (MC_SMALL_TILE_N, 0; 0, 48, 64 or 96),

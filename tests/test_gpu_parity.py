@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 import torch
 
-DEFAULT_CHAIN = 8388599 | (1 << 24) | (1 << 26) | (1 << 27) | (1 << 29)        # kChainDefault (mc_options.h): every schedule / fusion bit but the retired 3, 23, 25 and 28
+DEFAULT_CHAIN = 762806311        # kChainDefault (mc_options.h): every defined schedule / fusion bit (the retired ones are rejected)
 
 from helpers import (CTRL, CTRL_COPY, CTRL_FEATS, FULL, HML_FULL, HML_SMALL, KIT_SMALL, SMALL, SMALL_SEED, load,
                      step_noise_from_seed, synth_inputs)
@@ -606,7 +606,7 @@ def test_flop_ledger_books_the_executed_flops_of_a_step(full_model):
     d = build_diffusion(dict(beta_scheduler='linear', diffusion_steps=1000, model_mean_type='start_x', model_var_type='fixed_large'))
     x, xf, mask = synth_inputs(FULL, B, T, seed=3)
     want = bench.executed_flops_per_sample_step(bench.DIMS, T) * B
-    for tag, chain in (('two-stream', DEFAULT_CHAIN), ('single-stream', DEFAULT_CHAIN & ~((1 << 5) | (1 << 6) | (1 << 9) | (1 << 16)))):
+    for tag, chain in (('two-stream', DEFAULT_CHAIN), ('single-stream', DEFAULT_CHAIN & ~((1 << 5) | (1 << 16)))):
         ctx = nm.context(B, T, max_steps=1000)
         ctx.set_option('chain', chain)
         ctx.set_timesteps(d.timestep_map)
@@ -845,7 +845,7 @@ def test_baseline_control_configs_sampler_loop_lockstep(case):
 
 
 @pytest.mark.parametrize('chain', [DEFAULT_CHAIN & ~7, DEFAULT_CHAIN])
-def test_generic_fallback_path_vs_oracle(chain):
+def test_generic_fallback_path_vs_oracle(chain, monkeypatch):
     """chain mask with bits 0-2 cleared: the generic path -- plain gemm_k launches + row kernels instead of the fused
     expert / SFFN MLP, the fused gate and the register-chained proj / q/k/v kernels; the library also takes it whenever a width
     is outside the fused kernels' range, so it keeps its own parity test: small-config denoiser call + 3 DDPM steps vs the CPU
@@ -878,9 +878,16 @@ def test_generic_fallback_path_vs_oracle(chain):
     assert e1 <= TOL_STEP and e2 <= TOL_FINAL
     with pytest.raises(RuntimeError):
         ctx.set_option('no_such_switch', 1)
-    for b in (3, 23, 25, 28):          # retired chain bits: rejected, not ignored
+    for b in (3, 23, 25, 28, 4, 6, 7, 8, 9, 10, 11, 12, 13, 14, 19):          # retired chain bits: rejected, not ignored
         with pytest.raises(RuntimeError, match=f'chain bit {b} is retired'):
             ctx.set_option('chain', DEFAULT_CHAIN | (1 << b))
+    old_default = DEFAULT_CHAIN | sum(1 << b for b in (4, 6, 7, 8, 9, 10, 11, 12, 13, 14, 19))      # the default mask before these were retired
+    with pytest.raises(RuntimeError, match='chain bit 4 is retired'):
+        ctx.set_option('chain', old_default)
+    monkeypatch.setenv('MC_CHAIN', str(old_default))          # read when a context is created
+    with pytest.raises(RuntimeError, match=f'MC_CHAIN={old_default}'):
+        nm.context(B, T, max_steps=1)
+    monkeypatch.delenv('MC_CHAIN')
     with pytest.raises(RuntimeError):
         ctx.set_option('split_groups', 2)      # the large-batch schedule has exactly two sample groups
     with pytest.raises(RuntimeError, match='chain bit 30 is not defined'):

@@ -25,7 +25,7 @@ from helpers import FULL, bpr_keep, key_bits, skew_gates, synth_inputs
 
 pytestmark = pytest.mark.gpu
 
-DEFAULT_CHAIN = 763363319                      # kChainDefault (mc_options.h)
+DEFAULT_CHAIN = 762806311                      # kChainDefault (mc_options.h)
 TOL_STEP = 2e-4
 TAU = 1e-5                                     # R2: a token is "decided" when both fp64 gaps (1st-2nd, 2nd-3rd) exceed TAU * s1
 M2D = dict(FULL, L=64, F=256)                  # the L = 64 width (W.default_dims(L=64, F=256))
@@ -233,7 +233,7 @@ def test_full_batch_16_hot_pair(models):
 
 @pytest.mark.parametrize('kind', ['hot_pair', 'all_ties'])
 def test_batch_1_skewed_small_kernels(models, kind):
-    """B = 1 x 196: gate_small_k, route_small_k, the split-hidden expert MLP whose slice count (chain bit 13) is chosen on
+    """B = 1 x 196: gate_small_k, route_small_k, the split-hidden expert MLP whose slice count is chosen on
     the device from the real tile count -- which under skew (two experts at capacity, most others empty) is not the host's
     estimate."""
     res, coop = _run(models, 'FULL', kind, 1, 196)
@@ -265,7 +265,7 @@ def test_f16x3_expert_path_under_skew_vs_balanced(models):
 @pytest.mark.parametrize('kind', ['hot_pair', 'all_ties'])
 def test_production_layer_0_twin_dedupe_and_split_vs_oracle(models, kind):
     """A full-width model with NL = 1 at B = 64 on the production path (no stop_after_layers): twin dedupe and aliasing
-    (chain bits 4, 8), the twin split (bit 16), the large-batch schedule.  R1 against the captured routing, the twin-split
+    (base layer 0), the twin split (chain bit 16), the large-batch schedule.  R1 against the captured routing, the twin-split
     flag against what the reference keep flags imply (some token and its CFG twin kept differently), out2 against the
     oracle teacher-forced to the HIP routing, and two calls bit-identical."""
     from motioncraft_amd.engine import NativeModel

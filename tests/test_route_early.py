@@ -24,6 +24,7 @@ pytestmark = pytest.mark.gpu
 
 B, T = 3, 24
 LENGTHS = [24, 20, 7]
+DEFAULT_CHAIN = 762806311                      # kChainDefault (mc_options.h)
 DIMS = {'SMALL': SMALL, 'FULL': FULL}
 
 
@@ -68,9 +69,11 @@ def _inputs(dims, seed=71):
     return x, xf, mask, eps
 
 
-def _context(nm, xf, mask, early, tie='stable', delay=0, max_steps=2, timesteps=None):
+def _context(nm, xf, mask, early, tie='stable', delay=0, max_steps=2, timesteps=None, chain=None):
     ctx = nm.context(B, T, max_steps=max_steps)
     ctx.set_option('big_tokens', 0)
+    if chain is not None:
+        ctx.set_option('chain', chain)
     ctx.set_option('route_early', early)
     if delay:
         ctx.set_option('dbg_delay_us', delay)
@@ -223,23 +226,42 @@ def test_graph_replay_equals_eager(models, big_paths, name):
     assert torch.equal(got['eager'], got['graph']), float((got['eager'] - got['graph']).abs().max())
 
 
-@pytest.mark.parametrize('name', ['SMALL', 'FULL'])
-def test_late_streams_do_not_change_the_result(models, big_paths, name):
-    """dbg_delay_us holds the second (+300) or the first (-300) group's stream in front of every layer tail, so that group reaches the
-    next layer's gate late: the selection must wait for the late gate, the late group's projection for the selection."""
+_undelayed = {}          # (name, early, chain) -> (x, routing buffers) of the run without a delay, computed once per module
+
+
+def _late_run(models, name, early, chain, delay):
     dims, nm = models(name, 'hot_pair')
     x, xf, mask, eps = _inputs(dims)
-    got = {}
-    for delay in (0, 300, -300):
-        ctx = _context(nm, xf, mask, 1, delay=delay)
-        try:
-            got[delay] = (_two_steps(ctx, dims, x, eps), _routing_buffers(ctx))
-        finally:
-            ctx.close()
-    assert bool(torch.isfinite(got[0][0]).all())
+    key = (name, early, chain)
+    if delay == 0 and key in _undelayed:
+        return _undelayed[key]
+    ctx = _context(nm, xf, mask, early, delay=delay, chain=chain)
+    try:
+        got = (_two_steps(ctx, dims, x, eps), _routing_buffers(ctx))
+    finally:
+        ctx.close()
+    if delay == 0:
+        _undelayed[key] = got
+    return got
+
+
+@pytest.mark.parametrize('name', ['SMALL', 'FULL'])
+@pytest.mark.parametrize('chain', [DEFAULT_CHAIN, DEFAULT_CHAIN & ~(1 << 16)], ids=['default', 'no_twin_split'])
+@pytest.mark.parametrize('early', [1, 0])
+def test_late_streams_do_not_change_the_result(models, big_paths, name, chain, early):
+    """dbg_delay_us holds the second (+300) or the first (-300) group's stream in front of every layer tail, so that group reaches the
+    next layer's gate late: the selection (early) or the join in front of the routing (route_early = 0) must wait for the late gate,
+    the late group's projection for the selection and -- in the joined form and the unsplit twin layer (chain bit 16 cleared) -- for
+    the expert rows launched behind the routing.  Within each (early, chain) pair x and comb_w of the delayed runs equal the undelayed
+    run bit for bit, and the undelayed x of every pair equals that of (early, default)."""
+    base = _late_run(models, name, early, chain, 0)
+    assert bool(torch.isfinite(base[0]).all())
     for delay in (300, -300):
-        assert torch.equal(got[0][0], got[delay][0]), (delay, float((got[0][0] - got[delay][0]).abs().max()))
-        assert torch.equal(got[0][1]['comb_w'], got[delay][1]['comb_w']), delay
+        got = _late_run(models, name, early, chain, delay)
+        assert torch.equal(base[0], got[0]), (delay, float((base[0] - got[0]).abs().max()))
+        assert torch.equal(base[1]['comb_w'], got[1]['comb_w']), delay
+    ref = _late_run(models, name, 1, DEFAULT_CHAIN, 0)
+    assert torch.equal(ref[0], base[0]), float((ref[0] - base[0]).abs().max())
 
 
 def _ledger(lib, fn):

@@ -3,7 +3,7 @@
 mc_debug_flop_ledger is on, keyed "kernel@<grid work-items>" -- the key a rocprofv3 kernel trace gives a dispatch.  tools/kernel_roofline.py
 prices the per-kernel table with it, so no MFMA kernel of the step is left without FLOPs and the column sums to the executed FLOPs bench.py reports.
 
-    [MC_CHAIN=763297175] python tools/flop_ledger.py [batch, default 64] [f32|f16|f16x3] > profiles/rNN_flop_ledger[_serial].txt
+    [MC_CHAIN=762740743] python tools/flop_ledger.py [batch, default 64] [f32|f16|f16x3] > profiles/rNN_flop_ledger[_serial].txt
 
 Expert MLPs are booked at the routing's slot count (tokens x top-2 before capacity drops)."""
 import ctypes
