@@ -16,6 +16,8 @@
  *   mc_sample_step        GaussianDiffusion.p_sample / ddim_sample     gaussian_diffusion.py:634-696, 799-852
  *   mc_sample_step_inpaint  the same with y = {gt, outpainting_mask}   gaussian_diffusion.py:492-501, 855-877
  *   mc_sample_step_seeded   the same with pre_seq / transl_req         gaussian_diffusion.py:664-674, 816-820
+ *   mc_ctx_set_seams      no reference counterpart: all windows of a long sequence as rows of ONE batch, the overlapping frames of
+ *                         neighbouring windows blended after every denoiser call (the reference walks windows one by one, tools/m2d_test.py:139-232)
  *   mc_textenc_*          DiffusionTransformer.encode_text (CLIP text tower, text_pre_proj, textTransEncoder, text_ln)
  *                                                                      mogen/models/transformers/diffusion_transformer.py:109-172
  *   mc_evalenc_*          T2MContrastiveModel_SMPLX.encode_motion / encode_text (evaluation embeddings)
@@ -251,6 +253,21 @@ int mc_sample_loop(mc_ctx* c, float* x_dev, const int32_t* step_indices_host, co
 /* draw `draw` of the Philox stream keyed by `seed`: out_dev[n] = normals, bits_dev[n] = the raw 32-bit words (either may be NULL) */
 int mc_op_philox_normal(float* out_dev, uint32_t* bits_dev, int64_t n, uint64_t seed, uint64_t draw, void* stream);
 
+/* Coupled windows of a long sequence (no reference counterpart; the window-parallel scheme of DoubleTake / MultiDiffusion): the B rows of
+ * the context are windows of T frames, row b starting at global frame first_frame_host[b].  Rows b and b + 1 are NEIGHBOURS when
+ * first_frame[b + 1] == first_frame[b] + T - overlap: the last `overlap` frames of b and the first of b + 1 are the same frames.  Rows
+ * that are not neighbours must be disjoint (first_frame[b + 1] >= first_frame[b] + T: a new sequence); a partial overlap, a decreasing
+ * list, a negative entry, or an overlap outside 0 < 2 overlap <= T is MC_ERR_ARG.  While a table is set, the sampler update of
+ * mc_sample_step / mc_sample_loop (every mode) blends the two x0 predictions of a shared frame f,
+ *     x0 = w[f] x0_right + (1 - w[f]) x0_left,     w = weight_host[overlap] in [0, 1], or NULL: w[f] = (f + 1) / (overlap + 1),
+ * and gives both rows the SAME x_prev / x0 / history (computed once, with the LEFT row's noise element or Philox counter; the right
+ * row's noise on its first `overlap` frames is not read).  Every other element gets the bits of the uncoupled update.
+ * PRECONDITION (not checked): x_T is equal on shared frames; then x stays equal there bit for bit after every step.
+ * The table is uploaded on `stream` (the call synchronises it); overlap == 0 clears it (the other arguments are ignored).  Setting or
+ * clearing clears the multistep history flag.  While a table is set, mc_sample_step_inpaint, mc_sample_step_seeded and
+ * mc_ctx_graph_capture return MC_ERR_STATE; with a captured graph in the context, setting a table is MC_ERR_STATE. */
+int mc_ctx_set_seams(mc_ctx* c, int32_t overlap, const int32_t* first_frame_host, const float* weight_host, void* stream);
+
 /* hipGraph replay of mc_sample_step (BASELINE.json configs[4] "hipGraph-captured 50-step DDIM"): ONE graph serves every step
  * of the schedule -- the step index is a device-side integer, the FiLM tables and the sampler coefficients are addressed
  * with it inside the kernels, no host sync or per-step H2D copy (SURVEY.md section 3.1 lists the reference's per-step
@@ -391,6 +408,14 @@ int mc_op_sampler_update(const float* x_t_dev, const float* out_text_dev, const 
  * x0_dev may be NULL.  coefs->mode must be MC_SAMPLER_MULTISTEP. */
 int mc_op_sampler_multistep(const float* x_t_dev, const float* out_text_dev, const float* out_none_dev, float* x0_hist_dev,
                             float* x_prev_dev, float* x0_dev, int64_t n, const mc_step_coefs* coefs, void* stream);
+/* the seam-coupled update without a context (see mc_ctx_set_seams for the plan rules and the blend): operands [B, T, C], any mode.
+ * Modes 0 / 1: the noise is read from noise_dev, or with noise_dev == NULL drawn from the Philox stream (seed, draw) -- mutually
+ * exclusive: seed and draw must be 0 beside a noise tensor.  Mode 2: x0_hist_dev in-out as in mc_op_sampler_multistep (unused, may
+ * be NULL, in the other modes), no noise.  x_prev_dev may alias x_t_dev, x0_dev may be NULL.  Synchronises. */
+int mc_op_sampler_seam(const float* x_t_dev, const float* out_text_dev, const float* out_none_dev, const float* noise_dev, uint64_t seed,
+                       uint64_t draw, float* x0_hist_dev, float* x_prev_dev, float* x0_dev, int32_t B, int32_t T, int32_t C,
+                       int32_t overlap, const int32_t* first_frame_host, const float* weight_host, const mc_step_coefs* coefs,
+                       void* stream);
 
 /* Result post-processing of the 322-d motion.  pred_dev [B,T,322] normalised; lengths_dev [B]
  * int32 valid frames (NULL = T); mean/std_dev [322] fp64; taps_dev [4][MC_POST_MAXTAP] fp64 = normalised Gaussian

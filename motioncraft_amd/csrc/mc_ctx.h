@@ -131,6 +131,10 @@ struct mc_ctx {
     bool hist_valid = false;            // x0_hist holds the x0 of the previous step of THIS condition / schedule (a mode-2 step sets it)
     bool graph_multistep = false;       // the captured graph's table is mode 2 (a graph is captured for one table: its update kernel is fixed)
     std::vector<float> graph_k1;        // ... and its k1 per schedule index: mc_ctx_graph_step checks hist_valid on the host
+    // window coupling (mc_ctx_set_seams): while seam_ov > 0 sampler_update launches sampler_seam_k.  One device block, allocated by the
+    // first call that sets a table: [B] neighbour flags (ints), then [T / 2] right-window weights (floats)
+    int* seam_tab = nullptr;
+    int seam_ov = 0;
     int prec = MC_PREC_F32;     // MFMA operand precision of the per-step GEMM-shaped kernels (mc_ctx_set_precision)
     int* cap_idx = nullptr;      // [NL][2N] routing capture (tests): expert ids ...
     float* cap_w = nullptr;      // ... and combine weights (0 = dropped) of every layer
@@ -162,7 +166,8 @@ struct X0Parts {
 };
 int denoise_combined(mc_ctx* c, const float* x_t, int32_t step, const mc_step_coefs* k, void* stream, X0Parts* x0, const SeedArgs* seed = nullptr);
 // the sampler update behind denoise_combined, its kernel picked by the step's mode (under capture: by the graph's table) -- sampler_update_k
-// (modes 0 / 1; noise or rng) or sampler_multistep_k (mode 2; x0_hist must be allocated, the caller keeps the history-valid flag)
+// (modes 0 / 1; noise or rng) or sampler_multistep_k (mode 2; x0_hist must be allocated, the caller keeps the history-valid flag); with
+// a seam table set (mc_ctx_set_seams) sampler_seam_k in every mode
 int sampler_update(mc_ctx* c, const float* x_t, const X0Parts& x0p, const mc_step_coefs* k, const float* noise, float* x_prev, float* x0,
                    hipStream_t s, const RngArgs* rng = nullptr, const PadOut* pad = nullptr);
 #pragma GCC visibility pop

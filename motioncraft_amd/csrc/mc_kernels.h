@@ -59,6 +59,14 @@ int mc_launch_sampler_update(const float* x_t, const float* out_text, const floa
 int mc_launch_sampler_multistep(const float* x_t, const float* out_text, const float* out_none, float* x0_hist, float* x_prev,
                                 float* x0_out, long n, SamplerCoefs c, hipStream_t s, const SamplerCoefs* table = nullptr,
                                 const int* step_ptr = nullptr, const PadOut* pad = nullptr);
+// Seam-coupled update of B windows [B][T][C] (sampler_seam_k, all three modes): flags [B] ints on the device, bit 0 = the row shares
+// its first `ov` frames with the last `ov` of row b - 1, bit 1 = its last `ov` with the first of row b + 1 (the caller guarantees bit 1
+// of row b goes with bit 0 of row b + 1 and is clear on row B - 1); w [ov] = the right window's weight per shared frame; 0 < 2 ov <= T.
+// Modes 0 / 1: noise or rng as above (a seam element takes the LEFT row's draw); mode 2: x0_hist in-out, no noise.  No graph table.
+struct SeamTab { const int* flags = nullptr; const float* w = nullptr; int T = 0, C = 0, ov = 0; };
+int mc_launch_sampler_seam(const float* x_t, const float* out_text, const float* out_none, const float* noise, float* x0_hist,
+                           float* x_prev, float* x0_out, int B, SamplerCoefs c, const SeamTab& st, hipStream_t s,
+                           const RngArgs* rng = nullptr, const PadOut* pad = nullptr);
 // out[n] = the normals / bits[n] = the raw 32-bit words of draw `rng` (either may be null)
 int mc_launch_philox_fill(float* out, uint32_t* bits, long n, RngArgs rng, hipStream_t s);
 // out = table[*step].text_coef * x + table[*step].none_coef * y   (CFG combine of the two halves under graph replay)

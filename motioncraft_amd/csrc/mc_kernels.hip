@@ -390,6 +390,105 @@ __global__ __launch_bounds__(256) void sampler_multistep_k(const float* x_t, con
     }
 }
 
+// Seam-coupled update (window-parallel long sequences): the batch rows are windows of T frames; rows b and b + 1
+// flagged as neighbours share `ov` frames -- frames [T - ov, T) of b (its tail) are frames [0, ov) of b + 1 (its head).  A seam element
+//   x0 = w[f] x0_right + (1 - w[f]) x0_left;   x_prev = update(x_left, x0, noise_left / hist_left)
+// is computed ONCE, by the thread that owns the LEFT (tail) element, and stored to both rows (x_prev, x0_out, hist, xpad); head elements
+// of a row with a left neighbour are skipped by their own thread.  All three modes (c.mode is kernel-uniform), host noise or Philox.
+// Same flat groups of four as sampler_update_k, so every non-seam element sees the same Philox counter and the same device functions:
+// the same bits.  Groups that touch no overlap region keep the f32x4 path; the others go element by element (C is no multiple of 4: a
+// group can hold seam and plain elements at once).  x_prev may alias x_t: a thread reads its own x_t elements before it writes, and the
+// only foreign elements it writes are head elements, which no thread reads (2 ov <= T: a head element is never a tail element).
+// No graph table: a context with a seam table refuses capture.
+enum { SEAM_LEFT = 1, SEAM_RIGHT = 2 };      // SeamTab::flags[b]: the row has a left / a right neighbour
+template <bool RNG, bool VEC>
+__global__ __launch_bounds__(256) void sampler_seam_k(const float* x_t, const float* __restrict__ o_text,
+                                                      const float* __restrict__ o_none, const float* __restrict__ noise,
+                                                      float* hist, float* x_prev, float* x0_out, long n, SamplerCoefs c,
+                                                      SeamTab st, RngArgs rng, PadOut po) {
+    const SamplerDerived d = sampler_derive(c);
+    const bool ms = c.mode == 2;
+    const float kx = c.c2, k0 = c.c1, k1 = c.eta;
+    const bool use_hist = ms && k1 != 0.f;
+    const int TC = st.T * st.C, headC = st.ov * st.C, tailC = (st.T - st.ov) * st.C;
+    const long ngroups = (n + 3) >> 2;
+    for (long gi = (long)blockIdx.x * blockDim.x + threadIdx.x; gi < ngroups; gi += (long)gridDim.x * blockDim.x) {
+        const long i = gi * 4;
+        // classify the four elements: 0 plain, 1 head (skipped), 2 tail (seam owner)
+        int b = (int)(i / TC);
+        int rem = (int)(i - (long)b * TC);
+        int cls[4], rr[4];
+        int any = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            cls[j] = 0; rr[j] = rem;
+            if (i + j < n) {
+                const int fl = st.flags[b];
+                if (rem < headC && (fl & SEAM_LEFT)) cls[j] = 1;
+                else if (rem >= tailC && (fl & SEAM_RIGHT)) cls[j] = 2;
+            }
+            any |= cls[j];
+            if (++rem == TC) { rem = 0; ++b; }
+        }
+        if (VEC && i + 4 <= n && !any) {
+            const f32x4 x = *reinterpret_cast<const f32x4*>(x_t + i);
+            const f32x4 a = *reinterpret_cast<const f32x4*>(o_text + i), bb = *reinterpret_cast<const f32x4*>(o_none + i);
+            f32x4 nz = {0.f, 0.f, 0.f, 0.f}, hp = {0.f, 0.f, 0.f, 0.f};
+            if (!ms) {
+                if constexpr (RNG) nz = philox_normal4(gi, rng);
+                else nz = *reinterpret_cast<const f32x4*>(noise + i);
+            } else if (use_hist) hp = *reinterpret_cast<const f32x4*>(hist + i);
+            f32x4 out, x0v;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                x0v[j] = cfg_elem(a[j], bb[j], c);
+                out[j] = ms ? multistep_elem(x[j], x0v[j], hp[j], kx, k0, k1) : sampler_elem(x[j], x0v[j], nz[j], c, d);
+            }
+            *reinterpret_cast<f32x4*>(x_prev + i) = out;
+            if (ms) *reinterpret_cast<f32x4*>(hist + i) = x0v;
+            if (x0_out) *reinterpret_cast<f32x4*>(x0_out + i) = x0v;
+            if (po.xpad) {
+                long row = i / po.C;
+                int col = (int)(i - row * po.C);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    po.xpad[row * po.Cp + col] = out[j];
+                    if (++col == po.C) { col = 0; ++row; }
+                }
+            }
+        } else {
+            f32x4 nz = {0.f, 0.f, 0.f, 0.f};
+            if constexpr (RNG) { if (!ms) nz = philox_normal4(gi, rng); }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (i + j >= n || cls[j] == 1) continue;         // (head: written by the left neighbour's tail thread)
+                const long e = i + j;
+                float x0 = cfg_elem(o_text[e], o_none[e], c);
+                long er = -1;
+                if (cls[j] == 2) {                               // (b + 1, f, ch): the flags say that row exists
+                    er = e + headC;                              // = e + TC - tailC
+                    const float w = st.w[(rr[j] - tailC) / st.C];
+                    const float x0r = cfg_elem(o_text[er], o_none[er], c);
+                    x0 = fmaf(w, x0r, __fmul_rn(__fsub_rn(1.f, w), x0));
+                }
+                float o;
+                if (ms) o = multistep_elem(x_t[e], x0, use_hist ? hist[e] : 0.f, kx, k0, k1);
+                else o = sampler_elem(x_t[e], x0, RNG ? nz[j] : noise[e], c, d);
+                x_prev[e] = o;
+                if (ms) hist[e] = x0;
+                if (x0_out) x0_out[e] = x0;
+                if (po.xpad) po.xpad[e / po.C * po.Cp + e % po.C] = o;
+                if (er >= 0) {
+                    x_prev[er] = o;
+                    if (ms) hist[er] = x0;
+                    if (x0_out) x0_out[er] = x0;
+                    if (po.xpad) po.xpad[er / po.C * po.Cp + er % po.C] = o;
+                }
+            }
+        }
+    }
+}
+
 // the same draws written to memory (tests; callers that want the loop's noise stream)
 __global__ __launch_bounds__(256) void philox_fill_k(float* __restrict__ out, uint32_t* __restrict__ bits, long n, RngArgs rng) {
     const long ngroups = (n + 3) >> 2;
@@ -637,6 +736,35 @@ int mc_launch_sampler_multistep(const float* x_t, const float* out_text, const f
     MC_REQUIRE(!po.xpad || (po.C > 0 && po.Cp >= po.C), "multistep update: bad padded-copy shape");
     if (vec) hipLaunchKernelGGL((sampler_multistep_k<true>), dim3(blocks), dim3(256), 0, s, x_t, out_text, out_none, x0_hist, x_prev, x0_out, n, c, table, step_ptr, po);
     else hipLaunchKernelGGL((sampler_multistep_k<false>), dim3(blocks), dim3(256), 0, s, x_t, out_text, out_none, x0_hist, x_prev, x0_out, n, c, table, step_ptr, po);
+    MC_LAUNCH_CHECK();
+    return MC_OK;
+}
+
+int mc_launch_sampler_seam(const float* x_t, const float* out_text, const float* out_none, const float* noise, float* x0_hist, float* x_prev,
+                           float* x0_out, int B, SamplerCoefs c, const SeamTab& st, hipStream_t s, const RngArgs* rng, const PadOut* pad) {
+    MC_REQUIRE(x_t && out_text && out_none && x_prev && st.flags && st.w && B >= 0, "seam update: null operand");
+    MC_REQUIRE(st.T > 0 && st.C > 0 && st.ov > 0 && 2 * st.ov <= st.T, "seam update: overlap %d outside (0, %d / 2]", st.ov, st.T);
+    MC_REQUIRE((long)st.T * st.C <= 0x7fffffffL, "seam update: a window of %d x %d floats", st.T, st.C);
+    MC_REQUIRE(c.mode >= 0 && c.mode <= 2, "seam update: unknown sampler mode %d", c.mode);
+    const bool ms = c.mode == 2;
+    MC_REQUIRE(ms || noise || rng, "seam update: neither a noise tensor nor a Philox draw given");
+    MC_REQUIRE(!ms || x0_hist, "seam update: mode 2 without a history buffer");
+    MC_REQUIRE(!ms || (x0_hist != x_t && x0_hist != x_prev && x0_hist != x0_out && x0_hist != out_text && x0_hist != out_none),
+               "seam update: the history buffer aliases another operand");
+    const long n = (long)B * st.T * st.C;
+    if (n == 0) return MC_OK;
+    const bool vec = ((uintptr_t)x_t | (uintptr_t)out_text | (uintptr_t)out_none | (uintptr_t)x_prev | (uintptr_t)x0_out |
+                      (uintptr_t)(ms ? nullptr : noise) | (uintptr_t)(ms ? x0_hist : nullptr)) % 16 == 0;
+    int blocks = cdiv((n + 3) / 4, 256);
+    if (blocks > 2048) blocks = 2048;
+    const bool dev_rng = !ms && rng && !noise;
+    const RngArgs ra = dev_rng ? *rng : RngArgs();
+    const PadOut po = pad ? *pad : PadOut();
+    MC_REQUIRE(!po.xpad || (po.C == st.C && po.Cp >= po.C), "seam update: bad padded-copy shape");
+#define MC_SS(R, V) hipLaunchKernelGGL((sampler_seam_k<R, V>), dim3(blocks), dim3(256), 0, s, x_t, out_text, out_none, noise, x0_hist, x_prev, x0_out, n, c, st, ra, po)
+    if (dev_rng) { if (vec) MC_SS(true, true); else MC_SS(true, false); }
+    else { if (vec) MC_SS(false, true); else MC_SS(false, false); }
+#undef MC_SS
     MC_LAUNCH_CHECK();
     return MC_OK;
 }

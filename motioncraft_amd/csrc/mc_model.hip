@@ -633,6 +633,64 @@ static int hist_require(const mc_ctx* c, float k1, int32_t step) {
     return MC_OK;
 }
 
+// ---- coupled windows (sampler_seam_k): the seam table of a context / of the context-free op ----
+// B windows of T frames at global first frames ff[b], neighbours sharing `ov` frames -> per-row flags (bit 0: left neighbour, bit 1: right)
+// and the right-window weights.  Rows b, b + 1 are neighbours when ff[b + 1] == ff[b] + T - ov and must otherwise be disjoint.
+static int seam_plan(const char* who, int B, int T, int ov, const int32_t* ff, const float* w, std::vector<int>* flags, std::vector<float>* wt) {
+    MC_REQUIRE(B >= 1 && T >= 1, "%s: %d windows of %d frames", who, B, T);
+    MC_REQUIRE(ov > 0 && 2L * ov <= T, "%s: overlap %d outside (0, T / 2 = %d] (a frame may lie in two windows at most)", who, ov, T / 2);
+    MC_REQUIRE(ff, "%s: null first_frame", who);
+    const long stride = T - ov;
+    flags->assign(B, 0);
+    for (int b = 0; b < B; ++b) {
+        MC_REQUIRE(ff[b] >= 0, "%s: first_frame[%d] = %d is negative", who, b, ff[b]);
+        if (b + 1 == B) break;
+        const long gap = (long)ff[b + 1] - ff[b];
+        if (gap == stride) { (*flags)[b] |= 2; (*flags)[b + 1] |= 1; }
+        else MC_REQUIRE(gap >= T, "%s: first_frame[%d] = %d after first_frame[%d] = %d: neither its neighbour (+%ld) nor disjoint from it (>= +%d)",
+                        who, b + 1, ff[b + 1], b, ff[b], stride, T);
+    }
+    wt->resize(ov);
+    for (int f = 0; f < ov; ++f) {
+        if (w) MC_REQUIRE(w[f] >= 0.f && w[f] <= 1.f, "%s: weight[%d] = %g outside [0, 1]", who, f, (double)w[f]);
+        (*wt)[f] = w ? w[f] : (float)((double)(f + 1) / (double)(ov + 1));
+    }
+    return MC_OK;
+}
+static int seam_refuse(const mc_ctx* c, const char* who) {
+    if (c->seam_ov > 0) {
+        mc_set_error("%s: the context has a seam table set (mc_ctx_set_seams): coupled windows take mc_sample_step / mc_sample_loop only; clear it with overlap = 0", who);
+        return MC_ERR_STATE;
+    }
+    return MC_OK;
+}
+
+int mc_ctx_set_seams(mc_ctx* c, int32_t overlap, const int32_t* first_frame, const float* weight, void* stream) {
+    MC_REQUIRE(c, "null context");
+    if (overlap == 0) {
+        if (c->seam_ov > 0) c->hist_valid = false;       // (multistep sampler: the previous x0 belongs to the coupled walk)
+        c->seam_ov = 0;
+        return MC_OK;
+    }
+    std::vector<int> flags;
+    std::vector<float> wt;
+    int r;
+    if ((r = seam_plan("mc_ctx_set_seams", c->B, c->T, overlap, first_frame, weight, &flags, &wt))) return r;
+    if (c->graph_exec) {
+        mc_set_error("mc_ctx_set_seams: the context holds a captured graph of the uncoupled step (mc_ctx_graph_release first)");
+        return MC_ERR_STATE;
+    }
+    if (!c->seam_tab && (r = ws_alloc(c, &c->seam_tab, (size_t)c->B + (size_t)c->T / 2)) != MC_OK) return r;
+    hipStream_t s = (hipStream_t)stream;
+    c->seam_ov = 0;
+    MC_HIP(hipMemcpyAsync(c->seam_tab, flags.data(), sizeof(int) * c->B, hipMemcpyHostToDevice, s));
+    MC_HIP(hipMemcpyAsync(c->seam_tab + c->B, wt.data(), sizeof(float) * overlap, hipMemcpyHostToDevice, s));
+    MC_HIP(hipStreamSynchronize(s));                 // (the two vectors are temporaries)
+    c->seam_ov = overlap;
+    c->hist_valid = false;
+    return MC_OK;
+}
+
 int mc_sample_step(mc_ctx* c, const float* x_t, int32_t step, const mc_step_coefs* k, const float* noise,
                    float* x_prev, float* x0, void* stream) {
     MC_REQUIRE(c && x_t && k && x_prev, "null argument");
@@ -706,6 +764,7 @@ int mc_op_philox_normal(float* out, uint32_t* bits, int64_t n, uint64_t seed, ui
 int mc_ctx_graph_capture(mc_ctx* c, float* x_dev, const float* noise_dev, const mc_step_coefs* coefs_host, int32_t num_steps,
                          void* stream) {
     MC_REQUIRE(c && x_dev && coefs_host, "null argument");
+    if (int rs = seam_refuse(c, "mc_ctx_graph_capture")) return rs;
     MC_REQUIRE(c->have_cond, "mc_ctx_set_condition not called");
     MC_REQUIRE(num_steps >= 1 && num_steps == c->S, "num_steps=%d must equal the schedule set by mc_ctx_set_timesteps (%d)", num_steps, c->S);
     MC_REQUIRE(!c->cap_idx, "routing capture (tests) and graph replay are mutually exclusive");
@@ -770,6 +829,7 @@ int mc_ctx_graph_release(mc_ctx* c) {
 int mc_sample_step_seeded(mc_ctx* c, float* x_t, int32_t step, const mc_step_coefs* k, const float* noise,
                           const mc_seed* sd, float* x_prev, float* x0, void* stream) {
     MC_REQUIRE(c && x_t && k && noise && x_prev && sd, "null argument");
+    if (int rs = seam_refuse(c, "mc_sample_step_seeded")) return rs;
     MC_REQUIRE(!is_multistep(k), "mc_sample_step_seeded: the multistep sampler (mode 2) has no pre_seq / transl_req seeding");
     MC_REQUIRE(sd->pre_len >= 0 && sd->pre_len <= c->T, "pre_seq has %d frames, the window %d", sd->pre_len, c->T);
     MC_REQUIRE(sd->num_transl >= 0 && sd->num_transl <= MC_MAX_TRANSL, "num_transl=%d outside [0, %d]", sd->num_transl, MC_MAX_TRANSL);
@@ -792,6 +852,7 @@ int mc_sample_step_seeded(mc_ctx* c, float* x_t, int32_t step, const mc_step_coe
 int mc_sample_step_inpaint(mc_ctx* c, const float* x_t, int32_t step, const mc_step_coefs* k, const float* noise,
                            const mc_inpaint* ip, float* x_prev, float* x0, void* stream) {
     MC_REQUIRE(c && x_t && k && noise && x_prev && ip, "null argument");
+    if (int rs = seam_refuse(c, "mc_sample_step_inpaint")) return rs;
     MC_REQUIRE(!is_multistep(k), "mc_sample_step_inpaint: the multistep sampler (mode 2) has no outpainting (RePaint) form");
     X0Parts p;
     if (int r = denoise_combined(c, x_t, step, k, stream, &p)) return r;
@@ -1027,6 +1088,36 @@ int mc_op_sampler_multistep(const float* x_t, const float* ot, const float* on, 
     MC_REQUIRE(x_t && ot && on && x0_hist && x_prev && k && n >= 0, "bad argument");
     MC_REQUIRE(is_multistep(k), "mc_op_sampler_multistep: coefficients of mode %d (MC_SAMPLER_MULTISTEP = 2 expected)", k->mode);
     return mc_launch_sampler_multistep(x_t, ot, on, x0_hist, x_prev, x0, n, to_coefs(k), (hipStream_t)stream);
+}
+
+int mc_op_sampler_seam(const float* x_t, const float* ot, const float* on, const float* noise, uint64_t seed, uint64_t draw, float* x0_hist,
+                       float* x_prev, float* x0, int32_t B, int32_t T, int32_t C, int32_t overlap, const int32_t* first_frame,
+                       const float* weight, const mc_step_coefs* k, void* stream) {
+    MC_REQUIRE(x_t && ot && on && x_prev && k && C >= 1, "mc_op_sampler_seam: bad argument");
+    int r;
+    if ((r = check_mode(k))) return r;
+    const bool ms = is_multistep(k);
+    MC_REQUIRE(ms || !noise || (seed == 0 && draw == 0), "mc_op_sampler_seam: noise_dev and a Philox draw (seed / draw) are mutually exclusive");
+    MC_REQUIRE(!ms || x0_hist, "mc_op_sampler_seam: mode 2 needs x0_hist_dev");
+    std::vector<int> flags;
+    std::vector<float> wt;
+    if ((r = seam_plan("mc_op_sampler_seam", B, T, overlap, first_frame, weight, &flags, &wt))) return r;
+    hipStream_t s = (hipStream_t)stream;
+    int* tab = nullptr;
+    MC_HIP(hipMalloc((void**)&tab, sizeof(int) * ((size_t)B + overlap)));
+    SeamTab st;
+    st.flags = tab; st.w = reinterpret_cast<const float*>(tab + B); st.T = T; st.C = C; st.ov = overlap;
+    r = MC_OK;
+    if (hipMemcpyAsync(tab, flags.data(), sizeof(int) * B, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(tab + B, wt.data(), sizeof(float) * overlap, hipMemcpyHostToDevice, s) != hipSuccess) {
+        mc_set_error("mc_op_sampler_seam: table upload failed");
+        r = MC_ERR_HIP;
+    }
+    const RngArgs rng = rng_args(seed, draw);
+    if (r == MC_OK) r = mc_launch_sampler_seam(x_t, ot, on, noise, ms ? x0_hist : nullptr, x_prev, x0, B, to_coefs(k), st, s, noise ? nullptr : &rng);
+    (void)hipStreamSynchronize(s);                   // (the table is a temporary)
+    (void)hipFree(tab);
+    return r;
 }
 
 }  // extern "C"

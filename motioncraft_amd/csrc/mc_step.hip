@@ -827,6 +827,14 @@ int sampler_update(mc_ctx* c, const float* x_t, const X0Parts& x0p, const mc_ste
     const SamplerCoefs* table = c->graph_mode ? c->gcoefs : nullptr;
     const int* step_ptr = c->graph_mode ? c->gstep : nullptr;
     const bool multistep = c->graph_mode ? c->graph_multistep : k->mode == MC_SAMPLER_MULTISTEP;
+    if (c->seam_ov > 0) {        // coupled windows: one kernel for every mode (no graph table: capture is refused while the seam table is set)
+        if (c->graph_mode) { mc_set_error("sampler update under graph capture with a seam table set"); return MC_ERR_STATE; }
+        MC_REQUIRE(!multistep || c->x0_hist, "multistep update without a history buffer");
+        SeamTab st;
+        st.flags = c->seam_tab; st.w = reinterpret_cast<const float*>(c->seam_tab + c->B);
+        st.T = c->T; st.C = c->m->cfg.input_feats; st.ov = c->seam_ov;
+        return mc_launch_sampler_seam(x_t, x0p.a, x0p.second(), noise, multistep ? c->x0_hist : nullptr, x_prev, x0, c->B, x0p.coefs(k), st, s, rng, pad);
+    }
     if (!multistep) return mc_launch_sampler_update(x_t, x0p.a, x0p.second(), noise, x_prev, x0, n, x0p.coefs(k), s, table, step_ptr, rng, pad);
     MC_REQUIRE(c->x0_hist, "multistep update without a history buffer");
     return mc_launch_sampler_multistep(x_t, x0p.a, x0p.second(), c->x0_hist, x_prev, x0, n, x0p.coefs(k), s, table, step_ptr, pad);

@@ -215,8 +215,44 @@ class GaussianDiffusion:
             h_prev = h
         return out
 
+    @staticmethod
+    def _seams_of(model_kwargs, graph, pre_seq, transl_req):
+        """``model_kwargs['seams'] = dict(first_frame=..., overlap=..., weights=None)``: the rows of the batch are coupled windows of a
+        long sequence (``NativeContext.set_seams``; ``longform.sample_long_coupled`` builds it).  What does not go with it raises here,
+        before anything runs."""
+        seams = (model_kwargs or {}).get('seams', None)
+        if seams is None:
+            return None
+        if graph:
+            raise ValueError('graph replay does not cover coupled windows (model_kwargs["seams"]): the captured step is the uncoupled one')
+        keep = ((model_kwargs.get('y', {}) or {}).get('outpainting_mask', None))
+        if keep is not None and bool(keep.any()):
+            raise NotImplementedError('coupled windows (model_kwargs["seams"]) together with an outpainting mask (RePaint)')
+        if pre_seq is not None or transl_req:
+            raise NotImplementedError('coupled windows (model_kwargs["seams"]) together with pre_seq / transl_req seeding')
+        extra = set(seams) - {'first_frame', 'overlap', 'weights'}
+        if extra or 'first_frame' not in seams or 'overlap' not in seams:
+            raise ValueError(f'model_kwargs["seams"]: dict(first_frame=..., overlap=..., weights=None), got keys {sorted(seams)}')
+        return dict(first_frame=seams['first_frame'], overlap=seams['overlap'], weights=seams.get('weights', None))
+
     def _loop(self, mode, model, shape, noise, model_kwargs, device, progress, eta, step_noise, generator,
               num_steps=None, trajectory=None, pre_seq=None, transl_req=None, graph=False, fused=True):
+        """the walk of ``_walk``; with ``model_kwargs['seams']`` the context's seam table is set before it and cleared after it, whatever
+        happens in between (per-step and fused path alike: the library picks the coupled update wherever a table is set)"""
+        seams = self._seams_of(model_kwargs, graph, pre_seq, transl_req)
+        if seams is None:
+            return self._walk(mode, model, shape, noise, model_kwargs, device, progress, eta, step_noise, generator, num_steps,
+                              trajectory, pre_seq, transl_req, graph, fused)
+        held = []
+        try:
+            return self._walk(mode, model, shape, noise, model_kwargs, device, progress, eta, step_noise, generator, num_steps,
+                              trajectory, pre_seq, transl_req, graph, fused, seams=seams, seam_held=held)
+        finally:
+            for ctx in held:
+                ctx.clear_seams()
+
+    def _walk(self, mode, model, shape, noise, model_kwargs, device, progress, eta, step_noise, generator,
+              num_steps=None, trajectory=None, pre_seq=None, transl_req=None, graph=False, fused=True, seams=None, seam_held=None):
         if model_kwargs is None:
             model_kwargs = {}
         if not isinstance(shape, (tuple, list)):
@@ -226,6 +262,9 @@ class GaussianDiffusion:
             device = torch.device('cuda', torch.cuda.current_device())
         inp = self._inpaint_operands(mode, model_kwargs, shape, device)
         ctx = model.sampling_context(B, T, self.timestep_map, model_kwargs, device)
+        if seams is not None:
+            seam_held.append(ctx)
+            ctx.set_seams(**seams)
         if noise is not None:
             img = noise.to(device=device, dtype=torch.float32).contiguous().clone()
         else:
@@ -428,6 +467,7 @@ class GaussianDiffusion:
             raise ValueError(f'order={order!r}: the multistep solver is implemented for order 1 and 2')
         if model_kwargs is None:
             model_kwargs = {}
+        seams = self._seams_of(model_kwargs, graph, pre_seq, transl_req)
         keep = ((model_kwargs.get('y', {}) or {}).get('outpainting_mask', None))
         if keep is not None and bool(keep.any()):
             raise NotImplementedError('dpm_solver_sample_loop with an outpainting mask (RePaint): not implemented for the '
@@ -442,6 +482,15 @@ class GaussianDiffusion:
         if device is None:
             device = torch.device('cuda', torch.cuda.current_device())
         ctx = model.sampling_context(B, T, self.timestep_map, model_kwargs, device)
+        if seams is None:
+            return self._multistep_walk(ctx, model, shape, noise, device, progress, order, generator, num_steps, trajectory, graph, fused)
+        try:                                                  # coupled windows: the table is set for this walk only
+            ctx.set_seams(**seams)
+            return self._multistep_walk(ctx, model, shape, noise, device, progress, order, generator, num_steps, trajectory, graph, fused)
+        finally:
+            ctx.clear_seams()
+
+    def _multistep_walk(self, ctx, model, shape, noise, device, progress, order, generator, num_steps, trajectory, graph, fused):
         if noise is not None:
             img = noise.to(device=device, dtype=torch.float32).contiguous().clone()
         else:

@@ -58,6 +58,7 @@ class NativeContext:
         self.timesteps = None
         self._keep = []
         self._graph_state = None
+        self.seams = None              # dict(first_frame, overlap) while a seam table is set (set_seams)
 
     @property
     def workspace_bytes(self):
@@ -210,6 +211,27 @@ class NativeContext:
         _lib.check(self.lib.mc_sample_loop(self.handle, _ptr(x), idx, arr, n, _ptr(noise), int(seed) & (2 ** 64 - 1),
                                            int(draw0) & (2 ** 64 - 1), _ptr(x0), _stream()), 'mc_sample_loop')
         return x
+
+    def set_seams(self, first_frame, overlap, weights=None):
+        """Couple the B rows of this context as windows of a long sequence (mc_ctx_set_seams): ``first_frame[b]`` = the global frame
+        index of row b's frame 0; rows whose first frames differ by ``T - overlap`` are neighbours and share ``overlap`` frames, every
+        other pair of consecutive rows must be disjoint.  While the table is set, ``sample_step`` / ``sample_loop`` blend the two x0
+        predictions of a shared frame (``weights[f]`` = the right window's share, default ``(f + 1) / (overlap + 1)``) and keep the
+        shared frames of x bit-equal in both rows -- given an x_T that is equal there, which is the caller's part.  The plan is
+        checked here (``longform.check_seams``) before the library sees it; ``overlap=0`` clears the table."""
+        from .longform import check_seams
+        if int(overlap) == 0:
+            return self.clear_seams()
+        ff, w = check_seams(first_frame, self.T, overlap, weights, rows=self.B)
+        self._drop_graph()             # a captured graph replays the uncoupled update
+        arr = (ctypes.c_int32 * self.B)(*ff)
+        warr = (ctypes.c_float * len(w))(*w) if w is not None else None
+        _lib.check(self.lib.mc_ctx_set_seams(self.handle, int(overlap), arr, warr, _stream()), 'mc_ctx_set_seams')
+        self.seams = dict(first_frame=ff, overlap=int(overlap))
+
+    def clear_seams(self):
+        _lib.check(self.lib.mc_ctx_set_seams(self.handle, 0, None, None, _stream()), 'mc_ctx_set_seams')
+        self.seams = None
 
     def graph_capture(self, x, noise, coefs):
         """Capture mc_sample_step into ONE hipGraph for the whole schedule.  ``x`` [B,T,C] is updated in place by every

@@ -9,6 +9,9 @@ sequentially dependent; otherwise they are independent and the overlap is simply
 Reference quirk kept as the default: the ``gt`` handed to the next window is the previous output AFTER
 ``* std + mean`` (``m2d_test.py:193,206-212``), although the sampler works on normalised motion; pass
 ``gt_space='normalised'`` to feed the normalised frames instead.
+
+``sample_long_coupled`` (end of the file) is a third mode with no counterpart in the reference: all windows of a sequence in one
+batch, their shared frames coupled at every sampler step.
 """
 import numpy as np
 import torch
@@ -244,3 +247,146 @@ def sample_long_batched(model, total_frames, motion_length, pre_frames=30, c=Non
     full = _gather_ragged(local, lengths, owners, input_dim, dev) if (shard and mcd.is_dist()) else local
     return [full[s] for s in range(S)], windows
 
+
+
+# ---- coupled windows: all windows of a sequence in ONE batch, seams blended per step --------------------------------------------------
+# The third mode beside the two above (no reference counterpart; the window-parallel scheme of PriorMDM's DoubleTake handshake and of
+# MultiDiffusion's overlap averaging): every window of a sequence is a row of the same model call, after every denoiser call the two x0
+# predictions that cover the same frames are blended into one, and both windows take their sampler update from it with the same noise
+# (engine.NativeContext.set_seams, csrc sampler_seam_k).  The overlapping frames of x_t stay bit-equal in both windows through the whole
+# walk, so the stitched motion has no seam by construction -- and nothing is sequential across windows.  What it does to sample QUALITY
+# against RePaint windows is unmeasured (no trained checkpoint here).  As for every batched call, the tutel capacity couples the tokens
+# of one model call: parity of a coupled batch is "this batch on the oracle".
+
+
+def check_seams(first_frame, motion_length, overlap, weights=None, rows=None):
+    """The plan rules of ``mc_ctx_set_seams``, checked on the host: ``0 < 2 overlap <= motion_length`` (a frame lies in two windows at
+    most); consecutive rows are neighbours (``first_frame[b + 1] == first_frame[b] + motion_length - overlap``) or disjoint
+    (``>= first_frame[b] + motion_length``); no negative entry; ``weights``: ``overlap`` numbers in [0, 1].  Returns (first_frame as a
+    list of ints, weights as a list of floats or None); raises ValueError."""
+    T = int(motion_length)
+    if int(overlap) != overlap or not 0 < 2 * int(overlap) <= T:
+        raise ValueError(f'overlap={overlap!r}: an integer with 0 < 2 overlap <= motion_length ({T})')
+    ov = int(overlap)
+    ff = [int(v) for v in first_frame]
+    if any(int(v) != v for v in first_frame):
+        raise ValueError('first_frame: integers')
+    if not ff or (rows is not None and len(ff) != int(rows)):
+        raise ValueError(f'first_frame has {len(ff)} entries for {rows if rows is not None else "at least one"} rows')
+    if any(v < 0 or v >= 2 ** 31 - T for v in ff):
+        raise ValueError('first_frame: entries in [0, 2^31 - motion_length)')
+    for b in range(len(ff) - 1):
+        gap = ff[b + 1] - ff[b]
+        if gap != T - ov and gap < T:
+            raise ValueError(f'first_frame[{b + 1}] = {ff[b + 1]} after first_frame[{b}] = {ff[b]}: neither its neighbour (+{T - ov}) '
+                             f'nor disjoint from it (>= +{T})')
+    w = None
+    if weights is not None:
+        w = [float(v) for v in weights]
+        if len(w) != ov or not all(0.0 <= v <= 1.0 for v in w):
+            raise ValueError(f'weights: {ov} numbers in [0, 1]')
+    return ff, w
+
+
+def seam_plan(total_frames, motion_length, overlap):
+    """(number of windows, first frame of every window, stitched length) of one sequence: ``window_starts`` with ``pre_frames = overlap``."""
+    if not 0 < 2 * int(overlap) <= int(motion_length):
+        raise ValueError(f'overlap={overlap!r}: 0 < 2 overlap <= motion_length ({motion_length})')
+    n, stride = window_starts(int(total_frames), int(motion_length), int(overlap))
+    if n < 1:
+        raise ValueError('sequence shorter than one window')
+    return n, [i * stride for i in range(n)], (n - 1) * stride + int(motion_length)
+
+
+def sample_long_coupled(model, total_frames, motion_length, overlap, c=None, text=None, weights=None, noise=None, mean=None, std=None,
+                        input_dim=322, device=None, condition_kwargs=None, inference_kwargs=None, max_batch=160, shard=True,
+                        c_rows_per_frame=1):
+    """S sequences, ALL windows of a sequence as consecutive rows of one model call, seams coupled at every step (block comment above).
+
+    total_frames / c / text / condition_kwargs / c_rows_per_frame / shard as in ``sample_long_batched``; ``overlap`` plays the part of
+    ``pre_frames`` (stride = motion_length - overlap, 0 < 2 overlap <= motion_length).  weights: the right window's share per shared
+    frame (default ``(f + 1) / (overlap + 1)``).  The model calls are chunked by WHOLE sequences up to ``max_batch`` windows; a sequence
+    with more windows than that is an error.  The initial noise is drawn once per GLOBAL frame (``inference_kwargs['generator']``, or
+    ``noise``: a list of S tensors [stitched frames of s, input_dim]) and gathered into the windows, so x_T agrees on shared frames.
+    inference_kwargs: dict, or callable(pairs) -> dict as in ``sample_long_batched`` (``noise`` / ``graph`` / ``pre_seq`` do not go
+    with this mode).  Stitching is RePaint mode's: the first stride frames of every window but the last; the shared frames are
+    asserted equal first.  Returns (list of S stitched de-normalised motions -- all S on every rank --, dict (sequence, window) ->
+    window output of this rank's sequences)."""
+    dev = device or torch.device('cuda', torch.cuda.current_device())
+    S = len(total_frames) if not isinstance(total_frames, int) else (len(c) if c is not None else (len(text) if isinstance(text, (list, tuple)) else 1))
+    totals = [int(total_frames)] * S if isinstance(total_frames, int) else [int(t) for t in total_frames]
+    texts = list(text) if isinstance(text, (list, tuple)) else [text or ''] * S
+    if len(texts) != S or (c is not None and len(c) != S) or (noise is not None and len(noise) != S):
+        raise ValueError('text / c / noise must have one entry per sequence')
+    L, ov = int(motion_length), int(overlap)
+    plans = [seam_plan(t, L, ov) for t in totals]
+    stride = L - ov
+    if weights is not None:
+        check_seams([0], L, ov, weights)
+    for s, (n, _, _) in enumerate(plans):
+        if n > max_batch:
+            raise ValueError(f'sequence {s} has {n} windows, more than max_batch={max_batch}: the windows of one sequence share a model call')
+    from . import dist as mcd
+    rank, ws = mcd.world() if shard else (0, 1)
+    owners = [rank_sequences(S, r, ws) for r in range(ws)]
+    mine = owners[rank]
+    r = _rows_per_frame(c_rows_per_frame)
+    cs = None if c is None else [_condition_rows(x, totals[s], r, f'c[{s}]') for s, x in enumerate(c)]
+    cond = {k: v for k, v in (condition_kwargs or {}).items()}
+    for k, v in cond.items():
+        if not torch.is_tensor(v) or v.shape[0] != S:
+            raise ValueError(f'condition_kwargs[{k!r}] must be a tensor with one row per sequence ({S})')
+    windows = {}
+
+    def run(seqs):
+        pairs = [(s, w) for s in seqs for w in range(plans[s][0])]
+        b = len(pairs)
+        inf = inference_kwargs(pairs) if callable(inference_kwargs) else dict(inference_kwargs or {})
+        for k in ('noise', 'graph', 'pre_seq', 'transl_req'):
+            if inf.get(k) is not None and inf.get(k) is not False:
+                raise ValueError(f'inference_kwargs[{k!r}] does not go with coupled windows')
+        first, x_T, base = [], [], 0
+        for s in seqs:
+            n, ff, frames = plans[s]
+            if noise is not None:
+                z = torch.as_tensor(noise[s], dtype=torch.float32).to(dev)
+                if tuple(z.shape) != (frames, input_dim):
+                    raise ValueError(f'noise[{s}] of shape {tuple(z.shape)}: expected {(frames, input_dim)}')
+            else:
+                z = torch.randn(frames, input_dim, device=dev, generator=inf.get('generator'))
+            x_T += [z[f:f + L] for f in ff]                 # one draw per global frame: x_T agrees on shared frames
+            first += [base + f for f in ff]
+            base += frames                                  # the next sequence starts past this one's last window: disjoint rows
+        inf['noise'] = torch.stack(x_T)
+        kw = dict(motion=torch.zeros(b, L, input_dim, device=dev), motion_mask=torch.ones(b, L, device=dev),
+                  motion_length=torch.full((b, 1), L, device=dev).long(), num_intervals=1,
+                  motion_metas=[{'text': texts[s]} for s, _ in pairs], seams=dict(first_frame=first, overlap=ov, weights=weights))
+        if cs is not None:
+            kw['c'] = torch.stack([cs[s][w * stride * r:(w * stride + L) * r] for s, w in pairs]).to(dev)
+        idx = torch.tensor([s for s, _ in pairs])
+        for k, v in cond.items():
+            kw[k] = v[idx.to(v.device)]
+        kw['inference_kwargs'] = inf
+        out = model(**kw)
+        for j, (s, w) in enumerate(pairs):
+            windows[(s, w)] = out[j]['pred_motion'][:L].detach().cpu().numpy()
+
+    chunk, used = [], 0
+    for s in mine:
+        if chunk and used + plans[s][0] > max_batch:
+            run(chunk)
+            chunk, used = [], 0
+        chunk.append(s)
+        used += plans[s][0]
+    if chunk:
+        run(chunk)
+    local = {}
+    for s in mine:
+        ws_ = [windows[(s, w)] for w in range(plans[s][0])]
+        for w in range(len(ws_) - 1):
+            if not np.array_equal(ws_[w][stride:], ws_[w + 1][:ov]):
+                raise RuntimeError(f'sequence {s}: windows {w} and {w + 1} differ on their shared frames (the sampler did not run coupled)')
+        local[s] = stitch_windows(ws_, ov, True, mean, std)
+    lengths = [p[2] for p in plans]
+    full = _gather_ragged(local, lengths, owners, input_dim, dev) if (shard and mcd.is_dist()) else local
+    return [full[s] for s in range(S)], windows

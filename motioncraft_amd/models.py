@@ -410,6 +410,8 @@ class MotionDiffusion:
             model_kwargs = self.model.get_precompute_condition(device=motion.device, text=text, **cond_kw)
             model_kwargs.update(motion_mask=motion_mask, sample_idx=sample_idx, motion_length=motion_length,
                                 num_intervals=num_intervals, c=c, y=y, patch_size=patch_size)
+            if kwargs.get('seams') is not None:       # coupled windows (longform.sample_long_coupled): the sampler loops set the seam table
+                model_kwargs['seams'] = kwargs['seams']
             inference_kwargs = kwargs.get('inference_kwargs', {})
         if self.inference_type == 'ddpm':
             output = self.diffusion_test.p_sample_loop(self.model, (B, T, dim_pose), clip_denoised=False,

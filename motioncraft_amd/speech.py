@@ -99,17 +99,24 @@ def speech_prompt(words):
 
 
 def sample_speech(model, wave, words=(), motion_length=64, pre_frames=4, samples_per_frame=SAMPLES_PER_FRAME, condition=None,
-                  batched=False, **driver_kwargs):
+                  batched=False, coupled=False, **driver_kwargs):
     """wave [N] at the condition's rate -> the gesture sequence of ``speech_frames(N)`` frames: the condition is built on the device,
     and window i of ``motion_length`` frames reads its rows ``[i * stride * spf, (i * stride + motion_length) * spf)``,
     stride = ``motion_length - pre_frames`` (s2g_test.py:144-155).  ``words``: the words of the prompt (one prompt for the clip;
     the reference forms it per window from a TextGrid, which is not read here).  ``condition``: an ``AudioCondition`` (default: a new
     one).  ``driver_kwargs`` go to the window driver: repaint, overlap_len, fix_very_first, first_gt, mean, std, gt_space,
     condition_kwargs, inference_kwargs, ...  Returns what ``longform.sample_long`` returns, or with ``batched=True`` what
-    ``longform.sample_long_batched`` returns for this one sequence."""
+    ``longform.sample_long_batched`` returns for this one sequence.  ``coupled=True``: all windows of the clip in one batch with their
+    shared frames coupled at every step (``longform.sample_long_coupled``; ``pre_frames`` is the overlap, ``driver_kwargs`` are that
+    driver's: weights, noise, mean, std, condition_kwargs, inference_kwargs, max_batch, ...); returns what that driver returns."""
+    if coupled and batched:
+        raise ValueError('coupled and batched name two different window drivers: pick one')
     cond = (condition if condition is not None else AudioCondition())(wave)
     total = speech_frames(cond.shape[0], samples_per_frame)
     text = speech_prompt(words)
+    if coupled:
+        return longform.sample_long_coupled(model, [total], motion_length, pre_frames, c=[cond], text=[text],
+                                            c_rows_per_frame=samples_per_frame, **driver_kwargs)
     if batched:
         return longform.sample_long_batched(model, [total], motion_length, pre_frames, c=[cond], text=[text],
                                             c_rows_per_frame=samples_per_frame, **driver_kwargs)

@@ -3,7 +3,7 @@
 120-260, and the ``res_<id>.npz`` of lines 440-448) on the device.
 
     python tools/s2g_sample.py CONFIG CHECKPOINT --wav CLIP.wav [--resample [--load_sr 22050]] [--words w1 w2 ... | --text "w1 w2 ..."] --out DIR \\
-        [--mean mean.npy --std std.npy] [--repaint --overlap_len N] [--seed S] [--fp16 split|plain] [--graph] [--betas GT.npz] \\
+        [--mean mean.npy --std std.npy] [--repaint --overlap_len N | --coupled] [--seed S] [--fp16 split|plain] [--graph] [--betas GT.npz] \\
         [--clip_feat feats.npy | --xf_out xf.npy | --random-condition SEED]
 
 CONFIG is an S2G config (``configs/stmogen/S2G_Beats2_*.py``: ``copy_blocks_num``, ``control_cond_feats``,
@@ -63,11 +63,16 @@ def parse_args():
     p.add_argument('--timestep_respacing', default='ddim50'), p.add_argument('--jump_n_sample', type=int, default=5)
     p.add_argument('--jump_length', type=int, default=3), p.add_argument('--addBlend', type=bool, default=True)
     p.add_argument('--no_repaint', action='store_true')
+    p.add_argument('--coupled', action='store_true',
+                   help='all windows of the clip in ONE batch, the --pre_frames shared frames of neighbours blended at every step (no seam, no '
+                        'sequential windows; 0 < 2 pre_frames <= motion_length)')
     p.add_argument('--fp16', choices=['split', 'plain'], default=None, help='fp16-MFMA mode: split = fp32-class hi/lo form')
     p.add_argument('--graph', action='store_true', help='hipGraph replay of the sampler step')
     a = p.parse_args()
     if a.load_sr is not None and not a.resample:
         p.error('--load_sr needs --resample')
+    if a.coupled and (a.repaint or a.graph):
+        p.error('--coupled is a window mode of its own: it goes with neither --repaint nor --graph')
     return a
 
 
@@ -105,11 +110,19 @@ def main():
         g = torch.Generator().manual_seed(a.random_condition)
         cond_kw['xf_out'] = torch.nn.functional.layer_norm(torch.randn(1, dims['Nt'], dims['Dt'], generator=g), (dims['Dt'],)).to(dev)
     gen = torch.Generator(device=dev).manual_seed(a.seed)
-    rec, windows = speech.sample_speech(
-        model, wav, words=a.words if a.words is not None else (a.text or '').split(), motion_length=a.motion_length, pre_frames=a.pre_frames,
-        samples_per_frame=a.samples_per_frame, repaint=a.repaint, overlap_len=a.overlap_len, fix_very_first=False,
-        mean=np.load(a.mean) if a.mean else None, std=np.load(a.std) if a.std else None, input_dim=dims['input_feats'], condition_kwargs=cond_kw,
-        inference_kwargs=dict(generator=gen, **({'graph': True} if a.graph else {})))
+    words = a.words if a.words is not None else (a.text or '').split()
+    stats = dict(mean=np.load(a.mean) if a.mean else None, std=np.load(a.std) if a.std else None)
+    if a.coupled:
+        recs, wins = speech.sample_speech(model, wav, words=words, motion_length=a.motion_length, pre_frames=a.pre_frames,
+                                          samples_per_frame=a.samples_per_frame, coupled=True, input_dim=dims['input_feats'],
+                                          condition_kwargs=cond_kw, inference_kwargs=dict(generator=gen), shard=False, **stats)
+        rec, windows = recs[0], [wins[(0, w)] for w in range(len(wins))]
+    else:
+        rec, windows = speech.sample_speech(
+            model, wav, words=words, motion_length=a.motion_length, pre_frames=a.pre_frames,
+            samples_per_frame=a.samples_per_frame, repaint=a.repaint, overlap_len=a.overlap_len, fix_very_first=False,
+            input_dim=dims['input_feats'], condition_kwargs=cond_kw,
+            inference_kwargs=dict(generator=gen, **({'graph': True} if a.graph else {})), **stats)
     pose, exps, trans = scoring.unpack_rec_motion(torch.from_numpy(rec))           # s2g_test.py:289-297
     if a.betas:
         with np.load(a.betas) as f:
