@@ -195,6 +195,23 @@ int mc_ctx_set_precision(mc_ctx* c, int32_t precision);
 #define MC_TIE_STABLE 0
 #define MC_TIE_REVERSE 1
 int mc_ctx_set_tie_policy(mc_ctx* c, int32_t policy);
+/* Capacity factor of THIS context (no reference counterpart as a runtime switch: the reference fixes 1.5 in st_attention.py:33).  The
+ * capacity cut is what makes a row of a batch depend on its batchmates: capacity = topk * int(cf * ceil(N / E)) is taken over all
+ * tokens of the call and batch-prioritised routing drops the lowest-scoring tokens of a full expert.
+ *   cf > 0   tutel's formula with this factor instead of the model's.  The default is the model's capacity_factor: nothing changes
+ *            unless this is called.
+ *   cf == 0  no (token, choice) pair is ever dropped, and no selection work runs (no histogram / radix pass, none of the cooperative
+ *            kernel's selection barriers, no selection pass of the early schedule): comb_w == gate bit for bit, the twin-split flag
+ *            is 0, counts / slot ranges / tile maps are those of a routing in which no expert overflowed.  A row's result then is a
+ *            function of its own request at a fixed (batch, frames, options).
+ *            [tutel-recall] tutel's own capacity_factor = 0 sizes the capacity to the largest expert load, i.e. drops nothing too.
+ *   cf < 0   MC_ERR_ARG (tutel's negative form -- a cap on the adaptive capacity -- is not built).
+ * Applies to the motion MoE of every layer slot (base and control) and to the hoisted text MoE, so the call clears the context's
+ * condition and the multistep history flag: mc_ctx_set_condition must follow before the next denoiser call (which otherwise fails
+ * as on a fresh context).  MC_ERR_STATE while a captured graph exists (mc_ctx_graph_release first).
+ * Checkpoints were trained with drops at 1.5; sample quality at 0 is unmeasured. */
+int mc_ctx_set_capacity_factor(mc_ctx* c, float cf);
+float mc_ctx_capacity_factor(const mc_ctx* c);
 /* Kernel-selection switches of ONE context (no reference counterpart: the reference has one code path; these exist for A/B
  * measurement and for the tests that pin alternative kernels to each other).  The MC_* environment variable of a key only seeds
  * the default of contexts created afterwards (and of context-free calls such as mc_op_gemm, read once per process); two contexts
@@ -252,6 +269,18 @@ int mc_sample_loop(mc_ctx* c, float* x_dev, const int32_t* step_indices_host, co
                    const float* noise_dev, uint64_t seed, uint64_t noise_draw0, float* x0_last_dev, void* stream);
 /* draw `draw` of the Philox stream keyed by `seed`: out_dev[n] = normals, bits_dev[n] = the raw 32-bit words (either may be NULL) */
 int mc_op_philox_normal(float* out_dev, uint32_t* bits_dev, int64_t n, uint64_t seed, uint64_t draw, void* stream);
+/* Row-keyed noise (no reference counterpart: the reference draws one randn over the batch).  While a seed table is set, the normal for
+ * element r in [0, T*C) of row b in draw d is element r of mc_op_philox_normal(n = T*C, seed = seeds[b], draw = d): key seeds[b],
+ * counter (r / 4, d), lane r % 4, the same Box-Muller.  A row gets exactly the noise a B = 1 call with that seed gets, whatever B is
+ * and wherever the row sits.  It is read by
+ *   mc_sample_loop with noise_dev == NULL: the `seed` argument is ignored, noise_draw0 + k stays the draw number (with a seam table
+ *       too: a seam element takes the LEFT row's key and the left element's row-local counter);
+ *   mc_ctx_draw_rows: out_dev [B,T,C] = draw `draw` of every row (MC_ERR_STATE without a table) -- every entry that takes noise_dev
+ *       (mc_sample_step, graph replay, the inpaint and seeded steps) reaches row-keyed noise through it.
+ * A noise_dev argument is read as it is, table or not; graph capture is unaffected.  seeds_host [B] is copied on `stream` (the call
+ * synchronises it); NULL clears the table. */
+int mc_ctx_set_row_seeds(mc_ctx* c, const uint64_t* seeds_host, void* stream);
+int mc_ctx_draw_rows(mc_ctx* c, float* out_dev, uint64_t draw, void* stream);
 
 /* Coupled windows of a long sequence (no reference counterpart; the window-parallel scheme of DoubleTake / MultiDiffusion): the B rows of
  * the context are windows of T frames, row b starting at global frame first_frame_host[b].  Rows b and b + 1 are NEIGHBOURS when

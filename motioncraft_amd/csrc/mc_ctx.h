@@ -135,6 +135,12 @@ struct mc_ctx {
     // first call that sets a table: [B] neighbour flags (ints), then [T / 2] right-window weights (floats)
     int* seam_tab = nullptr;
     int seam_ov = 0;
+    // independent requests: the capacity factor every MoE of this context routes with (the model's unless
+    // mc_ctx_set_capacity_factor changed it; 0 = nothing dropped), and the rows' Philox keys [B] (allocated by the first mc_ctx_set_row_seeds)
+    float cap_factor = 0.f;
+    bool keep_all = false;      // set by mc_ctx_set_capacity_factor(0) only: a MODEL whose own factor is 0 keeps today's meaning (capacity 0)
+    uint64_t* row_seeds = nullptr;
+    bool row_seeds_set = false;
     int prec = MC_PREC_F32;     // MFMA operand precision of the per-step GEMM-shaped kernels (mc_ctx_set_precision)
     int* cap_idx = nullptr;      // [NL][2N] routing capture (tests): expert ids ...
     float* cap_w = nullptr;      // ... and combine weights (0 = dropped) of every layer

@@ -50,10 +50,13 @@ struct RngArgs { uint32_t seed_lo = 0, seed_hi = 0, draw_lo = 0, draw_hi = 0; };
 // pad (mc_sample_loop): x_prev is also written as rows of Cp floats into xpad (the next step's pose-encoder GEMM operand; the pad
 // columns are not touched)
 struct PadOut { float* xpad = nullptr; int C = 0, Cp = 0; };
+// rows (with rng, noise == nullptr): every row of TC elements draws from its own stream -- key keys[2 b] | keys[2 b + 1] << 32, counter
+// (row-local element / 4, draw index); rng's seed is ignored (mc_ctx_set_row_seeds)
+struct RowKeys { const uint32_t* keys = nullptr; int TC = 0; };
 int mc_launch_sampler_update(const float* x_t, const float* out_text, const float* out_none,
                              const float* noise, float* x_prev, float* x0_out, long n,
                              SamplerCoefs c, hipStream_t s, const SamplerCoefs* table = nullptr, const int* step_ptr = nullptr,
-                             const RngArgs* rng = nullptr, const PadOut* pad = nullptr);
+                             const RngArgs* rng = nullptr, const PadOut* pad = nullptr, const RowKeys* rows = nullptr);
 // mode 2 (multistep): x_prev = c.c2 x_t + c.c1 x0 + c.eta x0_hist;  x0_hist <- x0 (in-out [n], read only when c.eta != 0); no noise.
 // table / step_ptr / pad as above
 int mc_launch_sampler_multistep(const float* x_t, const float* out_text, const float* out_none, float* x0_hist, float* x_prev,
@@ -66,7 +69,9 @@ int mc_launch_sampler_multistep(const float* x_t, const float* out_text, const f
 struct SeamTab { const int* flags = nullptr; const float* w = nullptr; int T = 0, C = 0, ov = 0; };
 int mc_launch_sampler_seam(const float* x_t, const float* out_text, const float* out_none, const float* noise, float* x0_hist,
                            float* x_prev, float* x0_out, int B, SamplerCoefs c, const SeamTab& st, hipStream_t s,
-                           const RngArgs* rng = nullptr, const PadOut* pad = nullptr);
+                           const RngArgs* rng = nullptr, const PadOut* pad = nullptr, const RowKeys* rows = nullptr);
+// out [B][rk.TC] = draw rng.draw_* of every row's own stream (rng's seed is ignored)
+int mc_launch_philox_rows_fill(float* out, int B, RowKeys rk, RngArgs rng, hipStream_t s);
 // out[n] = the normals / bits[n] = the raw 32-bit words of draw `rng` (either may be null)
 int mc_launch_philox_fill(float* out, uint32_t* bits, long n, RngArgs rng, hipStream_t s);
 // out = table[*step].text_coef * x + table[*step].none_coef * y   (CFG combine of the two halves under graph replay)
@@ -154,6 +159,9 @@ int mc_launch_gate_finish(const float* proj, const float* sim_n, const float* lo
 // Nsrc = N, or N/2 (twin mode); tokens >= gsplit get their own slot group (tile map at [max_tiles, 2 max_tiles))
 // select_only: the capacity cut alone (comb_w, twin-split flag, kept counts) from the sum of the two groups' counts, by the barrier-free
 // launch sequence; no slot plan, no fill -- safe beside running expert kernels (early routing, run_layer)
+// capacity == MC_ROUTE_KEEP_ALL (capacity factor 0): nothing is dropped and no selection work runs -- comb_w = gate for all N pairs, the
+// split flag 0, counts / slot ranges / tile maps of the zero-overflow case; one keep-all form per path (route_keepall_*_k)
+constexpr int MC_ROUTE_KEEP_ALL = -1;
 int mc_launch_route(long N, long Nsrc, long gsplit, int E, int capacity, RouteBufs rb, const McOptions& o, hipStream_t s, bool select_only = false);
 // early routing: sample group `group` (0 / 1) counts its (choice, expert) pairs in its own block ...
 int* mc_route_group_counts(const RouteBufs& rb, int group);

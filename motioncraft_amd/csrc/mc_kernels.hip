@@ -242,6 +242,38 @@ __device__ __forceinline__ f32x4 philox_normal4(long group, RngArgs rng) {
     return z;
 }
 
+// Row-keyed draws (mc_ctx_set_row_seeds): element r of row b of [B][TC] is element r of the Philox stream keyed by
+// keys[b] -- counter (r / 4, draw), lane r % 4 -- so a row's noise depends neither on B nor on where the row sits.  -> the normals of the
+// flat elements [i, i + 4), i % 4 == 0 (elements at or past n stay 0: no key is read for a row that does not exist).  One Philox call
+// where the four share a row and a counter (always when TC % 4 == 0); where TC % 4 != 0 shifts the rows against the flat groups, or a
+// group straddles two rows, one call per (row, counter) it touches: three at the most.
+__device__ __forceinline__ f32x4 philox_rows4(long i, long n, RowKeys rk, RngArgs rng) {
+    long b = i / rk.TC;
+    int r = (int)(i - b * rk.TC);
+    if ((r & 3) == 0 && r + 4 <= rk.TC && i + 4 <= n) {
+        rng.seed_lo = rk.keys[2 * b]; rng.seed_hi = rk.keys[2 * b + 1];
+        return philox_normal4(r >> 2, rng);
+    }
+    f32x4 z = {0.f, 0.f, 0.f, 0.f}, cur = z;
+    long cb = -1;
+    int cc = -1;
+    for (int j = 0; j < 4 && i + j < n; ++j) {
+        if (b != cb || (r >> 2) != cc) {
+            cb = b; cc = r >> 2;
+            rng.seed_lo = rk.keys[2 * b]; rng.seed_hi = rk.keys[2 * b + 1];
+            cur = philox_normal4(cc, rng);
+        }
+        const int l = r & 3;
+        z[j] = l == 0 ? cur[0] : l == 1 ? cur[1] : l == 2 ? cur[2] : cur[3];
+        if (++r == rk.TC) { r = 0; ++b; }
+    }
+    return z;
+}
+// the in-kernel noise of flat group gi: from the call's one stream (RngArgs, the default), or from the rows' own streams
+struct RowNoise { RngArgs rng; RowKeys rk; };
+__device__ __forceinline__ f32x4 noise4(long gi, long, RngArgs rng) { return philox_normal4(gi, rng); }
+__device__ __forceinline__ f32x4 noise4(long gi, long n, const RowNoise& r) { return philox_rows4(gi * 4, n, r.rk, r.rng); }
+
 struct SamplerDerived { float sigma_ddpm, sq_abp, dir, sigma; };
 __device__ __forceinline__ SamplerDerived sampler_derive(const SamplerCoefs& c) {
     SamplerDerived d;
@@ -273,12 +305,13 @@ __device__ __forceinline__ float cfg_elem(float a, float b, const SamplerCoefs& 
 // x_prev may alias x_t (in-place update: every element is read before it is written by the same thread; no __restrict__ on the two)
 // VEC: every operand 16-byte aligned (float4 loads / stores); otherwise the same groups of 4 elements go element by element
 // (C = 263 / 251 at odd B*T, or the second partial product of the folded tail at out2 + B*T*C: 8-byte aligned at best)
-template <bool RNG, bool VEC>
+// NZ: the in-kernel draw (RNG) -- RngArgs, or RowNoise while the context holds a seed table; same groups, same straddle rule
+template <bool RNG, bool VEC, class NZ = RngArgs>
 __global__ __launch_bounds__(256) void sampler_update_k(const float* x_t, const float* __restrict__ o_text,
                                                         const float* __restrict__ o_none, const float* __restrict__ noise,
                                                         float* x_prev, float* __restrict__ x0_out, long n,
                                                         SamplerCoefs c, const SamplerCoefs* __restrict__ table,
-                                                        const int* __restrict__ step_ptr, RngArgs rng, PadOut po) {
+                                                        const int* __restrict__ step_ptr, NZ rng, PadOut po) {
     if (table) {          // graph replay: this step's schedule coefficients from the device table
         const float tc = c.text_coef, nc = c.none_coef;
         c = table[*step_ptr];
@@ -293,7 +326,7 @@ __global__ __launch_bounds__(256) void sampler_update_k(const float* x_t, const 
             const f32x4 x = *reinterpret_cast<const f32x4*>(x_t + i);
             const f32x4 a = *reinterpret_cast<const f32x4*>(o_text + i), b = *reinterpret_cast<const f32x4*>(o_none + i);
             f32x4 nz;
-            if constexpr (RNG) nz = philox_normal4(gi, rng);
+            if constexpr (RNG) nz = noise4(gi, n, rng);
             else nz = *reinterpret_cast<const f32x4*>(noise + i);
             f32x4 out, x0v;
 #pragma unroll
@@ -314,7 +347,7 @@ __global__ __launch_bounds__(256) void sampler_update_k(const float* x_t, const 
             }
         } else {
             f32x4 nz = {0.f, 0.f, 0.f, 0.f};
-            if constexpr (RNG) nz = philox_normal4(gi, rng);
+            if constexpr (RNG) nz = noise4(gi, n, rng);
             for (int j = 0; j < 4 && i + j < n; ++j) {
                 const float x0 = cfg_elem(o_text[i + j], o_none[i + j], c);
                 const float z = RNG ? nz[j] : noise[i + j];
@@ -401,11 +434,11 @@ __global__ __launch_bounds__(256) void sampler_multistep_k(const float* x_t, con
 // only foreign elements it writes are head elements, which no thread reads (2 ov <= T: a head element is never a tail element).
 // No graph table: a context with a seam table refuses capture.
 enum { SEAM_LEFT = 1, SEAM_RIGHT = 2 };      // SeamTab::flags[b]: the row has a left / a right neighbour
-template <bool RNG, bool VEC>
+template <bool RNG, bool VEC, class NZ = RngArgs>
 __global__ __launch_bounds__(256) void sampler_seam_k(const float* x_t, const float* __restrict__ o_text,
                                                       const float* __restrict__ o_none, const float* __restrict__ noise,
                                                       float* hist, float* x_prev, float* x0_out, long n, SamplerCoefs c,
-                                                      SeamTab st, RngArgs rng, PadOut po) {
+                                                      SeamTab st, NZ rng, PadOut po) {
     const SamplerDerived d = sampler_derive(c);
     const bool ms = c.mode == 2;
     const float kx = c.c2, k0 = c.c1, k1 = c.eta;
@@ -435,7 +468,7 @@ __global__ __launch_bounds__(256) void sampler_seam_k(const float* x_t, const fl
             const f32x4 a = *reinterpret_cast<const f32x4*>(o_text + i), bb = *reinterpret_cast<const f32x4*>(o_none + i);
             f32x4 nz = {0.f, 0.f, 0.f, 0.f}, hp = {0.f, 0.f, 0.f, 0.f};
             if (!ms) {
-                if constexpr (RNG) nz = philox_normal4(gi, rng);
+                if constexpr (RNG) nz = noise4(gi, n, rng);
                 else nz = *reinterpret_cast<const f32x4*>(noise + i);
             } else if (use_hist) hp = *reinterpret_cast<const f32x4*>(hist + i);
             f32x4 out, x0v;
@@ -458,7 +491,7 @@ __global__ __launch_bounds__(256) void sampler_seam_k(const float* x_t, const fl
             }
         } else {
             f32x4 nz = {0.f, 0.f, 0.f, 0.f};
-            if constexpr (RNG) { if (!ms) nz = philox_normal4(gi, rng); }
+            if constexpr (RNG) { if (!ms) nz = noise4(gi, n, rng); }
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 if (i + j >= n || cls[j] == 1) continue;         // (head: written by the left neighbour's tail thread)
@@ -502,6 +535,20 @@ __global__ __launch_bounds__(256) void philox_fill_k(float* __restrict__ out, ui
             const f32x4 z = philox_normal4(gi, rng);
             for (int j = 0; j < 4 && gi * 4 + j < n; ++j) out[gi * 4 + j] = z[j];
         }
+    }
+}
+
+// mc_ctx_draw_rows: out [B][TC] = draw `rng.draw_*` of every row's own stream (philox_rows4).  Flat groups of four: one f32x4 store where
+// the group lies inside one row (out + 4 gi is 16-byte aligned when out is), element-wise where TC % 4 != 0 makes it straddle two rows
+// or at the ragged end.
+__global__ __launch_bounds__(256) void philox_rows_fill_k(float* __restrict__ out, long n, RowKeys rk, RngArgs rng, int vec) {
+    const long ngroups = (n + 3) >> 2;
+    for (long gi = (long)blockIdx.x * blockDim.x + threadIdx.x; gi < ngroups; gi += (long)gridDim.x * blockDim.x) {
+        const long i = gi * 4;
+        const f32x4 z = philox_rows4(i, n, rk, rng);
+        if (vec && i + 4 <= n && i / rk.TC == (i + 3) / rk.TC) *reinterpret_cast<f32x4*>(out + i) = z;
+        else
+            for (int j = 0; j < 4 && i + j < n; ++j) out[i + j] = z[j];
     }
 }
 
@@ -702,8 +749,10 @@ int mc_launch_softmax_rows_small(const float* W, float* out, int rows, int cols,
 }
 
 int mc_launch_sampler_update(const float* x_t, const float* out_text, const float* out_none, const float* noise, float* x_prev, float* x0_out, long n,
-                             SamplerCoefs c, hipStream_t s, const SamplerCoefs* table, const int* step_ptr, const RngArgs* rng, const PadOut* pad) {
+                             SamplerCoefs c, hipStream_t s, const SamplerCoefs* table, const int* step_ptr, const RngArgs* rng, const PadOut* pad,
+                             const RowKeys* rows) {
     MC_REQUIRE(noise || rng, "sampler update: neither a noise tensor nor a Philox draw given");
+    MC_REQUIRE(!rows || (rows->keys && rows->TC > 0 && n % rows->TC == 0), "sampler update: row keys for rows of %d elements, %ld in all", rows ? rows->TC : 0, n);
     // float4 path when every stream is 16-byte aligned (torch / workspace allocations are; out2 + B*T*C or noise + k*n need not be:
     // C = 263 / 251 / 322 with an odd B*T) -- otherwise the element-wise form of the same kernel (same groups, same Philox counters)
     const bool vec = ((uintptr_t)x_t | (uintptr_t)out_text | (uintptr_t)out_none | (uintptr_t)x_prev | (uintptr_t)x0_out | (uintptr_t)noise) % 16 == 0;
@@ -715,7 +764,11 @@ int mc_launch_sampler_update(const float* x_t, const float* out_text, const floa
     const PadOut po = pad ? *pad : PadOut();
     MC_REQUIRE(!po.xpad || (po.C > 0 && po.Cp >= po.C), "sampler update: bad padded-copy shape");
 #define MC_SU(R, V) hipLaunchKernelGGL((sampler_update_k<R, V>), dim3(blocks), dim3(256), 0, s, x_t, out_text, out_none, noise, x_prev, x0_out, n, c, table, step_ptr, ra, po)
-    if (dev_rng) { if (vec) MC_SU(true, true); else MC_SU(true, false); }
+    if (dev_rng && rows) {        // the rows' own streams (same kernel, RowNoise draw)
+        const RowNoise rn{ra, *rows};
+        if (vec) hipLaunchKernelGGL((sampler_update_k<true, true, RowNoise>), dim3(blocks), dim3(256), 0, s, x_t, out_text, out_none, noise, x_prev, x0_out, n, c, table, step_ptr, rn, po);
+        else hipLaunchKernelGGL((sampler_update_k<true, false, RowNoise>), dim3(blocks), dim3(256), 0, s, x_t, out_text, out_none, noise, x_prev, x0_out, n, c, table, step_ptr, rn, po);
+    } else if (dev_rng) { if (vec) MC_SU(true, true); else MC_SU(true, false); }
     else { if (vec) MC_SU(false, true); else MC_SU(false, false); }
 #undef MC_SU
     MC_LAUNCH_CHECK();
@@ -741,7 +794,9 @@ int mc_launch_sampler_multistep(const float* x_t, const float* out_text, const f
 }
 
 int mc_launch_sampler_seam(const float* x_t, const float* out_text, const float* out_none, const float* noise, float* x0_hist, float* x_prev,
-                           float* x0_out, int B, SamplerCoefs c, const SeamTab& st, hipStream_t s, const RngArgs* rng, const PadOut* pad) {
+                           float* x0_out, int B, SamplerCoefs c, const SeamTab& st, hipStream_t s, const RngArgs* rng, const PadOut* pad,
+                           const RowKeys* rows) {
+    MC_REQUIRE(!rows || (rows->keys && rows->TC == st.T * st.C), "seam update: row keys for rows of %d elements, windows of %d", rows ? rows->TC : 0, st.T * st.C);
     MC_REQUIRE(x_t && out_text && out_none && x_prev && st.flags && st.w && B >= 0, "seam update: null operand");
     MC_REQUIRE(st.T > 0 && st.C > 0 && st.ov > 0 && 2 * st.ov <= st.T, "seam update: overlap %d outside (0, %d / 2]", st.ov, st.T);
     MC_REQUIRE((long)st.T * st.C <= 0x7fffffffL, "seam update: a window of %d x %d floats", st.T, st.C);
@@ -762,7 +817,11 @@ int mc_launch_sampler_seam(const float* x_t, const float* out_text, const float*
     const PadOut po = pad ? *pad : PadOut();
     MC_REQUIRE(!po.xpad || (po.C == st.C && po.Cp >= po.C), "seam update: bad padded-copy shape");
 #define MC_SS(R, V) hipLaunchKernelGGL((sampler_seam_k<R, V>), dim3(blocks), dim3(256), 0, s, x_t, out_text, out_none, noise, x0_hist, x_prev, x0_out, n, c, st, ra, po)
-    if (dev_rng) { if (vec) MC_SS(true, true); else MC_SS(true, false); }
+    if (dev_rng && rows) {        // a seam element takes the LEFT row's key and its row-local counter (its owner is the left row's thread)
+        const RowNoise rn{ra, *rows};
+        if (vec) hipLaunchKernelGGL((sampler_seam_k<true, true, RowNoise>), dim3(blocks), dim3(256), 0, s, x_t, out_text, out_none, noise, x0_hist, x_prev, x0_out, n, c, st, rn, po);
+        else hipLaunchKernelGGL((sampler_seam_k<true, false, RowNoise>), dim3(blocks), dim3(256), 0, s, x_t, out_text, out_none, noise, x0_hist, x_prev, x0_out, n, c, st, rn, po);
+    } else if (dev_rng) { if (vec) MC_SS(true, true); else MC_SS(true, false); }
     else { if (vec) MC_SS(false, true); else MC_SS(false, false); }
 #undef MC_SS
     MC_LAUNCH_CHECK();
@@ -774,6 +833,17 @@ int mc_launch_philox_fill(float* out, uint32_t* bits, long n, RngArgs rng, hipSt
     int blocks = cdiv((n + 3) / 4, 256);
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(philox_fill_k, dim3(blocks), dim3(256), 0, s, out, bits, n, rng);
+    MC_LAUNCH_CHECK();
+    return MC_OK;
+}
+
+int mc_launch_philox_rows_fill(float* out, int B, RowKeys rk, RngArgs rng, hipStream_t s) {
+    MC_REQUIRE(out && rk.keys && rk.TC > 0 && B >= 0, "row draw: bad argument");
+    const long n = (long)B * rk.TC;
+    if (n == 0) return MC_OK;
+    int blocks = cdiv((n + 3) / 4, 256);
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(philox_rows_fill_k, dim3(blocks), dim3(256), 0, s, out, n, rk, rng, (uintptr_t)out % 16 == 0 ? 1 : 0);
     MC_LAUNCH_CHECK();
     return MC_OK;
 }

@@ -323,6 +323,7 @@ int mc_ctx_create(mc_model* m, int32_t batch, int32_t frames, int32_t max_steps,
     c->B = batch;
     c->T = frames;
     c->maxS = max_steps;
+    c->cap_factor = g.capacity_factor;
     const int L = g.latent_dim, H = g.num_parts, D = L * H, F = g.ffn_dim, Te = g.time_embed_dim, Dt = g.text_latent_dim;
     const long B2 = 2L * batch;
     c->rows = B2 * frames;
@@ -482,6 +483,21 @@ int mc_ctx_set_tie_policy(mc_ctx* c, int32_t policy) {
     c->have_cond = false;      // the hoisted text K/V were routed under the previous policy: set the condition again
     return MC_OK;
 }
+
+int mc_ctx_set_capacity_factor(mc_ctx* c, float cf) {
+    MC_REQUIRE(c, "null context");
+    MC_REQUIRE(cf >= 0.f, "capacity factor %g: > 0 (tutel's formula with it) or 0 (nothing dropped); tutel's negative form is not built", (double)cf);      // (NaN fails too)
+    if (c->graph_exec) {
+        mc_set_error("mc_ctx_set_capacity_factor: a captured graph holds the old routing launches (mc_ctx_graph_release first)");
+        return MC_ERR_STATE;
+    }
+    c->keep_all = cf == 0.f;
+    c->cap_factor = cf;
+    c->have_cond = false;      // the hoisted text K/V were routed under the previous capacity: set the condition again
+    c->hist_valid = false;     // (multistep sampler: the previous x0 was predicted under it too)
+    return MC_OK;
+}
+float mc_ctx_capacity_factor(const mc_ctx* c) { return c ? c->cap_factor : 0.f; }
 
 int mc_ctx_set_precision(mc_ctx* c, int32_t precision) {
     MC_REQUIRE(c, "null context");
@@ -753,6 +769,27 @@ int mc_sample_loop(mc_ctx* c, float* x, const int32_t* step_indices, const mc_st
     }
     c->xpad_ready = false;
     return MC_OK;
+}
+
+// ---- row-keyed noise: the seed table of a context ----
+int mc_ctx_set_row_seeds(mc_ctx* c, const uint64_t* seeds, void* stream) {
+    MC_REQUIRE(c, "null context");
+    if (!seeds) { c->row_seeds_set = false; return MC_OK; }
+    int r;
+    if (!c->row_seeds && (r = ws_alloc(c, &c->row_seeds, (size_t)c->B)) != MC_OK) return r;
+    hipStream_t s = (hipStream_t)stream;
+    c->row_seeds_set = false;
+    MC_HIP(hipMemcpyAsync(c->row_seeds, seeds, sizeof(uint64_t) * c->B, hipMemcpyHostToDevice, s));
+    MC_HIP(hipStreamSynchronize(s));                 // (the caller's array may be a temporary)
+    c->row_seeds_set = true;
+    return MC_OK;
+}
+int mc_ctx_draw_rows(mc_ctx* c, float* out, uint64_t draw, void* stream) {
+    MC_REQUIRE(c && out, "null argument");
+    if (!c->row_seeds_set) { mc_set_error("mc_ctx_draw_rows: no seed table set (mc_ctx_set_row_seeds)"); return MC_ERR_STATE; }
+    const long TC = (long)c->T * c->m->cfg.input_feats;
+    MC_REQUIRE(TC <= 0x7fffffffL, "mc_ctx_draw_rows: a row of %ld floats", TC);
+    return mc_launch_philox_rows_fill(out, c->B, RowKeys{reinterpret_cast<const uint32_t*>(c->row_seeds), (int)TC}, rng_args(0, draw), (hipStream_t)stream);
 }
 
 int mc_op_philox_normal(float* out, uint32_t* bits, int64_t n, uint64_t seed, uint64_t draw, void* stream) {

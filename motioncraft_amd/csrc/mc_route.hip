@@ -1004,6 +1004,216 @@ __global__ __launch_bounds__(SMALL_THREADS) void route_small_stream_k(const int*
     }
 }
 
+// ---------------------------------------------------------------------------------------
+// Keep-all routing (capacity factor 0, mc_ctx_set_capacity_factor): no (token, choice) pair is dropped, so nothing
+// ranks the tokens of the batch against each other -- no problem setup, no histogram, no radix pass, no threshold.  What is left of a
+// routing is  comb_w = gate  for all N pairs, the kept counts (= all pairs of the first Nsrc tokens), the slot ranges + tile map and the
+// compaction; the state words a selection would have written are left as its zero-overflow case leaves them (ST_ACTIVE 0, ST_ANY 0,
+// ST_SPLIT 0: a twin can never be split from its original).  One form per routing path, below.
+// ---------------------------------------------------------------------------------------
+// the words of a finished selection with nothing to select (threads [0, MAXP) of one workgroup)
+__device__ __forceinline__ void keepall_state(int* __restrict__ state, int tid) {
+    if (tid < MAXP) {
+        state[ST_ACTIVE + tid] = 0;
+        state[ST_RANK + tid] = 0;
+        state[ST_PREFIX + 2 * tid] = 0;
+        state[ST_PREFIX + 2 * tid + 1] = 0;
+    }
+    if (tid == 0) { state[ST_ANY] = 0; state[ST_DONE] = 0; state[ST_SPLIT] = 0; }
+}
+// slot ranges + tile counts from the kept counts `kept` [2][MAXE] (route_plan_k's serial part): one thread
+__device__ __forceinline__ void keepall_plan(const int* kept, int E, int max_tiles, int* __restrict__ state, int* s_off, int (*s_t0)[MAXE + 1]) {
+    int off = 0;
+    for (int g = 0; g < 2; ++g) {
+        int nt = 0;
+        for (int e = 0; e < E; ++e) {
+            s_off[g * MAXE + e] = off;
+            s_t0[g][e] = nt;
+            state[ST_OFF + g * MAXE + e] = off;
+            const int cnt = kept[g * MAXE + e];
+            off += cnt;
+            nt += (cnt + TILE_ROWS - 1) / TILE_ROWS;
+        }
+        for (int e = E; e < MAXE; ++e) { s_off[g * MAXE + e] = off; state[ST_OFF + g * MAXE + e] = off; }
+        s_t0[g][E] = nt;
+        state[ST_NTILES + g] = min(nt, max_tiles);
+    }
+    s_off[2 * MAXE] = off;
+    state[ST_OFF + 2 * MAXE] = off;
+}
+// ... and the tile map (its parallel part): the whole workgroup of `nthreads`
+__device__ __forceinline__ void keepall_tiles(int E, int max_tiles, const int* s_off, const int (*s_t0)[MAXE + 1], int* __restrict__ tile_group,
+                                              int* __restrict__ tile_row0, int* __restrict__ tile_nrows, int tid, int nthreads) {
+    for (int g = 0; g < 2; ++g)
+        for (int e = 0; e < E; ++e) {
+            const int ve = g * MAXE + e, t1 = min(s_t0[g][e + 1], max_tiles);
+            for (int t = s_t0[g][e] + tid; t < t1; t += nthreads) {
+                const int r = (t - s_t0[g][e]) * TILE_ROWS;
+                tile_group[g * max_tiles + t] = e;
+                tile_row0[g * max_tiles + t] = s_off[ve] + r;
+                tile_nrows[g * max_tiles + t] = min(TILE_ROWS, s_off[ve + 1] - s_off[ve] - r);
+            }
+        }
+}
+
+// The one-workgroup sizes (route_small_k / route_small_stream_k's place): two passes over the pairs, idx re-read from L2.
+__global__ __launch_bounds__(SMALL_THREADS) void route_keepall_small_k(const int* __restrict__ idx, const float* __restrict__ gate, long N, long Nsrc,
+                                                                      long gsplit, int E, float* __restrict__ comb_w, int* __restrict__ state,
+                                                                      int* __restrict__ src_row, int* __restrict__ dst_row,
+                                                                      int* __restrict__ tile_group, int* __restrict__ tile_row0,
+                                                                      int* __restrict__ tile_nrows, int max_tiles) {
+    __shared__ int s_kept[2 * MAXE], s_fill[2 * MAXE], s_off[2 * MAXE + 1], s_t0[2][MAXE + 1];
+    const int tid = threadIdx.x;
+    if (tid < 2 * MAXE) { s_kept[tid] = 0; s_fill[tid] = 0; }
+    __syncthreads();
+    for (long a = tid; a < 2 * N; a += SMALL_THREADS) {
+        const long tok = a >> 1;
+        const long as = tok >= Nsrc ? a - 2 * Nsrc : a;
+        comb_w[a] = gate[as];
+        if (tok < Nsrc) {
+            const int e = idx[a];
+            if (e >= 0 && e < E) atomicAdd(&s_kept[(tok >= gsplit ? MAXE : 0) + e], 1);
+        }
+    }
+    keepall_state(state, tid);
+    if (tid < MAXP) state[ST_CNT + tid] = 0;                     // counts handed back clean, as route_small_k does (mc_route_cleans_counts)
+    __syncthreads();
+    if (tid < 2 * MAXE) { state[ST_KEPT + tid] = s_kept[tid]; state[ST_FILL + tid] = 0; }
+    if (tid == 0) keepall_plan(s_kept, E, max_tiles, state, s_off, s_t0);
+    __syncthreads();
+    keepall_tiles(E, max_tiles, s_off, s_t0, tile_group, tile_row0, tile_nrows, tid, SMALL_THREADS);
+    for (long a = tid; a < 2 * Nsrc; a += SMALL_THREADS) {
+        const int e = idx[a];
+        if (e < 0 || e >= E) continue;
+        const int le = ((a >> 1) >= gsplit ? MAXE : 0) + e;
+        const int slot = s_off[le] + atomicAdd(&s_fill[le], 1);
+        src_row[slot] = (int)(a >> 1);
+        dst_row[slot] = (int)a;
+    }
+}
+
+// The cooperative kernel's place: same grid and pair -> thread mapping as route_coop_k, but ONE grid barrier -- the one in front of the
+// plan, which needs every workgroup's kept counts.  The barriers of the problem setup and of every radix pass served the selection only.
+// ST_KEPT and ST_FILL are zero on entry (the launcher's memset in front of the kernel: nobody is left to zero them behind a barrier).
+template <int PER>
+__global__ __launch_bounds__(256) void route_keepall_coop_k(const int* __restrict__ idx, const float* __restrict__ gate, long N, long Nsrc, long gsplit,
+                                                            int E, float* __restrict__ comb_w, int* state, int* __restrict__ src_row,
+                                                            int* __restrict__ dst_row, int* __restrict__ tile_group, int* __restrict__ tile_row0,
+                                                            int* __restrict__ tile_nrows, int max_tiles) {
+    __shared__ int s_cnt[2 * MAXE], s_base[2 * MAXE], s_kept[2 * MAXE];
+    __shared__ int s_off[2 * MAXE + 1], s_t0[2][MAXE + 1];
+    __shared__ int s_last, s_gen;
+    const int tid = threadIdx.x, nwg = (int)gridDim.x;
+    int* bar = state + ST_BAR;
+    auto pair_of = [&](int i) { return ((long)blockIdx.x * PER + i) * 256 + tid; };
+    if (tid < 2 * MAXE) s_cnt[tid] = 0;
+    __syncthreads();
+    int le[PER], lp[PER];      // slot group x expert of the pair (-1: no slot) and its place among this workgroup's pairs of it
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+        const long a = pair_of(i);
+        le[i] = -1; lp[i] = 0;
+        if (a >= 2 * N) continue;
+        const long tok = a >> 1;
+        comb_w[a] = gate[tok >= Nsrc ? a - 2 * Nsrc : a];
+        if (tok >= Nsrc) continue;
+        const int e = idx[a];
+        if (e < 0 || e >= E) continue;
+        le[i] = (tok >= gsplit ? MAXE : 0) + e;
+        lp[i] = atomicAdd(&s_cnt[le[i]], 1);
+    }
+    if (blockIdx.x == 0) {
+        keepall_state(state, tid);
+        if (tid < MAXP) state[ST_CNT + tid] = 0;                 // (nobody reads the gate's counts here)
+    }
+    __syncthreads();
+    if (tid < 2 * MAXE && s_cnt[tid]) atomicAdd(&state[ST_KEPT + tid], s_cnt[tid]);
+    if (!grid_sync(bar, nwg, &s_last, &s_gen, [&] {
+        if (tid < 2 * MAXE) s_kept[tid] = ld_state(&state[ST_KEPT + tid]);
+        __syncthreads();
+        if (tid == 0) keepall_plan(s_kept, E, max_tiles, state, s_off, s_t0);
+        __syncthreads();
+        keepall_tiles(E, max_tiles, s_off, s_t0, tile_group, tile_row0, tile_nrows, tid, 256);
+    })) return;
+    if (tid < 2 * MAXE && s_cnt[tid]) s_base[tid] = ld_state(&state[ST_OFF + tid]) + atomicAdd(&state[ST_FILL + tid], s_cnt[tid]);
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+        if (le[i] < 0) continue;
+        const long a = pair_of(i);
+        const int slot = s_base[le[i]] + lp[i];
+        src_row[slot] = (int)(a >> 1);
+        dst_row[slot] = (int)a;
+    }
+}
+
+// The launch sequence's place, first launch: comb_w = gate, kept counts (ST_KEPT zero on entry: the launcher's memset); route_plan_k and
+// route_keepall_fill_k follow.  early (the selection-only routing of the early schedule, this launch alone): the slot plans exist already,
+// the kept counts are the two groups' gate counts, and counts and fill cursors are handed back zeroed as route_init_k hands them back.
+__global__ __launch_bounds__(256) void route_keepall_k(const int* __restrict__ idx, const float* __restrict__ gate, long N, long Nsrc, long gsplit,
+                                                       int E, float* __restrict__ comb_w, int* __restrict__ state, int early) {
+    __shared__ int s_kept[2 * MAXE];
+    const int tid = threadIdx.x;
+    if (tid < 2 * MAXE) s_kept[tid] = 0;
+    __syncthreads();
+    for (long a = (long)blockIdx.x * 256 + tid; a < 2 * N; a += (long)gridDim.x * 256) {
+        const long tok = a >> 1;
+        comb_w[a] = gate[tok >= Nsrc ? a - 2 * Nsrc : a];
+        if (early || tok >= Nsrc) continue;
+        const int e = idx[a];
+        if (e >= 0 && e < E) atomicAdd(&s_kept[(tok >= gsplit ? MAXE : 0) + e], 1);
+    }
+    __syncthreads();
+    if (!early && tid < 2 * MAXE && s_kept[tid]) atomicAdd(&state[ST_KEPT + tid], s_kept[tid]);
+    if (blockIdx.x != 0) return;
+    keepall_state(state, tid);
+    if (early && tid < 2 * MAXE) {
+        const int g = tid / MAXE, e = tid % MAXE;
+        const int* cnt = state + (g ? ST_CNT1 : ST_CNT);
+        state[ST_KEPT + tid] = e < E ? cnt[e] + cnt[MAXE + e] : 0;
+        state[ST_FILL + tid] = 0;
+    }
+    __syncthreads();
+    if (early && tid < MAXP) { state[ST_CNT + tid] = 0; state[ST_CNT1 + tid] = 0; }
+}
+
+// ... and its compaction: route_fill_k over every pair of the first Nsrc tokens (a kept pair is not told from its weight here: a second
+// choice whose softmax score underflowed has gate 0 and still owns a slot)
+__global__ __launch_bounds__(256) void route_keepall_fill_k(const int* __restrict__ idx, long Nsrc, long gsplit, int E, int* __restrict__ state,
+                                                            int* __restrict__ src_row, int* __restrict__ dst_row) {
+    constexpr int PER = 8;  // pairs per thread
+    __shared__ int s_cnt[2 * MAXE];
+    __shared__ int s_base[2 * MAXE];
+    if (threadIdx.x < 2 * MAXE) s_cnt[threadIdx.x] = 0;
+    __syncthreads();
+    const long a0 = ((long)blockIdx.x * 256 + threadIdx.x) * PER;
+    int le[PER], lp[PER];
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+        const long a = a0 + i;
+        le[i] = -1;
+        if (a < 2 * Nsrc) {
+            const int e = idx[a];
+            if (e >= 0 && e < E) {
+                le[i] = ((a >> 1) >= gsplit ? MAXE : 0) + e;
+                lp[i] = atomicAdd(&s_cnt[le[i]], 1);
+            }
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 * MAXE && s_cnt[threadIdx.x])
+        s_base[threadIdx.x] = state[ST_OFF + threadIdx.x] + atomicAdd(&state[ST_FILL + threadIdx.x], s_cnt[threadIdx.x]);
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+        if (le[i] < 0) continue;
+        const long a = a0 + i;
+        const int slot = s_base[le[i]] + lp[i];
+        src_row[slot] = (int)(a >> 1);
+        dst_row[slot] = (int)a;
+    }
+}
+
 }  // namespace
 
 size_t mc_route_state_ints(int) { return ST_TOTAL; }
@@ -1101,6 +1311,39 @@ int mc_launch_route(long N, long Nsrc, long gsplit, int E, int capacity, RouteBu
     MC_REQUIRE(Nsrc == N || 2 * Nsrc == N, "route: Nsrc=%ld must be N or N/2 (N=%ld)", Nsrc, N);
     MC_REQUIRE(Nsrc == N || rb.tie_xor == 0xFFFFFFFFu, "route: the twin mode needs the stable tie order (a twin must rank right behind its original)");
     MC_REQUIRE(!select_only || !mc_route_is_small(o, N), "route: the selection-only mode is not for the one-workgroup sizes");
+    MC_REQUIRE(capacity >= 0 || capacity == MC_ROUTE_KEEP_ALL, "route: capacity %d", capacity);
+    if (capacity == MC_ROUTE_KEEP_ALL) {          // same three paths, none of their selection work
+        if (mc_route_is_small(o, N)) {
+            hipLaunchKernelGGL(route_keepall_small_k, dim3(1), dim3(SMALL_THREADS), 0, s, rb.idx, rb.gate, N, Nsrc, gsplit, E, rb.comb_w, rb.state,
+                               rb.src_row, rb.dst_row, rb.tile_group, rb.tile_row0, rb.tile_nrows, rb.max_tiles);
+            MC_LAUNCH_CHECK();
+            return MC_OK;
+        }
+        int blocks = cdiv(2 * N, 256 * 8);
+        if (blocks > 1024) blocks = 1024;
+        if (select_only) {
+            hipLaunchKernelGGL(route_keepall_k, dim3(blocks), dim3(256), 0, s, rb.idx, rb.gate, N, Nsrc, gsplit, E, rb.comb_w, rb.state, 1);
+            MC_LAUNCH_CHECK();
+            return MC_OK;
+        }
+        MC_HIP(hipMemsetAsync(rb.state + ST_KEPT, 0, sizeof(int) * 4 * MAXE, s));      // ST_KEPT, ST_FILL
+        if (o.route_coop && 2 * N <= COOP_MAX_WG * 256 * COOP_PER) {
+            const int per = o.route_per ? (int)o.route_per : (cdiv(2 * N, 256L * COOP_PER) > 256 ? 16 : 10);      // (route_coop_k's grid: what the context reserved)
+            const int nwg = cdiv(2 * N, 256L * per);
+#define MC_ROUTE_KEEPALL(P)                                                                                                          \
+    hipLaunchKernelGGL(route_keepall_coop_k<P>, dim3(nwg), dim3(256), 0, s, rb.idx, rb.gate, N, Nsrc, gsplit, E, rb.comb_w, rb.state, rb.src_row, \
+                       rb.dst_row, rb.tile_group, rb.tile_row0, rb.tile_nrows, rb.max_tiles)
+            if (per == 16) MC_ROUTE_KEEPALL(16); else MC_ROUTE_KEEPALL(10);
+#undef MC_ROUTE_KEEPALL
+            MC_LAUNCH_CHECK();
+            return MC_OK;
+        }
+        hipLaunchKernelGGL(route_keepall_k, dim3(blocks), dim3(256), 0, s, rb.idx, rb.gate, N, Nsrc, gsplit, E, rb.comb_w, rb.state, 0);
+        hipLaunchKernelGGL(route_plan_k, dim3(1), dim3(256), 0, s, rb.state, E, rb.tile_group, rb.tile_row0, rb.tile_nrows, rb.max_tiles);
+        hipLaunchKernelGGL(route_keepall_fill_k, dim3(cdiv(2 * Nsrc, 256 * 8)), dim3(256), 0, s, rb.idx, Nsrc, gsplit, E, rb.state, rb.src_row, rb.dst_row);
+        MC_LAUNCH_CHECK();
+        return MC_OK;
+    }
     if (mc_route_is_small(o, N)) {
 #define MC_ROUTE_SMALL(KERNEL)                                                                                                       \
     hipLaunchKernelGGL(KERNEL, dim3(1), dim3(SMALL_THREADS), 0, s, rb.idx, rb.gate, rb.key, N, Nsrc, gsplit, E, capacity,   \

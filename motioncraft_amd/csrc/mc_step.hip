@@ -157,9 +157,13 @@ static int moe_proj(const mc_ctx* c, const MoeW& w, float* Y, long ldy, long tok
     return mc_launch_gemm(GM_COMB, p, 1, 0, s);
 }
 
-static int moe_capacity(const mc_model_config& g, long Ntok) {      // tutel extract_critical
+// the ONE place a capacity is computed: tutel extract_critical with the context's factor (the model's unless mc_ctx_set_capacity_factor
+// changed it); factor 0 = no pair is dropped, which the routing takes as "no selection at all" (MC_ROUTE_KEEP_ALL)
+static int moe_capacity(const mc_ctx* c, long Ntok) {
+    const mc_model_config& g = c->m->cfg;
     const int E = g.num_experts;
-    return g.topk * (int)((double)g.capacity_factor * (double)((Ntok + E - 1) / E));
+    if (c->keep_all) return MC_ROUTE_KEEP_ALL;
+    return g.topk * (int)((double)c->cap_factor * (double)((Ntok + E - 1) / E));
 }
 
 // One tutel MoE layer + GELU + proj (class MOE, st_attention.py:49-56) over Ntok tokens whose
@@ -176,7 +180,7 @@ int run_moe(mc_ctx* c, const MoeW& w, const float* z, long Ntok, float* out, lon
         if ((r = dense(c, z, din, w.gate_w, din, w.gate_b, nullptr, 0, c->proj, 256, Ntok, 256, din, ACT_NONE, s))) return r;
         if ((r = mc_launch_gate_finish(c->proj, w.sim_n, w.scale, Ntok, E, c->rb, s))) return r;
     }
-    const int capacity = moe_capacity(g, Ntok);
+    const int capacity = moe_capacity(c, Ntok);
     c->cnt_clean = false;
     c->early_clean = false;      // (the fill of this routing uses the cursors)
     c->led_nsrc = twin ? Ntok / 2 : Ntok;
@@ -606,7 +610,7 @@ static int moe_front(mc_ctx* c, int i, float* hs, const LayerPlan& p, hipStream_
         if ((r = experts(1, c->side))) return r;
         MC_HIP(hipStreamWaitEvent(s, c->ev_gate1, 0));     // the cut ranks the whole batch: both gates must have arrived
     } else if ((r = mc_launch_route_fill_group(1, p.gsplit, 0, E, c->rb, s))) return r;      // (an empty second group: no tiles)
-    if ((r = mc_launch_route(c->N, p.nsrc, p.gsplit, E, moe_capacity(g, c->N), c->rb, c->opt, s, true))) return r;
+    if ((r = mc_launch_route(c->N, p.nsrc, p.gsplit, E, moe_capacity(c, c->N), c->rb, c->opt, s, true))) return r;
     c->cnt_clean = c->early_clean = true;
     MC_HIP(hipEventRecord(c->ev_sel, s));
     if (both) MC_HIP(hipStreamWaitEvent(c->side, c->ev_sel, 0));      // group 1's projection reads comb_w and the twin-split flag
@@ -827,15 +831,18 @@ int sampler_update(mc_ctx* c, const float* x_t, const X0Parts& x0p, const mc_ste
     const SamplerCoefs* table = c->graph_mode ? c->gcoefs : nullptr;
     const int* step_ptr = c->graph_mode ? c->gstep : nullptr;
     const bool multistep = c->graph_mode ? c->graph_multistep : k->mode == MC_SAMPLER_MULTISTEP;
+    // a seed table (mc_ctx_set_row_seeds): an in-kernel draw takes every row's own key; a noise tensor is read as it is
+    const RowKeys rk{reinterpret_cast<const uint32_t*>(c->row_seeds), (int)(n / c->B)};
+    const RowKeys* rows = c->row_seeds_set && rng && !noise ? &rk : nullptr;
     if (c->seam_ov > 0) {        // coupled windows: one kernel for every mode (no graph table: capture is refused while the seam table is set)
         if (c->graph_mode) { mc_set_error("sampler update under graph capture with a seam table set"); return MC_ERR_STATE; }
         MC_REQUIRE(!multistep || c->x0_hist, "multistep update without a history buffer");
         SeamTab st;
         st.flags = c->seam_tab; st.w = reinterpret_cast<const float*>(c->seam_tab + c->B);
         st.T = c->T; st.C = c->m->cfg.input_feats; st.ov = c->seam_ov;
-        return mc_launch_sampler_seam(x_t, x0p.a, x0p.second(), noise, multistep ? c->x0_hist : nullptr, x_prev, x0, c->B, x0p.coefs(k), st, s, rng, pad);
+        return mc_launch_sampler_seam(x_t, x0p.a, x0p.second(), noise, multistep ? c->x0_hist : nullptr, x_prev, x0, c->B, x0p.coefs(k), st, s, rng, pad, rows);
     }
-    if (!multistep) return mc_launch_sampler_update(x_t, x0p.a, x0p.second(), noise, x_prev, x0, n, x0p.coefs(k), s, table, step_ptr, rng, pad);
+    if (!multistep) return mc_launch_sampler_update(x_t, x0p.a, x0p.second(), noise, x_prev, x0, n, x0p.coefs(k), s, table, step_ptr, rng, pad, rows);
     MC_REQUIRE(c->x0_hist, "multistep update without a history buffer");
     return mc_launch_sampler_multistep(x_t, x0p.a, x0p.second(), c->x0_hist, x_prev, x0, n, x0p.coefs(k), s, table, step_ptr, pad);
 }

@@ -235,11 +235,37 @@ class GaussianDiffusion:
             raise ValueError(f'model_kwargs["seams"]: dict(first_frame=..., overlap=..., weights=None), got keys {sorted(seams)}')
         return dict(first_frame=seams['first_frame'], overlap=seams['overlap'], weights=seams.get('weights', None))
 
+    @staticmethod
+    def _seeds_of(seeds, shape, noise, step_noise, generator, transl_req=None):
+        """``seeds``: one Philox key per batch row (``NativeContext.set_row_seeds``) -- x_T is draw 0 of every row's own stream and
+        the n-th ``randn_like`` of the walk is draw ``1 + n``, so a row's noise depends on its seed alone.  Exclusive with every other
+        source of noise."""
+        if seeds is None:
+            return None
+        if noise is not None or step_noise is not None or generator is not None:
+            raise ValueError('seeds= is exclusive with noise=, step_noise= and generator=: every draw comes from the rows\' own streams')
+        if transl_req:
+            raise NotImplementedError('seeds= together with transl_req: its randn(2) draws are per call, not per row')
+        from .engine import check_seeds
+        return check_seeds(seeds, shape[0])
+
     def _loop(self, mode, model, shape, noise, model_kwargs, device, progress, eta, step_noise, generator,
-              num_steps=None, trajectory=None, pre_seq=None, transl_req=None, graph=False, fused=True):
+              num_steps=None, trajectory=None, pre_seq=None, transl_req=None, graph=False, fused=True, seeds=None):
         """the walk of ``_walk``; with ``model_kwargs['seams']`` the context's seam table is set before it and cleared after it, whatever
-        happens in between (per-step and fused path alike: the library picks the coupled update wherever a table is set)"""
+        happens in between (per-step and fused path alike: the library picks the coupled update wherever a table is set); the seed
+        table of ``seeds`` likewise"""
         seams = self._seams_of(model_kwargs, graph, pre_seq, transl_req)
+        seeds = self._seeds_of(seeds, shape, noise, step_noise, generator, transl_req)
+        if seeds is not None:
+            held, seeded = [], []
+            try:
+                return self._walk(mode, model, shape, noise, model_kwargs, device, progress, eta, step_noise, generator, num_steps,
+                                  trajectory, pre_seq, transl_req, graph, fused, seams=seams, seam_held=held, seeds=seeds, seed_held=seeded)
+            finally:
+                for ctx in held:
+                    ctx.clear_seams()
+                for ctx in seeded:
+                    ctx.clear_row_seeds()
         if seams is None:
             return self._walk(mode, model, shape, noise, model_kwargs, device, progress, eta, step_noise, generator, num_steps,
                               trajectory, pre_seq, transl_req, graph, fused)
@@ -252,7 +278,8 @@ class GaussianDiffusion:
                 ctx.clear_seams()
 
     def _walk(self, mode, model, shape, noise, model_kwargs, device, progress, eta, step_noise, generator,
-              num_steps=None, trajectory=None, pre_seq=None, transl_req=None, graph=False, fused=True, seams=None, seam_held=None):
+              num_steps=None, trajectory=None, pre_seq=None, transl_req=None, graph=False, fused=True, seams=None, seam_held=None,
+              seeds=None, seed_held=None):
         if model_kwargs is None:
             model_kwargs = {}
         if not isinstance(shape, (tuple, list)):
@@ -265,7 +292,11 @@ class GaussianDiffusion:
         if seams is not None:
             seam_held.append(ctx)
             ctx.set_seams(**seams)
-        if noise is not None:
+        if seeds is not None:
+            seed_held.append(ctx)
+            ctx.set_row_seeds(seeds)
+            img = ctx.draw_rows(0)                                            # x_T: draw 0 of every row
+        elif noise is not None:
             img = noise.to(device=device, dtype=torch.float32).contiguous().clone()
         else:
             img = torch.randn(*shape, device=device, generator=generator)
@@ -322,6 +353,8 @@ class GaussianDiffusion:
             so there ``step_noise`` is an iterator (or a callable of the running draw number)."""
             n = draw_no[0]
             draw_no[0] += 1
+            if seeds is not None:
+                return ctx.draw_rows(1 + n)                                   # the n-th randn_like of the walk: draw 1 + n
             if step_noise is None:
                 return torch.randn(*shape, device=device, generator=generator)
             if hasattr(step_noise, '__next__'):
@@ -377,7 +410,9 @@ class GaussianDiffusion:
             # gathered into [steps, B, T, C] chunks of at most ~512 MB and the same entry point reads them
             idx = [i for i, _ in plan]
             coefs = [self.step_coefs(i, mode, model.cfg_scale, eta) for i in idx]
-            if step_noise is None:
+            if seeds is not None:
+                ctx.sample_loop(img, idx, coefs, noise=None, seed=0, draw0=1)     # step k: draw 1 + k of every row's own stream
+            elif step_noise is None:
                 gdev = generator.device if generator is not None else torch.device('cpu')
                 key = int(torch.randint(0, 2 ** 62, (1,), generator=generator, device=gdev).item())
                 ctx.sample_loop(img, idx, coefs, noise=None, seed=key, draw0=0)
@@ -397,7 +432,9 @@ class GaussianDiffusion:
             elif seeded:
                 a_, b_ = np.float32(self.sqrt_alphas_cumprod[i]), np.float32(self.sqrt_one_minus_alphas_cumprod[i])
                 pre_noise = None
-                if pre_seq is not None:
+                if pre_seq is not None and seeds is not None:
+                    pre_noise = draw(i)[:, :pre_seq.shape[1]].contiguous()    # a smaller tensor: the leading elements of each row's draw
+                elif pre_seq is not None:
                     pre_noise = (next(step_noise).to(device=device, dtype=torch.float32).contiguous() if step_noise is not None
                                  else torch.randn(*pre_seq.shape, device=device, generator=generator))
                 transl = []
@@ -432,35 +469,38 @@ class GaussianDiffusion:
 
     def p_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                       model_kwargs=None, device=None, pre_seq=None, transl_req=None, progress=False,
-                      step_noise=None, generator=None, num_steps=None, trajectory=None, graph=False, fused=True):
+                      step_noise=None, generator=None, num_steps=None, trajectory=None, graph=False, fused=True, seeds=None):
         """gaussian_diffusion.py:698-797.  Extras beside the reference's arguments: ``step_noise`` (the per-step draws, for runs on
         the reference's seeds), ``generator``, ``num_steps``, ``trajectory``, ``graph`` (hipGraph replay) and ``fused`` (default:
         the whole loop is ONE library call, mc_sample_loop, with the per-step noise drawn on the device when no step_noise is
-        given; False: one mc_sample_step per step with torch.randn draws)."""
+        given; False: one mc_sample_step per step with torch.randn draws).  ``seeds``: B ints in [0, 2^64), one per batch row -- x_T and
+        every per-step draw then come from the row's own Philox stream (``_seeds_of``), the same bits on the fused, the per-step and
+        the graph path; exclusive with ``noise``, ``step_noise`` and ``generator``."""
         self._check_supported(clip_denoised, denoised_fn, cond_fn, model_kwargs, pre_seq, transl_req)
         return self._loop('ddpm', model, shape, noise, model_kwargs, device, progress, 0.0, step_noise, generator,
-                          num_steps, trajectory, pre_seq=pre_seq, transl_req=transl_req, graph=graph, fused=fused)
+                          num_steps, trajectory, pre_seq=pre_seq, transl_req=transl_req, graph=graph, fused=fused, seeds=seeds)
 
     def ddim_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                          model_kwargs=None, device=None, progress=False, eta=0.0, pre_seq=None,
-                         step_noise=None, generator=None, num_steps=None, trajectory=None, graph=False, fused=True):
+                         step_noise=None, generator=None, num_steps=None, trajectory=None, graph=False, fused=True, seeds=None):
         self._check_supported(clip_denoised, denoised_fn, cond_fn, model_kwargs, pre_seq)
         if self.opt is not None and getattr(self.opt, 'same_overlap_noisy', False):
             raise NotImplementedError('opt.same_overlap_noisy: the reference writes self.saved_noisy_tail '
                                       '(gaussian_diffusion.py:879-881) without ever creating it, so that option has '
                                       'no defined behaviour to reproduce')
         return self._loop('ddim', model, shape, noise, model_kwargs, device, progress, float(eta), step_noise,
-                          generator, num_steps, trajectory, pre_seq=pre_seq, graph=graph, fused=fused)
+                          generator, num_steps, trajectory, pre_seq=pre_seq, graph=graph, fused=fused, seeds=seeds)
 
 
     def dpm_solver_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                                model_kwargs=None, device=None, progress=False, order=2, generator=None, num_steps=None,
-                               trajectory=None, graph=False, fused=True, pre_seq=None, transl_req=None):
+                               trajectory=None, graph=False, fused=True, pre_seq=None, transl_req=None, seeds=None):
         """DPM-Solver++ (2M) on the model's x0 prediction: a second-order multistep walk down the (spaced) schedule, one denoiser call
         per step like DDIM, meant for 10-20 steps (``respace='ddimN'`` or ``'logsnrN'``).  The reference has no such sampler; the
         coefficients are ``multistep_coefs`` (first-order first and last finite step, ``x = x0`` at index 0), ``order=1`` is DDIM with
         eta = 0.  Deterministic given ``noise``: no per-step draw exists, ``generator`` only draws x_T when ``noise`` is None.
-        ``num_steps`` / ``trajectory`` / ``graph`` / ``fused`` as in the other two loops.  No outpainting (RePaint) and no
+        ``num_steps`` / ``trajectory`` / ``graph`` / ``fused`` as in the other two loops; ``seeds`` (one per row) draws x_T from the rows'
+        own streams instead (draw 0), exclusive with ``noise`` and ``generator``.  No outpainting (RePaint) and no
         pre_seq / transl_req seeding: those raise."""
         self._check_supported(clip_denoised, denoised_fn, cond_fn, model_kwargs, pre_seq, transl_req)
         if order not in (1, 2):
@@ -468,6 +508,7 @@ class GaussianDiffusion:
         if model_kwargs is None:
             model_kwargs = {}
         seams = self._seams_of(model_kwargs, graph, pre_seq, transl_req)
+        seeds = self._seeds_of(seeds, shape, noise, None, generator)
         keep = ((model_kwargs.get('y', {}) or {}).get('outpainting_mask', None))
         if keep is not None and bool(keep.any()):
             raise NotImplementedError('dpm_solver_sample_loop with an outpainting mask (RePaint): not implemented for the '
@@ -482,16 +523,26 @@ class GaussianDiffusion:
         if device is None:
             device = torch.device('cuda', torch.cuda.current_device())
         ctx = model.sampling_context(B, T, self.timestep_map, model_kwargs, device)
-        if seams is None:
+        if seams is None and seeds is None:
             return self._multistep_walk(ctx, model, shape, noise, device, progress, order, generator, num_steps, trajectory, graph, fused)
-        try:                                                  # coupled windows: the table is set for this walk only
-            ctx.set_seams(**seams)
-            return self._multistep_walk(ctx, model, shape, noise, device, progress, order, generator, num_steps, trajectory, graph, fused)
+        try:                                                  # coupled windows / row seeds: the tables are set for this walk only
+            if seams is not None:
+                ctx.set_seams(**seams)
+            if seeds is not None:
+                ctx.set_row_seeds(seeds)
+            return self._multistep_walk(ctx, model, shape, noise, device, progress, order, generator, num_steps, trajectory, graph, fused,
+                                        seeded=seeds is not None)
         finally:
-            ctx.clear_seams()
+            if seams is not None:
+                ctx.clear_seams()
+            if seeds is not None:
+                ctx.clear_row_seeds()
 
-    def _multistep_walk(self, ctx, model, shape, noise, device, progress, order, generator, num_steps, trajectory, graph, fused):
-        if noise is not None:
+    def _multistep_walk(self, ctx, model, shape, noise, device, progress, order, generator, num_steps, trajectory, graph, fused,
+                        seeded=False):
+        if seeded:
+            img = ctx.draw_rows(0)                                # x_T: draw 0 of every row's own stream
+        elif noise is not None:
             img = noise.to(device=device, dtype=torch.float32).contiguous().clone()
         else:
             img = torch.randn(*shape, device=device, generator=generator)

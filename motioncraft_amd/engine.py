@@ -23,6 +23,19 @@ def _dev_f32(t, name):
     return t
 
 
+def check_seeds(seeds, rows):
+    """``seeds`` as a list of ``rows`` ints in [0, 2^64) (one Philox key per batch row), or ValueError"""
+    try:
+        out = [int(s) for s in seeds]
+    except (TypeError, ValueError):
+        raise ValueError(f'seeds must be a sequence of {rows} ints, got {seeds!r}') from None
+    if len(out) != rows:
+        raise ValueError(f'{len(out)} seeds for a batch of {rows} rows')
+    if any(not 0 <= s < 2 ** 64 for s in out):
+        raise ValueError('every seed must lie in [0, 2^64)')
+    return out
+
+
 class NativeModel(_lib.NativeObject):
     def __init__(self, dims, state_dict, cfg_scale=6.5, capacity_factor=1.5, dyn_heads=8, device=None,
                  condition_cfg=True):
@@ -59,6 +72,7 @@ class NativeContext:
         self._keep = []
         self._graph_state = None
         self.seams = None              # dict(first_frame, overlap) while a seam table is set (set_seams)
+        self.row_seeds = None          # the rows' Philox keys while a seed table is set (set_row_seeds)
 
     @property
     def workspace_bytes(self):
@@ -232,6 +246,43 @@ class NativeContext:
     def clear_seams(self):
         _lib.check(self.lib.mc_ctx_set_seams(self.handle, 0, None, None, _stream()), 'mc_ctx_set_seams')
         self.seams = None
+
+    def set_capacity_factor(self, cf):
+        """Capacity factor of every MoE of this context (mc_ctx_set_capacity_factor): > 0 tutel's formula with it, 0 = no (token,
+        choice) is dropped and no selection work runs; negative raises.  The library forgets the condition (the hoisted text MoE is
+        routed too): ``set_condition`` must follow."""
+        self._drop_graph()             # a captured graph has the routing launches of the old factor baked in
+        self._keep = []
+        _lib.check(self.lib.mc_ctx_set_capacity_factor(self.handle, float(cf)), 'mc_ctx_set_capacity_factor')
+
+    @property
+    def capacity_factor(self):
+        return float(self.lib.mc_ctx_capacity_factor(self.handle))
+
+    def set_row_seeds(self, seeds):
+        """One Philox key per row (mc_ctx_set_row_seeds): ``seeds`` = B ints in [0, 2^64).  While set, ``sample_loop`` without
+        ``noise`` and ``draw_rows`` give row b element r of draw d of ``mc_op_philox_normal(T * C, seeds[b], d)``, whatever B is and
+        wherever the row sits; ``None`` clears the table."""
+        if seeds is None:
+            return self.clear_row_seeds()
+        seeds = check_seeds(seeds, self.B)
+        arr = (ctypes.c_uint64 * self.B)(*seeds)
+        _lib.check(self.lib.mc_ctx_set_row_seeds(self.handle, arr, _stream()), 'mc_ctx_set_row_seeds')
+        self.row_seeds = seeds
+
+    def clear_row_seeds(self):
+        _lib.check(self.lib.mc_ctx_set_row_seeds(self.handle, None, _stream()), 'mc_ctx_set_row_seeds')
+        self.row_seeds = None
+
+    def draw_rows(self, draw, out=None):
+        """[B,T,C] = draw number ``draw`` of every row's own stream (mc_ctx_draw_rows); needs a seed table."""
+        if out is None:
+            out = torch.empty(self.B, self.T, self.C, device='cuda', dtype=torch.float32)
+        out = _dev_f32(out, 'out')
+        if tuple(out.shape) != (self.B, self.T, self.C):
+            raise ValueError(f'out shape {tuple(out.shape)} != {(self.B, self.T, self.C)}')
+        _lib.check(self.lib.mc_ctx_draw_rows(self.handle, _ptr(out), int(draw) & (2 ** 64 - 1), _stream()), 'mc_ctx_draw_rows')
+        return out
 
     def graph_capture(self, x, noise, coefs):
         """Capture mc_sample_step into ONE hipGraph for the whole schedule.  ``x`` [B,T,C] is updated in place by every

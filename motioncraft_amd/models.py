@@ -185,6 +185,12 @@ class STMoGenTransformer:
             ctx.set_precision(self.precision)
         if ctx.timesteps != [int(t) for t in timestep_map]:
             ctx.set_timesteps(timestep_map)
+        # model_kwargs['capacity_factor'] (0: nothing dropped, a row no longer depends on its batchmates); absent = the model's own,
+        # also for a cached context an earlier call left at another value
+        cf = model_kwargs.get('capacity_factor', None)
+        cf = float(self.native.cfg.capacity_factor) if cf is None else float(cf)
+        if ctx.capacity_factor != cf:
+            ctx.set_capacity_factor(cf)
         c = model_kwargs.get('c', None)
         if c is not None and not self._control:
             raise ValueError('a control condition `c` was given but the model has no control branch: wrap it with '
@@ -367,6 +373,7 @@ class MotionDiffusion:
             self.model = build_submodule(model)
         self.loss_recon = build_loss(loss_recon)
         self.diffusion_train_cfg = diffusion_train
+        self.diffusion_test_cfg = diffusion_test        # (serve.RequestBatcher respaces it)
         self.diffusion_test = build_diffusion(diffusion_test, opt=opt)
         self.training = False
 
@@ -412,7 +419,9 @@ class MotionDiffusion:
                                 num_intervals=num_intervals, c=c, y=y, patch_size=patch_size)
             if kwargs.get('seams') is not None:       # coupled windows (longform.sample_long_coupled): the sampler loops set the seam table
                 model_kwargs['seams'] = kwargs['seams']
-            inference_kwargs = kwargs.get('inference_kwargs', {})
+            inference_kwargs = dict(kwargs.get('inference_kwargs', {}))
+            if 'capacity_factor' in inference_kwargs:      # a setting of the context, not of the loop (sampling_context applies it)
+                model_kwargs['capacity_factor'] = inference_kwargs.pop('capacity_factor')
         if self.inference_type == 'ddpm':
             output = self.diffusion_test.p_sample_loop(self.model, (B, T, dim_pose), clip_denoised=False,
                                                        progress=False, model_kwargs=model_kwargs, **inference_kwargs)

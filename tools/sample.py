@@ -7,7 +7,7 @@ positions with --pose_npy), everything between the condition features and the fi
         [--clip_feat feats.npy | --xf_out xf.npy | --random-condition SEED]  [--mean mean.npy --std std.npy]  [--pose_npy joints.npy]
         [--anim_dir frames/ | --anim_avi clip.avi [--anim_size 1000x1000] [--anim_fps 20]]
         [--smplx_model SMPLX_NEUTRAL.npz --joints_npy joints.npy [--verts_npy verts.npy] [--render_dir frames/ | --render_avi clip.avi [--render_size 960x720]]]
-        [--avi_quality 90]  [--sampler ddpm|ddim|dpmpp [--steps N [--spacing time|logsnr]]]
+        [--avi_quality 90]  [--sampler ddpm|ddim|dpmpp [--steps N [--spacing time|logsnr]]]  [--seeds a,b,c] [--no_drop]
 
 The CLIP tokenizer is not available offline: prompts only name the output file unless the `clip` package is importable
 (then they are tokenized and encoded by the device CLIP tower when the checkpoint carries clip.* weights).
@@ -61,6 +61,10 @@ def parse_args():
     p.add_argument('--random-condition', type=int, default=None, metavar='SEED')
     p.add_argument('--mean'), p.add_argument('--std')
     p.add_argument('--seed', type=int, default=0)
+    # independent requests: one Philox key per sample instead of the one --seed of the call, and routing without token drops -- with both,
+    # a sample is a function of its own prompt, length and seed at this batch size (quality at --no_drop with trained weights: unmeasured)
+    p.add_argument('--seeds', default=None, metavar='A,B,C', help='one integer seed per sample (replaces --seed): row-keyed noise')
+    p.add_argument('--no_drop', action='store_true', help='MoE capacity factor 0: no token is dropped (default: the model\'s 1.5)')
     # long-sequence / RePaint options read by the sampler through cfg.model['opt'] (tools/visualize.py:96-110)
     p.add_argument('--repaint', action='store_true'), p.add_argument('--overlap_len', type=int, default=0)
     p.add_argument('--same_overlap_noisy', action='store_true'), p.add_argument('--no_resample', action='store_true')
@@ -149,10 +153,23 @@ def main():
     mask = torch.zeros(n, T, device=dev)
     for i, m in enumerate(a.motion_length):
         mask[i, :m] = 1
+    if a.seeds is not None:
+        try:
+            seeds = [int(v, 0) for v in a.seeds.split(',')]
+        except ValueError:
+            raise SystemExit(f'--seeds takes comma-separated integers, got {a.seeds!r}')
+        if len(seeds) != n:
+            raise SystemExit(f'--seeds names {len(seeds)} seeds for {n} samples')
+        ikw = dict(seeds=seeds)
+    else:
+        ikw = dict(generator=torch.Generator(device=dev).manual_seed(a.seed))
+    if a.no_drop:
+        ikw['capacity_factor'] = 0
+    if a.graph:
+        ikw['graph'] = True
     kw = dict(motion=torch.zeros(n, T, C, device=dev), motion_mask=mask,
               motion_length=torch.tensor(a.motion_length, device=dev).long(), num_intervals=n,
-              motion_metas=[{'text': t} for t in a.text],
-              inference_kwargs=dict(generator=torch.Generator(device=dev).manual_seed(a.seed), **({'graph': True} if a.graph else {})))
+              motion_metas=[{'text': t} for t in a.text], inference_kwargs=ikw)
     if a.xf_out:
         kw['xf_out'] = torch.from_numpy(np.load(a.xf_out)).float().to(dev)
     elif a.clip_feat:

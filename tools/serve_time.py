@@ -1,0 +1,139 @@
+#!/usr/bin/env python
+"""Timing of independent requests in one batch, synthetic weights, fp32, each figure the median of --reps runs
+after one warm-up:
+
+  routing   one denoiser call (mc_denoise) at capacity factor 1.5 against 0 (keep-all routing: no selection work); the difference over
+            the layers is the routing time a layer saves.  The two calls also differ in the expert rows they compute where the schedule
+            computes kept pairs only (one stream / joined groups); the early two-group schedule computes every pair either way
+  noise     the fused DDPM loop (mc_sample_loop, noise drawn in the sampler-update kernel): one seed per call (flat) against a seed table
+  batcher   serve.RequestBatcher: R requests of a --steps DDIM walk through B = 1 calls against through one B = R batch
+
+usage: serve_time.py [--small] [--batch B] [--requests R] [--steps N] [--reps K] [--only routing,noise,batcher]
+  --small: the reduced test config (24 frames) instead of the 0.125b architecture (196 frames)"""
+import argparse
+import os
+import sys
+import time
+
+import torch
+
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
+sys.path.insert(0, ROOT)
+import motioncraft_amd as mc                                                  # noqa: E402
+from motioncraft_amd.diffusion import build_diffusion                         # noqa: E402
+from motioncraft_amd.serve import Request, RequestBatcher                     # noqa: E402
+from motioncraft_amd.synthetic import make_state_dict, default_dims           # noqa: E402
+
+p = argparse.ArgumentParser()
+p.add_argument('--small', action='store_true')
+p.add_argument('--batch', type=int, default=64)
+p.add_argument('--requests', type=int, default=16)
+p.add_argument('--steps', type=int, default=50)
+p.add_argument('--reps', type=int, default=3)
+p.add_argument('--only', default='routing,noise,batcher')
+a = p.parse_args()
+only = set(a.only.split(','))
+
+cfg = mc.Config.fromfile(os.path.join(ROOT, 'tests', 'configs', 'stmogen_small.py'))
+T = 24 if a.small else 196
+if not a.small:
+    d = default_dims()
+    m = cfg.model.model
+    m.max_seq_len, m.latent_dim, m.num_layers, m.time_embed_dim = T, d['L'] * d['H'], d['NL'], d['Te']
+    blk = m.ca_block_cfg
+    blk.latent_dim, blk.text_latent_dim, blk.time_embed_dim, blk.max_seq_len, blk.max_text_seq_len = d['L'], d['Dt'], d['Te'], T, d['Nt']
+    blk.ffn_dim = d['F']
+    m.ffn_cfg.latent_dim, m.ffn_cfg.ffn_dim, m.ffn_cfg.time_embed_dim = d['L'], d['F'], d['Te']
+    m.text_encoder.latent_dim = d['Dt']
+    m.pose_encoder_cfg.latent_dim = m.pose_decoder_cfg.latent_dim = d['L']
+schedule = dict(beta_scheduler='linear', diffusion_steps=1000, model_mean_type='start_x', model_var_type='fixed_large')
+cfg.model.diffusion_test = dict(schedule, respace=f'ddim{a.steps}')
+arch = mc.build_architecture(cfg.model)
+arch.load_state_dict({'model.' + k: v for k, v in make_state_dict(arch.model.dims, 0).items()})
+dims = arch.model.dims
+C = dims['input_feats']
+print(f'# {"small" if a.small else "0.125b"} config, T = {T}, fp32, synthetic weights; medians of {a.reps} after one warm-up', flush=True)
+
+
+def median_of(fn):
+    fn()
+    vals = sorted(fn() for _ in range(a.reps))
+    return vals[len(vals) // 2], vals[0], vals[-1]
+
+
+def events_ms(fn, calls):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    e0.record()
+    for _ in range(calls):
+        fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) / calls
+
+
+def inputs(B, seed=0):
+    g = torch.Generator().manual_seed(seed)
+    xf = torch.nn.functional.layer_norm(torch.randn(B, dims['Nt'], dims['Dt'], generator=g), (dims['Dt'],)).cuda()
+    lengths = [int(v) for v in torch.randint(T // 3, T + 1, (B,), generator=g)]
+    mask = torch.zeros(B, T, device='cuda')
+    for b, n in enumerate(lengths):
+        mask[b, :n] = 1
+    return torch.randn(B, T, C, generator=g).cuda(), xf, mask, lengths
+
+
+B = a.batch
+if 'routing' in only or 'noise' in only:
+    x, xf, mask, _ = inputs(B)
+    dd = build_diffusion(dict(schedule, respace='ddim10'))
+    ctx = arch.model.native.context(B, T, max_steps=10)
+    ctx.set_timesteps(dd.timestep_map)
+    if 'routing' in only:
+        NL = dims['NL']
+        res = {}
+        for cf in (1.5, 0.0, 1.5, 0.0):            # (twice, interleaved: a drift of the machine shows as a difference between equal settings)
+            ctx.set_capacity_factor(cf)
+            ctx.set_condition(xf, mask)
+            out2 = torch.empty(2 * B, T, C, device='cuda')
+            med, lo, hi = median_of(lambda: events_ms(lambda: ctx.denoise(x, 5, out2=out2), 5))
+            res.setdefault(cf, []).append(med)
+            print(f'B={B} denoiser call, capacity factor {cf:3.1f}: median {med:8.3f} ms   min {lo:8.3f}   max {hi:8.3f}   (5 calls per run)', flush=True)
+        diff = min(res[1.5]) - min(res[0.0])
+        print(f'B={B} keep-all routing saves {diff * 1e3:7.1f} us per call = {diff * 1e3 / NL:6.1f} us per layer ({NL} layers; coop routing: '
+              f'{ctx.uses_coop_routing})', flush=True)
+        ctx.set_capacity_factor(1.5)
+        ctx.set_condition(xf, mask)
+    if 'noise' in only:
+        idx = list(range(10))[::-1]
+        coefs = [dd.step_coefs(i, 'ddpm', arch.model.cfg_scale) for i in idx]
+        for name, seeds in (('flat (one seed per call)', None), ('seed table (row keys)', list(range(100, 100 + B))),
+                            ('flat (one seed per call)', None), ('seed table (row keys)', list(range(100, 100 + B)))):
+            ctx.set_row_seeds(seeds)
+            xd = x.clone()
+            med, lo, hi = median_of(lambda: events_ms(lambda: ctx.sample_loop(xd, idx, coefs, noise=None, seed=7, draw0=1), 1) / 10)
+            print(f'B={B} fused DDPM loop, {name:26s}: median {med:8.4f} ms per step   min {lo:8.4f}   max {hi:8.4f}   (10-step loops)', flush=True)
+        ctx.clear_row_seeds()
+    ctx.close()
+
+if 'batcher' in only:
+    R = a.requests
+    g = torch.Generator().manual_seed(1)
+    reqs = [Request(length=int(torch.randint(T // 3, T + 1, (1,), generator=g)), seed=500 + i,
+                    xf_out=torch.nn.functional.layer_norm(torch.randn(dims['Nt'], dims['Dt'], generator=g), (dims['Dt'],)).cuda())
+            for i in range(R)]
+    for batch in (1, R):
+        bt = RequestBatcher(arch, batch=batch, frames=T, sampler='ddim', steps=a.steps)
+
+        def run():
+            for r in reqs:
+                bt.submit(r)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = bt.run()
+            torch.cuda.synchronize()
+            assert len(out) == R
+            return time.perf_counter() - t0
+        med, lo, hi = median_of(run)
+        print(f'{R} requests, {a.steps}-step DDIM, through B={batch:<3d} calls: median {med * 1e3:8.1f} ms = {R / med:7.2f} requests/s   '
+              f'(min {lo * 1e3:8.1f} ms, max {hi * 1e3:8.1f} ms)', flush=True)
+arch.model.release()
