@@ -297,6 +297,31 @@ int mc_ctx_draw_rows(mc_ctx* c, float* out_dev, uint64_t draw, void* stream);
  * mc_ctx_graph_capture return MC_ERR_STATE; with a captured graph in the context, setting a table is MC_ERR_STATE. */
 int mc_ctx_set_seams(mc_ctx* c, int32_t overlap, const int32_t* first_frame_host, const float* weight_host, void* stream);
 
+/* Per-row schedules: every request row b of the batch at its own schedule index and under its own coefficients,
+ * the guidance weight (text_coef / none_coef) among them -- the reference's denoiser takes ts as a [B] tensor and its CFG weight is per
+ * sample.  Row r of any [B T]- or [2 B T]-row operand belongs to request row (r / T) % B; sample b + B is the CFG twin of b.
+ * mc_sample_rows: num_ticks ticks back to back, no return to the host between them; a tick is denoise, CFG combine, sampler update with
+ *   row b at schedule index step_index_host[k][b] under coefs_host[k][b], x_dev [B,T,C] updated in place.  The noise of tick k is read
+ *   from noise_dev + k B T C, or with noise_dev == NULL drawn in the kernel from the rows' keys (mc_ctx_set_row_seeds; MC_ERR_STATE
+ *   without a table): row b takes draw draw_host[k][b], counter (row-local element / 4, draw).  x0_dev (may be NULL): x0 of the last tick.
+ *   All entries of a call share one sampler mode (mixed: MC_ERR_ARG); an index outside the schedule is MC_ERR_ARG; num_ticks <=
+ *   max_steps.  The kernels are the forms mc_sample_step picks at the same shape and options, so equal entries in every row give its bits.
+ *   Mode 2: the "history valid" state is one flag per row -- a tick sets its rows' flags, eta != 0 on a row whose flag is clear is
+ *   MC_ERR_STATE, a row with eta == 0 does not read the history.  Whatever sets or clears the context's flag (see mc_sample_step) sets
+ *   or clears every row's.  The tables travel through context-owned pinned staging and device tables [max_steps][B], allocated by the
+ *   first call of the mode; the call waits for the previous upload's event, never for the device.  Every argument is checked before
+ *   the first launch: a call refused for its arguments or the context's state changes nothing.  A launch failure (MC_ERR_HIP) in
+ *   tick k is not such a refusal: x_dev and the history have been advanced by ticks [0, k) and those ticks' row flags are kept.
+ * mc_denoise_rows: mc_denoise (full model, both decoded halves in out2_dev [2B,T,C], no combine) with row b at step_index_host[b].
+ * mc_ctx_set_condition_rows: mc_ctx_set_condition (the whole batch's text K/V are recomputed; at capacity factor 0 an unchanged row
+ *   keeps its bits), but only rows with fresh_host[b] != 0 lose their history flag.
+ * NOT in this mode: graph capture or replay (a context that holds a captured graph, or a capturing stream: MC_ERR_STATE), a seam table
+ * (MC_ERR_STATE), the inpaint and seeded steps (no rows entry). */
+int mc_sample_rows(mc_ctx* c, float* x_dev, int32_t num_ticks, const int32_t* step_index_host, const mc_step_coefs* coefs_host,
+                   const uint64_t* draw_host, const float* noise_dev, float* x0_dev, void* stream);
+int mc_denoise_rows(mc_ctx* c, const float* x_t_dev, const int32_t* step_index_host, float* out2_dev, void* stream);
+int mc_ctx_set_condition_rows(mc_ctx* c, const float* xf_out_dev, const float* mask_dev, const uint8_t* fresh_host, void* stream);
+
 /* hipGraph replay of mc_sample_step (BASELINE.json configs[4] "hipGraph-captured 50-step DDIM"): ONE graph serves every step
  * of the schedule -- the step index is a device-side integer, the FiLM tables and the sampler coefficients are addressed
  * with it inside the kernels, no host sync or per-step H2D copy (SURVEY.md section 3.1 lists the reference's per-step
@@ -437,6 +462,18 @@ int mc_op_sampler_update(const float* x_t_dev, const float* out_text_dev, const 
  * x0_dev may be NULL.  coefs->mode must be MC_SAMPLER_MULTISTEP. */
 int mc_op_sampler_multistep(const float* x_t_dev, const float* out_text_dev, const float* out_none_dev, float* x0_hist_dev,
                             float* x_prev_dev, float* x0_dev, int64_t n, const mc_step_coefs* coefs, void* stream);
+/* The per-row kernel forms of mc_sample_rows without a context (both synchronise; coefs_host [B] is one entry per request row).
+ * mc_op_gemm_tail_rows: mc_op_gemm_tail with (wc, wu) of row r = coefs_host[r / T].{text_coef, none_coef}; M % T == 0, B = M / T.
+ *   variant 1 = gemm_tail_k, 2 = gemm_tail2_k, 3 = the small-batch form (axpby_pair_rows_k, then the grouped 64 x 64 GEMM); c2_dev
+ *   [M][N] scratch for variants 2 and 3.
+ * mc_op_sampler_rows: the update of [B][TC] with element e under coefs_host[e / TC] (one mode for all rows), x0 = out_text + out_none
+ *   (the two partial products of the folded tail).  Modes 0 / 1 read noise_dev; mode 2 has x0_hist_dev in-out (read where the row's
+ *   eta != 0).  Operands that are not all 16-byte aligned take the element form of the kernel. */
+int mc_op_gemm_tail_rows(const float* h_dev, const float* a_dev, const float* w_dev, const float* bias_dev, float* c_dev, float* c2_dev,
+                         int32_t M, int32_t N, int32_t K, const mc_step_coefs* coefs_host, int32_t T, int32_t variant, void* stream);
+int mc_op_sampler_rows(const float* x_t_dev, const float* out_text_dev, const float* out_none_dev, const float* noise_dev,
+                       float* x0_hist_dev, float* x_prev_dev, float* x0_dev, int32_t B, int32_t TC, const mc_step_coefs* coefs_host,
+                       void* stream);
 /* the seam-coupled update without a context (see mc_ctx_set_seams for the plan rules and the blend): operands [B, T, C], any mode.
  * Modes 0 / 1: the noise is read from noise_dev, or with noise_dev == NULL drawn from the Philox stream (seed, draw) -- mutually
  * exclusive: seed and draw must be 0 beside a noise tensor.  Mode 2: x0_hist_dev in-out as in mc_op_sampler_multistep (unused, may

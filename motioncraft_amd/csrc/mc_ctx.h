@@ -141,6 +141,18 @@ struct mc_ctx {
     bool keep_all = false;      // set by mc_ctx_set_capacity_factor(0) only: a MODEL whose own factor is 0 keeps today's meaning (capacity 0)
     uint64_t* row_seeds = nullptr;
     bool row_seeds_set = false;
+    // per-row schedules (mc_sample_rows / mc_denoise_rows).  rows_mode is set for the launches of one tick only:
+    // film_block, denoise_combined and sampler_update then hand `rowtab` (the tick's slices of the device tables) to the same kernel
+    // forms they pick anyway.  The tables [maxS][B] and their pinned staging are allocated by the first call of the mode; rs_ev is
+    // recorded behind every upload, so the next call waits for that copy alone before it rewrites the staging.
+    bool rows_mode = false;
+    RowTab rowtab;
+    int* rs_step = nullptr;
+    SamplerCoefs* rs_coefs = nullptr;
+    uint64_t* rs_draw = nullptr;
+    void* rs_stage = nullptr;           // pinned: [maxS][B] ints | SamplerCoefs | uint64
+    hipEvent_t rs_ev = nullptr;
+    std::vector<uint8_t> hist_rows;     // multistep "history valid" per request row (all cleared / set wherever hist_valid is)
     int prec = MC_PREC_F32;     // MFMA operand precision of the per-step GEMM-shaped kernels (mc_ctx_set_precision)
     int* cap_idx = nullptr;      // [NL][2N] routing capture (tests): expert ids ...
     float* cap_w = nullptr;      // ... and combine weights (0 = dropped) of every layer
@@ -154,6 +166,9 @@ int dense(const mc_ctx* c, const float* A, long lda, const float* W, long ldw, c
           float* C, long ldc, long M, int N, int K, int act, hipStream_t s);
 int run_moe(mc_ctx* c, const MoeW& w, const float* z, long Ntok, float* out, long ldout, bool gated, bool twin, long gsplit,
             hipStream_t s, const HalfW* hw, const HalfW* hw2);
+// the multistep history flags: the context's one and every request row's move together wherever an entry of the uniform mode sets or
+// clears the flag (mc_sample_rows / mc_ctx_set_condition_rows work on single rows)
+inline void hist_set(mc_ctx* c, bool valid) { c->hist_valid = valid; c->hist_rows.assign((size_t)c->B, valid ? 1 : 0); }
 inline float* deferred_a(const mc_ctx* c) { return c->a_tail ? c->a_tail : c->a; }      // where the deferred last FiLM block's fp32 rows live
 bool a_holds_planes(const mc_ctx* c);
 int denoise_impl(mc_ctx* c, const float* x_t, int32_t step, float* out2_dev, int32_t stop_after, void* stream, const SeedArgs* seed);

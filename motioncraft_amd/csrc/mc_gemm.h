@@ -98,10 +98,14 @@ struct TailArgs {
     long ldc = 0;
     int M = 0, N = 0, K = 0;        // K per group
     float wc = 1.f, wu = 0.f;       // CFG weights ...
+    int rows_T = 0;                 // ... or (mc_sample_rows, rows_T > 0: the ROWS instantiations) per request row: A row r takes
+                                    // coef_table[((r / rows_T) % rows_B) * coef_stride + {0, 1}], step_ptr null
     const float* coef_table = nullptr;   // ... or (graph replay) read from coef_table[*step_ptr * coef_stride + {0, 1}]
     const int* step_ptr = nullptr;
     long coef_stride = 0;
     int tune = -1;                  // kTune* bits; every caller sets them (>= 0)
+    int rows_B = 0;
 };
+static_assert(sizeof(TailArgs) == 152, "TailArgs: rows_T / rows_B fill the two padding words; the default kernels' argument offsets stay put");
 int mc_launch_gemm_tail(const TailArgs& g, hipStream_t stream);
 bool mc_gemm_tail_two_outputs(const TailArgs& g);      // true: this launch writes the two partial products C and C2 (x0 = C + C2), else C alone

@@ -837,7 +837,11 @@ __device__ __forceinline__ void vm_wait(int n) {
     }
 }
 
-template <int NBLK>
+// ROWS (mc_sample_rows): the CFG weights per request row -- A slab row r takes coef_table[((min(r, M - 1) / rows_T)
+// % rows_B) coef_stride + {0, 1}].  A thread's slab rows are fixed before the k-loop, so its two pairs are fetched once (tracked loads, landed
+// before the first counted load is issued: the hand-counted waits see the queue they were counted for) and the loop keeps its shape.
+// ROWS = false is the kernel as it was (TailArgs keeps its size and offsets: rows_T / rows_B sit in its two padding words).
+template <int NBLK, bool ROWS = false>
 __global__ __launch_bounds__(256) void gemm_tail_k(TailArgs g) {
     constexpr int NB = 16 * NBLK, NWP = NB / 8;
     constexpr int STAGE = (SM + NB) * BK;
@@ -849,7 +853,7 @@ __global__ __launch_bounds__(256) void gemm_tail_k(TailArgs g) {
     const int row0 = tm * SM;
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
     float wc = g.wc, wu = g.wu;
-    if (g.coef_table) { wc = g.coef_table[(long)*g.step_ptr * g.coef_stride]; wu = g.coef_table[(long)*g.step_ptr * g.coef_stride + 1]; }
+    if (!ROWS && g.coef_table) { wc = g.coef_table[(long)*g.step_ptr * g.coef_stride]; wu = g.coef_table[(long)*g.step_ptr * g.coef_stride + 1]; }
     // A slab slots of this thread: (row, 16-byte position) = ((tid + 256 j) >> 3, (tid + 256 j) & 7); position p of row r holds chunk p ^ (r & 7)
     long aoff[2];
     int alds[2];
@@ -858,6 +862,16 @@ __global__ __launch_bounds__(256) void gemm_tail_k(TailArgs g) {
         const int i = tid + 256 * j, row = i >> 3, pos = i & 7;
         aoff[j] = (long)min(row0 + row, g.M - 1) * g.lda + ((pos ^ (row & 7)) << 2);
         alds[j] = row * BK + (pos << 2);
+    }
+    float wcr[2] = {wc, wc}, wur[2] = {wu, wu};
+    if constexpr (ROWS) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const long rb = (min(row0 + ((tid + 256 * j) >> 3), g.M - 1) / g.rows_T) % g.rows_B;
+            wcr[j] = g.coef_table[rb * g.coef_stride];
+            wur[j] = g.coef_table[rb * g.coef_stride + 1];
+        }
+        asm volatile("" : "+v"(wcr[0]), "+v"(wcr[1]), "+v"(wur[0]), "+v"(wur[1]));
     }
     const int dr = lane >> 3, dc = ((lane & 7) ^ dr) * 4;
     constexpr int MAXW = (NWP + 3) / 4;
@@ -881,7 +895,7 @@ __global__ __launch_bounds__(256) void gemm_tail_k(TailArgs g) {
         for (int j = 0; j < 2; ++j) {
             f32x4 v;
 #pragma unroll
-            for (int i = 0; i < 4; ++i) v[i] = wc * c[j][i] + wu * u[j][i];
+            for (int i = 0; i < 4; ++i) v[i] = wcr[j] * c[j][i] + wur[j] * u[j][i];
             *reinterpret_cast<f32x4*>(St + alds[j]) = v;
         }
     };
@@ -980,7 +994,7 @@ constexpr int T2_WROW0 = 16 * T2_MAXRT;                                 // first
 
 __device__ __forceinline__ int t2_swz(int row) { return (0x78 >> (2 * ((row >> 2) & 3))) & 3; }      // F = {0, 2, 3, 1}, two bits each: 0b01111000 >> {0, 2, 4, 6}
 
-template <int NBW>        // blocks per wave handled by the static part (a wave's piece has <= NBW + 1 blocks)
+template <int NBW, bool ROWS = false>        // blocks per wave handled by the static part (a wave's piece has <= NBW + 1 blocks); ROWS: as in gemm_tail_k
 __global__ __launch_bounds__(256, 2) void gemm_tail2_k(TailArgs g, int ncb, long nblocks) {
     static_assert(NBW % 4 == 0 && NBW >= 4 && NBW <= 16, "NBW");
     constexpr int PH = 4;                                                // blocks per fragment phase (8 spills address registers at NBW = 16, and spill reloads share the vmcnt queue)
@@ -988,7 +1002,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tail2_k(TailArgs g, int ncb, long
     const int tid = threadIdx.x, lane = tid & 63;
     const int qw = __builtin_amdgcn_readfirstlane(tid >> 6);
     float wc = g.wc, wu = g.wu;
-    if (g.coef_table) { wc = g.coef_table[(long)*g.step_ptr * g.coef_stride]; wu = g.coef_table[(long)*g.step_ptr * g.coef_stride + 1]; }
+    if (!ROWS && g.coef_table) { wc = g.coef_table[(long)*g.step_ptr * g.coef_stride]; wu = g.coef_table[(long)*g.step_ptr * g.coef_stride + 1]; }
     // workgroup -> (block range, K group); consecutive ranges (neighbouring rows) share an XCD's L2
     const int G = gridDim.x >> 1, rid = xcd_remap((int)blockIdx.x, (int)gridDim.x);
     const int wg = rid >> 1, grp = rid & 1;
@@ -1024,6 +1038,18 @@ __global__ __launch_bounds__(256, 2) void gemm_tail2_k(TailArgs g, int ncb, long
         a_go[j] = grow * g.lda + ((pos ^ t2_swz(row)) << 2);
         a_lds[j] = row * T2_BK + (pos << 2);
     }
+    float wcr[2] = {wc, wc}, wur[2] = {wu, wu};
+    if constexpr (ROWS) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            long grow = (long)rt_first * 16 + ((tid + 256 * j) >> 2);
+            if (grow > g.M - 1) grow = g.M - 1;
+            const long rb = (grow / g.rows_T) % g.rows_B;
+            wcr[j] = g.coef_table[rb * g.coef_stride];
+            wur[j] = g.coef_table[rb * g.coef_stride + 1];
+        }
+        asm volatile("" : "+v"(wcr[0]), "+v"(wcr[1]), "+v"(wur[0]), "+v"(wur[1]));
+    }
     const int nslot = (qw < nrt ? 1 : 0) + ((4 + qw) < nrt ? 1 : 0);                           // slots of this wave's threads (uniform): 64 slots per row tile
     const int na = 2 * nslot;
     // ---- W DMA: piece p = rows [16 p, 16 p + 16) of the group's weight, pieces qw, qw + 4, ... of this wave ----
@@ -1055,7 +1081,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tail2_k(TailArgs g, int ncb, long
             if (j < nslot) {
                 f32x4 v;
 #pragma unroll
-                for (int i = 0; i < 4; ++i) v[i] = wc * c[j][i] + wu * u[j][i];
+                for (int i = 0; i < 4; ++i) v[i] = wcr[j] * c[j][i] + wur[j] * u[j][i];
                 *reinterpret_cast<f32x4*>(St + a_lds[j]) = v;
             }
     };
@@ -1281,7 +1307,8 @@ bool mc_gemm_tail_two_outputs(const TailArgs& g) { return tail2_grid(g, g.tune, 
 static int tail_kernels_scratch_free() {
     static const int verdict = [] {
         const void* fns[] = {(const void*)gemm_tail_k<3>, (const void*)gemm_tail2_k<4>, (const void*)gemm_tail2_k<8>, (const void*)gemm_tail2_k<12>,
-                             (const void*)gemm_tail2_k<16>};
+                             (const void*)gemm_tail2_k<16>, (const void*)gemm_tail_k<3, true>, (const void*)gemm_tail2_k<4, true>,
+                             (const void*)gemm_tail2_k<8, true>, (const void*)gemm_tail2_k<12, true>, (const void*)gemm_tail2_k<16, true>};
         for (const void* f : fns) {
             hipFuncAttributes at;
             if (hipFuncGetAttributes(&at, f) != hipSuccess) return -1;
@@ -1301,6 +1328,8 @@ int mc_launch_gemm_tail(const TailArgs& g, hipStream_t stream) {
                "gemm_tail: unsupported shape (M=%d N=%d K=%d)", g.M, g.N, g.K);
     if (g.M <= 0 || g.N <= 0) return MC_OK;
     MC_REQUIRE((long)g.N * g.ldw * 4 < (1L << 32), "gemm_tail: weight beyond 4 GB");
+    const bool rows = g.rows_T > 0;      // per-row CFG weights: the same kernel forms over the same grids, ROWS instantiations
+    MC_REQUIRE(!rows || (g.coef_table && g.rows_B > 0 && g.coef_stride >= 2 && !g.step_ptr), "gemm_tail: per-row weights need a table, B, a stride and no graph step");
     TailArgs gg = g;
     // tune bit 10 (round 5): the block-range form, A read once, one partial product per K group (gemm_tail2_k)
     int per_wave = 0;
@@ -1309,7 +1338,13 @@ int mc_launch_gemm_tail(const TailArgs& g, hipStream_t stream) {
         const long nblocks = (long)cdiv(g.M, 16) * ncb;
         dim3 grid(2 * G);                      // (range, K group)
         MC_LEDGER("gemm_tail2_k", grid, 2.0 * g.M * g.N * g.K * 2);      // both K groups
-        if (per_wave <= 5) hipLaunchKernelGGL((gemm_tail2_k<4>), grid, dim3(256), 0, stream, gg, ncb, nblocks);
+        if (rows) {
+            if (per_wave <= 5) hipLaunchKernelGGL((gemm_tail2_k<4, true>), grid, dim3(256), 0, stream, gg, ncb, nblocks);
+            else if (per_wave <= 9) hipLaunchKernelGGL((gemm_tail2_k<8, true>), grid, dim3(256), 0, stream, gg, ncb, nblocks);
+            else if (per_wave <= 13) hipLaunchKernelGGL((gemm_tail2_k<12, true>), grid, dim3(256), 0, stream, gg, ncb, nblocks);
+            else hipLaunchKernelGGL((gemm_tail2_k<16, true>), grid, dim3(256), 0, stream, gg, ncb, nblocks);
+        }
+        else if (per_wave <= 5) hipLaunchKernelGGL((gemm_tail2_k<4>), grid, dim3(256), 0, stream, gg, ncb, nblocks);
         else if (per_wave <= 9) hipLaunchKernelGGL((gemm_tail2_k<8>), grid, dim3(256), 0, stream, gg, ncb, nblocks);
         else if (per_wave <= 13) hipLaunchKernelGGL((gemm_tail2_k<12>), grid, dim3(256), 0, stream, gg, ncb, nblocks);
         else hipLaunchKernelGGL((gemm_tail2_k<16>), grid, dim3(256), 0, stream, gg, ncb, nblocks);
@@ -1318,7 +1353,8 @@ int mc_launch_gemm_tail(const TailArgs& g, hipStream_t stream) {
     }
     dim3 grid(cdiv(g.M, SM) * cdiv(g.N, 48));
     MC_LEDGER("gemm_tail_k", grid, 2.0 * g.M * g.N * g.K * 2);
-    hipLaunchKernelGGL((gemm_tail_k<3>), grid, dim3(256), 0, stream, gg);
+    if (rows) hipLaunchKernelGGL((gemm_tail_k<3, true>), grid, dim3(256), 0, stream, gg);
+    else hipLaunchKernelGGL((gemm_tail_k<3>), grid, dim3(256), 0, stream, gg);
     MC_LAUNCH_CHECK();
     return MC_OK;
 }

@@ -23,10 +23,13 @@ struct StepRef {
     const int* ptr = nullptr;
     long stride = 0;             // floats per step of the table behind the pointer argument
 };
+// rt (mc_sample_rows): every row at the schedule index of its request row, rt->step[((row0 + r) / rt->T) % rt->B], `ss` = the table's
+// row of index 0 (film_rows_k<FilmRowSteps>; null: the default instantiation)
+struct RowTab;
 int mc_launch_film_rows(const float* Y1, const float* Y2, const float* gamma, const float* beta,
                         const float* ss, float* A, long rows, int D, hipStream_t s, TwinAlias y1_alias = TwinAlias(), long row0 = 0,
                         StepRef step = StepRef(), int y1_parts = 1, long y1_pstride = 0,    // y1_parts > 1: Y1 = sum of that many partial planes
-                        int planes = 0, long plane_stride = 0);   // planes 1 / 2: A is written as fp16 plane(s) [rows][D] halves (hi | lo plane_stride halves behind) for gemm_hd_k; + 4: FRAGMENT-MAJOR planes for gemm_hf_k (rows % 32 == 0)
+                        int planes = 0, long plane_stride = 0, const RowTab* rt = nullptr);   // planes 1 / 2: A is written as fp16 plane(s) [rows][D] halves (hi | lo plane_stride halves behind) for gemm_hd_k; + 4: FRAGMENT-MAJOR planes for gemm_hf_k (rows % 32 == 0)
 // te[s][0:D] = cat(cos(t_s f), sin(t_s f))
 int mc_launch_timestep_embedding(const int* t_orig, float* te, int S, int D, hipStream_t s);
 int mc_launch_silu(const float* X, float* Y, long n, hipStream_t s);
@@ -53,6 +56,9 @@ struct PadOut { float* xpad = nullptr; int C = 0, Cp = 0; };
 // rows (with rng, noise == nullptr): every row of TC elements draws from its own stream -- key keys[2 b] | keys[2 b + 1] << 32, counter
 // (row-local element / 4, draw index); rng's seed is ignored (mc_ctx_set_row_seeds)
 struct RowKeys { const uint32_t* keys = nullptr; int TC = 0; };
+// Per-row schedules (mc_sample_rows): device tables of one tick -- step[B] schedule indices, coefs[B], draw[B]
+// Philox draw numbers (read only with in-kernel noise).  Row r of a [B T]- or [2 B T]-row operand belongs to request row (r / T) % B.
+struct RowTab { const int* step = nullptr; const SamplerCoefs* coefs = nullptr; const uint64_t* draw = nullptr; int B = 0, T = 0; };
 int mc_launch_sampler_update(const float* x_t, const float* out_text, const float* out_none,
                              const float* noise, float* x_prev, float* x0_out, long n,
                              SamplerCoefs c, hipStream_t s, const SamplerCoefs* table = nullptr, const int* step_ptr = nullptr,
@@ -62,6 +68,15 @@ int mc_launch_sampler_update(const float* x_t, const float* out_text, const floa
 int mc_launch_sampler_multistep(const float* x_t, const float* out_text, const float* out_none, float* x0_hist, float* x_prev,
                                 float* x0_out, long n, SamplerCoefs c, hipStream_t s, const SamplerCoefs* table = nullptr,
                                 const int* step_ptr = nullptr, const PadOut* pad = nullptr);
+// The two updates with the coefficients of element e from rt.coefs[e / TC] (modes 0 / 1, or mode 2: one mode per launch, the caller
+// checks); x0 = tc out_text + nc out_none.  noise == nullptr: drawn in the kernel from the rows' keys at draw rt.draw[row].  A flat
+// group of four that straddles two rows takes each element's own row's entry.
+int mc_launch_sampler_update_rows(const float* x_t, const float* out_text, const float* out_none, const float* noise, float* x_prev,
+                                  float* x0_out, long n, float tc, float nc, const RowTab& rt, int TC, hipStream_t s,
+                                  const RowKeys* keys = nullptr, const PadOut* pad = nullptr);
+int mc_launch_sampler_multistep_rows(const float* x_t, const float* out_text, const float* out_none, float* x0_hist, float* x_prev,
+                                     float* x0_out, long n, float tc, float nc, const RowTab& rt, int TC, hipStream_t s,
+                                     const PadOut* pad = nullptr);
 // Seam-coupled update of B windows [B][T][C] (sampler_seam_k, all three modes): flags [B] ints on the device, bit 0 = the row shares
 // its first `ov` frames with the last `ov` of row b - 1, bit 1 = its last `ov` with the first of row b + 1 (the caller guarantees bit 1
 // of row b goes with bit 0 of row b + 1 and is clear on row B - 1); w [ov] = the right window's weight per shared frame; 0 < 2 ov <= T.
@@ -113,6 +128,10 @@ int mc_launch_axpby(const float* x, const float* y, float a, float b, float* out
 // out0 = a x0 + b y0 and out1 = a x1 + b y1 in one launch; table != null: (a, b) = table[*step_ptr].{text_coef, none_coef}
 int mc_launch_axpby_pair(const float* x0, const float* y0, float* out0, const float* x1, const float* y1, float* out1, float a, float b,
                          const SamplerCoefs* table, const int* step_ptr, long n, hipStream_t s);
+// the two combines over rows of D floats with (a, b) = rt.coefs[(row / rt.T) % rt.B].{text_coef, none_coef}
+int mc_launch_axpby_rows(const float* x, const float* y, const RowTab& rt, int D, float* out, long n, hipStream_t s);
+int mc_launch_axpby_pair_rows(const float* x0, const float* y0, float* out0, const float* x1, const float* y1, float* out1, const RowTab& rt,
+                              int D, long n, hipStream_t s);
 
 // ---- mc_post.hip ----------------------------------------------------------------------
 // de-normalise + 322 -> (poses 165, expressions 100, trans 3) + Gaussian temporal filter (tools/visualize.py:217-246)

@@ -1,6 +1,7 @@
 // HBM-bound row kernels of the STMoGen denoiser (gfx950): LayerNorm rows, StylizationBlock
 // prologue (LN + FiLM + SiLU), timestep embedding, CFG-combine + DDPM/DDIM update.
 // All loads/stores are 16 B per lane, rows are reduced with wavefront shuffles (wave = 64).
+#include <type_traits>
 #include "mc_common.h"
 #include "mc_kernels.h"
 #include "mc_chain.h"
@@ -48,12 +49,20 @@ __global__ __launch_bounds__(256) void ln_rows_k(const float* __restrict__ X, lo
 // scale/shift = emb_layers(emb) are batch-invariant (same timestep for the whole batch) and
 // precomputed per (step, layer, block): ss[0:D] = scale, ss[D:2D] = shift.
 // ---------------------------------------------------------------------------------------
+// RS (mc_sample_rows): FilmOneStep -- the whole launch sits at one schedule index (the default: nothing is read,
+// the instruction stream of the kernel without the parameter); FilmRowSteps -- every row at the index of its request row,
+// step[((row0 + r) / T) % B] (sample b + B is the CFG twin of b), with `ss` the table's row of index 0: one scalar table load per wave.
+// `r` is the row this wave really works on (the fragment-major remap included); the twin alias only redirects the Y1 READ, the
+// row's own schedule index stays its own (a twin shares its original's entry anyway).
 constexpr int FILM_MAXC = 8;  // 8 float4 chunks x 64 lanes = 2048 channels
+struct FilmOneStep {};
+struct FilmRowSteps { const int* step; int B, T; long stride; };
+template <class RS = FilmOneStep>
 __global__ __launch_bounds__(256, 6) void film_rows_k(const float* __restrict__ Y1, const float* __restrict__ Y2,
                                                    const float* __restrict__ gamma, const float* __restrict__ beta,
                                                    const float* __restrict__ ss, float* __restrict__ A,
                                                    long rows, int D, TwinAlias y1_alias, long row0, StepRef step, int y1_parts,
-                                                   long y1_pstride, int planes, long plane_stride) {
+                                                   long y1_pstride, int planes, long plane_stride, RS rs) {
     extern __shared__ __attribute__((aligned(16))) _Float16 film_stage[];      // fragment-major mode only: [plane][4 rows][D + 8] halves
     if (step.ptr) ss += (long)(*step.ptr) * step.stride;
     const int lane = threadIdx.x & 63;
@@ -67,6 +76,11 @@ __global__ __launch_bounds__(256, 6) void film_rows_k(const float* __restrict__ 
         r = rb * 32 + (j & 7) * 4 + (threadIdx.x >> 6);
     }
     if (r >= rows) return;
+    if constexpr (std::is_same<RS, FilmRowSteps>::value) {
+        // (a wave holds one row: the index is wave-uniform -- 32-bit division on the scalar side, `ss` stays a scalar pointer)
+        const int rq = __builtin_amdgcn_readfirstlane((int)(((unsigned)(row0 + r) / (unsigned)rs.T) % (unsigned)rs.B));
+        ss += (long)rs.step[rq] * rs.stride;
+    }
     // CFG twin aliasing (base layer 0): Y1 rows that were not produced are read from their twin
     long r1 = r;
     if (y1_alias.split_flag && row0 + r >= y1_alias.from && *y1_alias.split_flag == 0) r1 = r - y1_alias.from;
@@ -423,6 +437,143 @@ __global__ __launch_bounds__(256) void sampler_multistep_k(const float* x_t, con
     }
 }
 
+// ---- per-row schedules (mc_sample_rows) ----
+// Every request row b of [B][TC] walks its own schedule: element e takes coefs[e / TC], and under a seed table draw number draw[e / TC]
+// (key keys[b], counter (row-local element / 4, draw[b])).  Kernels of their own beside sampler_update_k / sampler_multistep_k (whose
+// instruction streams stay put) over the SAME device functions, flat groups of four, VEC rule and PadOut, so that equal entries in
+// every row give the uniform kernels' bits.  A group that straddles two rows (TC % 4 != 0) goes on in the next row's coefficients from
+// its first element there: every element takes its own row's, the rule philox_rows4 follows for keys.
+// text_coef / none_coef of an entry are the CFG weights of the decoder tail in front (RowTab::coefs); here x0 arrives combined, as one
+// array or two partial products, so the two weights are the launch's (tc, nc) like in the graph-table form.
+__device__ __forceinline__ SamplerCoefs row_coefs(const SamplerCoefs* __restrict__ tab, long b, float tc, float nc) {
+    SamplerCoefs c = tab[b];
+    c.text_coef = tc; c.none_coef = nc;
+    return c;
+}
+// philox_rows4 with the draw number per row
+__device__ __forceinline__ f32x4 philox_rows4d(long i, long n, RowKeys rk, const uint64_t* __restrict__ draw) {
+    long b = i / rk.TC;
+    int r = (int)(i - b * rk.TC);
+    RngArgs rng;
+    f32x4 z = {0.f, 0.f, 0.f, 0.f}, cur = z;
+    long cb = -1;
+    int cc = -1;
+    for (int j = 0; j < 4 && i + j < n; ++j) {
+        if (b != cb || (r >> 2) != cc) {
+            cb = b; cc = r >> 2;
+            rng.seed_lo = rk.keys[2 * b]; rng.seed_hi = rk.keys[2 * b + 1];
+            rng.draw_lo = (uint32_t)draw[b]; rng.draw_hi = (uint32_t)(draw[b] >> 32);
+            cur = philox_normal4(cc, rng);
+        }
+        const int l = r & 3;
+        z[j] = l == 0 ? cur[0] : l == 1 ? cur[1] : l == 2 ? cur[2] : cur[3];
+        if (++r == rk.TC) { r = 0; ++b; }
+    }
+    return z;
+}
+
+template <bool RNG, bool VEC>
+__global__ __launch_bounds__(256) void sampler_update_rows_k(const float* x_t, const float* __restrict__ o_text,
+                                                             const float* __restrict__ o_none, const float* __restrict__ noise,
+                                                             float* x_prev, float* __restrict__ x0_out, long n, float tc, float nc,
+                                                             const SamplerCoefs* __restrict__ tab, RowKeys rk,
+                                                             const uint64_t* __restrict__ draw, PadOut po) {
+    const long ngroups = (n + 3) >> 2;
+    for (long gi = (long)blockIdx.x * blockDim.x + threadIdx.x; gi < ngroups; gi += (long)gridDim.x * blockDim.x) {
+        const long i = gi * 4;
+        long b = i / rk.TC;
+        int r = (int)(i - b * rk.TC);
+        SamplerCoefs c = row_coefs(tab, b, tc, nc);
+        SamplerDerived d = sampler_derive(c);
+        f32x4 nz = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (RNG) nz = philox_rows4d(i, n, rk, draw);
+        if (VEC && i + 4 <= n) {
+            const f32x4 x = *reinterpret_cast<const f32x4*>(x_t + i);
+            const f32x4 a = *reinterpret_cast<const f32x4*>(o_text + i), bb = *reinterpret_cast<const f32x4*>(o_none + i);
+            if constexpr (!RNG) nz = *reinterpret_cast<const f32x4*>(noise + i);
+            f32x4 out, x0v;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                x0v[j] = cfg_elem(a[j], bb[j], c);
+                out[j] = sampler_elem(x[j], x0v[j], nz[j], c, d);
+                if (j < 3 && ++r == rk.TC) { r = 0; ++b; c = row_coefs(tab, b, tc, nc); d = sampler_derive(c); }
+            }
+            *reinterpret_cast<f32x4*>(x_prev + i) = out;
+            if (x0_out) *reinterpret_cast<f32x4*>(x0_out + i) = x0v;
+            if (po.xpad) {
+                long row = i / po.C;
+                int col = (int)(i - row * po.C);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    po.xpad[row * po.Cp + col] = out[j];
+                    if (++col == po.C) { col = 0; ++row; }
+                }
+            }
+        } else {
+            for (int j = 0; j < 4 && i + j < n; ++j) {
+                const float x0 = cfg_elem(o_text[i + j], o_none[i + j], c);
+                const float z = RNG ? nz[j] : noise[i + j];
+                const float o = sampler_elem(x_t[i + j], x0, z, c, d);
+                x_prev[i + j] = o;
+                if (x0_out) x0_out[i + j] = x0;
+                if (po.xpad) po.xpad[(i + j) / po.C * po.Cp + (i + j) % po.C] = o;
+                if (i + j + 1 < n && ++r == rk.TC) { r = 0; ++b; c = row_coefs(tab, b, tc, nc); d = sampler_derive(c); }
+            }
+        }
+    }
+}
+
+// mode 2 per row: kx, k0, k1 of the element's row; the history is read only where the row's k1 != 0 (a row's first step meets whatever
+// the buffer holds there, and 0 x NaN would be NaN)
+template <bool VEC>
+__global__ __launch_bounds__(256) void sampler_multistep_rows_k(const float* x_t, const float* __restrict__ o_text,
+                                                                const float* __restrict__ o_none, float* __restrict__ hist,
+                                                                float* x_prev, float* __restrict__ x0_out, long n, float tc, float nc,
+                                                                const SamplerCoefs* __restrict__ tab, int TC, PadOut po) {
+    const long ngroups = (n + 3) >> 2;
+    for (long gi = (long)blockIdx.x * blockDim.x + threadIdx.x; gi < ngroups; gi += (long)gridDim.x * blockDim.x) {
+        const long i = gi * 4;
+        long b = i / TC;
+        int r = (int)(i - b * TC);
+        SamplerCoefs c = row_coefs(tab, b, tc, nc);
+        if (VEC && i + 4 <= n) {
+            const f32x4 x = *reinterpret_cast<const f32x4*>(x_t + i);
+            const f32x4 a = *reinterpret_cast<const f32x4*>(o_text + i), bb = *reinterpret_cast<const f32x4*>(o_none + i);
+            const f32x4 hv = *reinterpret_cast<const f32x4*>(hist + i);
+            f32x4 out, x0v;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                x0v[j] = cfg_elem(a[j], bb[j], c);
+                out[j] = multistep_elem(x[j], x0v[j], c.eta != 0.f ? hv[j] : 0.f, c.c2, c.c1, c.eta);
+                if (j < 3 && ++r == TC) { r = 0; ++b; c = row_coefs(tab, b, tc, nc); }
+            }
+            *reinterpret_cast<f32x4*>(x_prev + i) = out;
+            *reinterpret_cast<f32x4*>(hist + i) = x0v;
+            if (x0_out) *reinterpret_cast<f32x4*>(x0_out + i) = x0v;
+            if (po.xpad) {
+                long row = i / po.C;
+                int col = (int)(i - row * po.C);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    po.xpad[row * po.Cp + col] = out[j];
+                    if (++col == po.C) { col = 0; ++row; }
+                }
+            }
+        } else {
+            for (int j = 0; j < 4 && i + j < n; ++j) {
+                const float x0 = cfg_elem(o_text[i + j], o_none[i + j], c);
+                const float hp = c.eta != 0.f ? hist[i + j] : 0.f;
+                const float o = multistep_elem(x_t[i + j], x0, hp, c.c2, c.c1, c.eta);
+                x_prev[i + j] = o;
+                hist[i + j] = x0;
+                if (x0_out) x0_out[i + j] = x0;
+                if (po.xpad) po.xpad[(i + j) / po.C * po.Cp + (i + j) % po.C] = o;
+                if (i + j + 1 < n && ++r == TC) { r = 0; ++b; c = row_coefs(tab, b, tc, nc); }
+            }
+        }
+    }
+}
+
 // Seam-coupled update (window-parallel long sequences): the batch rows are windows of T frames; rows b and b + 1
 // flagged as neighbours share `ov` frames -- frames [T - ov, T) of b (its tail) are frames [0, ov) of b + 1 (its head).  A seam element
 //   x0 = w[f] x0_right + (1 - w[f]) x0_left;   x_prev = update(x_left, x0, noise_left / hist_left)
@@ -684,6 +835,28 @@ __global__ __launch_bounds__(256) void axpby_pair_k(AxpbySet s0, AxpbySet s1, fl
         s.out[i] = a * s.x[i] + b * s.y[i];
 }
 
+// The two combines with the CFG weights per request row (mc_sample_rows): element i lies in row i / D of [B T][D], request row
+// (i / D / T) % B, and takes coefs[that].{text_coef, none_coef}.  The expressions are those of axpby_k / axpby_pair_k.
+__device__ __forceinline__ long cfg_row(long i, int D, int T, int B) { return (i / D / T) % B; }
+__global__ __launch_bounds__(256) void axpby_rows_k(const float* __restrict__ x, const float* __restrict__ y,
+                                                    const SamplerCoefs* __restrict__ coefs, int D, int T, int B,
+                                                    float* __restrict__ out, long n) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const long rb = cfg_row(i, D, T, B);
+        const float a = coefs[rb].text_coef, b = coefs[rb].none_coef;
+        out[i] = a * x[i] + b * y[i];
+    }
+}
+__global__ __launch_bounds__(256) void axpby_pair_rows_k(AxpbySet s0, AxpbySet s1, const SamplerCoefs* __restrict__ coefs, int D, int T,
+                                                         int B, long n) {
+    const AxpbySet s = blockIdx.y ? s1 : s0;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const long rb = cfg_row(i, D, T, B);
+        const float a = coefs[rb].text_coef, b = coefs[rb].none_coef;
+        s.out[i] = a * s.x[i] + b * s.y[i];
+    }
+}
+
 __global__ void set_int_k(int* dst, int value) { *dst = value; }
 // tests only: hold a stream for `ticks` of the 100 MHz s_memtime counter (one lane; mc_ctx_set_option("dbg_delay_us"))
 __global__ void spin_k(long ticks) {
@@ -707,15 +880,20 @@ int mc_launch_ln_rows(const float* X, long ldx, int x_col, const float* gamma, c
 
 int mc_launch_film_rows(const float* Y1, const float* Y2, const float* gamma, const float* beta,
                         const float* ss, float* A, long rows, int D, hipStream_t s, TwinAlias y1_alias, long row0, StepRef step,
-                        int y1_parts, long y1_pstride, int planes, long plane_stride) {
+                        int y1_parts, long y1_pstride, int planes, long plane_stride, const RowTab* rt) {
     MC_REQUIRE(D % 4 == 0 && D <= FILM_MAXC * 256, "film_rows: unsupported D=%d", D);
     MC_REQUIRE(planes >= 0 && (planes & 3) <= 2 && (planes & ~7) == 0 && (!(planes & 4) || ((planes & 3) != 0 && rows % 32 == 0 && D % 16 == 0)),
                "film_rows: planes=%d (rows=%ld D=%d)", planes, rows, D);
     if (rows <= 0) return MC_OK;
     const long nwg = (planes & 4) ? (long)cdiv(rows / 32, 8) * 64 : (long)cdiv(rows, 4);
     const size_t lds = (planes & 4) ? (size_t)(planes & 3) * 4 * (D + 8) * 2 : 0;
-    hipLaunchKernelGGL(film_rows_k, dim3((unsigned)nwg), dim3(256), lds, s, Y1, Y2, gamma, beta, ss, A, rows, D, y1_alias, row0, step,
-                       y1_parts < 1 ? 1 : y1_parts, y1_pstride, planes, plane_stride);
+    if (rt) {        // per-row schedule indices: `ss` is the table's row of index 0
+        MC_REQUIRE(rt->step && rt->B > 0 && rt->T > 0 && !step.ptr, "film_rows: row steps need a table, B, T and no graph step");
+        hipLaunchKernelGGL((film_rows_k<FilmRowSteps>), dim3((unsigned)nwg), dim3(256), lds, s, Y1, Y2, gamma, beta, ss, A, rows, D, y1_alias, row0, step,
+                           y1_parts < 1 ? 1 : y1_parts, y1_pstride, planes, plane_stride, FilmRowSteps{rt->step, rt->B, rt->T, 2L * D});
+    } else
+        hipLaunchKernelGGL((film_rows_k<FilmOneStep>), dim3((unsigned)nwg), dim3(256), lds, s, Y1, Y2, gamma, beta, ss, A, rows, D, y1_alias, row0, step,
+                           y1_parts < 1 ? 1 : y1_parts, y1_pstride, planes, plane_stride, FilmOneStep{});
     MC_LAUNCH_CHECK();
     return MC_OK;
 }
@@ -789,6 +967,67 @@ int mc_launch_sampler_multistep(const float* x_t, const float* out_text, const f
     MC_REQUIRE(!po.xpad || (po.C > 0 && po.Cp >= po.C), "multistep update: bad padded-copy shape");
     if (vec) hipLaunchKernelGGL((sampler_multistep_k<true>), dim3(blocks), dim3(256), 0, s, x_t, out_text, out_none, x0_hist, x_prev, x0_out, n, c, table, step_ptr, po);
     else hipLaunchKernelGGL((sampler_multistep_k<false>), dim3(blocks), dim3(256), 0, s, x_t, out_text, out_none, x0_hist, x_prev, x0_out, n, c, table, step_ptr, po);
+    MC_LAUNCH_CHECK();
+    return MC_OK;
+}
+
+// the per-row forms: the same vector rule, grids and PadOut checks as the two launchers above
+int mc_launch_sampler_update_rows(const float* x_t, const float* out_text, const float* out_none, const float* noise, float* x_prev,
+                                  float* x0_out, long n, float tc, float nc, const RowTab& rt, int TC, hipStream_t s, const RowKeys* keys,
+                                  const PadOut* pad) {
+    MC_REQUIRE(x_t && out_text && out_none && x_prev && rt.coefs && rt.B > 0 && TC > 0 && n == (long)rt.B * TC,
+               "row sampler update: %ld elements for %d rows of %d", n, rt.B, TC);
+    const bool dev_rng = !noise;
+    MC_REQUIRE(!dev_rng || (keys && keys->keys && keys->TC == TC && rt.draw), "row sampler update: no noise tensor, and no seed table / draw numbers");
+    const bool vec = ((uintptr_t)x_t | (uintptr_t)out_text | (uintptr_t)out_none | (uintptr_t)x_prev | (uintptr_t)x0_out | (uintptr_t)noise) % 16 == 0;
+    int blocks = cdiv((n + 3) / 4, 256);
+    if (blocks > 2048) blocks = 2048;
+    if (blocks < 1) blocks = 1;
+    const PadOut po = pad ? *pad : PadOut();
+    MC_REQUIRE(!po.xpad || (po.C > 0 && po.Cp >= po.C), "row sampler update: bad padded-copy shape");
+    const RowKeys rk{dev_rng ? keys->keys : nullptr, TC};
+#define MC_SUR(R, V) hipLaunchKernelGGL((sampler_update_rows_k<R, V>), dim3(blocks), dim3(256), 0, s, x_t, out_text, out_none, noise, x_prev, x0_out, n, tc, nc, rt.coefs, rk, rt.draw, po)
+    if (dev_rng) { if (vec) MC_SUR(true, true); else MC_SUR(true, false); }
+    else { if (vec) MC_SUR(false, true); else MC_SUR(false, false); }
+#undef MC_SUR
+    MC_LAUNCH_CHECK();
+    return MC_OK;
+}
+
+int mc_launch_sampler_multistep_rows(const float* x_t, const float* out_text, const float* out_none, float* x0_hist, float* x_prev,
+                                     float* x0_out, long n, float tc, float nc, const RowTab& rt, int TC, hipStream_t s, const PadOut* pad) {
+    MC_REQUIRE(x_t && out_text && out_none && x0_hist && x_prev && rt.coefs && rt.B > 0 && TC > 0 && n == (long)rt.B * TC,
+               "row multistep update: %ld elements for %d rows of %d", n, rt.B, TC);
+    MC_REQUIRE(x0_hist != x_t && x0_hist != x_prev && x0_hist != x0_out && x0_hist != out_text && x0_hist != out_none,
+               "row multistep update: the history buffer aliases another operand");
+    const bool vec = ((uintptr_t)x_t | (uintptr_t)out_text | (uintptr_t)out_none | (uintptr_t)x_prev | (uintptr_t)x0_out | (uintptr_t)x0_hist) % 16 == 0;
+    int blocks = cdiv((n + 3) / 4, 256);
+    if (blocks > 2048) blocks = 2048;
+    const PadOut po = pad ? *pad : PadOut();
+    MC_REQUIRE(!po.xpad || (po.C > 0 && po.Cp >= po.C), "row multistep update: bad padded-copy shape");
+    if (vec) hipLaunchKernelGGL((sampler_multistep_rows_k<true>), dim3(blocks), dim3(256), 0, s, x_t, out_text, out_none, x0_hist, x_prev, x0_out, n, tc, nc, rt.coefs, TC, po);
+    else hipLaunchKernelGGL((sampler_multistep_rows_k<false>), dim3(blocks), dim3(256), 0, s, x_t, out_text, out_none, x0_hist, x_prev, x0_out, n, tc, nc, rt.coefs, TC, po);
+    MC_LAUNCH_CHECK();
+    return MC_OK;
+}
+
+int mc_launch_axpby_rows(const float* x, const float* y, const RowTab& rt, int D, float* out, long n, hipStream_t s) {
+    MC_REQUIRE(rt.coefs && rt.B > 0 && rt.T > 0 && D > 0, "axpby rows: no coefficient table");
+    if (n <= 0) return MC_OK;
+    int blocks = cdiv(n, 256);
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(axpby_rows_k, dim3(blocks), dim3(256), 0, s, x, y, rt.coefs, D, rt.T, rt.B, out, n);
+    MC_LAUNCH_CHECK();
+    return MC_OK;
+}
+
+int mc_launch_axpby_pair_rows(const float* x0, const float* y0, float* out0, const float* x1, const float* y1, float* out1, const RowTab& rt,
+                              int D, long n, hipStream_t s) {
+    MC_REQUIRE(rt.coefs && rt.B > 0 && rt.T > 0 && D > 0, "axpby pair rows: no coefficient table");
+    if (n <= 0) return MC_OK;
+    int blocks = cdiv(n, 256);
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(axpby_pair_rows_k, dim3(blocks, 2), dim3(256), 0, s, AxpbySet{x0, y0, out0}, AxpbySet{x1, y1, out1}, rt.coefs, D, rt.T, rt.B, n);
     MC_LAUNCH_CHECK();
     return MC_OK;
 }

@@ -424,6 +424,8 @@ void mc_ctx_destroy(mc_ctx* c) {
         if (c->side_cand[k]) { (void)hipStreamSynchronize(c->side_cand[k]); (void)hipStreamDestroy(c->side_cand[k]); }
     for (hipEvent_t e : {c->ev_fork, c->ev_join, c->ev_side, c->ev_stag, c->ev_gate1, c->ev_sel, c->ev_front})
         if (e) (void)hipEventDestroy(e);
+    if (c->rs_ev) { (void)hipEventSynchronize(c->rs_ev); (void)hipEventDestroy(c->rs_ev); }
+    if (c->rs_stage) (void)hipHostFree(c->rs_stage);
     for (void* p : c->allocs) (void)hipFree(p);
     delete c;
 }
@@ -494,7 +496,7 @@ int mc_ctx_set_capacity_factor(mc_ctx* c, float cf) {
     c->keep_all = cf == 0.f;
     c->cap_factor = cf;
     c->have_cond = false;      // the hoisted text K/V were routed under the previous capacity: set the condition again
-    c->hist_valid = false;     // (multistep sampler: the previous x0 was predicted under it too)
+    hist_set(c, false);     // (multistep sampler: the previous x0 was predicted under it too)
     return MC_OK;
 }
 float mc_ctx_capacity_factor(const mc_ctx* c) { return c ? c->cap_factor : 0.f; }
@@ -543,7 +545,7 @@ int mc_ctx_enable_capture(mc_ctx* c) {
 int mc_ctx_set_timesteps(mc_ctx* c, const int32_t* t_orig_host, int32_t S, void* stream) {
     MC_REQUIRE(c && t_orig_host, "null argument");
     MC_REQUIRE(S >= 1 && S <= c->maxS, "num_steps=%d exceeds context max_steps=%d", S, c->maxS);
-    c->hist_valid = false;       // (multistep sampler: the previous x0 belongs to the old schedule)
+    hist_set(c, false);       // (multistep sampler: the previous x0 belongs to the old schedule)
     hipStream_t s = (hipStream_t)stream;
     const mc_model_config& g = c->m->cfg;
     const int D = g.latent_dim * g.num_parts, Te = g.time_embed_dim;
@@ -569,7 +571,7 @@ int mc_ctx_set_timesteps(mc_ctx* c, const int32_t* t_orig_host, int32_t S, void*
 // condition batch (the MoE capacity couples both halves, so both are routed together).
 int mc_ctx_set_condition(mc_ctx* c, const float* xf_out_dev, const float* mask_dev, void* stream) {
     MC_REQUIRE(c && xf_out_dev && mask_dev, "null argument");
-    c->hist_valid = false;       // (multistep sampler: the previous x0 belongs to the old condition)
+    hist_set(c, false);       // (multistep sampler: the previous x0 belongs to the old condition)
     hipStream_t s = (hipStream_t)stream;
     const mc_model_config& g = c->m->cfg;
     const int L = g.latent_dim, Dt = g.text_latent_dim, Nt = g.max_text_len;
@@ -592,7 +594,7 @@ int mc_ctx_set_condition(mc_ctx* c, const float* xf_out_dev, const float* mask_d
 // step-invariant, evaluated once per condition batch.
 int mc_ctx_set_control(mc_ctx* c, const float* c_feat_dev, int32_t Tc, void* stream) {
     MC_REQUIRE(c, "null context");
-    c->hist_valid = false;       // (multistep sampler: the previous x0 belongs to the old control condition)
+    hist_set(c, false);       // (multistep sampler: the previous x0 belongs to the old control condition)
     const mc_model_config& g = c->m->cfg;
     if (!c_feat_dev) { c->have_ctrl = false; return MC_OK; }
     MC_REQUIRE(g.num_ctrl_layers > 0, "the model has no control branch");
@@ -684,7 +686,7 @@ static int seam_refuse(const mc_ctx* c, const char* who) {
 int mc_ctx_set_seams(mc_ctx* c, int32_t overlap, const int32_t* first_frame, const float* weight, void* stream) {
     MC_REQUIRE(c, "null context");
     if (overlap == 0) {
-        if (c->seam_ov > 0) c->hist_valid = false;       // (multistep sampler: the previous x0 belongs to the coupled walk)
+        if (c->seam_ov > 0) hist_set(c, false);       // (multistep sampler: the previous x0 belongs to the coupled walk)
         c->seam_ov = 0;
         return MC_OK;
     }
@@ -703,7 +705,7 @@ int mc_ctx_set_seams(mc_ctx* c, int32_t overlap, const int32_t* first_frame, con
     MC_HIP(hipMemcpyAsync(c->seam_tab + c->B, wt.data(), sizeof(float) * overlap, hipMemcpyHostToDevice, s));
     MC_HIP(hipStreamSynchronize(s));                 // (the two vectors are temporaries)
     c->seam_ov = overlap;
-    c->hist_valid = false;
+    hist_set(c, false);
     return MC_OK;
 }
 
@@ -721,7 +723,7 @@ int mc_sample_step(mc_ctx* c, const float* x_t, int32_t step, const mc_step_coef
     X0Parts p;
     if ((r = denoise_combined(c, x_t, step, k, stream, &p))) return r;
     if ((r = sampler_update(c, x_t, p, k, noise, x_prev, x0, (hipStream_t)stream))) return r;
-    if (ms && !c->graph_mode) c->hist_valid = true;
+    if (ms && !c->graph_mode) hist_set(c, true);
     return MC_OK;
 }
 
@@ -764,7 +766,7 @@ int mc_sample_loop(mc_ctx* c, float* x, const int32_t* step_indices, const mc_st
         r = sampler_update(c, x, p, &coefs[k], noise ? noise + (long)k * n : nullptr, x, k + 1 == num_steps ? x0_last : nullptr, (hipStream_t)stream,
                            noise ? nullptr : &rng, more ? &po : nullptr);
         if (r != MC_OK) { c->xpad_ready = false; return r; }
-        if (ms) c->hist_valid = true;
+        if (ms) hist_set(c, true);
         c->xpad_ready = more;
     }
     c->xpad_ready = false;
@@ -795,6 +797,155 @@ int mc_ctx_draw_rows(mc_ctx* c, float* out, uint64_t draw, void* stream) {
 int mc_op_philox_normal(float* out, uint32_t* bits, int64_t n, uint64_t seed, uint64_t draw, void* stream) {
     MC_REQUIRE(out || bits, "null argument");
     return mc_launch_philox_fill(out, bits, n, rng_args(seed, draw), (hipStream_t)stream);
+}
+
+// ---- per-row schedules: every request row of the batch at its own schedule index and guidance scale ----
+// Not in this mode: graph capture / replay (a context that holds a captured graph, or a capturing stream, is MC_ERR_STATE), a seam table
+// (MC_ERR_STATE), the inpaint and seeded steps (they have no rows entry).
+static int rows_refuse(const mc_ctx* c, const char* who, hipStream_t s) {
+    if (c->graph_mode || c->graph_exec) {
+        mc_set_error("%s: the context holds a captured graph (mc_ctx_graph_release first): row steps are not replayed", who);
+        return MC_ERR_STATE;
+    }
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &st) != hipSuccess) { (void)hipGetLastError(); st = hipStreamCaptureStatusNone; }
+    if (st != hipStreamCaptureStatusNone) { mc_set_error("%s: the stream is capturing: row steps are not captured", who); return MC_ERR_STATE; }
+    if (c->seam_ov > 0) { mc_set_error("%s: the context has a seam table set (mc_ctx_set_seams): clear it with overlap = 0", who); return MC_ERR_STATE; }
+    if (!c->have_cond) { mc_set_error("%s: mc_ctx_set_condition not called", who); return MC_ERR_STATE; }
+    return MC_OK;
+}
+// device tables [maxS][B] and their pinned staging, on the first call of the mode
+static int rows_tables(mc_ctx* c) {
+    if (c->rs_stage) return MC_OK;
+    const size_t n = (size_t)c->maxS * c->B;
+    int r;
+    if (!c->rs_step && (r = ws_alloc(c, &c->rs_step, n)) != MC_OK) return r;
+    if (!c->rs_coefs && (r = ws_alloc(c, &c->rs_coefs, n)) != MC_OK) return r;
+    if (!c->rs_draw && (r = ws_alloc(c, &c->rs_draw, n)) != MC_OK) return r;
+    if (!c->rs_ev) MC_HIP(hipEventCreateWithFlags(&c->rs_ev, hipEventDisableTiming));
+    MC_HIP(hipHostMalloc(&c->rs_stage, n * (sizeof(int) + sizeof(SamplerCoefs) + sizeof(uint64_t)), hipHostMallocDefault));
+    return MC_OK;
+}
+// n = ticks * B entries of each table -> staging -> device on `s`.  The staging is free once the previous upload's copies are done:
+// the call waits for the event behind them, never for the device.
+static int rows_upload(mc_ctx* c, size_t n, const int32_t* step, const mc_step_coefs* coefs, const uint64_t* draw, hipStream_t s) {
+    const size_t cap = (size_t)c->maxS * c->B;
+    MC_HIP(hipEventSynchronize(c->rs_ev));      // (never recorded: returns at once)
+    uint64_t* sd = reinterpret_cast<uint64_t*>(c->rs_stage);
+    SamplerCoefs* sc = reinterpret_cast<SamplerCoefs*>(sd + cap);
+    int* si = reinterpret_cast<int*>(sc + cap);
+    for (size_t i = 0; i < n; ++i) si[i] = step[i];
+    MC_HIP(hipMemcpyAsync(c->rs_step, si, sizeof(int) * n, hipMemcpyHostToDevice, s));
+    if (coefs) {
+        for (size_t i = 0; i < n; ++i) sc[i] = to_coefs(&coefs[i]);
+        MC_HIP(hipMemcpyAsync(c->rs_coefs, sc, sizeof(SamplerCoefs) * n, hipMemcpyHostToDevice, s));
+    }
+    if (draw) {
+        for (size_t i = 0; i < n; ++i) sd[i] = draw[i];
+        MC_HIP(hipMemcpyAsync(c->rs_draw, sd, sizeof(uint64_t) * n, hipMemcpyHostToDevice, s));
+    }
+    MC_HIP(hipEventRecord(c->rs_ev, s));
+    return MC_OK;
+}
+static RowTab rows_tick(const mc_ctx* c, int k) {
+    RowTab t;
+    t.step = c->rs_step + (size_t)k * c->B; t.coefs = c->rs_coefs + (size_t)k * c->B; t.draw = c->rs_draw + (size_t)k * c->B;
+    t.B = c->B; t.T = c->T;
+    return t;
+}
+
+int mc_denoise_rows(mc_ctx* c, const float* x_t, const int32_t* step_index, float* out2_dev, void* stream) {
+    MC_REQUIRE(c && x_t && step_index, "null argument");
+    hipStream_t s = (hipStream_t)stream;
+    int r;
+    if ((r = rows_refuse(c, "mc_denoise_rows", s))) return r;
+    for (int b = 0; b < c->B; ++b)
+        MC_REQUIRE(step_index[b] >= 0 && step_index[b] < c->S, "row %d: step_index %d outside the %d-step schedule", b, step_index[b], c->S);
+    if ((r = rows_tables(c))) return r;
+    if ((r = rows_upload(c, (size_t)c->B, step_index, nullptr, nullptr, s))) return r;
+    c->rowtab = rows_tick(c, 0);
+    c->rows_mode = true;
+    r = denoise_impl(c, x_t, 0, out2_dev, -1, stream, nullptr);
+    c->rows_mode = false;
+    return r;
+}
+
+int mc_sample_rows(mc_ctx* c, float* x, int32_t num_ticks, const int32_t* step_index, const mc_step_coefs* coefs, const uint64_t* draw,
+                   const float* noise, float* x0_last, void* stream) {
+    MC_REQUIRE(c && x && step_index && coefs, "null argument");
+    MC_REQUIRE(num_ticks >= 0 && num_ticks <= c->maxS, "num_ticks=%d outside [0, max_steps=%d]", num_ticks, c->maxS);
+    hipStream_t s = (hipStream_t)stream;
+    int r;
+    if ((r = rows_refuse(c, "mc_sample_rows", s))) return r;
+    if (num_ticks == 0) return MC_OK;
+    const int B = c->B;
+    const size_t ne = (size_t)num_ticks * B;
+    // every check before the first launch: a refused call leaves the context as it found it
+    for (size_t i = 0; i < ne; ++i) {
+        if ((r = check_mode(&coefs[i]))) return r;
+        MC_REQUIRE(coefs[i].mode == coefs[0].mode, "tick %d row %d: sampler mode %d beside mode %d (one mode per call)", (int)(i / B), (int)(i % B),
+                   coefs[i].mode, coefs[0].mode);
+        MC_REQUIRE(step_index[i] >= 0 && step_index[i] < c->S, "tick %d row %d: step_index %d outside the %d-step schedule", (int)(i / B), (int)(i % B),
+                   step_index[i], c->S);
+    }
+    const bool ms = is_multistep(&coefs[0]);
+    if (!ms && !noise) {
+        if (!c->row_seeds_set) { mc_set_error("mc_sample_rows: noise_dev == NULL needs a seed table (mc_ctx_set_row_seeds)"); return MC_ERR_STATE; }
+        MC_REQUIRE(draw, "mc_sample_rows: noise_dev == NULL needs draw_host");
+    }
+    std::vector<uint8_t> flags = c->hist_rows;
+    flags.resize((size_t)B, 0);
+    if (ms) {
+        for (size_t i = 0; i < ne; ++i) {
+            const int b = (int)(i % B);
+            if (coefs[i].eta != 0.f && !flags[b]) {
+                mc_set_error("mc_sample_rows: tick %d, row %d reads the previous x0 (k1 = %g) but holds none: no multistep step of this row since its "
+                             "condition was set", (int)(i / B), b, (double)coefs[i].eta);
+                return MC_ERR_STATE;
+            }
+            flags[b] = 1;
+        }
+        if ((r = hist_alloc(c))) return r;
+    }
+    if ((r = rows_tables(c))) return r;
+    if ((r = rows_upload(c, ne, step_index, coefs, !ms && !noise ? draw : nullptr, s))) return r;
+    const long n = (long)B * c->T * c->m->cfg.input_feats;
+    PadOut po;
+    po.xpad = c->xpad; po.C = c->m->cfg.input_feats; po.Cp = c->m->Cp;
+    const bool fold_pad = c->xpad != nullptr;
+    c->xpad_ready = false;
+    const RngArgs rng;         // (rows mode reads the draw numbers from the table)
+    r = MC_OK;
+    int ran = 0;               // ticks whose launches were all enqueued
+    for (int k = 0; k < num_ticks && r == MC_OK; ++k) {
+        const mc_step_coefs* ck = coefs + (size_t)k * B;
+        c->rowtab = rows_tick(c, k);
+        c->rows_mode = true;
+        X0Parts p;
+        r = denoise_combined(c, x, 0, ck, stream, &p);
+        const bool more = fold_pad && k + 1 < num_ticks;
+        if (r == MC_OK)
+            r = sampler_update(c, x, p, ck, noise ? noise + (long)k * n : nullptr, x, k + 1 == num_ticks ? x0_last : nullptr, s,
+                               noise || ms ? nullptr : &rng, more ? &po : nullptr);
+        c->rows_mode = false;
+        c->xpad_ready = r == MC_OK && more;
+        if (r == MC_OK) ++ran;
+    }
+    c->xpad_ready = false;
+    // a launch failure in tick k leaves x and the history advanced by ticks [0, k): their flags are kept (every tick updates every row)
+    if (ms && ran == num_ticks) c->hist_rows = flags;
+    else if (ms && ran > 0) c->hist_rows.assign((size_t)B, 1);
+    return r;
+}
+
+int mc_ctx_set_condition_rows(mc_ctx* c, const float* xf_out_dev, const float* mask_dev, const uint8_t* fresh, void* stream) {
+    MC_REQUIRE(c && xf_out_dev && mask_dev && fresh, "null argument");
+    std::vector<uint8_t> keep = c->hist_rows;
+    keep.resize((size_t)c->B, 0);
+    const int r = mc_ctx_set_condition(c, xf_out_dev, mask_dev, stream);      // (clears the context's flag and every row's)
+    if (r != MC_OK) return r;
+    for (int b = 0; b < c->B; ++b) c->hist_rows[b] = fresh[b] ? 0 : keep[b];
+    return MC_OK;
 }
 
 // ---- hipGraph replay of mc_sample_step -------------------------------------------------------------------------------
@@ -853,7 +1004,7 @@ int mc_ctx_graph_step(mc_ctx* c, int32_t step, void* stream) {
     if (c->graph_multistep && (r = hist_require(c, c->graph_k1[step], step))) return r;
     if ((r = mc_launch_set_int(c->gstep, step, s))) return r;
     MC_HIP(hipGraphLaunch(c->graph_exec, s));
-    if (c->graph_multistep) c->hist_valid = true;
+    if (c->graph_multistep) hist_set(c, true);
     return MC_OK;
 }
 
@@ -1125,6 +1276,92 @@ int mc_op_sampler_multistep(const float* x_t, const float* ot, const float* on, 
     MC_REQUIRE(x_t && ot && on && x0_hist && x_prev && k && n >= 0, "bad argument");
     MC_REQUIRE(is_multistep(k), "mc_op_sampler_multistep: coefficients of mode %d (MC_SAMPLER_MULTISTEP = 2 expected)", k->mode);
     return mc_launch_sampler_multistep(x_t, ot, on, x0_hist, x_prev, x0, n, to_coefs(k), (hipStream_t)stream);
+}
+
+// ---- the per-row kernel forms as context-free ops (tests): the coefficient table is a temporary device copy, so both synchronise ----
+static int rows_tab_upload(const mc_step_coefs* coefs, int B, SamplerCoefs** dev, hipStream_t s) {
+    std::vector<SamplerCoefs> tab((size_t)B);
+    for (int b = 0; b < B; ++b) tab[b] = to_coefs(&coefs[b]);
+    MC_HIP(hipMalloc((void**)dev, sizeof(SamplerCoefs) * B));
+    if (hipMemcpyAsync(*dev, tab.data(), sizeof(SamplerCoefs) * B, hipMemcpyHostToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
+        (void)hipFree(*dev);
+        mc_set_error("row coefficient table upload failed");
+        return MC_ERR_HIP;
+    }
+    return MC_OK;
+}
+
+int mc_op_gemm_tail_rows(const float* h, const float* a, const float* w, const float* bias, float* cdev, float* c2dev, int32_t M, int32_t N,
+                         int32_t K, const mc_step_coefs* coefs, int32_t T, int32_t variant, void* stream) {
+    MC_REQUIRE(h && a && w && bias && cdev && coefs && M > 0 && N > 0 && K > 0 && K % 32 == 0, "bad gemm_tail_rows args");
+    MC_REQUIRE(T > 0 && M % T == 0, "gemm_tail_rows: M=%d rows are no whole request rows of T=%d", M, T);
+    MC_REQUIRE(variant >= 1 && variant <= 3, "gemm_tail_rows variant %d (1 column tiles, 2 block ranges, 3 pair combine + grouped GEMM)", variant);
+    MC_REQUIRE(variant == 1 || c2dev, "gemm_tail_rows variants 2 and 3 need the scratch output c2_dev [M][N]");
+    hipStream_t s = (hipStream_t)stream;
+    const McOptions* o = mc_process_options();
+    if (!o) return MC_ERR_ARG;
+    RowTab rt;
+    rt.B = M / T; rt.T = T;
+    SamplerCoefs* tab = nullptr;
+    int r;
+    if ((r = rows_tab_upload(coefs, rt.B, &tab, s))) return r;
+    rt.coefs = tab;
+    float* comb = nullptr;
+    if (variant == 3) {
+        // the small-batch form of denoise_combined: h_c | a_c by axpby_pair_rows_k, then the two skinny products as one grouped GEMM
+        const long MK = (long)M * K;
+        if (hipMalloc((void**)&comb, sizeof(float) * 2 * MK) != hipSuccess) { (void)hipFree(tab); mc_set_error("gemm_tail_rows: scratch allocation failed"); return MC_ERR_HIP; }
+        r = mc_launch_axpby_pair_rows(h, h + MK, comb, a, a + MK, comb + MK, rt, K, MK, s);
+        GemmArgs t;
+        mc_gemm_opts(*o, t);
+        t.A = comb; t.lda = K; t.a_gstride = MK; t.W = w; t.ldw = K; t.w_gstride = (long)N * K;
+        t.bias = bias; t.b_gstride = N; t.C = cdev; t.ldc = N; t.c_gstride = (long)(c2dev - cdev);
+        t.M = M; t.N = N; t.K = K;
+        if (r == MC_OK) r = mc_launch_gemm_small(t, s, 2);
+        if (r == MC_OK) r = mc_launch_axpby(cdev, c2dev, 1.f, 1.f, cdev, (long)M * N, s);
+    } else {
+        TailArgs t;
+        t.H = h; t.Af = a; t.half = (long)M * K; t.lda = K; t.W = w; t.ldw = K; t.w_gstride = (long)N * K; t.bias = bias; t.b_gstride = N;
+        t.C = cdev; t.ldc = N; t.M = M; t.N = N; t.K = K; t.C2 = c2dev;
+        t.coef_table = reinterpret_cast<const float*>(tab) + offsetof(SamplerCoefs, text_coef) / sizeof(float);
+        t.coef_stride = sizeof(SamplerCoefs) / sizeof(float);
+        t.rows_T = T; t.rows_B = rt.B;
+        t.tune = variant == 1 ? ((int)o->gemm_tune & ~kTuneTail2) : ((int)o->gemm_tune | kTuneTail2);
+        if (variant == 2 && !mc_gemm_tail_two_outputs(t)) {
+            mc_set_error("gemm_tail_rows variant 2: the block-range form is not eligible for M=%d N=%d K=%d", M, N, K);
+            r = MC_ERR_ARG;
+        }
+        if (r == MC_OK) r = mc_launch_gemm_tail(t, s);
+        if (r == MC_OK && mc_gemm_tail_two_outputs(t)) r = mc_launch_axpby(cdev, c2dev, 1.f, 1.f, cdev, (long)M * N, s);
+    }
+    (void)hipStreamSynchronize(s);                   // (the table and the scratch are temporaries)
+    (void)hipFree(tab);
+    if (comb) (void)hipFree(comb);
+    return r;
+}
+
+int mc_op_sampler_rows(const float* x_t, const float* ot, const float* on, const float* noise, float* x0_hist, float* x_prev, float* x0,
+                       int32_t B, int32_t TC, const mc_step_coefs* coefs, void* stream) {
+    MC_REQUIRE(x_t && ot && on && x_prev && coefs && B >= 1 && TC >= 1, "mc_op_sampler_rows: bad argument");
+    int r;
+    for (int b = 0; b < B; ++b) {
+        if ((r = check_mode(&coefs[b]))) return r;
+        MC_REQUIRE(coefs[b].mode == coefs[0].mode, "mc_op_sampler_rows: row %d in mode %d beside mode %d (one mode per call)", b, coefs[b].mode, coefs[0].mode);
+    }
+    const bool ms = is_multistep(&coefs[0]);
+    MC_REQUIRE(ms ? x0_hist != nullptr : noise != nullptr, "mc_op_sampler_rows: mode 2 needs x0_hist_dev, the other modes noise_dev");
+    hipStream_t s = (hipStream_t)stream;
+    RowTab rt;
+    rt.B = B; rt.T = 1;
+    SamplerCoefs* tab = nullptr;
+    if ((r = rows_tab_upload(coefs, B, &tab, s))) return r;
+    rt.coefs = tab;
+    const long n = (long)B * TC;
+    r = ms ? mc_launch_sampler_multistep_rows(x_t, ot, on, x0_hist, x_prev, x0, n, 1.f, 1.f, rt, TC, s)
+           : mc_launch_sampler_update_rows(x_t, ot, on, noise, x_prev, x0, n, 1.f, 1.f, rt, TC, s);
+    (void)hipStreamSynchronize(s);
+    (void)hipFree(tab);
+    return r;
 }
 
 int mc_op_sampler_seam(const float* x_t, const float* ot, const float* on, const float* noise, uint64_t seed, uint64_t draw, float* x0_hist,

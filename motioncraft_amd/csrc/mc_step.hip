@@ -226,7 +226,8 @@ static int film_block(mc_ctx* c, float* hs, const float* y1, const float* y2, co
     // (gemm_hf_k); needs whole 32-row blocks (a sample group of B x 196 frames with B % 8 == 0 has them), else the row-major planes + gemm_hd_k
     const bool frag_major = planes && chain_on(c, kChainFragMajor) && row0 % 32 == 0 && nrows % 32 == 0 && D % 64 == 0 && D >= 192;
     if ((r = mc_launch_film_rows(y1_parts > 1 ? y1 : y1 + o, y2 ? y2 + o : nullptr, ln_g, ln_b, ss, a_out, nrows, D, s, y1_alias, row0, sref,
-                                 y1_parts, nrows * D, planes ? ((split3(c) ? 2 : 1) | (frag_major ? 4 : 0)) : 0, pstride))) return r;
+                                 y1_parts, nrows * D, planes ? ((split3(c) ? 2 : 1) | (frag_major ? 4 : 0)) : 0, pstride,
+                                 c->rows_mode ? &c->rowtab : nullptr))) return r;      // (rows mode: `ss` is the table's row of index 0, every row adds its own)
     if (ev_after_rows) MC_HIP(hipEventRecord(ev_after_rows, s));
     if (prologue_only) return MC_OK;
     // h = h + Linear(a)          (st_attention.py:172 / stmogen.py:606)
@@ -686,6 +687,7 @@ int denoise_impl(mc_ctx* c, const float* x_t, int32_t step, float* out2_dev, int
     MC_REQUIRE(c->have_cond, "mc_ctx_set_condition not called");
     MC_REQUIRE(step >= 0 && step < c->S, "step_index %d outside the %d-step schedule", step, c->S);
     if (c->graph_mode) step = 0;       // host-side table pointers address step 0; the kernels add *gstep rows
+    if (c->rows_mode) step = 0;        // ... or every row its own index (mc_sample_rows / mc_denoise_rows checked them on the host)
     hipStream_t s = (hipStream_t)stream;
     const mc_model_config& g = c->m->cfg;
     const int L = g.latent_dim, H = g.num_parts, D = L * H, C = g.input_feats;
@@ -774,7 +776,10 @@ int denoise_combined(mc_ctx* c, const float* x_t, int32_t step, const mc_step_co
     const long BT = (long)c->B * c->T;
     const LayerW& w = c->lw[g.num_layers - 1];
     *x0 = X0Parts{c->out2, nullptr};       // (every form below leaves its one or first output in out2)
+    // rows mode (mc_sample_rows): the same forms below, their CFG weights read per request row from the tick's table
+    const RowTab* const rt = c->rows_mode ? &c->rowtab : nullptr;
     auto combine = [&](const float* x, const float* y, float* out) -> int {      // w x + (1 - w) y, w = this step's CFG weight
+        if (rt) return mc_launch_axpby_rows(x, y, *rt, D, out, BT * D, s);
         if (c->graph_mode) return mc_launch_cfg_combine_tab(x, y, c->gcoefs, c->gstep, out, BT * D, s);
         return mc_launch_axpby(x, y, k->text_coef, k->none_coef, out, BT * D, s);
     };
@@ -792,6 +797,11 @@ int denoise_combined(mc_ctx* c, const float* x_t, int32_t step, const mc_step_co
             t.coef_stride = sizeof(SamplerCoefs) / sizeof(float);
             t.step_ptr = c->gstep;
         }
+        if (rt) {
+            t.coef_table = reinterpret_cast<const float*>(rt->coefs) + offsetof(SamplerCoefs, text_coef) / sizeof(float);
+            t.coef_stride = sizeof(SamplerCoefs) / sizeof(float);
+            t.rows_T = rt->T; t.rows_B = rt->B;
+        }
         t.tune = (int)c->opt.gemm_tune;
         t.C2 = c->out2 + BT * C;               // (out2 holds [2 B T][C]: room for one partial product per K group)
         if ((r = mc_launch_gemm_tail(t, s))) return r;
@@ -800,7 +810,8 @@ int denoise_combined(mc_ctx* c, const float* x_t, int32_t step, const mc_step_co
     }
     if (folded) {
         // h_c and a_c in one launch
-        if ((r = mc_launch_axpby_pair(c->h, c->h + BT * D, c->z2, deferred_a(c), deferred_a(c) + BT * D, c->z2 + BT * D, k->text_coef, k->none_coef,
+        if (rt) { if ((r = mc_launch_axpby_pair_rows(c->h, c->h + BT * D, c->z2, deferred_a(c), deferred_a(c) + BT * D, c->z2 + BT * D, *rt, D, BT * D, s))) return r; }
+        else if ((r = mc_launch_axpby_pair(c->h, c->h + BT * D, c->z2, deferred_a(c), deferred_a(c) + BT * D, c->z2 + BT * D, k->text_coef, k->none_coef,
                                       c->graph_mode ? c->gcoefs : nullptr, c->graph_mode ? c->gstep : nullptr, BT * D, s))) return r;
         // ... and that Linear composed with the decoder is one [C, D] matrix (folded at pack time):
         //   x0 = [dec(h_c) + Wd b] + [a_c (Wd W)^T]
@@ -834,6 +845,17 @@ int sampler_update(mc_ctx* c, const float* x_t, const X0Parts& x0p, const mc_ste
     // a seed table (mc_ctx_set_row_seeds): an in-kernel draw takes every row's own key; a noise tensor is read as it is
     const RowKeys rk{reinterpret_cast<const uint32_t*>(c->row_seeds), (int)(n / c->B)};
     const RowKeys* rows = c->row_seeds_set && rng && !noise ? &rk : nullptr;
+    if (c->rows_mode) {          // per-row schedules: the two row kernels (one mode per call, checked by mc_sample_rows; no graph, no seams)
+        if (c->graph_mode || c->seam_ov > 0) { mc_set_error("per-row sampler update under graph capture or with a seam table set"); return MC_ERR_STATE; }
+        const SamplerCoefs u = x0p.coefs(k);
+        if (!multistep) {
+            MC_REQUIRE(noise || c->row_seeds_set, "per-row sampler update without a noise tensor needs a seed table (mc_ctx_set_row_seeds)");
+            return mc_launch_sampler_update_rows(x_t, x0p.a, x0p.second(), noise, x_prev, x0, n, u.text_coef, u.none_coef, c->rowtab, rk.TC, s,
+                                                 noise ? nullptr : &rk, pad);
+        }
+        MC_REQUIRE(c->x0_hist, "multistep update without a history buffer");
+        return mc_launch_sampler_multistep_rows(x_t, x0p.a, x0p.second(), c->x0_hist, x_prev, x0, n, u.text_coef, u.none_coef, c->rowtab, rk.TC, s, pad);
+    }
     if (c->seam_ov > 0) {        // coupled windows: one kernel for every mode (no graph table: capture is refused while the seam table is set)
         if (c->graph_mode) { mc_set_error("sampler update under graph capture with a seam table set"); return MC_ERR_STATE; }
         MC_REQUIRE(!multistep || c->x0_hist, "multistep update without a history buffer");

@@ -226,6 +226,70 @@ class NativeContext:
                                            int(draw0) & (2 ** 64 - 1), _ptr(x0), _stream()), 'mc_sample_loop')
         return x
 
+    # ---- per-row schedules ---------------------------------------------------
+    def _row_table(self, rows, what, conv=int):
+        rows = [[conv(v) for v in r] for r in rows]
+        if any(len(r) != self.B for r in rows):
+            raise ValueError(f'{what}: every tick has one entry per row ({self.B})')
+        return rows
+
+    def denoise_rows(self, x_t, step_index, out2=None):
+        """``denoise`` with row b at schedule index ``step_index[b]`` (mc_denoise_rows): -> out2 [2B,T,C], both decoded halves."""
+        x = _dev_f32(x_t, 'x_t')
+        if tuple(x.shape) != (self.B, self.T, self.C):
+            raise ValueError(f'x_t shape {tuple(x.shape)} != {(self.B, self.T, self.C)}')
+        idx = self._row_table([step_index], 'step_index')[0]
+        if out2 is None:
+            out2 = torch.empty(2 * self.B, self.T, self.C, device=x.device, dtype=torch.float32)
+        _lib.check(self.lib.mc_denoise_rows(self.handle, _ptr(x), (ctypes.c_int32 * self.B)(*idx), _ptr(out2), _stream()),
+                   'mc_denoise_rows')
+        return out2
+
+    def sample_rows(self, x, step_index, coefs, draws=None, noise=None, x0=None):
+        """Ticks back to back in one library call (mc_sample_rows): in tick k row b takes the step at schedule index
+        ``step_index[k][b]`` under ``coefs[k][b]`` (its guidance weight included); ``x`` [B,T,C] is updated IN PLACE.  ``noise``
+        [ticks,B,T,C], or None: drawn on the device from the rows' seed table, row b at draw number ``draws[k][b]``.  One sampler mode
+        per call.  Asynchronous on the current stream."""
+        x = _dev_f32(x, 'x')
+        if tuple(x.shape) != (self.B, self.T, self.C):
+            raise ValueError(f'x shape {tuple(x.shape)} != {(self.B, self.T, self.C)}')
+        idx = self._row_table(step_index, 'step_index')
+        n = len(idx)
+        if len(coefs) != n or any(len(r) != self.B for r in coefs):
+            raise ValueError('coefs: one StepCoefs per tick and row')
+        if noise is not None:
+            noise = _dev_f32(noise, 'noise')
+            if tuple(noise.shape) != (n, self.B, self.T, self.C):
+                raise ValueError(f'noise shape {tuple(noise.shape)} != {(n, self.B, self.T, self.C)}')
+        darr = None
+        if draws is not None:
+            d = self._row_table(draws, 'draws', lambda v: int(v) & (2 ** 64 - 1))
+            if len(d) != n:
+                raise ValueError('draws: one row of draw numbers per tick')
+            darr = (ctypes.c_uint64 * (n * self.B))(*[v for r in d for v in r])
+        iarr = (ctypes.c_int32 * (n * self.B))(*[v for r in idx for v in r])
+        carr = (_lib.StepCoefs * (n * self.B))(*[c for r in coefs for c in r])
+        _lib.check(self.lib.mc_sample_rows(self.handle, _ptr(x), n, iarr, carr, darr, _ptr(noise), _ptr(x0), _stream()),
+                   'mc_sample_rows')
+        return x
+
+    def set_condition_rows(self, xf_out, motion_mask, fresh):
+        """``set_condition`` for a batch in which only the rows with ``fresh[b]`` true hold a new request (mc_ctx_set_condition_rows):
+        the text K/V of the whole batch are recomputed, the multistep history of the other rows stays valid."""
+        xf = _dev_f32(xf_out, 'xf_out')
+        mask = _dev_f32(motion_mask, 'motion_mask')
+        d = self.model.dims
+        if tuple(xf.shape) != (self.B, d['Nt'], d['Dt']):
+            raise ValueError(f'xf_out shape {tuple(xf.shape)} != {(self.B, d["Nt"], d["Dt"])}')
+        if mask.numel() != self.B * self.T:
+            raise ValueError(f'motion_mask has {mask.numel()} elements, expected {self.B * self.T}')
+        fresh = [bool(f) for f in fresh]
+        if len(fresh) != self.B:
+            raise ValueError(f'fresh: one flag per row ({self.B}), got {len(fresh)}')
+        self._keep = [xf, mask]
+        _lib.check(self.lib.mc_ctx_set_condition_rows(self.handle, _ptr(xf), _ptr(mask), (ctypes.c_uint8 * self.B)(*fresh), _stream()),
+                   'mc_ctx_set_condition_rows')
+
     def set_seams(self, first_frame, overlap, weights=None):
         """Couple the B rows of this context as windows of a long sequence (mc_ctx_set_seams): ``first_frame[b]`` = the global frame
         index of row b's frame 0; rows whose first frames differ by ``T - overlap`` are neighbours and share ``overlap`` frames, every

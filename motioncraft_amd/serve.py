@@ -1,4 +1,5 @@
-"""Independent requests through one batched context: ``Request`` + ``RequestBatcher``.
+"""Independent requests through one batched context: ``Request`` + ``RequestBatcher`` (whole batches, one walk per call) and
+``ContinuousBatcher`` (requests join a running batch at any step and leave when their own walk ends: DESIGN.md section 4o).
 
 The library is fastest when it batches, and with row-keyed noise (``seeds=``) and drop-free MoE routing (``capacity_factor=0``) a row
 of a batch is a request: its result does not depend on what the other rows hold.
@@ -19,9 +20,10 @@ DUMMY_SEED = 0
 
 class Request:
     """One generation request: the condition (``xf_out`` [Nt, Dt], the text encoder's output -- or ``text``, encoded on submit),
-    ``length`` frames (1 .. the batcher's ``frames``), ``seed`` in [0, 2^64) and optionally a control condition ``c`` [Tc, Fc]."""
+    ``length`` frames (1 .. the batcher's ``frames``), ``seed`` in [0, 2^64) and optionally a control condition ``c`` [Tc, Fc].
+    ``guidance_scale``: the request's own classifier-free guidance scale (``ContinuousBatcher``; None: the model's)."""
 
-    def __init__(self, length, seed, xf_out=None, text=None, c=None):
+    def __init__(self, length, seed, xf_out=None, text=None, c=None, guidance_scale=None):
         if (xf_out is None) == (text is None):
             raise ValueError('a request carries exactly one of xf_out and text')
         if text is not None and not isinstance(text, str):
@@ -34,7 +36,10 @@ class Request:
             raise ValueError(f'xf_out of one request is [Nt, Dt], got {tuple(xf_out.shape)}')
         if c is not None and c.dim() != 2:
             raise ValueError(f'the control condition of one request is [Tc, Fc], got {tuple(c.shape)}')
+        if guidance_scale is not None and (isinstance(guidance_scale, bool) or float(guidance_scale) != float(guidance_scale)):
+            raise ValueError(f'guidance_scale must be a number or None, got {guidance_scale!r}')
         self.length, self.seed, self.xf_out, self.text, self.c = int(length), int(seed), xf_out, text, c
+        self.guidance_scale = None if guidance_scale is None else float(guidance_scale)
 
 
 class RequestBatcher:
@@ -137,3 +142,225 @@ class RequestBatcher:
         else:
             out = diffusion.dpm_solver_sample_loop(net, (B, T, C), order=self.order, **common)
         return net.post_process(out)
+
+
+class ContinuousBatcher:
+    """Requests join a running batch at any step and leave when their own walk ends.
+
+    Every row of the (batch, frames) context walks the same schedule, each from its own start: a row admitted at tick t sits at walk
+    position 0 while its neighbours are anywhere else, and takes its own guidance scale (``Request.guidance_scale``).  The result of a
+    request is the function ``RequestBatcher`` states (capacity factor 0), bit for bit the bits ``RequestBatcher`` gives it.
+
+    Same constructor vocabulary as ``RequestBatcher``.  ``submit()`` -> handle; ``tick(n=1)`` does one round; ``run()`` ticks until the
+    queue and the rows are empty; ``poll()`` -> the finished ``{handle: pred_motion[:length]}`` since the last poll.
+
+    One ``tick(n)`` round:
+      1. pending requests are admitted into open rows (lowest row first, submission order).  x_T of such a row is draw 0 of its seed;
+         the condition of the batch is replaced with only the new rows marked fresh (``set_condition_rows``).
+      2. every row advances by the same number of steps in ONE ``mc_sample_rows`` call: ``n``, clipped to the smallest remaining walk of
+         an occupied row, so that no row passes its end (its result would be overwritten) and a waiting request gets the row at once.
+         The walk's k-th step of a row takes draw 1 + k of its seed.
+      3. rows that reached the end of their walk are retired.
+    Open rows run the fixed dummy request at walk position 0 (a retired row keeps its old condition until the next admission replaces
+    it), so the call shape never changes.  Requests with and without a control condition never share a call: a request whose control
+    shape differs from the running rows' waits until they drained, and control requests are admitted into an empty batch only (setting
+    the control condition clears every row's multistep history).
+
+    The context is the model's cached (batch, frames) one: do not interleave another sampler on the same model and shape with a
+    running batcher.
+
+    ``runner`` (host tests) replaces the model: an object with ``steps`` and
+      ``condition(xf_out [B,Nt,Dt], lengths [B], seeds [B], fresh [B], c)``  -- rows with ``fresh[b]`` start at draw 0 of ``seeds[b]``
+      ``advance(pos [n][B], scales [B])``     -- n steps, row b of step k at walk position ``pos[k][b]`` (schedule index steps-1-pos)
+      ``result()`` -> [B, frames, C]          -- the rows as they stand, post-processed."""
+
+    def __init__(self, model, batch, frames, sampler='ddim', steps=None, capacity_factor=0, eta=0.0, order=2, runner=None):
+        if sampler not in SAMPLERS:
+            raise ValueError(f'sampler {sampler!r}: one of {SAMPLERS}')
+        if int(batch) < 1 or int(frames) < 1:
+            raise ValueError(f'batch and frames must be positive, got {batch!r}, {frames!r}')
+        if steps is not None and int(steps) < 1:
+            raise ValueError(f'steps must be positive, got {steps!r}')
+        if float(capacity_factor) < 0:
+            raise ValueError(f'capacity_factor must be >= 0, got {capacity_factor!r}')
+        self.model, self.batch, self.frames = model, int(batch), int(frames)
+        self.sampler, self.steps, self.capacity_factor = sampler, None if steps is None else int(steps), float(capacity_factor)
+        self.eta, self.order = float(eta), int(order)
+        self.runner = runner if runner is not None else _RowsRunner(self)
+        self.walk = int(self.runner.steps)            # steps of one request's walk
+        if self.walk < 1:
+            raise ValueError(f'the schedule has {self.walk} steps')
+        self._rows = [None] * self.batch              # per row: None (open) or [handle, Request, walk position]
+        self._pending = []
+        self._done = {}
+        self._next = 0
+        self._conditioned = False
+        self._stale = [False] * self.batch            # rows retired since the last condition call (still holding their old condition)
+        self.ticks = 0                                # steps the batch has taken
+        self.submitted_at, self.finished_at = {}, {}  # handle -> self.ticks at submit() / at retirement
+
+    # ---- queue ------------------------------------------------------------------------------------
+    def submit(self, request):
+        """Queue ``request``; -> its handle (the key of ``poll()``'s result)."""
+        if not isinstance(request, Request):
+            raise ValueError('submit() takes a Request')
+        if request.length > self.frames:
+            raise ValueError(f'request of {request.length} frames in a batcher of {self.frames}')
+        if request.xf_out is None:
+            xf = self.model.model.encode_text([request.text], None, None)[0]
+            request = Request(request.length, request.seed, xf_out=xf, c=request.c, guidance_scale=request.guidance_scale)
+        handle = self._next
+        self._next += 1
+        self._pending.append((handle, request))
+        self.submitted_at[handle] = self.ticks
+        return handle
+
+    @property
+    def occupied(self):
+        """handles of the running rows (None: an open row)"""
+        return [None if r is None else r[0] for r in self._rows]
+
+    @staticmethod
+    def _group(r):
+        return None if r.c is None else tuple(r.c.shape)
+
+    def _admit(self):
+        """step 1 of a round; -> the rows that took a new request"""
+        running = [r for r in self._rows if r is not None]
+        fresh = []
+        if not self._pending:
+            return fresh
+        group = self._group(running[0][1]) if running else self._group(self._pending[0][1])
+        if group is not None and running:
+            return fresh                              # control requests start in an empty batch only
+        for b in range(self.batch):
+            if self._rows[b] is not None:
+                continue
+            k = next((k for k, (_, r) in enumerate(self._pending) if self._group(r) == group), None)
+            if k is None:
+                break
+            handle, r = self._pending.pop(k)
+            self._rows[b] = [handle, r, 0]
+            fresh.append(b)
+        return fresh
+
+    def _condition(self, fresh):
+        live = [r[1] for r in self._rows if r is not None]
+        first = live[0]
+        flags = [b in fresh for b in range(self.batch)]
+        if not self._conditioned or first.c is not None:      # the first call, or a control group (an empty batch): the open rows' dummy starts too
+            flags = [True] * self.batch
+        else:                                         # a retired row that stays open takes the dummy now
+            flags = [f or (self._rows[b] is None and self._stale[b]) for b, f in enumerate(flags)]
+        xf = torch.stack([r[1].xf_out if r is not None else torch.zeros_like(first.xf_out) for r in self._rows])
+        lengths = [r[1].length if r is not None else self.frames for r in self._rows]
+        seeds = [r[1].seed if r is not None else DUMMY_SEED for r in self._rows]
+        c = None
+        if first.c is not None:
+            c = torch.stack([r[1].c if r is not None else torch.zeros_like(first.c) for r in self._rows])
+        self.runner.condition(xf, lengths, seeds, flags, c)
+        self._conditioned = True
+        self._stale = [False] * self.batch
+
+    def tick(self, n=1):
+        """One round (class docstring); -> the steps the batch advanced by (0: nothing to run)."""
+        if isinstance(n, bool) or int(n) != n or int(n) < 1:
+            raise ValueError(f'tick(n): a positive number of steps, got {n!r}')
+        fresh = self._admit()
+        if fresh:
+            self._condition(fresh)
+        live = [r for r in self._rows if r is not None]
+        if not live:
+            return 0
+        n = min(int(n), min(self.walk - r[2] for r in live))
+        pos = [[(r[2] + k) if r is not None else 0 for r in self._rows] for k in range(n)]
+        scales = [r[1].guidance_scale if r is not None else None for r in self._rows]
+        self.runner.advance(pos, scales)
+        self.ticks += n
+        out = None
+        for b, r in enumerate(self._rows):
+            if r is None:
+                continue
+            r[2] += n
+            if r[2] == self.walk:
+                if out is None:
+                    out = self.runner.result()
+                self._done[r[0]] = out[b, :r[1].length].clone()
+                self.finished_at[r[0]] = self.ticks
+                self._rows[b] = None
+                self._stale[b] = True
+        return n
+
+    def run(self):
+        """Tick until the queue and the rows are empty; -> ``poll()``."""
+        while self._pending or any(r is not None for r in self._rows):
+            if self.tick(self.walk) == 0:
+                raise RuntimeError('pending requests but nothing to run')      # (cannot happen: an empty batch admits the head of the queue)
+        return self.poll()
+
+    def poll(self):
+        """-> ``{handle: pred_motion[:length]}`` of the requests finished since the last poll"""
+        out, self._done = self._done, {}
+        return out
+
+
+class _RowsRunner:
+    """the model behind ``ContinuousBatcher``: the (batch, frames) context of the model, ``x`` [B, frames, C] in place"""
+
+    def __init__(self, owner):
+        from .diffusion import build_diffusion
+        self.o = owner
+        cfg = dict(owner.model.diffusion_test_cfg)
+        if owner.steps is not None:
+            cfg['respace'] = str(owner.steps) if owner.sampler == 'ddpm' else f'ddim{owner.steps}'
+        self.diffusion = build_diffusion(cfg, opt=owner.model.opt)
+        self.steps = self.diffusion.num_timesteps
+        self.ctx, self.x, self.group = None, None, ()
+        self._coefs = {}                              # scale -> the StepCoefs of a whole walk, by walk position
+
+    def condition(self, xf_out, lengths, seeds, fresh, c):
+        from . import lib as _lib
+        from .engine import _ptr, _stream
+        o, net = self.o, self.o.model.model
+        dev = torch.device('cuda', torch.cuda.current_device())
+        B, T, C = o.batch, o.frames, net.dims['input_feats']
+        mask = torch.zeros(B, T, device=dev)
+        for b, n in enumerate(lengths):
+            mask[b, :n] = 1
+        group = None if c is None else tuple(c.shape)
+        # The control features reach the context through sampling_context alone, so every admission of a control group goes through it
+        # (such a group starts in an empty batch: every row is fresh, the history of no running row is lost); so does a change of group.
+        if self.ctx is None or c is not None or group != self.group:
+            kw = dict(xf_out=xf_out.to(dev), motion_mask=mask, c=c, capacity_factor=o.capacity_factor)
+            self.ctx = net.sampling_context(B, T, self.diffusion.timestep_map, kw, dev)
+            self.group = group
+            if self.x is None:
+                self.x = torch.zeros(B, T, C, device=dev)
+        else:
+            self.ctx.set_condition_rows(xf_out.to(dev), mask, fresh)
+        self.ctx.set_row_seeds(seeds)
+        for b, f in enumerate(fresh):
+            if f:                                     # x_T of the row: draw 0 of its own stream
+                _lib.check(self.ctx.lib.mc_op_philox_normal(_ptr(self.x[b]), None, T * C, int(seeds[b]) & (2 ** 64 - 1), 0, _stream()),
+                           'mc_op_philox_normal')
+
+    def _walk_coefs(self, scale):
+        o, d = self.o, self.diffusion
+        scale = float(o.model.model.cfg_scale if scale is None else scale)
+        if scale not in self._coefs:
+            idx = list(range(self.steps))[::-1]
+            if o.sampler == 'dpmpp':
+                self._coefs[scale] = d.multistep_coefs(idx, scale, o.order)
+            else:
+                self._coefs[scale] = [d.step_coefs(i, o.sampler, scale, o.eta if o.sampler == 'ddim' else 0.0) for i in idx]
+        return self._coefs[scale]
+
+    def advance(self, pos, scales):
+        walks = [self._walk_coefs(s) for s in scales]
+        idx = [[self.steps - 1 - p for p in row] for row in pos]
+        coefs = [[walks[b][p] for b, p in enumerate(row)] for row in pos]
+        draws = [[1 + p for p in row] for row in pos]
+        self.ctx.sample_rows(self.x, idx, coefs, draws=draws)
+
+    def result(self):
+        return self.o.model.model.post_process(self.x.clone())

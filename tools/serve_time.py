@@ -7,8 +7,15 @@ after one warm-up:
             computes kept pairs only (one stream / joined groups); the early two-group schedule computes every pair either way
   noise     the fused DDPM loop (mc_sample_loop, noise drawn in the sampler-update kernel): one seed per call (flat) against a seed table
   batcher   serve.RequestBatcher: R requests of a --steps DDIM walk through B = 1 calls against through one B = R batch
+  rows       one sampler step: mc_sample_step against mc_sample_rows with the same index and coefficients in
+            every row (the same kernel forms, the weights and the FiLM row read through the row tables), interleaved; and one
+            mc_ctx_set_condition_rows (the whole batch's text MoE per layer: the cost of an admission) beside it
+  arrivals  the fixed arrival list ARRIVALS below (request i arrives at tick ARRIVALS[i]; a tick is one sampler step of the batch)
+            replayed through serve.RequestBatcher (a batch starts when the batcher is idle, with whatever has arrived, and runs its
+            whole walk) and through serve.ContinuousBatcher (a request takes an open row at the next tick): requests/s and the mean
+            and maximum ticks from arrival to completion
 
-usage: serve_time.py [--small] [--batch B] [--requests R] [--steps N] [--reps K] [--only routing,noise,batcher]
+usage: serve_time.py [--small] [--batch B] [--requests R] [--steps N] [--reps K] [--only routing,noise,batcher,rows,arrivals]
   --small: the reduced test config (24 frames) instead of the 0.125b architecture (196 frames)"""
 import argparse
 import os
@@ -21,7 +28,7 @@ ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
 sys.path.insert(0, ROOT)
 import motioncraft_amd as mc                                                  # noqa: E402
 from motioncraft_amd.diffusion import build_diffusion                         # noqa: E402
-from motioncraft_amd.serve import Request, RequestBatcher                     # noqa: E402
+from motioncraft_amd.serve import ContinuousBatcher, Request, RequestBatcher  # noqa: E402
 from motioncraft_amd.synthetic import make_state_dict, default_dims           # noqa: E402
 
 p = argparse.ArgumentParser()
@@ -31,6 +38,9 @@ p.add_argument('--requests', type=int, default=16)
 p.add_argument('--steps', type=int, default=50)
 p.add_argument('--reps', type=int, default=3)
 p.add_argument('--only', default='routing,noise,batcher')
+# request i arrives at tick ARRIVALS[i]: a burst, a trickle one step apart, a lull, a second burst that overfills B = 16, stragglers
+ARRIVALS = [0, 0, 0, 0, 1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 15, 20, 26, 33, 41, 50, 70, 70, 70, 70, 70, 70, 70, 70, 70, 70, 70, 70, 70, 70, 70, 70,
+            70, 70, 71, 73, 76, 80, 85, 91, 98, 120, 150, 151]
 a = p.parse_args()
 only = set(a.only.split(','))
 
@@ -136,4 +146,74 @@ if 'batcher' in only:
         med, lo, hi = median_of(run)
         print(f'{R} requests, {a.steps}-step DDIM, through B={batch:<3d} calls: median {med * 1e3:8.1f} ms = {R / med:7.2f} requests/s   '
               f'(min {lo * 1e3:8.1f} ms, max {hi * 1e3:8.1f} ms)', flush=True)
+if 'rows' in only:
+    x, xf, mask, _ = inputs(B)
+    dd = build_diffusion(dict(schedule, respace='ddim10'))
+    ctx = arch.model.native.context(B, T, max_steps=10)
+    ctx.set_timesteps(dd.timestep_map)
+    ctx.set_condition(xf, mask)
+    c5 = dd.step_coefs(5, 'ddim', arch.model.cfg_scale)
+    noise = torch.randn(1, B, T, C, device='cuda')
+    xd = x.clone()
+    arms = {'mc_sample_step': lambda: ctx.sample_step(xd, 5, c5, noise[0], x_prev=xd),
+            'mc_sample_rows (uniform tables)': lambda: ctx.sample_rows(xd, [[5] * B], [[c5] * B], noise=noise),
+            'mc_ctx_set_condition_rows': lambda: ctx.set_condition_rows(xf, mask, [True] + [False] * (B - 1))}
+    for name in list(arms) * 2:                    # (twice, interleaved)
+        med, lo, hi = median_of(lambda: events_ms(arms[name], 5))
+        print(f'B={B} {name:32s}: median {med:8.3f} ms   min {lo:8.3f}   max {hi:8.3f}   (5 calls per run)', flush=True)
+    ctx.close()
+
+if 'arrivals' in only:
+    g = torch.Generator().manual_seed(2)
+    reqs = [Request(length=int(torch.randint(T // 3, T + 1, (1,), generator=g)), seed=900 + i,
+                    xf_out=torch.nn.functional.layer_norm(torch.randn(dims['Nt'], dims['Dt'], generator=g), (dims['Dt'],)).cuda())
+            for i in range(len(ARRIVALS))]
+    R = len(reqs)
+
+    def replay_whole():
+        """RequestBatcher: idle -> one batch of what has arrived (at most B), its whole walk; the clock advances by the walk"""
+        bt = RequestBatcher(arch, batch=B, frames=T, sampler='ddim', steps=a.steps)
+        tick, k, waiting, lat = 0, 0, [], []
+        while k < R or waiting:
+            while k < R and ARRIVALS[k] <= tick:
+                waiting.append(k)
+                k += 1
+            if not waiting:
+                tick = ARRIVALS[k]
+                continue
+            part, waiting = waiting[:B], waiting[B:]
+            for i in part:
+                bt.submit(reqs[i])
+            assert len(bt.run()) == len(part)
+            tick += a.steps
+            lat += [tick - ARRIVALS[i] for i in part]
+        return lat
+
+    def replay_continuous():
+        bt = ContinuousBatcher(arch, batch=B, frames=T, sampler='ddim', steps=a.steps)
+        k, done, lat = 0, 0, []
+        while done < R:
+            while k < R and ARRIVALS[k] <= bt.ticks:
+                bt.submit(reqs[k])
+                k += 1
+            if bt.tick() == 0:
+                bt.ticks = ARRIVALS[k]              # idle: the clock jumps to the next arrival
+            for h in bt.poll():
+                lat.append(bt.finished_at[h] - ARRIVALS[h])
+                done += 1
+        return lat
+
+    for name, fn in (('RequestBatcher', replay_whole), ('ContinuousBatcher', replay_continuous)) * 2:
+        box = {}
+
+        def run():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            box['lat'] = fn()
+            torch.cuda.synchronize()
+            return time.perf_counter() - t0
+        med, lo, hi = median_of(run)
+        lat = box['lat']
+        print(f'{R} arrivals, {a.steps}-step DDIM, B={B}, {name:17s}: median {med * 1e3:8.1f} ms = {R / med:7.2f} requests/s   '
+              f'(min {lo * 1e3:8.1f}, max {hi * 1e3:8.1f} ms);  ticks to completion: mean {sum(lat) / len(lat):6.1f}, max {max(lat)}', flush=True)
 arch.model.release()
