@@ -322,6 +322,28 @@ int mc_sample_rows(mc_ctx* c, float* x_dev, int32_t num_ticks, const int32_t* st
 int mc_denoise_rows(mc_ctx* c, const float* x_t_dev, const int32_t* step_index_host, float* out2_dev, void* stream);
 int mc_ctx_set_condition_rows(mc_ctx* c, const float* xf_out_dev, const float* mask_dev, const uint8_t* fresh_host, void* stream);
 
+/* Edited rows: "these frames or channels are given, generate the rest" per request row -- keyframes,
+ * in-betweening, continuing a motion, re-generating some body parts.  The reference's model_kwargs['y'] = {gt, outpainting_mask}
+ * (gaussian_diffusion.py:492-501, 855-877) in the row form.  gt_dev [B,T,C] fp32 and keep_dev [B,T,C] bytes (non-zero: given), both in
+ * model space (normalised), are COPIED into context-owned tables on `stream` (device to device, asynchronous): rows with
+ * fresh_host[b] != 0, or every row with fresh_host == NULL; the other rows keep what they hold (nothing, before their first upload).
+ * gt_dev == keep_dev == NULL clears the table: the flag is dropped and the keep bytes are zeroed on `stream` (the buffers stay allocated), so
+ * after a clear no row holds a kept region until it is uploaded again; exactly one of them NULL is MC_ERR_ARG.
+ * While a table is set, the sampler update of mc_sample_rows takes, for an element with keep != 0,
+ *     x0 = gt                                             (a select: gt where keep == 0 is never read into a result, a NaN included)
+ *     mode 0: x_prev = the DDPM update of (x, x0)         mode 2: x_prev = the multistep update of (x, x0), history <- x0
+ *     mode 1: x_prev = sqrt(ab_prev) gt + sqrt(1 - ab_prev) z2
+ * with z2 = draw number draw_host[k][b] ^ 2^63 of the row's seed, at the row-local counter of the step draw: a row's kept-region noise
+ * depends on its seed alone.  x0_dev, the history and the next step's pose-encoder operand receive the edited values; every other
+ * element, and every element of a row whose keep bytes are all zero, gets the bits it gets without a table.  At schedule index 0 all
+ * three samplers leave the kept region of x equal to gt bit for bit.  No cross-fade, no resampling jumps: mc_sample_step_inpaint.
+ * State: with a captured graph or a seam table in the context, setting a table is MC_ERR_STATE.  While a table is set,
+ * mc_ctx_set_seams, mc_ctx_graph_capture, mc_ctx_graph_step, mc_sample_step, mc_sample_loop, mc_sample_step_inpaint and
+ * mc_sample_step_seeded return MC_ERR_STATE, and mc_sample_rows in mode 1 with noise_dev != NULL returns MC_ERR_ARG (modes 0 and 2
+ * take either noise source).  Every refusal leaves the context as it was.  The table does not touch the multistep history flags, and
+ * mc_ctx_set_condition / mc_ctx_set_condition_rows do not touch the table. */
+int mc_ctx_set_edit_rows(mc_ctx* c, const float* gt_dev, const uint8_t* keep_dev, const uint8_t* fresh_host, void* stream);
+
 /* hipGraph replay of mc_sample_step (BASELINE.json configs[4] "hipGraph-captured 50-step DDIM"): ONE graph serves every step
  * of the schedule -- the step index is a device-side integer, the FiLM tables and the sampler coefficients are addressed
  * with it inside the kernels, no host sync or per-step H2D copy (SURVEY.md section 3.1 lists the reference's per-step
@@ -474,6 +496,14 @@ int mc_op_gemm_tail_rows(const float* h_dev, const float* a_dev, const float* w_
 int mc_op_sampler_rows(const float* x_t_dev, const float* out_text_dev, const float* out_none_dev, const float* noise_dev,
                        float* x0_hist_dev, float* x_prev_dev, float* x0_dev, int32_t B, int32_t TC, const mc_step_coefs* coefs_host,
                        void* stream);
+/* mc_op_sampler_rows with a kept region (see mc_ctx_set_edit_rows): gt_dev [B][TC] floats, keep_dev [B][TC] bytes.  Modes 0 / 1 take
+ * either noise_dev (and, mode 1, gt_noise_dev [B][TC]: the kept region's second normal), or seeds_host [B] + draw_host [B]: both
+ * noises are then drawn in the kernel, row b from key seeds_host[b] at draws draw_host[b] and draw_host[b] ^ 2^63; the two sources
+ * exclude each other.  Mode 2: x0_hist_dev in-out, no noise of either kind.  Mixed modes are MC_ERR_ARG.  Synchronises. */
+int mc_op_sampler_edit_rows(const float* x_t_dev, const float* out_text_dev, const float* out_none_dev, const float* noise_dev,
+                            const float* gt_noise_dev, const float* gt_dev, const uint8_t* keep_dev, const uint64_t* seeds_host,
+                            const uint64_t* draw_host, float* x0_hist_dev, float* x_prev_dev, float* x0_dev, int32_t B, int32_t TC,
+                            const mc_step_coefs* coefs_host, void* stream);
 /* the seam-coupled update without a context (see mc_ctx_set_seams for the plan rules and the blend): operands [B, T, C], any mode.
  * Modes 0 / 1: the noise is read from noise_dev, or with noise_dev == NULL drawn from the Philox stream (seed, draw) -- mutually
  * exclusive: seed and draw must be 0 beside a noise tensor.  Mode 2: x0_hist_dev in-out as in mc_op_sampler_multistep (unused, may

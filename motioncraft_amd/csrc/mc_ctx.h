@@ -153,6 +153,12 @@ struct mc_ctx {
     void* rs_stage = nullptr;           // pinned: [maxS][B] ints | SamplerCoefs | uint64
     hipEvent_t rs_ev = nullptr;
     std::vector<uint8_t> hist_rows;     // multistep "history valid" per request row (all cleared / set wherever hist_valid is)
+    // edited rows (mc_ctx_set_edit_rows): the kept region per request row, gt [B,T,C] floats and keep [B,T,C]
+    // bytes, allocated by the first call that sets a table.  While edit_set, sampler_update launches the edit kernels in rows mode and
+    // every entry without a rows form refuses (edit_refuse).
+    float* edit_gt = nullptr;
+    uint8_t* edit_keep = nullptr;
+    bool edit_set = false;
     int prec = MC_PREC_F32;     // MFMA operand precision of the per-step GEMM-shaped kernels (mc_ctx_set_precision)
     int* cap_idx = nullptr;      // [NL][2N] routing capture (tests): expert ids ...
     float* cap_w = nullptr;      // ... and combine weights (0 = dropped) of every layer

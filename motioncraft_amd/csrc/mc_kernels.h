@@ -77,6 +77,17 @@ int mc_launch_sampler_update_rows(const float* x_t, const float* out_text, const
 int mc_launch_sampler_multistep_rows(const float* x_t, const float* out_text, const float* out_none, float* x0_hist, float* x_prev,
                                      float* x0_out, long n, float tc, float nc, const RowTab& rt, int TC, hipStream_t s,
                                      const PadOut* pad = nullptr);
+// The two row updates with a kept region (mc_ctx_set_edit_rows): gt [B][TC] floats and keep [B][TC] bytes on the
+// device; where keep != 0, x0 = gt (a select) and, in mode 1, x_prev = sqrt(ab_prev) gt + sqrt(1 - ab_prev) z2 with z2 read from gt_noise
+// (beside a noise tensor) or drawn from the rows' keys at draw rt.draw[row] ^ 2^63 (noise == nullptr).  kword is the launcher's (the keep
+// table is 4-byte aligned: whole groups read their four bytes as one word).  All-zero keep bytes give the row kernels' bits.
+struct EditTab { const float* gt = nullptr; const uint8_t* keep = nullptr; const float* gt_noise = nullptr; int kword = 0; };
+int mc_launch_sampler_edit_rows(const float* x_t, const float* out_text, const float* out_none, const float* noise, EditTab et, float* x_prev,
+                                float* x0_out, long n, float tc, float nc, const RowTab& rt, int TC, int mode, hipStream_t s,
+                                const RowKeys* keys = nullptr, const PadOut* pad = nullptr);      // mode: the table's (0 or 1)
+int mc_launch_sampler_multistep_edit_rows(const float* x_t, const float* out_text, const float* out_none, float* x0_hist, EditTab et,
+                                          float* x_prev, float* x0_out, long n, float tc, float nc, const RowTab& rt, int TC, hipStream_t s,
+                                          const PadOut* pad = nullptr);
 // Seam-coupled update of B windows [B][T][C] (sampler_seam_k, all three modes): flags [B] ints on the device, bit 0 = the row shares
 // its first `ov` frames with the last `ov` of row b - 1, bit 1 = its last `ov` with the first of row b + 1 (the caller guarantees bit 1
 // of row b goes with bit 0 of row b + 1 and is clear on row B - 1); w [ov] = the right window's weight per shared frame; 0 < 2 ov <= T.

@@ -450,8 +450,8 @@ __device__ __forceinline__ SamplerCoefs row_coefs(const SamplerCoefs* __restrict
     c.text_coef = tc; c.none_coef = nc;
     return c;
 }
-// philox_rows4 with the draw number per row
-__device__ __forceinline__ f32x4 philox_rows4d(long i, long n, RowKeys rk, const uint64_t* __restrict__ draw) {
+// philox_rows4 with the draw number per row, draw[b] ^ flip (flip: 0 for the step noise, MC_EDIT_DRAW_FLIP for the kept region's, section 4p)
+__device__ __forceinline__ f32x4 philox_rows4x(long i, long n, RowKeys rk, const uint64_t* __restrict__ draw, uint64_t flip) {
     long b = i / rk.TC;
     int r = (int)(i - b * rk.TC);
     RngArgs rng;
@@ -461,8 +461,9 @@ __device__ __forceinline__ f32x4 philox_rows4d(long i, long n, RowKeys rk, const
     for (int j = 0; j < 4 && i + j < n; ++j) {
         if (b != cb || (r >> 2) != cc) {
             cb = b; cc = r >> 2;
+            const uint64_t dr = draw[b] ^ flip;
             rng.seed_lo = rk.keys[2 * b]; rng.seed_hi = rk.keys[2 * b + 1];
-            rng.draw_lo = (uint32_t)draw[b]; rng.draw_hi = (uint32_t)(draw[b] >> 32);
+            rng.draw_lo = (uint32_t)dr; rng.draw_hi = (uint32_t)(dr >> 32);
             cur = philox_normal4(cc, rng);
         }
         const int l = r & 3;
@@ -471,6 +472,7 @@ __device__ __forceinline__ f32x4 philox_rows4d(long i, long n, RowKeys rk, const
     }
     return z;
 }
+__device__ __forceinline__ f32x4 philox_rows4d(long i, long n, RowKeys rk, const uint64_t* __restrict__ draw) { return philox_rows4x(i, n, rk, draw, 0); }
 
 template <bool RNG, bool VEC>
 __global__ __launch_bounds__(256) void sampler_update_rows_k(const float* x_t, const float* __restrict__ o_text,
@@ -562,6 +564,150 @@ __global__ __launch_bounds__(256) void sampler_multistep_rows_k(const float* x_t
         } else {
             for (int j = 0; j < 4 && i + j < n; ++j) {
                 const float x0 = cfg_elem(o_text[i + j], o_none[i + j], c);
+                const float hp = c.eta != 0.f ? hist[i + j] : 0.f;
+                const float o = multistep_elem(x_t[i + j], x0, hp, c.c2, c.c1, c.eta);
+                x_prev[i + j] = o;
+                hist[i + j] = x0;
+                if (x0_out) x0_out[i + j] = x0;
+                if (po.xpad) po.xpad[(i + j) / po.C * po.Cp + (i + j) % po.C] = o;
+                if (i + j + 1 < n && ++r == TC) { r = 0; ++b; c = row_coefs(tab, b, tc, nc); }
+            }
+        }
+    }
+}
+
+// ---- edited rows (mc_ctx_set_edit_rows) ----
+// Element e of [B][TC] with keep[e] != 0 is GIVEN: x0 = keep ? gt : cfg_elem(..) -- a select, never a product, so whatever gt holds
+// where keep == 0 (a NaN included) reaches no output -- and the row kernels' update goes on from that x0 (gaussian_diffusion.py:492-501).
+// Mode 1 also replaces the new sample there, x_prev = sqrt(ab_prev) gt + sqrt(1 - ab_prev) z2 (:855-877 without the cross-fade), z2 a
+// second normal: read from gt_noise, or (RNG) draw number draw[b] ^ 2^63 of the row's key at the row-local counter of the step draw,
+// drawn only for groups that hold a kept element.  Kernels of their own beside the two row kernels over the same device functions, flat
+// groups of four, VEC rule, straddle rule and PadOut: a row whose keep bytes are all zero gets the row kernels' bits.  The four keep
+// bytes of a whole group inside n are one 32-bit load (kword: the table is 4-byte aligned); gt is read only for groups with a kept
+// element.  x0_out, the history (mode 2) and xpad receive the edited values.
+constexpr uint64_t MC_EDIT_DRAW_FLIP = 0x8000000000000000ull;
+__device__ __forceinline__ uint32_t keep4(const uint8_t* __restrict__ keep, long i, long n, int kword) {
+    if (kword && i + 4 <= n) return *reinterpret_cast<const uint32_t*>(keep + i);
+    uint32_t w = 0;
+    for (int j = 0; j < 4 && i + j < n; ++j) w |= (keep[i + j] ? 1u : 0u) << (8 * j);
+    return w;
+}
+__device__ __forceinline__ bool kept(uint32_t kw, int j) { return ((kw >> (8 * j)) & 0xffu) != 0; }
+// the kept region's new sample in mode 1
+__device__ __forceinline__ float edit_renoise(float g, float z2, const SamplerCoefs& c, const SamplerDerived& d) {
+    return fmaf(d.sq_abp, g, __fmul_rn(sqrtf(1.f - c.ab_prev), z2));
+}
+
+template <bool RNG, bool VEC>
+__global__ __launch_bounds__(256) void sampler_edit_rows_k(const float* x_t, const float* __restrict__ o_text,
+                                                           const float* __restrict__ o_none, const float* __restrict__ noise, EditTab et,
+                                                           float* x_prev, float* __restrict__ x0_out, long n, float tc, float nc,
+                                                           const SamplerCoefs* __restrict__ tab, RowKeys rk,
+                                                           const uint64_t* __restrict__ draw, PadOut po) {
+    const long ngroups = (n + 3) >> 2;
+    for (long gi = (long)blockIdx.x * blockDim.x + threadIdx.x; gi < ngroups; gi += (long)gridDim.x * blockDim.x) {
+        const long i = gi * 4;
+        long b = i / rk.TC;
+        int r = (int)(i - b * rk.TC);
+        SamplerCoefs c = row_coefs(tab, b, tc, nc);
+        SamplerDerived d = sampler_derive(c);
+        const uint32_t kw = keep4(et.keep, i, n, et.kword);
+        const bool renoise = kw != 0 && c.mode == 1;           // (one mode per launch)
+        f32x4 nz = {0.f, 0.f, 0.f, 0.f}, z2 = nz, g = nz;
+        if constexpr (RNG) {
+            nz = philox_rows4d(i, n, rk, draw);
+            if (renoise) z2 = philox_rows4x(i, n, rk, draw, MC_EDIT_DRAW_FLIP);
+        }
+        if (VEC && i + 4 <= n) {
+            const f32x4 x = *reinterpret_cast<const f32x4*>(x_t + i);
+            const f32x4 a = *reinterpret_cast<const f32x4*>(o_text + i), bb = *reinterpret_cast<const f32x4*>(o_none + i);
+            if constexpr (!RNG) {
+                nz = *reinterpret_cast<const f32x4*>(noise + i);
+                if (renoise) z2 = *reinterpret_cast<const f32x4*>(et.gt_noise + i);
+            }
+            if (kw) g = *reinterpret_cast<const f32x4*>(et.gt + i);
+            f32x4 out, x0v;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const bool k = kept(kw, j);
+                const float x0m = cfg_elem(a[j], bb[j], c);
+                x0v[j] = k ? g[j] : x0m;
+                const float o = sampler_elem(x[j], x0v[j], nz[j], c, d);
+                out[j] = (k && c.mode == 1) ? edit_renoise(g[j], z2[j], c, d) : o;
+                if (j < 3 && ++r == rk.TC) { r = 0; ++b; c = row_coefs(tab, b, tc, nc); d = sampler_derive(c); }
+            }
+            *reinterpret_cast<f32x4*>(x_prev + i) = out;
+            if (x0_out) *reinterpret_cast<f32x4*>(x0_out + i) = x0v;
+            if (po.xpad) {
+                long row = i / po.C;
+                int col = (int)(i - row * po.C);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    po.xpad[row * po.Cp + col] = out[j];
+                    if (++col == po.C) { col = 0; ++row; }
+                }
+            }
+        } else {
+            for (int j = 0; j < 4 && i + j < n; ++j) {
+                const bool k = kept(kw, j);
+                const float gj = k ? et.gt[i + j] : 0.f;
+                const float x0m = cfg_elem(o_text[i + j], o_none[i + j], c);
+                const float x0 = k ? gj : x0m;
+                const float z = RNG ? nz[j] : noise[i + j];
+                float o = sampler_elem(x_t[i + j], x0, z, c, d);
+                if (k && c.mode == 1) o = edit_renoise(gj, RNG ? z2[j] : et.gt_noise[i + j], c, d);
+                x_prev[i + j] = o;
+                if (x0_out) x0_out[i + j] = x0;
+                if (po.xpad) po.xpad[(i + j) / po.C * po.Cp + (i + j) % po.C] = o;
+                if (i + j + 1 < n && ++r == rk.TC) { r = 0; ++b; c = row_coefs(tab, b, tc, nc); d = sampler_derive(c); }
+            }
+        }
+    }
+}
+
+// mode 2 with the kept region: x0 = keep ? gt : cfg_elem(..);  x_prev = multistep_elem(x, x0, hist, ..);  hist <- x0 (the edited one)
+template <bool VEC>
+__global__ __launch_bounds__(256) void sampler_multistep_edit_rows_k(const float* x_t, const float* __restrict__ o_text,
+                                                                     const float* __restrict__ o_none, float* __restrict__ hist, EditTab et,
+                                                                     float* x_prev, float* __restrict__ x0_out, long n, float tc, float nc,
+                                                                     const SamplerCoefs* __restrict__ tab, int TC, PadOut po) {
+    const long ngroups = (n + 3) >> 2;
+    for (long gi = (long)blockIdx.x * blockDim.x + threadIdx.x; gi < ngroups; gi += (long)gridDim.x * blockDim.x) {
+        const long i = gi * 4;
+        long b = i / TC;
+        int r = (int)(i - b * TC);
+        SamplerCoefs c = row_coefs(tab, b, tc, nc);
+        const uint32_t kw = keep4(et.keep, i, n, et.kword);
+        if (VEC && i + 4 <= n) {
+            const f32x4 x = *reinterpret_cast<const f32x4*>(x_t + i);
+            const f32x4 a = *reinterpret_cast<const f32x4*>(o_text + i), bb = *reinterpret_cast<const f32x4*>(o_none + i);
+            const f32x4 hv = *reinterpret_cast<const f32x4*>(hist + i);
+            f32x4 g = {0.f, 0.f, 0.f, 0.f};
+            if (kw) g = *reinterpret_cast<const f32x4*>(et.gt + i);
+            f32x4 out, x0v;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float x0m = cfg_elem(a[j], bb[j], c);
+                x0v[j] = kept(kw, j) ? g[j] : x0m;
+                out[j] = multistep_elem(x[j], x0v[j], c.eta != 0.f ? hv[j] : 0.f, c.c2, c.c1, c.eta);
+                if (j < 3 && ++r == TC) { r = 0; ++b; c = row_coefs(tab, b, tc, nc); }
+            }
+            *reinterpret_cast<f32x4*>(x_prev + i) = out;
+            *reinterpret_cast<f32x4*>(hist + i) = x0v;
+            if (x0_out) *reinterpret_cast<f32x4*>(x0_out + i) = x0v;
+            if (po.xpad) {
+                long row = i / po.C;
+                int col = (int)(i - row * po.C);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    po.xpad[row * po.Cp + col] = out[j];
+                    if (++col == po.C) { col = 0; ++row; }
+                }
+            }
+        } else {
+            for (int j = 0; j < 4 && i + j < n; ++j) {
+                const float x0m = cfg_elem(o_text[i + j], o_none[i + j], c);
+                const float x0 = kept(kw, j) ? et.gt[i + j] : x0m;
                 const float hp = c.eta != 0.f ? hist[i + j] : 0.f;
                 const float o = multistep_elem(x_t[i + j], x0, hp, c.c2, c.c1, c.eta);
                 x_prev[i + j] = o;
@@ -1007,6 +1153,57 @@ int mc_launch_sampler_multistep_rows(const float* x_t, const float* out_text, co
     MC_REQUIRE(!po.xpad || (po.C > 0 && po.Cp >= po.C), "row multistep update: bad padded-copy shape");
     if (vec) hipLaunchKernelGGL((sampler_multistep_rows_k<true>), dim3(blocks), dim3(256), 0, s, x_t, out_text, out_none, x0_hist, x_prev, x0_out, n, tc, nc, rt.coefs, TC, po);
     else hipLaunchKernelGGL((sampler_multistep_rows_k<false>), dim3(blocks), dim3(256), 0, s, x_t, out_text, out_none, x0_hist, x_prev, x0_out, n, tc, nc, rt.coefs, TC, po);
+    MC_LAUNCH_CHECK();
+    return MC_OK;
+}
+
+// the edited forms: the same grids and checks; gt (and gt_noise where it is read) join the vector rule
+int mc_launch_sampler_edit_rows(const float* x_t, const float* out_text, const float* out_none, const float* noise, EditTab et, float* x_prev,
+                                float* x0_out, long n, float tc, float nc, const RowTab& rt, int TC, int mode, hipStream_t s,
+                                const RowKeys* keys, const PadOut* pad) {
+    MC_REQUIRE(x_t && out_text && out_none && x_prev && rt.coefs && rt.B > 0 && TC > 0 && n == (long)rt.B * TC,
+               "edited row sampler update: %ld elements for %d rows of %d", n, rt.B, TC);
+    MC_REQUIRE(et.gt && et.keep, "edited row sampler update: no gt / keep table");
+    const bool dev_rng = !noise;
+    MC_REQUIRE(!dev_rng || (keys && keys->keys && keys->TC == TC && rt.draw), "edited row sampler update: no noise tensor, and no seed table / draw numbers");
+    MC_REQUIRE(mode == 0 || mode == 1, "edited row sampler update: mode %d (0 or 1: the table's one mode)", mode);
+    if (dev_rng || mode == 0) et.gt_noise = nullptr;      // (both noises come from the rows' streams; mode 0 draws no second one)
+    MC_REQUIRE(mode == 0 || dev_rng || et.gt_noise, "edited row sampler update: mode 1 beside a noise tensor needs the kept region's noise tensor");
+    const bool vec = ((uintptr_t)x_t | (uintptr_t)out_text | (uintptr_t)out_none | (uintptr_t)x_prev | (uintptr_t)x0_out | (uintptr_t)noise |
+                      (uintptr_t)et.gt | (uintptr_t)et.gt_noise) % 16 == 0;
+    et.kword = (uintptr_t)et.keep % 4 == 0 ? 1 : 0;
+    int blocks = cdiv((n + 3) / 4, 256);
+    if (blocks > 2048) blocks = 2048;
+    if (blocks < 1) blocks = 1;
+    const PadOut po = pad ? *pad : PadOut();
+    MC_REQUIRE(!po.xpad || (po.C > 0 && po.Cp >= po.C), "edited row sampler update: bad padded-copy shape");
+    const RowKeys rk{dev_rng ? keys->keys : nullptr, TC};
+#define MC_SER(R, V) hipLaunchKernelGGL((sampler_edit_rows_k<R, V>), dim3(blocks), dim3(256), 0, s, x_t, out_text, out_none, noise, et, x_prev, x0_out, n, tc, nc, rt.coefs, rk, rt.draw, po)
+    if (dev_rng) { if (vec) MC_SER(true, true); else MC_SER(true, false); }
+    else { if (vec) MC_SER(false, true); else MC_SER(false, false); }
+#undef MC_SER
+    MC_LAUNCH_CHECK();
+    return MC_OK;
+}
+
+int mc_launch_sampler_multistep_edit_rows(const float* x_t, const float* out_text, const float* out_none, float* x0_hist, EditTab et,
+                                          float* x_prev, float* x0_out, long n, float tc, float nc, const RowTab& rt, int TC, hipStream_t s,
+                                          const PadOut* pad) {
+    MC_REQUIRE(x_t && out_text && out_none && x0_hist && x_prev && rt.coefs && rt.B > 0 && TC > 0 && n == (long)rt.B * TC,
+               "edited row multistep update: %ld elements for %d rows of %d", n, rt.B, TC);
+    MC_REQUIRE(et.gt && et.keep, "edited row multistep update: no gt / keep table");
+    MC_REQUIRE(x0_hist != x_t && x0_hist != x_prev && x0_hist != x0_out && x0_hist != out_text && x0_hist != out_none && x0_hist != et.gt,
+               "edited row multistep update: the history buffer aliases another operand");
+    const bool vec = ((uintptr_t)x_t | (uintptr_t)out_text | (uintptr_t)out_none | (uintptr_t)x_prev | (uintptr_t)x0_out | (uintptr_t)x0_hist |
+                      (uintptr_t)et.gt) % 16 == 0;
+    et.kword = (uintptr_t)et.keep % 4 == 0 ? 1 : 0;
+    et.gt_noise = nullptr;
+    int blocks = cdiv((n + 3) / 4, 256);
+    if (blocks > 2048) blocks = 2048;
+    const PadOut po = pad ? *pad : PadOut();
+    MC_REQUIRE(!po.xpad || (po.C > 0 && po.Cp >= po.C), "edited row multistep update: bad padded-copy shape");
+    if (vec) hipLaunchKernelGGL((sampler_multistep_edit_rows_k<true>), dim3(blocks), dim3(256), 0, s, x_t, out_text, out_none, x0_hist, et, x_prev, x0_out, n, tc, nc, rt.coefs, TC, po);
+    else hipLaunchKernelGGL((sampler_multistep_edit_rows_k<false>), dim3(blocks), dim3(256), 0, s, x_t, out_text, out_none, x0_hist, et, x_prev, x0_out, n, tc, nc, rt.coefs, TC, po);
     MC_LAUNCH_CHECK();
     return MC_OK;
 }

@@ -683,6 +683,15 @@ static int seam_refuse(const mc_ctx* c, const char* who) {
     return MC_OK;
 }
 
+// ---- edited rows (mc_ctx_set_edit_rows): every entry without a rows form refuses while a table is set ----
+static int edit_refuse(const mc_ctx* c, const char* who) {
+    if (c->edit_set) {
+        mc_set_error("%s: the context has an edit table set (mc_ctx_set_edit_rows): edited rows take mc_sample_rows only; clear it with gt_dev = keep_dev = NULL", who);
+        return MC_ERR_STATE;
+    }
+    return MC_OK;
+}
+
 int mc_ctx_set_seams(mc_ctx* c, int32_t overlap, const int32_t* first_frame, const float* weight, void* stream) {
     MC_REQUIRE(c, "null context");
     if (overlap == 0) {
@@ -690,6 +699,7 @@ int mc_ctx_set_seams(mc_ctx* c, int32_t overlap, const int32_t* first_frame, con
         c->seam_ov = 0;
         return MC_OK;
     }
+    if (int re = edit_refuse(c, "mc_ctx_set_seams")) return re;
     std::vector<int> flags;
     std::vector<float> wt;
     int r;
@@ -713,6 +723,7 @@ int mc_sample_step(mc_ctx* c, const float* x_t, int32_t step, const mc_step_coef
                    float* x_prev, float* x0, void* stream) {
     MC_REQUIRE(c && x_t && k && x_prev, "null argument");
     int r;
+    if ((r = edit_refuse(c, "mc_sample_step"))) return r;
     if ((r = check_mode(k))) return r;
     const bool ms = c->graph_mode ? c->graph_multistep : is_multistep(k);
     MC_REQUIRE(noise || ms, "null argument (noise_dev may be NULL in mode 2 only)");
@@ -742,6 +753,7 @@ int mc_sample_loop(mc_ctx* c, float* x, const int32_t* step_indices, const mc_st
                    const float* noise, uint64_t seed, uint64_t noise_draw0, float* x0_last, void* stream) {
     MC_REQUIRE(c && x && step_indices && coefs, "null argument");
     MC_REQUIRE(num_steps >= 0, "num_steps < 0");
+    if (int re = edit_refuse(c, "mc_sample_loop")) return re;
     const long n = (long)c->B * c->T * c->m->cfg.input_feats;
     // the sampler update of step k also writes x_{t-1} at the padded row stride the pose-encoder GEMM of step k + 1 stages from
     // (no pad_rows_k launch between the steps; the first step of a loop pads, which also zeroes the pad columns)
@@ -889,6 +901,8 @@ int mc_sample_rows(mc_ctx* c, float* x, int32_t num_ticks, const int32_t* step_i
                    step_index[i], c->S);
     }
     const bool ms = is_multistep(&coefs[0]);
+    MC_REQUIRE(!(c->edit_set && coefs[0].mode == MC_SAMPLER_DDIM && noise),
+               "mc_sample_rows: with an edit table set, mode 1 takes noise_dev == NULL (the kept region's noise is a draw of the row's seed)");
     if (!ms && !noise) {
         if (!c->row_seeds_set) { mc_set_error("mc_sample_rows: noise_dev == NULL needs a seed table (mc_ctx_set_row_seeds)"); return MC_ERR_STATE; }
         MC_REQUIRE(draw, "mc_sample_rows: noise_dev == NULL needs draw_host");
@@ -948,11 +962,51 @@ int mc_ctx_set_condition_rows(mc_ctx* c, const float* xf_out_dev, const float* m
     return MC_OK;
 }
 
+// The kept region of every request row: rows with fresh[b] != 0 (NULL: all) are copied device to device into the
+// context's tables on `s`; the others keep what they hold.  The tables are zeroed when they are allocated, so a row never set keeps nothing.
+int mc_ctx_set_edit_rows(mc_ctx* c, const float* gt, const uint8_t* keep, const uint8_t* fresh, void* stream) {
+    MC_REQUIRE(c, "null context");
+    if (!gt && !keep) {
+        // nothing stays kept behind a clear: a later upload of some fresh rows must not bring a retired row's region back
+        if (c->edit_keep) MC_HIP(hipMemsetAsync(c->edit_keep, 0, (size_t)c->B * c->T * c->m->cfg.input_feats, (hipStream_t)stream));
+        c->edit_set = false;
+        return MC_OK;
+    }
+    MC_REQUIRE(gt && keep, "mc_ctx_set_edit_rows: gt_dev and keep_dev are both given, or both NULL (which clears the table)");
+    if (c->graph_mode || c->graph_exec) {
+        mc_set_error("mc_ctx_set_edit_rows: the context holds a captured graph (mc_ctx_graph_release first): edited rows are not replayed");
+        return MC_ERR_STATE;
+    }
+    if (c->seam_ov > 0) { mc_set_error("mc_ctx_set_edit_rows: the context has a seam table set (mc_ctx_set_seams): clear it with overlap = 0"); return MC_ERR_STATE; }
+    const size_t TC = (size_t)c->T * c->m->cfg.input_feats, n = (size_t)c->B * TC;
+    hipStream_t s = (hipStream_t)stream;
+    int r;
+    if (!c->edit_gt) {
+        if ((r = ws_alloc(c, &c->edit_gt, n)) != MC_OK) return r;
+        MC_HIP(hipMemsetAsync(c->edit_gt, 0, sizeof(float) * n, s));
+    }
+    if (!c->edit_keep) {
+        if ((r = ws_alloc(c, &c->edit_keep, n)) != MC_OK) return r;
+        MC_HIP(hipMemsetAsync(c->edit_keep, 0, n, s));
+    }
+    for (int b = 0; b < c->B;) {          // one copy per run of fresh rows
+        if (fresh && !fresh[b]) { ++b; continue; }
+        int e = b + 1;
+        while (e < c->B && (!fresh || fresh[e])) ++e;
+        MC_HIP(hipMemcpyAsync(c->edit_gt + b * TC, gt + b * TC, sizeof(float) * TC * (e - b), hipMemcpyDeviceToDevice, s));
+        MC_HIP(hipMemcpyAsync(c->edit_keep + b * TC, keep + b * TC, TC * (e - b), hipMemcpyDeviceToDevice, s));
+        b = e;
+    }
+    c->edit_set = true;
+    return MC_OK;
+}
+
 // ---- hipGraph replay of mc_sample_step -------------------------------------------------------------------------------
 int mc_ctx_graph_capture(mc_ctx* c, float* x_dev, const float* noise_dev, const mc_step_coefs* coefs_host, int32_t num_steps,
                          void* stream) {
     MC_REQUIRE(c && x_dev && coefs_host, "null argument");
     if (int rs = seam_refuse(c, "mc_ctx_graph_capture")) return rs;
+    if (int re = edit_refuse(c, "mc_ctx_graph_capture")) return re;
     MC_REQUIRE(c->have_cond, "mc_ctx_set_condition not called");
     MC_REQUIRE(num_steps >= 1 && num_steps == c->S, "num_steps=%d must equal the schedule set by mc_ctx_set_timesteps (%d)", num_steps, c->S);
     MC_REQUIRE(!c->cap_idx, "routing capture (tests) and graph replay are mutually exclusive");
@@ -997,7 +1051,9 @@ int mc_ctx_graph_capture(mc_ctx* c, float* x_dev, const float* noise_dev, const 
 }
 
 int mc_ctx_graph_step(mc_ctx* c, int32_t step, void* stream) {
-    MC_REQUIRE(c && c->graph_exec, "no captured graph (mc_ctx_graph_capture)");
+    MC_REQUIRE(c, "null context");
+    if (int re = edit_refuse(c, "mc_ctx_graph_step")) return re;
+    MC_REQUIRE(c->graph_exec, "no captured graph (mc_ctx_graph_capture)");
     MC_REQUIRE(step >= 0 && step < c->graph_steps, "step_index %d outside the %d captured steps", step, c->graph_steps);
     hipStream_t s = (hipStream_t)stream;
     int r;
@@ -1018,6 +1074,7 @@ int mc_sample_step_seeded(mc_ctx* c, float* x_t, int32_t step, const mc_step_coe
                           const mc_seed* sd, float* x_prev, float* x0, void* stream) {
     MC_REQUIRE(c && x_t && k && noise && x_prev && sd, "null argument");
     if (int rs = seam_refuse(c, "mc_sample_step_seeded")) return rs;
+    if (int re = edit_refuse(c, "mc_sample_step_seeded")) return re;
     MC_REQUIRE(!is_multistep(k), "mc_sample_step_seeded: the multistep sampler (mode 2) has no pre_seq / transl_req seeding");
     MC_REQUIRE(sd->pre_len >= 0 && sd->pre_len <= c->T, "pre_seq has %d frames, the window %d", sd->pre_len, c->T);
     MC_REQUIRE(sd->num_transl >= 0 && sd->num_transl <= MC_MAX_TRANSL, "num_transl=%d outside [0, %d]", sd->num_transl, MC_MAX_TRANSL);
@@ -1041,6 +1098,7 @@ int mc_sample_step_inpaint(mc_ctx* c, const float* x_t, int32_t step, const mc_s
                            const mc_inpaint* ip, float* x_prev, float* x0, void* stream) {
     MC_REQUIRE(c && x_t && k && noise && x_prev && ip, "null argument");
     if (int rs = seam_refuse(c, "mc_sample_step_inpaint")) return rs;
+    if (int re = edit_refuse(c, "mc_sample_step_inpaint")) return re;
     MC_REQUIRE(!is_multistep(k), "mc_sample_step_inpaint: the multistep sampler (mode 2) has no outpainting (RePaint) form");
     X0Parts p;
     if (int r = denoise_combined(c, x_t, step, k, stream, &p)) return r;
@@ -1361,6 +1419,54 @@ int mc_op_sampler_rows(const float* x_t, const float* ot, const float* on, const
            : mc_launch_sampler_update_rows(x_t, ot, on, noise, x_prev, x0, n, 1.f, 1.f, rt, TC, s);
     (void)hipStreamSynchronize(s);
     (void)hipFree(tab);
+    return r;
+}
+
+int mc_op_sampler_edit_rows(const float* x_t, const float* ot, const float* on, const float* noise, const float* gt_noise, const float* gt,
+                            const uint8_t* keep, const uint64_t* seeds, const uint64_t* draw, float* x0_hist, float* x_prev, float* x0, int32_t B,
+                            int32_t TC, const mc_step_coefs* coefs, void* stream) {
+    MC_REQUIRE(x_t && ot && on && gt && keep && x_prev && coefs && B >= 1 && TC >= 1, "mc_op_sampler_edit_rows: bad argument");
+    int r;
+    for (int b = 0; b < B; ++b) {
+        if ((r = check_mode(&coefs[b]))) return r;
+        MC_REQUIRE(coefs[b].mode == coefs[0].mode, "mc_op_sampler_edit_rows: row %d in mode %d beside mode %d (one mode per call)", b, coefs[b].mode, coefs[0].mode);
+    }
+    const bool ms = is_multistep(&coefs[0]);
+    const bool dev_rng = seeds != nullptr || draw != nullptr;
+    if (ms) MC_REQUIRE(x0_hist && !noise && !gt_noise && !dev_rng, "mc_op_sampler_edit_rows: mode 2 needs x0_hist_dev and takes no noise");
+    else {
+        MC_REQUIRE(!dev_rng || (seeds && draw && !noise && !gt_noise), "mc_op_sampler_edit_rows: (seeds_host, draw_host) come together and exclude the noise tensors");
+        MC_REQUIRE(dev_rng || noise, "mc_op_sampler_edit_rows: modes 0 / 1 need noise_dev, or (seeds_host, draw_host)");
+        MC_REQUIRE(dev_rng || coefs[0].mode == MC_SAMPLER_DDPM || gt_noise, "mc_op_sampler_edit_rows: mode 1 beside noise_dev needs gt_noise_dev");
+    }
+    hipStream_t s = (hipStream_t)stream;
+    RowTab rt;
+    rt.B = B; rt.T = 1;
+    SamplerCoefs* tab = nullptr;
+    if ((r = rows_tab_upload(coefs, B, &tab, s))) return r;
+    rt.coefs = tab;
+    uint64_t* kd = nullptr;               // [B] keys | [B] draw numbers
+    if (dev_rng) {
+        std::vector<uint64_t> h((size_t)2 * B);
+        for (int b = 0; b < B; ++b) { h[b] = seeds[b]; h[(size_t)B + b] = draw[b]; }
+        if (hipMalloc((void**)&kd, sizeof(uint64_t) * 2 * B) != hipSuccess ||
+            hipMemcpyAsync(kd, h.data(), sizeof(uint64_t) * 2 * B, hipMemcpyHostToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
+            if (kd) (void)hipFree(kd);
+            (void)hipFree(tab);
+            mc_set_error("mc_op_sampler_edit_rows: seed table upload failed");
+            return MC_ERR_HIP;
+        }
+        rt.draw = kd + B;
+    }
+    EditTab et;
+    et.gt = gt; et.keep = keep; et.gt_noise = gt_noise;
+    const RowKeys rk{reinterpret_cast<const uint32_t*>(kd), TC};
+    const long n = (long)B * TC;
+    r = ms ? mc_launch_sampler_multistep_edit_rows(x_t, ot, on, x0_hist, et, x_prev, x0, n, 1.f, 1.f, rt, TC, s)
+           : mc_launch_sampler_edit_rows(x_t, ot, on, noise, et, x_prev, x0, n, 1.f, 1.f, rt, TC, coefs[0].mode, s, dev_rng ? &rk : nullptr);
+    (void)hipStreamSynchronize(s);
+    (void)hipFree(tab);
+    if (kd) (void)hipFree(kd);
     return r;
 }
 

@@ -848,6 +848,19 @@ int sampler_update(mc_ctx* c, const float* x_t, const X0Parts& x0p, const mc_ste
     if (c->rows_mode) {          // per-row schedules: the two row kernels (one mode per call, checked by mc_sample_rows; no graph, no seams)
         if (c->graph_mode || c->seam_ov > 0) { mc_set_error("per-row sampler update under graph capture or with a seam table set"); return MC_ERR_STATE; }
         const SamplerCoefs u = x0p.coefs(k);
+        if (c->edit_set) {       // a kept region (mc_ctx_set_edit_rows): the edit kernels, the same forms otherwise
+            EditTab et;
+            et.gt = c->edit_gt; et.keep = c->edit_keep;
+            if (!multistep) {
+                MC_REQUIRE(noise || c->row_seeds_set, "per-row sampler update without a noise tensor needs a seed table (mc_ctx_set_row_seeds)");
+                MC_REQUIRE(!noise || k->mode == MC_SAMPLER_DDPM, "edited rows in mode 1 draw the kept region's noise from the seed table: no noise tensor");
+                return mc_launch_sampler_edit_rows(x_t, x0p.a, x0p.second(), noise, et, x_prev, x0, n, u.text_coef, u.none_coef, c->rowtab, rk.TC,
+                                                   k->mode, s, noise ? nullptr : &rk, pad);
+            }
+            MC_REQUIRE(c->x0_hist, "multistep update without a history buffer");
+            return mc_launch_sampler_multistep_edit_rows(x_t, x0p.a, x0p.second(), c->x0_hist, et, x_prev, x0, n, u.text_coef, u.none_coef, c->rowtab,
+                                                         rk.TC, s, pad);
+        }
         if (!multistep) {
             MC_REQUIRE(noise || c->row_seeds_set, "per-row sampler update without a noise tensor needs a seed table (mc_ctx_set_row_seeds)");
             return mc_launch_sampler_update_rows(x_t, x0p.a, x0p.second(), noise, x_prev, x0, n, u.text_coef, u.none_coef, c->rowtab, rk.TC, s,

@@ -73,6 +73,7 @@ class NativeContext:
         self._graph_state = None
         self.seams = None              # dict(first_frame, overlap) while a seam table is set (set_seams)
         self.row_seeds = None          # the rows' Philox keys while a seed table is set (set_row_seeds)
+        self.edit_rows = False         # an edit table is set (set_edit_rows); read by serve: the first upload after a clear sends every row
 
     @property
     def workspace_bytes(self):
@@ -289,6 +290,35 @@ class NativeContext:
         self._keep = [xf, mask]
         _lib.check(self.lib.mc_ctx_set_condition_rows(self.handle, _ptr(xf), _ptr(mask), (ctypes.c_uint8 * self.B)(*fresh), _stream()),
                    'mc_ctx_set_condition_rows')
+
+    def set_edit_rows(self, gt, keep, fresh=None):
+        """The kept region of every request row (mc_ctx_set_edit_rows): ``gt`` [B,T,C] float32 and ``keep``
+        [B,T,C] bool / uint8 (non-zero: the element is given), both in model space, contiguous on the device.  Rows with ``fresh[b]``
+        true (None: every row) are copied into the context's tables; the others keep what they hold.  While a table is set,
+        ``sample_rows`` takes x0 = gt on the kept elements (and, DDIM, re-noises them from the row's own seed); every entry without a
+        rows form raises."""
+        g = _dev_f32(gt, 'gt')
+        shape = (self.B, self.T, self.C)
+        if not isinstance(keep, torch.Tensor) or keep.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f'keep must be a bool or uint8 tensor, got {getattr(keep, "dtype", type(keep).__name__)}')
+        if not keep.is_cuda or not keep.is_contiguous():
+            raise ValueError('keep must be a contiguous device tensor')
+        if tuple(g.shape) != shape or tuple(keep.shape) != shape:
+            raise ValueError(f'gt / keep shape {tuple(g.shape)} / {tuple(keep.shape)} != {shape}')
+        farr = None
+        if fresh is not None:
+            fresh = [bool(f) for f in fresh]
+            if len(fresh) != self.B:
+                raise ValueError(f'fresh: one flag per row ({self.B}), got {len(fresh)}')
+            farr = (ctypes.c_uint8 * self.B)(*fresh)
+        _lib.check(self.lib.mc_ctx_set_edit_rows(self.handle, _ptr(g), keep.data_ptr(), farr, _stream()), 'mc_ctx_set_edit_rows')
+        self._keep_edit = (g, keep)    # (the copies are asynchronous on the current stream; a refused call keeps the previous sources)
+        self.edit_rows = True
+
+    def clear_edit_rows(self):
+        _lib.check(self.lib.mc_ctx_set_edit_rows(self.handle, None, None, None, _stream()), 'mc_ctx_set_edit_rows')
+        self._keep_edit = None
+        self.edit_rows = False
 
     def set_seams(self, first_frame, overlap, weights=None):
         """Couple the B rows of this context as windows of a long sequence (mc_ctx_set_seams): ``first_frame[b]`` = the global frame

@@ -247,6 +247,16 @@ class STMoGenTransformer:
             motion = motion * std + mean
         return motion
 
+    def pre_process(self, motion):
+        """The inverse of ``post_process`` -- the reference's ``Normalize`` transform, ``(motion - mean) / (std + 1e-9)``: a motion in
+        data space -> model space (``serve.Edit`` hands its kept frames through it).  The identity without ``post_process_cfg``."""
+        if self.post_process_cfg is not None:
+            import numpy as np
+            mean = torch.from_numpy(np.load(self.post_process_cfg['mean_path'])).type_as(motion)
+            std = torch.from_numpy(np.load(self.post_process_cfg['std_path'])).type_as(motion)
+            motion = (motion - mean) / (std + 1e-9)
+        return motion
+
     def scale_func(self, timestep):
         w = (1 - (1000 - timestep) / 1000) * self.cfg_scale + 1
         return {'text_coef': w, 'none_coef': 1 - w}
@@ -310,6 +320,9 @@ class ControlT2MHalf:
 
     def post_process(self, output):
         return self.base_model.post_process(output)
+
+    def pre_process(self, motion):
+        return self.base_model.pre_process(motion)
 
     def load_state_dict(self, state_dict, strict=True):
         self.base_model.load_state_dict(state_dict, strict=strict)

@@ -18,12 +18,102 @@ SAMPLERS = ('ddpm', 'ddim', 'dpmpp')
 DUMMY_SEED = 0
 
 
+class Edit:
+    """The given part of a motion: ``motion`` [n, C] in de-normalised (data) space and ``keep`` bool [n, C] --
+    where ``keep`` is set the element is given, everything else (and frames n .. the request's length) is generated around it.
+    ``keyframes`` / ``inbetween`` / ``parts`` build the usual masks.  The batchers normalise ``motion`` with the model's
+    ``pre_process`` and hand the row to ``mc_ctx_set_edit_rows``; at the end of the walk the kept elements ARE the given ones."""
+
+    def __init__(self, motion, keep):
+        if not isinstance(motion, torch.Tensor) or motion.dim() != 2 or not motion.is_floating_point():
+            raise ValueError(f'motion of an edit is a float tensor [n, C], got {getattr(motion, "shape", type(motion).__name__)}')
+        if not isinstance(keep, torch.Tensor) or keep.dtype != torch.bool or tuple(keep.shape) != tuple(motion.shape):
+            raise ValueError(f'keep must be a bool tensor of motion\'s shape {tuple(motion.shape)}, got '
+                             f'{getattr(keep, "dtype", type(keep).__name__)} {tuple(getattr(keep, "shape", ()))}')
+        if motion.shape[0] < 1:
+            raise ValueError('an edit holds at least one frame')
+        if not bool(keep.any()):
+            raise ValueError('keep is all False: nothing is given (submit the request without an edit)')
+        if not bool(torch.isfinite(motion[keep]).all()):
+            raise ValueError('motion is not finite where keep is set')
+        self.motion, self.keep = motion, keep
+
+    @property
+    def frames(self):
+        return int(self.motion.shape[0])
+
+    @property
+    def feats(self):
+        return int(self.motion.shape[1])
+
+    @staticmethod
+    def _frame_list(frames, n):
+        out = []
+        for f in frames:
+            if isinstance(f, bool) or int(f) != f or not 0 <= int(f) < n:
+                raise ValueError(f'frame {f!r} outside the {n} frames of motion')
+            out.append(int(f))
+        if not out:
+            raise ValueError('no frame given')
+        return out
+
+    @classmethod
+    def keyframes(cls, motion, frames):
+        """``frames`` of ``motion`` are given on all channels"""
+        keep = torch.zeros(motion.shape, dtype=torch.bool)
+        keep[cls._frame_list(frames, motion.shape[0])] = True
+        return cls(motion, keep)
+
+    @classmethod
+    def inbetween(cls, motion, head, tail):
+        """the first ``head`` and the last ``tail`` frames of ``motion`` are given, the frames between them generated"""
+        n = motion.shape[0]
+        for v in (head, tail):
+            if isinstance(v, bool) or int(v) != v or int(v) < 0:
+                raise ValueError(f'head / tail are frame counts, got {v!r}')
+        if head + tail < 1 or head + tail > n:
+            raise ValueError(f'head + tail = {head + tail} outside [1, {n}]')
+        return cls.keyframes(motion, list(range(int(head))) + list(range(n - int(tail), n)))
+
+    @classmethod
+    def parts(cls, motion, names, dataset, frames=None):
+        """the channels of the body parts ``names`` (``synthetic.part_layout(dataset)``) are given, on ``frames`` (None: all)"""
+        from .synthetic import part_layout
+        known, channels, _ = part_layout(dataset)
+        names = [names] if isinstance(names, str) else list(names)
+        bad = [n for n in names if n not in known]
+        if bad or not names:
+            raise ValueError(f'parts {bad or names!r}: the parts of {dataset!r} are {known}')
+        C = 1 + max(c for n in known for c in channels[n])
+        if motion.dim() != 2 or motion.shape[1] < C:
+            raise ValueError(f'motion has {tuple(motion.shape)[-1]} channels, the {dataset!r} layout reaches channel {C - 1}')
+        rows = list(range(motion.shape[0])) if frames is None else cls._frame_list(frames, motion.shape[0])
+        keep = torch.zeros(motion.shape, dtype=torch.bool)
+        cols = sorted({c for n in names for c in channels[n]})
+        keep[torch.tensor(rows)[:, None], torch.tensor(cols)[None, :]] = True
+        return cls(motion, keep)
+
+    def tables(self, frames, pre_process=None):
+        """-> (gt [frames, C] float32 in model space, keep [frames, C] uint8) on the CPU: frames past the edit's are free"""
+        motion = self.motion.detach().float().cpu()
+        keep = self.keep.cpu()
+        motion = torch.where(keep, motion, torch.zeros_like(motion))          # (what is not given never reaches the device)
+        if pre_process is not None:
+            motion = pre_process(motion)
+        gt = torch.zeros(frames, self.feats)
+        kp = torch.zeros(frames, self.feats, dtype=torch.uint8)
+        gt[:self.frames] = motion
+        kp[:self.frames] = keep.to(torch.uint8)
+        return gt, kp
+
+
 class Request:
     """One generation request: the condition (``xf_out`` [Nt, Dt], the text encoder's output -- or ``text``, encoded on submit),
     ``length`` frames (1 .. the batcher's ``frames``), ``seed`` in [0, 2^64) and optionally a control condition ``c`` [Tc, Fc].
-    ``guidance_scale``: the request's own classifier-free guidance scale (``ContinuousBatcher``; None: the model's)."""
+    ``guidance_scale``: the request's own classifier-free guidance scale (``ContinuousBatcher``; None: the model's).
+    ``edit``: an ``Edit`` -- the frames / channels of the result that are given (at most ``length`` frames)."""
 
-    def __init__(self, length, seed, xf_out=None, text=None, c=None, guidance_scale=None):
+    def __init__(self, length, seed, xf_out=None, text=None, c=None, guidance_scale=None, edit=None):
         if (xf_out is None) == (text is None):
             raise ValueError('a request carries exactly one of xf_out and text')
         if text is not None and not isinstance(text, str):
@@ -38,8 +128,22 @@ class Request:
             raise ValueError(f'the control condition of one request is [Tc, Fc], got {tuple(c.shape)}')
         if guidance_scale is not None and (isinstance(guidance_scale, bool) or float(guidance_scale) != float(guidance_scale)):
             raise ValueError(f'guidance_scale must be a number or None, got {guidance_scale!r}')
+        if edit is not None:
+            if not isinstance(edit, Edit):
+                raise ValueError(f'edit must be an Edit, got {type(edit).__name__}')
+            if edit.frames > int(length):
+                raise ValueError(f'the edit holds {edit.frames} frames, the request {int(length)}')
         self.length, self.seed, self.xf_out, self.text, self.c = int(length), int(seed), xf_out, text, c
+        self.edit = edit
         self.guidance_scale = None if guidance_scale is None else float(guidance_scale)
+
+
+def _check_edit(model, request):
+    """an edit's channel count against the model's (host tests run without a model)"""
+    if request.edit is not None and model is not None:
+        C = model.model.dims['input_feats']
+        if request.edit.feats != C:
+            raise ValueError(f'the edit has {request.edit.feats} channels, the model {C}')
 
 
 class RequestBatcher:
@@ -47,7 +151,11 @@ class RequestBatcher:
 
     ``model``: a ``MotionDiffusion`` (its denoiser and its test schedule's configuration are used).  ``sampler`` in ``SAMPLERS``;
     ``steps``: respace the schedule to that many steps (None: the configured schedule).  ``runner`` replaces the model call (tests):
-    ``runner(xf_out [B,Nt,Dt], lengths [B], seeds [B], c [B,Tc,Fc] or None) -> [B, frames, C]``."""
+    ``runner(xf_out [B,Nt,Dt], lengths [B], seeds [B], c [B,Tc,Fc] or None) -> [B, frames, C]``; a batch that holds a request with an
+    ``Edit`` calls it with ``edits=[Edit or None] * B`` too.
+
+    A batch with an edit runs through ``mc_sample_rows`` with uniform tables (every row at walk position k in tick k, draw 1 + k): the
+    path ``ContinuousBatcher`` takes, so a request gets the same bits from both.  Batches without one take the fused loop as before."""
 
     def __init__(self, model, batch, frames, sampler='ddim', steps=None, capacity_factor=0, eta=0.0, order=2, runner=None):
         if sampler not in SAMPLERS:
@@ -73,10 +181,11 @@ class RequestBatcher:
             raise ValueError('submit() takes a Request')
         if request.length > self.frames:
             raise ValueError(f'request of {request.length} frames in a batcher of {self.frames}')
+        _check_edit(self.model, request)
         if request.xf_out is None:
             # one prompt per encoder call: the condition of a request must not depend on what it is encoded beside
             xf = self.model.model.encode_text([request.text], None, None)[0]
-            request = Request(request.length, request.seed, xf_out=xf, c=request.c)
+            request = Request(request.length, request.seed, xf_out=xf, c=request.c, edit=request.edit)
         handle = self._next
         self._next += 1
         self._pending.append((handle, request))
@@ -108,7 +217,8 @@ class RequestBatcher:
             c = None
             if first.c is not None:
                 c = torch.stack([reqs[h].c if h is not None else torch.zeros_like(first.c) for h in rows])
-            pred = self.runner(xf, lengths, seeds, c)
+            edits = [reqs[h].edit if h is not None else None for h in rows]
+            pred = self.runner(xf, lengths, seeds, c, edits=edits) if any(e is not None for e in edits) else self.runner(xf, lengths, seeds, c)
             for b, h in enumerate(rows):
                 if h is not None:
                     results[h] = pred[b, :reqs[h].length]
@@ -125,7 +235,9 @@ class RequestBatcher:
             self._diffusion = build_diffusion(cfg, opt=self.model.opt)
         return self._diffusion
 
-    def _run_model(self, xf_out, lengths, seeds, c):
+    def _run_model(self, xf_out, lengths, seeds, c, edits=None):
+        if edits is not None and any(e is not None for e in edits):
+            return self._run_rows(xf_out, lengths, seeds, c, edits)
         net, diffusion = self.model.model, self._schedule()
         dev = torch.device('cuda', torch.cuda.current_device())
         B, T, C = self.batch, self.frames, net.dims['input_feats']
@@ -142,6 +254,17 @@ class RequestBatcher:
         else:
             out = diffusion.dpm_solver_sample_loop(net, (B, T, C), order=self.order, **common)
         return net.post_process(out)
+
+    def _run_rows(self, xf_out, lengths, seeds, c, edits):
+        """a batch with an edit: ``ContinuousBatcher``'s model call with every row fresh and the whole walk in one call"""
+        rr = _RowsRunner(self)
+        B = self.batch
+        rr.condition(xf_out, lengths, seeds, [True] * B, c, edits=edits)
+        try:
+            rr.advance([[k] * B for k in range(rr.steps)], [None] * B)
+            return rr.result()
+        finally:
+            rr.clear_edits()           # (the context is the model's cached one: the fused loop refuses it while a table is set)
 
 
 class ContinuousBatcher:
@@ -169,8 +292,15 @@ class ContinuousBatcher:
     The context is the model's cached (batch, frames) one: do not interleave another sampler on the same model and shape with a
     running batcher.
 
+    Edits (``Request.edit``): the kept region of an admitted row is uploaded with its admission; rows without an edit, dummy rows and
+    (at the next admission) stale retired rows get an empty one, and the table is cleared when the last running row with an edit
+    retires.  A request without an edit keeps its bits whatever its batchmates carry.
+
     ``runner`` (host tests) replaces the model: an object with ``steps`` and
-      ``condition(xf_out [B,Nt,Dt], lengths [B], seeds [B], fresh [B], c)``  -- rows with ``fresh[b]`` start at draw 0 of ``seeds[b]``
+      ``condition(xf_out [B,Nt,Dt], lengths [B], seeds [B], fresh [B], c)``  -- rows with ``fresh[b]`` start at draw 0 of ``seeds[b]``;
+                                   called with ``edits=[Edit or None] * B`` too (the rows as they stand; those with ``fresh[b]`` are to
+                                   be uploaded) while a running row carries an edit or a table is set
+      ``clear_edits()``                       -- no running row carries an edit any more (only ever called after such a ``condition``)
       ``advance(pos [n][B], scales [B])``     -- n steps, row b of step k at walk position ``pos[k][b]`` (schedule index steps-1-pos)
       ``result()`` -> [B, frames, C]          -- the rows as they stand, post-processed."""
 
@@ -195,6 +325,7 @@ class ContinuousBatcher:
         self._done = {}
         self._next = 0
         self._conditioned = False
+        self._edit_on = False                         # the runner holds an edit table
         self._stale = [False] * self.batch            # rows retired since the last condition call (still holding their old condition)
         self.ticks = 0                                # steps the batch has taken
         self.submitted_at, self.finished_at = {}, {}  # handle -> self.ticks at submit() / at retirement
@@ -206,9 +337,10 @@ class ContinuousBatcher:
             raise ValueError('submit() takes a Request')
         if request.length > self.frames:
             raise ValueError(f'request of {request.length} frames in a batcher of {self.frames}')
+        _check_edit(self.model, request)
         if request.xf_out is None:
             xf = self.model.model.encode_text([request.text], None, None)[0]
-            request = Request(request.length, request.seed, xf_out=xf, c=request.c, guidance_scale=request.guidance_scale)
+            request = Request(request.length, request.seed, xf_out=xf, c=request.c, guidance_scale=request.guidance_scale, edit=request.edit)
         handle = self._next
         self._next += 1
         self._pending.append((handle, request))
@@ -258,9 +390,21 @@ class ContinuousBatcher:
         c = None
         if first.c is not None:
             c = torch.stack([r[1].c if r is not None else torch.zeros_like(first.c) for r in self._rows])
-        self.runner.condition(xf, lengths, seeds, flags, c)
+        edits = [r[1].edit if r is not None else None for r in self._rows]
+        if self._edit_on or any(e is not None for e in edits):
+            self.runner.condition(xf, lengths, seeds, flags, c, edits=edits)
+            self._edit_on = True
+            self._settle_edits()
+        else:
+            self.runner.condition(xf, lengths, seeds, flags, c)
         self._conditioned = True
         self._stale = [False] * self.batch
+
+    def _settle_edits(self):
+        """clear the runner's table once no running row carries an edit"""
+        if self._edit_on and not any(r is not None and r[1].edit is not None for r in self._rows):
+            self.runner.clear_edits()
+            self._edit_on = False
 
     def tick(self, n=1):
         """One round (class docstring); -> the steps the batch advanced by (0: nothing to run)."""
@@ -289,6 +433,7 @@ class ContinuousBatcher:
                 self.finished_at[r[0]] = self.ticks
                 self._rows[b] = None
                 self._stale[b] = True
+        self._settle_edits()
         return n
 
     def run(self):
@@ -318,7 +463,7 @@ class _RowsRunner:
         self.ctx, self.x, self.group = None, None, ()
         self._coefs = {}                              # scale -> the StepCoefs of a whole walk, by walk position
 
-    def condition(self, xf_out, lengths, seeds, fresh, c):
+    def condition(self, xf_out, lengths, seeds, fresh, c, edits=None):
         from . import lib as _lib
         from .engine import _ptr, _stream
         o, net = self.o, self.o.model.model
@@ -338,11 +483,31 @@ class _RowsRunner:
                 self.x = torch.zeros(B, T, C, device=dev)
         else:
             self.ctx.set_condition_rows(xf_out.to(dev), mask, fresh)
+        if edits is not None:
+            self._upload_edits(edits, fresh, dev)
         self.ctx.set_row_seeds(seeds)
         for b, f in enumerate(fresh):
             if f:                                     # x_T of the row: draw 0 of its own stream
                 _lib.check(self.ctx.lib.mc_op_philox_normal(_ptr(self.x[b]), None, T * C, int(seeds[b]) & (2 ** 64 - 1), 0, _stream()),
                            'mc_op_philox_normal')
+
+    def _upload_edits(self, edits, fresh, dev):
+        """the tables of the rows with ``fresh[b]``: the row's edit in model space, or nothing kept.  Into a context that holds no table
+        (the first edit, or the first after a clear) EVERY row is uploaded, each with its own edit or nothing kept: whatever
+        an earlier table left on a row that now runs a request without an edit must not come back with the flag."""
+        o, net = self.o, self.o.model.model
+        B, T, C = o.batch, o.frames, net.dims['input_feats']
+        every = not getattr(self.ctx, 'edit_rows', False)
+        gt = torch.zeros(B, T, C)
+        keep = torch.zeros(B, T, C, dtype=torch.uint8)
+        for b, e in enumerate(edits):
+            if e is not None and (fresh[b] or every):
+                gt[b], keep[b] = e.tables(T, net.pre_process)
+        self.ctx.set_edit_rows(gt.to(dev), keep.to(dev), None if every else fresh)
+
+    def clear_edits(self):
+        if self.ctx is not None:
+            self.ctx.clear_edit_rows()
 
     def _walk_coefs(self, scale):
         o, d = self.o, self.diffusion

@@ -8,6 +8,7 @@ positions with --pose_npy), everything between the condition features and the fi
         [--anim_dir frames/ | --anim_avi clip.avi [--anim_size 1000x1000] [--anim_fps 20]]
         [--smplx_model SMPLX_NEUTRAL.npz --joints_npy joints.npy [--verts_npy verts.npy] [--render_dir frames/ | --render_avi clip.avi [--render_size 960x720]]]
         [--avi_quality 90]  [--sampler ddpm|ddim|dpmpp [--steps N [--spacing time|logsnr]]]  [--seeds a,b,c] [--no_drop]
+        [--edit_npz edit.npz [--keep_frames 0-9,150-195] [--keep_parts lleg,rleg,root]]     (one --text, with --no_drop)
 
 The CLIP tokenizer is not available offline: prompts only name the output file unless the `clip` package is importable
 (then they are tokenized and encoded by the device CLIP tower when the checkpoint carries clip.* weights).
@@ -28,7 +29,7 @@ from motioncraft_amd import postprocess, render, skeleton, synthetic, video   # 
 from motioncraft_amd.checkpoint import load_checkpoint          # noqa: E402
 
 
-def parse_args():
+def parse_args(argv=None):
     p = argparse.ArgumentParser(description='motioncraft_amd sampling')
     p.add_argument('config')
     p.add_argument('checkpoint')
@@ -80,7 +81,114 @@ def parse_args():
     p.add_argument('--steps', type=int, default=None, metavar='N', help='with --sampler dpmpp: respace the test schedule to N steps')
     p.add_argument('--spacing', choices=['time', 'logsnr'], default=None,
                    help='with --sampler dpmpp --steps N: uniform in the timestep (ddimN, default) or in the log-SNR (logsnrN)')
-    return p.parse_args()
+    # an edited motion: frames / channels of the ONE sample are given, the rest is generated around them.  The file
+    # holds `motion` [n, C] in the space of the saved result and `keep` [n, C], or `keep_frames` [k] and / or `keep_channels` [m] (one of
+    # them alone: all channels of the frames / the channels on all frames; both: their product); the two flags replace the file's mask.
+    # Sample quality of edited motions with released weights is unmeasured.
+    p.add_argument('--edit_npz', default=None, metavar='FILE', help='npz with motion [n,C] and keep [n,C] (or keep_frames / keep_channels): '
+                   'the given part of the sample; one --text, with --no_drop')
+    p.add_argument('--keep_frames', default=None, metavar='A-B,C', help='with --edit_npz: the given frames, e.g. 0-9,150-195')
+    p.add_argument('--keep_parts', default=None, metavar='P,Q', help='with --edit_npz: the given body parts, e.g. lleg,rleg,root')
+    return p.parse_args(argv)
+
+
+def parse_frames(spec, n):
+    """'0-9,150-195' -> the sorted frame list, every frame in [0, n)"""
+    out = set()
+    for part in spec.split(','):
+        try:
+            lo, _, hi = part.strip().partition('-')
+            lo, hi = int(lo), int(hi) if hi else int(lo)
+        except ValueError:
+            raise SystemExit(f'--keep_frames takes ranges like 0-9,150-195, got {spec!r}')
+        if not 0 <= lo <= hi < n:
+            raise SystemExit(f'--keep_frames {part!r} outside the {n} frames of the edit\'s motion')
+        out.update(range(lo, hi + 1))
+    return sorted(out)
+
+
+def check_edit_args(a):
+    """--edit_npz against the options it cannot run beside (before anything is built)"""
+    if a.edit_npz is None:
+        if a.keep_frames is not None or a.keep_parts is not None:
+            raise SystemExit('--keep_frames / --keep_parts belong to --edit_npz FILE')
+        return
+    if a.repaint or a.overlap_len or a.same_overlap_noisy:
+        raise SystemExit('--edit_npz edits ONE window: the long-sequence window modes (--repaint, --overlap_len, --same_overlap_noisy) keep '
+                         'their own outpainting')
+    if a.graph:
+        raise SystemExit('--edit_npz does not run under --graph (edited rows are not replayed)')
+    if len(a.text) != 1:
+        raise SystemExit(f'--edit_npz edits one sample, got {len(a.text)} prompts')
+    if not a.no_drop:
+        raise SystemExit('--edit_npz runs the request at MoE capacity factor 0: pass --no_drop')
+    if a.clip_feat:
+        raise SystemExit('--edit_npz takes the prompt, --xf_out or --random-condition, not --clip_feat')
+
+
+def load_edit(a, dataset, C, mean=None, std=None):
+    """-> serve.Edit from --edit_npz / --keep_frames / --keep_parts; ``mean`` / ``std`` (--mean / --std): the motion is normalised with
+    them, (motion - mean) / (std + 1e-9), like the saved result is de-normalised"""
+    from motioncraft_amd.serve import Edit
+    z = np.load(a.edit_npz)
+    if 'motion' not in z:
+        raise SystemExit(f'{a.edit_npz}: no array `motion`')
+    motion = np.asarray(z['motion'], dtype=np.float32)
+    if motion.ndim != 2 or motion.shape[1] != C:
+        raise SystemExit(f'{a.edit_npz}: motion is {motion.shape}, expected [n, {C}]')
+    n = motion.shape[0]
+    if n > a.motion_length[0]:
+        raise SystemExit(f'{a.edit_npz}: motion has {n} frames, --motion_length is {a.motion_length[0]}')
+    if mean is not None and std is not None:
+        motion = ((motion - mean) / (std + 1e-9)).astype(np.float32)
+    motion = torch.from_numpy(motion)
+    if a.keep_frames is not None or a.keep_parts is not None:
+        frames = parse_frames(a.keep_frames, n) if a.keep_frames is not None else None
+        if a.keep_parts is not None:
+            try:
+                return Edit.parts(motion, [v.strip() for v in a.keep_parts.split(',')], dataset, frames)
+            except ValueError as e:
+                raise SystemExit(f'--keep_parts: {e}')
+        return Edit.keyframes(motion, frames)
+    if 'keep' in z:
+        keep = np.asarray(z['keep'])
+        if keep.shape != motion.shape:
+            raise SystemExit(f'{a.edit_npz}: keep is {keep.shape}, motion {tuple(motion.shape)}')
+        keep = torch.from_numpy(keep != 0)
+    elif 'keep_frames' in z or 'keep_channels' in z:
+        fr = np.asarray(z['keep_frames']).astype(np.int64).reshape(-1) if 'keep_frames' in z else np.arange(n)
+        ch = np.asarray(z['keep_channels']).astype(np.int64).reshape(-1) if 'keep_channels' in z else np.arange(C)
+        if fr.size == 0 or ch.size == 0 or fr.min() < 0 or fr.max() >= n or ch.min() < 0 or ch.max() >= C:
+            raise SystemExit(f'{a.edit_npz}: keep_frames / keep_channels outside motion {tuple(motion.shape)}')
+        keep = torch.zeros(n, C, dtype=torch.bool)
+        keep[torch.from_numpy(fr)[:, None], torch.from_numpy(ch)[None, :]] = True
+    else:
+        raise SystemExit(f'{a.edit_npz}: no mask -- keep, keep_frames / keep_channels, or --keep_frames / --keep_parts')
+    try:
+        return Edit(motion, keep)
+    except ValueError as e:
+        raise SystemExit(f'{a.edit_npz}: {e}')
+
+
+def run_edit(model, a, edit, T, dev):
+    """the one request through serve.RequestBatcher at capacity factor 0 -> what model(**kw) returns for it"""
+    from motioncraft_amd.serve import Request, RequestBatcher
+    dims = model.model.dims
+    seed = int(a.seeds.split(',')[0], 0) if a.seeds is not None else a.seed
+    if a.xf_out:
+        cond = dict(xf_out=torch.from_numpy(np.load(a.xf_out)).float()[0].to(dev))
+    elif a.random_condition is not None:
+        g = torch.Generator().manual_seed(a.random_condition)
+        cond = dict(xf_out=torch.nn.functional.layer_norm(torch.randn(dims['Nt'], dims['Dt'], generator=g), (dims['Dt'],)).to(dev))
+    else:
+        cond = dict(text=a.text[0])
+    # the schedule is the model's (apply_sampler has respaced it); eta = 0 and order 2 are what MotionDiffusion.forward samples with
+    bt = RequestBatcher(model, batch=1, frames=T, sampler=model.inference_type, capacity_factor=0, eta=0.0, order=2)
+    h = bt.submit(Request(length=a.motion_length[0], seed=seed & (2 ** 64 - 1), edit=edit, **cond))
+    pred = bt.run()[h]
+    out = torch.zeros(T, dims['input_feats'])
+    out[:pred.shape[0]] = pred.cpu()
+    return [{'pred_motion': out}]
 
 
 def apply_sampler(cfg, a):
@@ -109,6 +217,7 @@ def apply_sampler(cfg, a):
 def main():
     a = parse_args()
     assert len(a.text) == len(a.motion_length)
+    check_edit_args(a)
     cfg = mc.Config.fromfile(a.config)
     cfg.model['opt'] = a
     apply_sampler(cfg, a)
@@ -153,34 +262,37 @@ def main():
     mask = torch.zeros(n, T, device=dev)
     for i, m in enumerate(a.motion_length):
         mask[i, :m] = 1
-    if a.seeds is not None:
-        try:
-            seeds = [int(v, 0) for v in a.seeds.split(',')]
-        except ValueError:
-            raise SystemExit(f'--seeds takes comma-separated integers, got {a.seeds!r}')
-        if len(seeds) != n:
-            raise SystemExit(f'--seeds names {len(seeds)} seeds for {n} samples')
-        ikw = dict(seeds=seeds)
-    else:
-        ikw = dict(generator=torch.Generator(device=dev).manual_seed(a.seed))
-    if a.no_drop:
-        ikw['capacity_factor'] = 0
-    if a.graph:
-        ikw['graph'] = True
-    kw = dict(motion=torch.zeros(n, T, C, device=dev), motion_mask=mask,
-              motion_length=torch.tensor(a.motion_length, device=dev).long(), num_intervals=n,
-              motion_metas=[{'text': t} for t in a.text], inference_kwargs=ikw)
-    if a.xf_out:
-        kw['xf_out'] = torch.from_numpy(np.load(a.xf_out)).float().to(dev)
-    elif a.clip_feat:
-        kw['clip_feat'] = torch.from_numpy(np.load(a.clip_feat)).float().to(dev)
-    elif a.random_condition is not None:
-        g = torch.Generator().manual_seed(a.random_condition)
-        kw['xf_out'] = torch.nn.functional.layer_norm(torch.randn(n, dims['Nt'], dims['Dt'], generator=g), (dims['Dt'],)).to(dev)
-    out = model(**kw)
-    os.makedirs(a.out, exist_ok=True)
     mean = np.load(a.mean) if a.mean else None
     std = np.load(a.std) if a.std else None
+    if a.edit_npz:
+        out = run_edit(model, a, load_edit(a, dims.get('dataset', 'motionx'), C, mean, std), T, dev)
+    else:
+        if a.seeds is not None:
+            try:
+                seeds = [int(v, 0) for v in a.seeds.split(',')]
+            except ValueError:
+                raise SystemExit(f'--seeds takes comma-separated integers, got {a.seeds!r}')
+            if len(seeds) != n:
+                raise SystemExit(f'--seeds names {len(seeds)} seeds for {n} samples')
+            ikw = dict(seeds=seeds)
+        else:
+            ikw = dict(generator=torch.Generator(device=dev).manual_seed(a.seed))
+        if a.no_drop:
+            ikw['capacity_factor'] = 0
+        if a.graph:
+            ikw['graph'] = True
+        kw = dict(motion=torch.zeros(n, T, C, device=dev), motion_mask=mask,
+                  motion_length=torch.tensor(a.motion_length, device=dev).long(), num_intervals=n,
+                  motion_metas=[{'text': t} for t in a.text], inference_kwargs=ikw)
+        if a.xf_out:
+            kw['xf_out'] = torch.from_numpy(np.load(a.xf_out)).float().to(dev)
+        elif a.clip_feat:
+            kw['clip_feat'] = torch.from_numpy(np.load(a.clip_feat)).float().to(dev)
+        elif a.random_condition is not None:
+            g = torch.Generator().manual_seed(a.random_condition)
+            kw['xf_out'] = torch.nn.functional.layer_norm(torch.randn(n, dims['Nt'], dims['Dt'], generator=g), (dims['Dt'],)).to(dev)
+        out = model(**kw)
+    os.makedirs(a.out, exist_ok=True)
     if dims.get('dataset', 'motionx') == 'motionx':
         pred = torch.stack([o['pred_motion'] for o in out]).to(dev).contiguous()
         post = postprocess.postprocess_smplx_stitched(pred, a.motion_length, mean, std)          # what save_smplx_npz writes

@@ -15,7 +15,11 @@ after one warm-up:
             whole walk) and through serve.ContinuousBatcher (a request takes an open row at the next tick): requests/s and the mean
             and maximum ticks from arrival to completion
 
-usage: serve_time.py [--small] [--batch B] [--requests R] [--steps N] [--reps K] [--only routing,noise,batcher,rows,arrivals]
+  edits      one mc_sample_rows tick (DDIM, capacity factor 0, noise drawn from the seed table) in three versions,
+            alternated in one process: (a) no edit table, (b) a table whose keep bytes are all zero, (c) a table with 25 % of the
+            elements kept; and mc_ctx_set_edit_rows for one fresh row beside mc_ctx_set_condition_rows
+
+usage: serve_time.py [--small] [--batch B] [--requests R] [--steps N] [--reps K] [--only routing,noise,batcher,rows,arrivals,edits]
   --small: the reduced test config (24 frames) instead of the 0.125b architecture (196 frames)"""
 import argparse
 import os
@@ -161,6 +165,41 @@ if 'rows' in only:
     for name in list(arms) * 2:                    # (twice, interleaved)
         med, lo, hi = median_of(lambda: events_ms(arms[name], 5))
         print(f'B={B} {name:32s}: median {med:8.3f} ms   min {lo:8.3f}   max {hi:8.3f}   (5 calls per run)', flush=True)
+    ctx.close()
+
+if 'edits' in only:
+    x, xf, mask, _ = inputs(B)
+    dd = build_diffusion(dict(schedule, respace=f'ddim{a.steps}'))
+    ctx = arch.model.native.context(B, T, max_steps=a.steps)
+    ctx.set_capacity_factor(0)
+    ctx.set_timesteps(dd.timestep_map)
+    ctx.set_condition(xf, mask)
+    ctx.set_row_seeds(list(range(100, 100 + B)))
+    step = a.steps // 2
+    ck = dd.step_coefs(step, 'ddim', arch.model.cfg_scale)
+    g = torch.Generator().manual_seed(3)
+    gt = torch.randn(B, T, C, generator=g).cuda()
+    keep0 = torch.zeros(B, T, C, dtype=torch.uint8, device='cuda')
+    keep25 = (torch.rand(B, T, C, generator=g) < 0.25).to(torch.uint8).cuda()
+    xd = x.clone()
+    fresh1 = [True] + [False] * (B - 1)
+    tick = lambda: ctx.sample_rows(xd, [[step] * B], [[ck] * B], draws=[[1] * B])
+
+    def version(keep):
+        if keep is None:
+            ctx.clear_edit_rows()
+        else:
+            ctx.set_edit_rows(gt, keep)
+        return median_of(lambda: events_ms(tick, 5))
+    arms = {'(a) mc_sample_rows tick, no table': lambda: version(None),
+            '(b) ... keep all zero': lambda: version(keep0),
+            '(c) ... 25 % kept': lambda: version(keep25),
+            'mc_ctx_set_edit_rows (one fresh row)': lambda: median_of(lambda: events_ms(lambda: ctx.set_edit_rows(gt, keep25, fresh1), 5)),
+            'mc_ctx_set_condition_rows': lambda: (ctx.clear_edit_rows(), median_of(lambda: events_ms(lambda: ctx.set_condition_rows(xf, mask, fresh1), 5)))[1]}
+    for name in list(arms) * 3:                    # (three rounds, alternated: the spread of equal settings is the machine's drift)
+        med, lo, hi = arms[name]()
+        print(f'B={B} {name:38s}: median {med:8.3f} ms   min {lo:8.3f}   max {hi:8.3f}   (5 calls per run)', flush=True)
+    ctx.clear_edit_rows()
     ctx.close()
 
 if 'arrivals' in only:
