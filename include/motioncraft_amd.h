@@ -315,8 +315,9 @@ int mc_ctx_set_seams(mc_ctx* c, int32_t overlap, const int32_t* first_frame_host
  * mc_denoise_rows: mc_denoise (full model, both decoded halves in out2_dev [2B,T,C], no combine) with row b at step_index_host[b].
  * mc_ctx_set_condition_rows: mc_ctx_set_condition (the whole batch's text K/V are recomputed; at capacity factor 0 an unchanged row
  *   keeps its bits), but only rows with fresh_host[b] != 0 lose their history flag.
- * NOT in this mode: graph capture or replay (a context that holds a captured graph, or a capturing stream: MC_ERR_STATE), a seam table
- * (MC_ERR_STATE), the inpaint and seeded steps (no rows entry). */
+ * NOT in this mode: graph capture or replay (a context that holds a captured graph, or a capturing stream: MC_ERR_STATE), the
+ * whole-batch seam table of mc_ctx_set_seams (MC_ERR_STATE), the inpaint and seeded steps (no rows entry).  The windows of a long
+ * request ARE rows of this mode: mc_ctx_set_seam_rows below couples them per row. */
 int mc_sample_rows(mc_ctx* c, float* x_dev, int32_t num_ticks, const int32_t* step_index_host, const mc_step_coefs* coefs_host,
                    const uint64_t* draw_host, const float* noise_dev, float* x0_dev, void* stream);
 int mc_denoise_rows(mc_ctx* c, const float* x_t_dev, const int32_t* step_index_host, float* out2_dev, void* stream);
@@ -343,6 +344,33 @@ int mc_ctx_set_condition_rows(mc_ctx* c, const float* xf_out_dev, const float* m
  * take either noise source).  Every refusal leaves the context as it was.  The table does not touch the multistep history flags, and
  * mc_ctx_set_condition / mc_ctx_set_condition_rows do not touch the table. */
 int mc_ctx_set_edit_rows(mc_ctx* c, const float* gt_dev, const uint8_t* keep_dev, const uint8_t* fresh_host, void* stream);
+
+/* Long requests among the rows: the windows of a request longer than T frames are request rows of
+ * mc_sample_rows, coupled on their shared frames like the windows of mc_ctx_set_seams -- but per row: any rows of the batch, each
+ * request at its own step and guidance scale, beside short requests.  Row b shows global frames [first_frame_host[b],
+ * first_frame_host[b] + T) of its request; right_host[b] is the row that holds the request's NEXT window (any row, lower or higher
+ * than b), or -1.  Windows overlap by `overlap` frames, 0 < 2 overlap <= T: the last `overlap` frames of row b are the first of row
+ * right_host[b].  MC_ERR_ARG, the context unchanged: right[b] outside [-1, B) or == b; a row named by two rows; first_frame < 0 or
+ * first_frame[right[b]] != first_frame[b] + T - overlap; a chain that does not end; a weight outside [0, 1]; overlap outside the range.
+ * While a table is set, the sampler update of mc_sample_rows blends the two x0 predictions of a shared frame f,
+ *     x0 = w[f] x0_right + (1 - w[f]) x0_left,     w = weight_host[overlap], or NULL: w[f] = (f + 1) / (overlap + 1),
+ * computes the update once under the LEFT row's table entry and gives both rows the same x_prev / x0 / history; every other element
+ * gets the bits it gets without a table.  The two rows of a seam must carry, in every tick of a call, the same step index, the same
+ * coefficient bytes, the same draw number and the same history flag, and (noise_dev == NULL) the same seed: mc_sample_rows checks this
+ * before its first launch (MC_ERR_ARG).
+ * Noise with noise_dev == NULL, the request-global counter rule: element r of row b in draw d is element first_frame[b] * C + r of
+ * mc_op_philox_normal(n, seed = seeds[b], draw = d) -- key seeds[b], counter ((first_frame[b] * C + r) / 4, d), 64-bit.  The two copies
+ * of a shared frame draw the same normal by construction; a row with first_frame 0 draws what it draws without a table.  x_T of a long
+ * request is draw 0 of that field gathered into its windows (the caller's part, as in mc_ctx_set_seams).  With noise_dev the owner
+ * reads its own (the left row's) element.
+ * The table lives in the context, is uploaded on `stream` (the call synchronises it) and is replaced as a whole by every call;
+ * overlap == 0 clears it (the other arguments are ignored).  Setting or clearing touches no multistep history flag.
+ * State: with a captured graph, an edit table or a seam table (mc_ctx_set_seams) in the context, setting a table is MC_ERR_STATE.
+ * While a table is set, mc_ctx_set_seams, mc_ctx_set_edit_rows, mc_ctx_graph_capture, mc_ctx_graph_step, mc_sample_step,
+ * mc_sample_loop, mc_sample_step_inpaint and mc_sample_step_seeded return MC_ERR_STATE.  Every refusal leaves the context as it was.
+ * B * T * C < 2^31 and T * C >= 4. */
+int mc_ctx_set_seam_rows(mc_ctx* c, int32_t overlap, const int32_t* right_host, const int32_t* first_frame_host, const float* weight_host,
+                         void* stream);
 
 /* hipGraph replay of mc_sample_step (BASELINE.json configs[4] "hipGraph-captured 50-step DDIM"): ONE graph serves every step
  * of the schedule -- the step index is a device-side integer, the FiLM tables and the sampler coefficients are addressed
@@ -512,6 +540,17 @@ int mc_op_sampler_seam(const float* x_t_dev, const float* out_text_dev, const fl
                        uint64_t draw, float* x0_hist_dev, float* x_prev_dev, float* x0_dev, int32_t B, int32_t T, int32_t C,
                        int32_t overlap, const int32_t* first_frame_host, const float* weight_host, const mc_step_coefs* coefs,
                        void* stream);
+
+/* the seam-coupled rows update without a context (sampler_seam_rows_k; see mc_ctx_set_seam_rows for the table rules, the blend and the
+ * noise): operands [B, T, C], coefs_host [B] one entry per row (one mode for all rows; the two rows of a seam carry equal entries:
+ * MC_ERR_ARG otherwise), x0 = out_text + out_none as in mc_op_sampler_rows.  Modes 0 / 1 take noise_dev, or seeds_host [B] +
+ * draw_host [B] (drawn in the kernel; the two sources exclude each other, and the rows of a seam share seed and draw number).  Mode 2:
+ * x0_hist_dev in-out (read where the row's eta != 0), no noise.  x_prev_dev may alias x_t_dev, x0_dev may be NULL.  Operands that are
+ * not all 16-byte aligned take the element form of the kernel.  Synchronises. */
+int mc_op_sampler_seam_rows(const float* x_t_dev, const float* out_text_dev, const float* out_none_dev, const float* noise_dev,
+                            const uint64_t* seeds_host, const uint64_t* draw_host, float* x0_hist_dev, float* x_prev_dev, float* x0_dev,
+                            int32_t B, int32_t T, int32_t C, int32_t overlap, const int32_t* right_host, const int32_t* first_frame_host,
+                            const float* weight_host, const mc_step_coefs* coefs_host, void* stream);
 
 /* Result post-processing of the 322-d motion.  pred_dev [B,T,322] normalised; lengths_dev [B]
  * int32 valid frames (NULL = T); mean/std_dev [322] fp64; taps_dev [4][MC_POST_MAXTAP] fp64 = normalised Gaussian

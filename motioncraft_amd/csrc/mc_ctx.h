@@ -159,6 +159,15 @@ struct mc_ctx {
     float* edit_gt = nullptr;
     uint8_t* edit_keep = nullptr;
     bool edit_set = false;
+    // seam-coupled windows in rows mode (mc_ctx_set_seam_rows): one device block, allocated by the first call
+    // that sets a table and replaced as a whole by every later one -- [B] SeamRow entries, then [T / 2] right-window weights.  While
+    // seam_rows_ov > 0 sampler_update launches sampler_seam_rows_k in rows mode and every entry without a rows form refuses
+    // (seam_rows_refuse).  seam_rows_right is the host's copy of right[]: mc_sample_rows checks that the two rows of a seam carry equal
+    // entries; row_seeds_host (mc_ctx_set_row_seeds) lets it check that they carry one seed.
+    SeamRow* seam_rows_tab = nullptr;
+    int seam_rows_ov = 0;
+    std::vector<int> seam_rows_right;
+    std::vector<uint64_t> row_seeds_host;
     int prec = MC_PREC_F32;     // MFMA operand precision of the per-step GEMM-shaped kernels (mc_ctx_set_precision)
     int* cap_idx = nullptr;      // [NL][2N] routing capture (tests): expert ids ...
     float* cap_w = nullptr;      // ... and combine weights (0 = dropped) of every layer
@@ -194,7 +203,8 @@ struct X0Parts {
 int denoise_combined(mc_ctx* c, const float* x_t, int32_t step, const mc_step_coefs* k, void* stream, X0Parts* x0, const SeedArgs* seed = nullptr);
 // the sampler update behind denoise_combined, its kernel picked by the step's mode (under capture: by the graph's table) -- sampler_update_k
 // (modes 0 / 1; noise or rng) or sampler_multistep_k (mode 2; x0_hist must be allocated, the caller keeps the history-valid flag); with
-// a seam table set (mc_ctx_set_seams) sampler_seam_k in every mode
+// a seam table set (mc_ctx_set_seams) sampler_seam_k in every mode; in rows mode the row kernels, the edit kernels under an edit table,
+// or sampler_seam_rows_k in every mode under a row seam table (mc_ctx_set_seam_rows)
 int sampler_update(mc_ctx* c, const float* x_t, const X0Parts& x0p, const mc_step_coefs* k, const float* noise, float* x_prev, float* x0,
                    hipStream_t s, const RngArgs* rng = nullptr, const PadOut* pad = nullptr);
 #pragma GCC visibility pop

@@ -96,6 +96,17 @@ struct SeamTab { const int* flags = nullptr; const float* w = nullptr; int T = 0
 int mc_launch_sampler_seam(const float* x_t, const float* out_text, const float* out_none, const float* noise, float* x0_hist,
                            float* x_prev, float* x0_out, int B, SamplerCoefs c, const SeamTab& st, hipStream_t s,
                            const RngArgs* rng = nullptr, const PadOut* pad = nullptr, const RowKeys* rows = nullptr);
+// Seam-coupled update in the per-row path (sampler_seam_rows_k; all three modes, `mode` the launch's one): the
+// rows update of mc_launch_sampler_update_rows / _multistep_rows with sampler_seam_k's blend between row b and row rows[b].right (ANY
+// row, or -1).  rows [B] and w [ov] on the device; the caller guarantees what mc_ctx_set_seam_rows checks (has_left of a row that is
+// some row's right neighbour and of no other, first frames a stride apart along a chain, equal coefficient entries on both rows of a
+// seam).  noise == nullptr (modes 0 / 1): drawn from keys[b] at draw rt.draw[b], counter ((first_frame[b] C + row-local element) / 4,
+// draw) -- the request-global counter rule.  n = B T C < 2^31 and T C >= 4.
+struct alignas(16) SeamRow { int right, has_left, first_frame, pad; };      // (16-byte aligned: a row's entry is one vector load)
+struct SeamRowsTab { const SeamRow* rows = nullptr; const float* w = nullptr; int T = 0, C = 0, ov = 0; };
+int mc_launch_sampler_seam_rows(const float* x_t, const float* out_text, const float* out_none, const float* noise, float* x0_hist,
+                                float* x_prev, float* x0_out, float tc, float nc, const RowTab& rt, const SeamRowsTab& st, int mode,
+                                hipStream_t s, const RowKeys* keys = nullptr, const PadOut* pad = nullptr);
 // out [B][rk.TC] = draw rng.draw_* of every row's own stream (rng's seed is ignored)
 int mc_launch_philox_rows_fill(float* out, int B, RowKeys rk, RngArgs rng, hipStream_t s);
 // out[n] = the normals / bits[n] = the raw 32-bit words of draw `rng` (either may be null)

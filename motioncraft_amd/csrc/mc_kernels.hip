@@ -819,6 +819,129 @@ __global__ __launch_bounds__(256) void sampler_seam_k(const float* x_t, const fl
     }
 }
 
+// ---- seam-coupled windows in the per-row path (mc_ctx_set_seam_rows) ----
+// sampler_seam_k's blend and ownership over sampler_update_rows_k's per-row entries: a long request takes ANY rows of the batch as its
+// windows.  Row b's entry of the table (SeamRow, 16-byte aligned: ONE load per group, no dependent second one; gfx950: global_load_dwordx3, the words in use) names its right neighbour right[b] (any
+// row, lower or higher, or -1), whether it has a left one, and the global frame its frame 0 shows.  A tail element of a row with a right
+// neighbour is the seam's owner: x0 = fmaf(w, x0_right, (1 - w) x0_left) over the two cfg_elem results, the update under the OWNER's
+// row entry (the host checked both rows of a seam carry equal entries), stored to both rows (x_prev, x0_out, hist, xpad); the right
+// element is e + (right[b] - b) TC - tailC.  Head elements of a row with a left neighbour are skipped by their own thread.
+// In place (x_prev == x_t): a thread reads its own x_t / hist elements before it writes them, and the only foreign elements it writes
+// are head elements, which NO thread reads (their own thread skips them; 2 ov <= T: a head element is never a tail element) -- that does
+// not depend on the sign of right[b] - b, so a right neighbour at a lower row index changes nothing.
+// Noise (RNG): the request-global counter rule -- element r of row b is element g = first_frame[b] C + r (64-bit) of the request's
+// stream: key keys[b] (every row of a request carries the request's seed), counter (g / 4, draw[b]), lane g % 4.  The two copies of a
+// shared frame have the same g, so they would draw the same normal; a row with first_frame 0 draws what philox_rows4x gives it.
+// Flat groups of four, VEC rule, straddle rule and PadOut as in sampler_update_rows_k; the index arithmetic is 32-bit (the launcher
+// requires n < 2^31: one unsigned division per group).  Groups that touch no overlap region keep f32x4 loads and stores, the others go
+// element by element.  The mode is launch-uniform (ms: mode 2; modes 0 / 1 through sampler_elem on the row's entry); the history is
+// read only where the row's k1 != 0.  No LDS, no atomics.
+__device__ __forceinline__ f32x4 philox_rows4g(uint32_t i, uint32_t n, RowKeys rk, const uint64_t* __restrict__ draw,
+                                               const SeamRow* __restrict__ rows, int C, int first0) {
+    uint32_t b = i / (uint32_t)rk.TC;
+    int r = (int)(i - b * (uint32_t)rk.TC);
+    RngArgs rng;
+    f32x4 z = {0.f, 0.f, 0.f, 0.f}, cur = z;
+    long cb = -1, cc = -1;
+    long g = (long)first0 * C + r;               // (first0: first_frame of the group's first row, from the entry the caller holds)
+    for (int j = 0; j < 4 && i + j < n; ++j) {
+        if ((long)b != cb || (g >> 2) != cc) {
+            cb = b; cc = g >> 2;
+            const uint64_t dr = draw[b];
+            rng.seed_lo = rk.keys[2 * b]; rng.seed_hi = rk.keys[2 * b + 1];
+            rng.draw_lo = (uint32_t)dr; rng.draw_hi = (uint32_t)(dr >> 32);
+            cur = philox_normal4(cc, rng);
+        }
+        const int l = (int)(g & 3);
+        z[j] = l == 0 ? cur[0] : l == 1 ? cur[1] : l == 2 ? cur[2] : cur[3];
+        ++g;
+        if (++r == rk.TC) { r = 0; ++b; if (i + j + 1 < n) g = (long)rows[b].first_frame * C; }
+    }
+    return z;
+}
+
+template <bool RNG, bool VEC>
+__global__ __launch_bounds__(256) void sampler_seam_rows_k(const float* x_t, const float* __restrict__ o_text,
+                                                           const float* __restrict__ o_none, const float* __restrict__ noise,
+                                                           float* hist, float* x_prev, float* x0_out, uint32_t n, float tc, float nc,
+                                                           const SamplerCoefs* __restrict__ tab, RowKeys rk,
+                                                           const uint64_t* __restrict__ draw, SeamRowsTab st, int ms, PadOut po) {
+    const int TC = rk.TC, headC = st.ov * st.C, tailC = (st.T - st.ov) * st.C;
+    const uint32_t ngroups = (n + 3) >> 2;
+    for (uint32_t gi = blockIdx.x * blockDim.x + threadIdx.x; gi < ngroups; gi += gridDim.x * blockDim.x) {
+        const uint32_t i = gi * 4;
+        uint32_t b = i / (uint32_t)TC;
+        int r = (int)(i - b * (uint32_t)TC);
+        const bool whole = i + 4 <= n;
+        SeamRow sr = st.rows[b];
+        // does the group touch an overlap region?  Its elements of row b are [r, min(r + 3, TC - 1)]; a straddling whole group goes on
+        // with elements [0, r + 3 - TC] of row b + 1 (TC >= 4: two rows at the most)
+        bool any = (sr.has_left && r < headC) || (sr.right >= 0 && (r + 3 >= tailC));
+        if (whole && r + 4 > TC) {
+            const SeamRow s1 = st.rows[b + 1];
+            any = any || s1.has_left || (s1.right >= 0 && r + 3 - TC >= tailC);
+        }
+        SamplerCoefs c = row_coefs(tab, b, tc, nc);
+        SamplerDerived d = sampler_derive(c);
+        f32x4 nz = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (RNG) { if (!ms) nz = philox_rows4g(i, n, rk, draw, st.rows, st.C, sr.first_frame); }
+        if (VEC && whole && !any) {
+            const f32x4 x = *reinterpret_cast<const f32x4*>(x_t + i);
+            const f32x4 a = *reinterpret_cast<const f32x4*>(o_text + i), bb = *reinterpret_cast<const f32x4*>(o_none + i);
+            f32x4 hv = {0.f, 0.f, 0.f, 0.f};
+            if (ms) hv = *reinterpret_cast<const f32x4*>(hist + i);
+            else if constexpr (!RNG) nz = *reinterpret_cast<const f32x4*>(noise + i);
+            f32x4 out, x0v;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                x0v[j] = cfg_elem(a[j], bb[j], c);
+                out[j] = ms ? multistep_elem(x[j], x0v[j], c.eta != 0.f ? hv[j] : 0.f, c.c2, c.c1, c.eta) : sampler_elem(x[j], x0v[j], nz[j], c, d);
+                if (j < 3 && ++r == TC) { r = 0; ++b; c = row_coefs(tab, b, tc, nc); d = sampler_derive(c); }
+            }
+            *reinterpret_cast<f32x4*>(x_prev + i) = out;
+            if (ms) *reinterpret_cast<f32x4*>(hist + i) = x0v;
+            if (x0_out) *reinterpret_cast<f32x4*>(x0_out + i) = x0v;
+            if (po.xpad) {
+                uint32_t row = i / (uint32_t)po.C;
+                int col = (int)(i - row * (uint32_t)po.C);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    po.xpad[(long)row * po.Cp + col] = out[j];
+                    if (++col == po.C) { col = 0; ++row; }
+                }
+            }
+        } else {
+            for (int j = 0; j < 4 && i + j < n; ++j) {
+                const uint32_t e = i + j;
+                if (!(sr.has_left && r < headC)) {               // (head: written by the left neighbour's tail thread)
+                    float x0 = cfg_elem(o_text[e], o_none[e], c);
+                    long er = -1;
+                    if (sr.right >= 0 && r >= tailC) {           // the seam's owner: (right[b], f, ch)
+                        er = (long)e + ((long)sr.right - (long)b) * TC - tailC;
+                        const float w = st.w[(r - tailC) / st.C];
+                        const float x0r = cfg_elem(o_text[er], o_none[er], c);
+                        x0 = fmaf(w, x0r, __fmul_rn(__fsub_rn(1.f, w), x0));
+                    }
+                    float o;
+                    if (ms) o = multistep_elem(x_t[e], x0, c.eta != 0.f ? hist[e] : 0.f, c.c2, c.c1, c.eta);
+                    else o = sampler_elem(x_t[e], x0, RNG ? nz[j] : noise[e], c, d);
+                    x_prev[e] = o;
+                    if (ms) hist[e] = x0;
+                    if (x0_out) x0_out[e] = x0;
+                    if (po.xpad) po.xpad[(long)(e / (uint32_t)po.C) * po.Cp + e % (uint32_t)po.C] = o;
+                    if (er >= 0) {
+                        x_prev[er] = o;
+                        if (ms) hist[er] = x0;
+                        if (x0_out) x0_out[er] = x0;
+                        if (po.xpad) po.xpad[er / po.C * po.Cp + er % po.C] = o;
+                    }
+                }
+                if (e + 1 < n && ++r == TC) { r = 0; ++b; sr = st.rows[b]; c = row_coefs(tab, b, tc, nc); d = sampler_derive(c); }
+            }
+        }
+    }
+}
+
 // the same draws written to memory (tests; callers that want the loop's noise stream)
 __global__ __launch_bounds__(256) void philox_fill_k(float* __restrict__ out, uint32_t* __restrict__ bits, long n, RngArgs rng) {
     const long ngroups = (n + 3) >> 2;
@@ -1260,6 +1383,38 @@ int mc_launch_sampler_seam(const float* x_t, const float* out_text, const float*
     } else if (dev_rng) { if (vec) MC_SS(true, true); else MC_SS(true, false); }
     else { if (vec) MC_SS(false, true); else MC_SS(false, false); }
 #undef MC_SS
+    MC_LAUNCH_CHECK();
+    return MC_OK;
+}
+
+int mc_launch_sampler_seam_rows(const float* x_t, const float* out_text, const float* out_none, const float* noise, float* x0_hist,
+                                float* x_prev, float* x0_out, float tc, float nc, const RowTab& rt, const SeamRowsTab& st, int mode,
+                                hipStream_t s, const RowKeys* keys, const PadOut* pad) {
+    MC_REQUIRE(x_t && out_text && out_none && x_prev && rt.coefs && rt.B > 0 && st.rows && st.w, "seam rows update: null operand");
+    MC_REQUIRE(st.T > 0 && st.C > 0 && st.ov > 0 && 2 * st.ov <= st.T, "seam rows update: overlap %d outside (0, %d / 2]", st.ov, st.T);
+    MC_REQUIRE(mode >= 0 && mode <= 2, "seam rows update: unknown sampler mode %d", mode);
+    const long nl = (long)rt.B * st.T * st.C, TCl = (long)st.T * st.C;
+    MC_REQUIRE(nl <= 0x7fffffffL && TCl >= 4, "seam rows update: %d rows of %d x %d floats (the kernel indexes in 32 bits; a row holds at least 4)", rt.B, st.T, st.C);
+    const int TC = (int)TCl;
+    const bool ms = mode == 2;
+    const bool dev_rng = !ms && !noise;
+    MC_REQUIRE(!dev_rng || (keys && keys->keys && keys->TC == TC && rt.draw), "seam rows update: no noise tensor, and no seed table / draw numbers");
+    MC_REQUIRE(!ms || x0_hist, "seam rows update: mode 2 without a history buffer");
+    MC_REQUIRE(!ms || (x0_hist != x_t && x0_hist != x_prev && x0_hist != x0_out && x0_hist != out_text && x0_hist != out_none),
+               "seam rows update: the history buffer aliases another operand");
+    const bool vec = ((uintptr_t)x_t | (uintptr_t)out_text | (uintptr_t)out_none | (uintptr_t)x_prev | (uintptr_t)x0_out |
+                      (uintptr_t)(ms ? nullptr : noise) | (uintptr_t)(ms ? x0_hist : nullptr)) % 16 == 0;
+    const uint32_t n = (uint32_t)nl;
+    int blocks = cdiv((nl + 3) / 4, 256);
+    if (blocks > 2048) blocks = 2048;
+    const PadOut po = pad ? *pad : PadOut();
+    MC_REQUIRE(!po.xpad || (po.C == st.C && po.Cp >= po.C), "seam rows update: bad padded-copy shape");
+    const RowKeys rk{dev_rng ? keys->keys : nullptr, TC};
+    float* const hist = ms ? x0_hist : nullptr;
+#define MC_SSR(R, V) hipLaunchKernelGGL((sampler_seam_rows_k<R, V>), dim3(blocks), dim3(256), 0, s, x_t, out_text, out_none, noise, hist, x_prev, x0_out, n, tc, nc, rt.coefs, rk, rt.draw, st, ms ? 1 : 0, po)
+    if (dev_rng) { if (vec) MC_SSR(true, true); else MC_SSR(true, false); }
+    else { if (vec) MC_SSR(false, true); else MC_SSR(false, false); }
+#undef MC_SSR
     MC_LAUNCH_CHECK();
     return MC_OK;
 }

@@ -3,6 +3,8 @@
 // call into is mc_step.hip; the model / context structs are in mc_ctx.h.
 #include "mc_ctx.h"
 
+#include <cstring>
+
 namespace {
 
 template <class T>
@@ -692,6 +694,80 @@ static int edit_refuse(const mc_ctx* c, const char* who) {
     return MC_OK;
 }
 
+// ---- seam-coupled windows in rows mode (mc_ctx_set_seam_rows): every entry without a rows form refuses while a table is set ----
+static int seam_rows_refuse(const mc_ctx* c, const char* who) {
+    if (c->seam_rows_ov > 0) {
+        mc_set_error("%s: the context has a row seam table set (mc_ctx_set_seam_rows): coupled request rows take mc_sample_rows only; clear it with overlap = 0", who);
+        return MC_ERR_STATE;
+    }
+    return MC_OK;
+}
+// B request rows, right[b] = the row holding the next window of b's request (any row, or -1), ff[b] = the global frame of b's frame 0
+// -> the device entries and the right-window weights.  Every rule is checked on the host: right[b] in [-1, B) and != b; a row is the
+// right neighbour of at most one row; ff[right[b]] == ff[b] + T - ov (first frames grow strictly along a chain, so no chain closes
+// into a cycle: a walk of more than B links is refused all the same); the has-left flags are derived from right[], consistent by that.
+static int seam_rows_plan(const char* who, int B, int T, int ov, const int32_t* right, const int32_t* ff, const float* w,
+                          std::vector<SeamRow>* rows, std::vector<float>* wt) {
+    MC_REQUIRE(B >= 1 && T >= 1, "%s: %d rows of %d frames", who, B, T);
+    MC_REQUIRE(ov > 0 && 2L * ov <= T, "%s: overlap %d outside (0, T / 2 = %d] (a frame may lie in two windows at most)", who, ov, T / 2);
+    MC_REQUIRE(right && ff, "%s: null right / first_frame", who);
+    const long stride = T - ov;
+    rows->assign((size_t)B, SeamRow{-1, 0, 0, 0});
+    for (int b = 0; b < B; ++b) {
+        MC_REQUIRE(ff[b] >= 0, "%s: first_frame[%d] = %d is negative", who, b, ff[b]);
+        MC_REQUIRE(right[b] >= -1 && right[b] < B && right[b] != b, "%s: right[%d] = %d (another row in [0, %d), or -1)", who, b, right[b], B);
+        (*rows)[b].right = right[b];
+        (*rows)[b].first_frame = ff[b];
+    }
+    for (int b = 0; b < B; ++b) {
+        const int rb = right[b];
+        if (rb < 0) continue;
+        MC_REQUIRE(!(*rows)[rb].has_left, "%s: row %d is the right neighbour of two rows (three-way overlaps are not served)", who, rb);
+        (*rows)[rb].has_left = 1;
+        MC_REQUIRE((long)ff[rb] == (long)ff[b] + stride, "%s: first_frame[%d] = %d, the right neighbour of row %d at %d: not one stride (%ld) behind it",
+                   who, rb, ff[rb], b, ff[b], stride);
+    }
+    for (int b = 0; b < B; ++b) {
+        int len = 0;
+        for (int v = right[b]; v >= 0; v = right[v]) MC_REQUIRE(++len < B, "%s: the chain from row %d does not end (a cycle)", who, b);
+    }
+    wt->resize(ov);
+    for (int f = 0; f < ov; ++f) {
+        if (w) MC_REQUIRE(w[f] >= 0.f && w[f] <= 1.f, "%s: weight[%d] = %g outside [0, 1]", who, f, (double)w[f]);
+        (*wt)[f] = w ? w[f] : (float)((double)(f + 1) / (double)(ov + 1));
+    }
+    return MC_OK;
+}
+
+int mc_ctx_set_seam_rows(mc_ctx* c, int32_t overlap, const int32_t* right, const int32_t* first_frame, const float* weight, void* stream) {
+    MC_REQUIRE(c, "null context");
+    if (overlap == 0) { c->seam_rows_ov = 0; c->seam_rows_right.clear(); return MC_OK; }      // (no history flag is touched: the rows walk on)
+    if (c->graph_mode || c->graph_exec) {
+        mc_set_error("mc_ctx_set_seam_rows: the context holds a captured graph (mc_ctx_graph_release first): row steps are not replayed");
+        return MC_ERR_STATE;
+    }
+    if (int re = edit_refuse(c, "mc_ctx_set_seam_rows")) return re;
+    if (int rs = seam_refuse(c, "mc_ctx_set_seam_rows")) return rs;
+    std::vector<SeamRow> rows;
+    std::vector<float> wt;
+    int r;
+    if ((r = seam_rows_plan("mc_ctx_set_seam_rows", c->B, c->T, overlap, right, first_frame, weight, &rows, &wt))) return r;
+    MC_REQUIRE((long)c->B * c->T * c->m->cfg.input_feats <= 0x7fffffffL && (long)c->T * c->m->cfg.input_feats >= 4,
+               "mc_ctx_set_seam_rows: a batch of %d x %d x %d floats", c->B, c->T, c->m->cfg.input_feats);
+    if (!c->seam_rows_tab && (r = ws_alloc(c, &c->seam_rows_tab, (size_t)c->B + ((size_t)c->T / 2 + 3) / 4)) != MC_OK) return r;
+    hipStream_t s = (hipStream_t)stream;
+    // every check has passed.  A copy that fails half way (MC_ERR_HIP) would leave new rows beside old weights and the old host right[]:
+    // no table is the safe state then, as in mc_ctx_set_seams
+    c->seam_rows_ov = 0;
+    c->seam_rows_right.clear();
+    MC_HIP(hipMemcpyAsync(c->seam_rows_tab, rows.data(), sizeof(SeamRow) * c->B, hipMemcpyHostToDevice, s));
+    MC_HIP(hipMemcpyAsync(c->seam_rows_tab + c->B, wt.data(), sizeof(float) * overlap, hipMemcpyHostToDevice, s));
+    MC_HIP(hipStreamSynchronize(s));                 // (the two vectors are temporaries)
+    c->seam_rows_ov = overlap;
+    c->seam_rows_right.assign(right, right + c->B);
+    return MC_OK;
+}
+
 int mc_ctx_set_seams(mc_ctx* c, int32_t overlap, const int32_t* first_frame, const float* weight, void* stream) {
     MC_REQUIRE(c, "null context");
     if (overlap == 0) {
@@ -700,6 +776,7 @@ int mc_ctx_set_seams(mc_ctx* c, int32_t overlap, const int32_t* first_frame, con
         return MC_OK;
     }
     if (int re = edit_refuse(c, "mc_ctx_set_seams")) return re;
+    if (int rr = seam_rows_refuse(c, "mc_ctx_set_seams")) return rr;
     std::vector<int> flags;
     std::vector<float> wt;
     int r;
@@ -724,6 +801,7 @@ int mc_sample_step(mc_ctx* c, const float* x_t, int32_t step, const mc_step_coef
     MC_REQUIRE(c && x_t && k && x_prev, "null argument");
     int r;
     if ((r = edit_refuse(c, "mc_sample_step"))) return r;
+    if (int rq = seam_rows_refuse(c, "mc_sample_step")) return rq;
     if ((r = check_mode(k))) return r;
     const bool ms = c->graph_mode ? c->graph_multistep : is_multistep(k);
     MC_REQUIRE(noise || ms, "null argument (noise_dev may be NULL in mode 2 only)");
@@ -754,6 +832,7 @@ int mc_sample_loop(mc_ctx* c, float* x, const int32_t* step_indices, const mc_st
     MC_REQUIRE(c && x && step_indices && coefs, "null argument");
     MC_REQUIRE(num_steps >= 0, "num_steps < 0");
     if (int re = edit_refuse(c, "mc_sample_loop")) return re;
+    if (int rq = seam_rows_refuse(c, "mc_sample_loop")) return rq;
     const long n = (long)c->B * c->T * c->m->cfg.input_feats;
     // the sampler update of step k also writes x_{t-1} at the padded row stride the pose-encoder GEMM of step k + 1 stages from
     // (no pad_rows_k launch between the steps; the first step of a loop pads, which also zeroes the pad columns)
@@ -795,6 +874,7 @@ int mc_ctx_set_row_seeds(mc_ctx* c, const uint64_t* seeds, void* stream) {
     c->row_seeds_set = false;
     MC_HIP(hipMemcpyAsync(c->row_seeds, seeds, sizeof(uint64_t) * c->B, hipMemcpyHostToDevice, s));
     MC_HIP(hipStreamSynchronize(s));                 // (the caller's array may be a temporary)
+    c->row_seeds_host.assign(seeds, seeds + c->B);
     c->row_seeds_set = true;
     return MC_OK;
 }
@@ -812,8 +892,9 @@ int mc_op_philox_normal(float* out, uint32_t* bits, int64_t n, uint64_t seed, ui
 }
 
 // ---- per-row schedules: every request row of the batch at its own schedule index and guidance scale ----
-// Not in this mode: graph capture / replay (a context that holds a captured graph, or a capturing stream, is MC_ERR_STATE), a seam table
-// (MC_ERR_STATE), the inpaint and seeded steps (they have no rows entry).
+// Not in this mode: graph capture / replay (a context that holds a captured graph, or a capturing stream, is MC_ERR_STATE), the
+// whole-batch seam table of mc_ctx_set_seams (MC_ERR_STATE), the inpaint and seeded steps (they have no rows entry).  Windows of a long
+// request ARE in this mode, through the row seam table of mc_ctx_set_seam_rows (section 4q).
 static int rows_refuse(const mc_ctx* c, const char* who, hipStream_t s) {
     if (c->graph_mode || c->graph_exec) {
         mc_set_error("%s: the context holds a captured graph (mc_ctx_graph_release first): row steps are not replayed", who);
@@ -909,6 +990,23 @@ int mc_sample_rows(mc_ctx* c, float* x, int32_t num_ticks, const int32_t* step_i
     }
     std::vector<uint8_t> flags = c->hist_rows;
     flags.resize((size_t)B, 0);
+    // a row seam table (mc_ctx_set_seam_rows): the two rows of a seam walk together -- equal step index, coefficient bytes and draw
+    // number in every tick, one seed, one history flag.  The kernel then takes the owner's (the left row's) entry for both.
+    if (c->seam_rows_ov > 0) {
+        for (int b = 0; b < B; ++b) {
+            const int rb = c->seam_rows_right[b];
+            if (rb < 0) continue;
+            for (int k = 0; k < num_ticks; ++k) {
+                const size_t i = (size_t)k * B + b, j = (size_t)k * B + rb;
+                MC_REQUIRE(step_index[i] == step_index[j] && memcmp(&coefs[i], &coefs[j], sizeof(mc_step_coefs)) == 0,
+                           "mc_sample_rows: tick %d: rows %d and %d share a seam but not their step index / coefficients", k, b, rb);
+                MC_REQUIRE(ms || noise || draw[i] == draw[j], "mc_sample_rows: tick %d: rows %d and %d share a seam but not their draw number", k, b, rb);
+            }
+            MC_REQUIRE(ms || noise || c->row_seeds_host[b] == c->row_seeds_host[rb],
+                       "mc_sample_rows: rows %d and %d share a seam but not their seed (every row of a request carries the request's)", b, rb);
+            MC_REQUIRE(!ms || flags[b] == flags[rb], "mc_sample_rows: rows %d and %d share a seam but not their multistep history flag", b, rb);
+        }
+    }
     if (ms) {
         for (size_t i = 0; i < ne; ++i) {
             const int b = (int)(i % B);
@@ -978,6 +1076,7 @@ int mc_ctx_set_edit_rows(mc_ctx* c, const float* gt, const uint8_t* keep, const 
         return MC_ERR_STATE;
     }
     if (c->seam_ov > 0) { mc_set_error("mc_ctx_set_edit_rows: the context has a seam table set (mc_ctx_set_seams): clear it with overlap = 0"); return MC_ERR_STATE; }
+    if (int rq = seam_rows_refuse(c, "mc_ctx_set_edit_rows")) return rq;
     const size_t TC = (size_t)c->T * c->m->cfg.input_feats, n = (size_t)c->B * TC;
     hipStream_t s = (hipStream_t)stream;
     int r;
@@ -1007,6 +1106,7 @@ int mc_ctx_graph_capture(mc_ctx* c, float* x_dev, const float* noise_dev, const 
     MC_REQUIRE(c && x_dev && coefs_host, "null argument");
     if (int rs = seam_refuse(c, "mc_ctx_graph_capture")) return rs;
     if (int re = edit_refuse(c, "mc_ctx_graph_capture")) return re;
+    if (int rq = seam_rows_refuse(c, "mc_ctx_graph_capture")) return rq;
     MC_REQUIRE(c->have_cond, "mc_ctx_set_condition not called");
     MC_REQUIRE(num_steps >= 1 && num_steps == c->S, "num_steps=%d must equal the schedule set by mc_ctx_set_timesteps (%d)", num_steps, c->S);
     MC_REQUIRE(!c->cap_idx, "routing capture (tests) and graph replay are mutually exclusive");
@@ -1053,6 +1153,7 @@ int mc_ctx_graph_capture(mc_ctx* c, float* x_dev, const float* noise_dev, const 
 int mc_ctx_graph_step(mc_ctx* c, int32_t step, void* stream) {
     MC_REQUIRE(c, "null context");
     if (int re = edit_refuse(c, "mc_ctx_graph_step")) return re;
+    if (int rq = seam_rows_refuse(c, "mc_ctx_graph_step")) return rq;
     MC_REQUIRE(c->graph_exec, "no captured graph (mc_ctx_graph_capture)");
     MC_REQUIRE(step >= 0 && step < c->graph_steps, "step_index %d outside the %d captured steps", step, c->graph_steps);
     hipStream_t s = (hipStream_t)stream;
@@ -1075,6 +1176,7 @@ int mc_sample_step_seeded(mc_ctx* c, float* x_t, int32_t step, const mc_step_coe
     MC_REQUIRE(c && x_t && k && noise && x_prev && sd, "null argument");
     if (int rs = seam_refuse(c, "mc_sample_step_seeded")) return rs;
     if (int re = edit_refuse(c, "mc_sample_step_seeded")) return re;
+    if (int rq = seam_rows_refuse(c, "mc_sample_step_seeded")) return rq;
     MC_REQUIRE(!is_multistep(k), "mc_sample_step_seeded: the multistep sampler (mode 2) has no pre_seq / transl_req seeding");
     MC_REQUIRE(sd->pre_len >= 0 && sd->pre_len <= c->T, "pre_seq has %d frames, the window %d", sd->pre_len, c->T);
     MC_REQUIRE(sd->num_transl >= 0 && sd->num_transl <= MC_MAX_TRANSL, "num_transl=%d outside [0, %d]", sd->num_transl, MC_MAX_TRANSL);
@@ -1099,6 +1201,7 @@ int mc_sample_step_inpaint(mc_ctx* c, const float* x_t, int32_t step, const mc_s
     MC_REQUIRE(c && x_t && k && noise && x_prev && ip, "null argument");
     if (int rs = seam_refuse(c, "mc_sample_step_inpaint")) return rs;
     if (int re = edit_refuse(c, "mc_sample_step_inpaint")) return re;
+    if (int rq = seam_rows_refuse(c, "mc_sample_step_inpaint")) return rq;
     MC_REQUIRE(!is_multistep(k), "mc_sample_step_inpaint: the multistep sampler (mode 2) has no outpainting (RePaint) form");
     X0Parts p;
     if (int r = denoise_combined(c, x_t, step, k, stream, &p)) return r;
@@ -1497,6 +1600,64 @@ int mc_op_sampler_seam(const float* x_t, const float* ot, const float* on, const
     if (r == MC_OK) r = mc_launch_sampler_seam(x_t, ot, on, noise, ms ? x0_hist : nullptr, x_prev, x0, B, to_coefs(k), st, s, noise ? nullptr : &rng);
     (void)hipStreamSynchronize(s);                   // (the table is a temporary)
     (void)hipFree(tab);
+    return r;
+}
+
+int mc_op_sampler_seam_rows(const float* x_t, const float* ot, const float* on, const float* noise, const uint64_t* seeds, const uint64_t* draw,
+                            float* x0_hist, float* x_prev, float* x0, int32_t B, int32_t T, int32_t C, int32_t overlap, const int32_t* right,
+                            const int32_t* first_frame, const float* weight, const mc_step_coefs* coefs, void* stream) {
+    MC_REQUIRE(x_t && ot && on && x_prev && coefs && B >= 1 && C >= 1, "mc_op_sampler_seam_rows: bad argument");
+    int r;
+    for (int b = 0; b < B; ++b) {
+        if ((r = check_mode(&coefs[b]))) return r;
+        MC_REQUIRE(coefs[b].mode == coefs[0].mode, "mc_op_sampler_seam_rows: row %d in mode %d beside mode %d (one mode per call)", b, coefs[b].mode, coefs[0].mode);
+    }
+    const bool ms = is_multistep(&coefs[0]);
+    const bool dev_rng = seeds != nullptr || draw != nullptr;
+    if (ms) MC_REQUIRE(x0_hist && !noise && !dev_rng, "mc_op_sampler_seam_rows: mode 2 needs x0_hist_dev and takes no noise");
+    else {
+        MC_REQUIRE(!dev_rng || (seeds && draw && !noise), "mc_op_sampler_seam_rows: (seeds_host, draw_host) come together and exclude noise_dev");
+        MC_REQUIRE(dev_rng || noise, "mc_op_sampler_seam_rows: modes 0 / 1 need noise_dev, or (seeds_host, draw_host)");
+    }
+    std::vector<SeamRow> rows;
+    std::vector<float> wt;
+    if ((r = seam_rows_plan("mc_op_sampler_seam_rows", B, T, overlap, right, first_frame, weight, &rows, &wt))) return r;
+    for (int b = 0; b < B; ++b) {
+        const int rb = right[b];
+        if (rb < 0) continue;
+        MC_REQUIRE(memcmp(&coefs[b], &coefs[rb], sizeof(mc_step_coefs)) == 0, "mc_op_sampler_seam_rows: rows %d and %d share a seam but not their coefficients", b, rb);
+        MC_REQUIRE(!dev_rng || (seeds[b] == seeds[rb] && draw[b] == draw[rb]), "mc_op_sampler_seam_rows: rows %d and %d share a seam but not their seed / draw number", b, rb);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    RowTab rt;
+    rt.B = B; rt.T = 1;
+    SamplerCoefs* tab = nullptr;
+    if ((r = rows_tab_upload(coefs, B, &tab, s))) return r;
+    rt.coefs = tab;
+    // one temporary block: [B] SeamRow | [overlap] weights (padded to 16 bytes) | [B] keys | [B] draw numbers
+    const size_t wq = ((size_t)overlap + 3) / 4, nq = (size_t)B + wq + (dev_rng ? (size_t)B : 0);
+    std::vector<SeamRow> h(nq, SeamRow{0, 0, 0, 0});
+    memcpy(h.data(), rows.data(), sizeof(SeamRow) * B);
+    memcpy(h.data() + B, wt.data(), sizeof(float) * overlap);
+    uint64_t* hk = reinterpret_cast<uint64_t*>(h.data() + B + wq);
+    if (dev_rng) for (int b = 0; b < B; ++b) { hk[b] = seeds[b]; hk[(size_t)B + b] = draw[b]; }
+    SeamRow* blk = nullptr;
+    if (hipMalloc((void**)&blk, sizeof(SeamRow) * nq) != hipSuccess ||
+        hipMemcpyAsync(blk, h.data(), sizeof(SeamRow) * nq, hipMemcpyHostToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
+        if (blk) (void)hipFree(blk);
+        (void)hipFree(tab);
+        mc_set_error("mc_op_sampler_seam_rows: table upload failed");
+        return MC_ERR_HIP;
+    }
+    SeamRowsTab st;
+    st.rows = blk; st.w = reinterpret_cast<const float*>(blk + B); st.T = T; st.C = C; st.ov = overlap;
+    const uint64_t* kd = reinterpret_cast<const uint64_t*>(blk + B + wq);
+    if (dev_rng) rt.draw = kd + B;
+    const RowKeys rk{reinterpret_cast<const uint32_t*>(kd), (int)((long)T * C)};
+    r = mc_launch_sampler_seam_rows(x_t, ot, on, noise, ms ? x0_hist : nullptr, x_prev, x0, 1.f, 1.f, rt, st, coefs[0].mode, s, dev_rng ? &rk : nullptr);
+    (void)hipStreamSynchronize(s);                   // (the tables are temporaries)
+    (void)hipFree(tab);
+    (void)hipFree(blk);
     return r;
 }
 

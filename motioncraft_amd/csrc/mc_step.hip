@@ -848,6 +848,16 @@ int sampler_update(mc_ctx* c, const float* x_t, const X0Parts& x0p, const mc_ste
     if (c->rows_mode) {          // per-row schedules: the two row kernels (one mode per call, checked by mc_sample_rows; no graph, no seams)
         if (c->graph_mode || c->seam_ov > 0) { mc_set_error("per-row sampler update under graph capture or with a seam table set"); return MC_ERR_STATE; }
         const SamplerCoefs u = x0p.coefs(k);
+        if (c->seam_rows_ov > 0) {       // windows of long requests among the rows (mc_ctx_set_seam_rows): one kernel for every mode
+            if (c->edit_set) { mc_set_error("per-row sampler update with a row seam table and an edit table set"); return MC_ERR_STATE; }
+            MC_REQUIRE(multistep || noise || c->row_seeds_set, "per-row sampler update without a noise tensor needs a seed table (mc_ctx_set_row_seeds)");
+            MC_REQUIRE(!multistep || c->x0_hist, "multistep update without a history buffer");
+            SeamRowsTab st;
+            st.rows = c->seam_rows_tab; st.w = reinterpret_cast<const float*>(c->seam_rows_tab + c->B);
+            st.T = c->T; st.C = c->m->cfg.input_feats; st.ov = c->seam_rows_ov;
+            return mc_launch_sampler_seam_rows(x_t, x0p.a, x0p.second(), multistep ? nullptr : noise, multistep ? c->x0_hist : nullptr, x_prev, x0,
+                                               u.text_coef, u.none_coef, c->rowtab, st, k->mode, s, noise || multistep ? nullptr : &rk, pad);
+        }
         if (c->edit_set) {       // a kept region (mc_ctx_set_edit_rows): the edit kernels, the same forms otherwise
             EditTab et;
             et.gt = c->edit_gt; et.keep = c->edit_keep;

@@ -74,6 +74,7 @@ class NativeContext:
         self.seams = None              # dict(first_frame, overlap) while a seam table is set (set_seams)
         self.row_seeds = None          # the rows' Philox keys while a seed table is set (set_row_seeds)
         self.edit_rows = False         # an edit table is set (set_edit_rows); read by serve: the first upload after a clear sends every row
+        self.seam_rows = None          # dict(right, first_frame, overlap) while a row seam table is set (set_seam_rows)
 
     @property
     def workspace_bytes(self):
@@ -340,6 +341,32 @@ class NativeContext:
     def clear_seams(self):
         _lib.check(self.lib.mc_ctx_set_seams(self.handle, 0, None, None, _stream()), 'mc_ctx_set_seams')
         self.seams = None
+
+    def set_seam_rows(self, right, first_frame, overlap, weights=None):
+        """Couple request rows of ``sample_rows`` as the windows of long requests (mc_ctx_set_seam_rows): row b
+        shows frames ``first_frame[b] ..`` of its request and ``right[b]`` is the row that holds the request's next window (any row),
+        or -1.  While the table is set, ``sample_rows`` blends the two x0 predictions of a shared frame (``weights[f]`` = the right
+        window's share, default ``(f + 1) / (overlap + 1)``), keeps the shared frames of x bit-equal in both rows and, without
+        ``noise``, draws every row at its request-global counter.  The rows of a seam must walk together (same step, coefficients,
+        draw number and seed).  The library checks the table; a refused call leaves the previous one set.  ``overlap=0`` clears it."""
+        if int(overlap) == 0:
+            return self.clear_seam_rows()
+        right, ff = [int(v) for v in right], [int(v) for v in first_frame]
+        if len(right) != self.B or len(ff) != self.B:
+            raise ValueError(f'right / first_frame: one entry per row ({self.B}), got {len(right)} / {len(ff)}')
+        warr = None
+        if weights is not None:
+            w = [float(v) for v in weights]
+            if len(w) != int(overlap):
+                raise ValueError(f'weights: one per shared frame ({int(overlap)}), got {len(w)}')
+            warr = (ctypes.c_float * len(w))(*w)
+        _lib.check(self.lib.mc_ctx_set_seam_rows(self.handle, int(overlap), (ctypes.c_int32 * self.B)(*right), (ctypes.c_int32 * self.B)(*ff),
+                                                 warr, _stream()), 'mc_ctx_set_seam_rows')
+        self.seam_rows = dict(right=right, first_frame=ff, overlap=int(overlap))
+
+    def clear_seam_rows(self):
+        _lib.check(self.lib.mc_ctx_set_seam_rows(self.handle, 0, None, None, None, _stream()), 'mc_ctx_set_seam_rows')
+        self.seam_rows = None
 
     def set_capacity_factor(self, cf):
         """Capacity factor of every MoE of this context (mc_ctx_set_capacity_factor): > 0 tutel's formula with it, 0 = no (token,

@@ -1,5 +1,6 @@
 """Independent requests through one batched context: ``Request`` + ``RequestBatcher`` (whole batches, one walk per call) and
-``ContinuousBatcher`` (requests join a running batch at any step and leave when their own walk ends: DESIGN.md section 4o).
+``ContinuousBatcher`` (requests join a running batch at any step and leave when their own walk ends: DESIGN.md section 4o; with
+``overlap=`` a request longer than ``frames`` runs as seam-coupled windows on any open rows: section 4q).
 
 The library is fastest when it batches, and with row-keyed noise (``seeds=``) and drop-free MoE routing (``capacity_factor=0``) a row
 of a batch is a request: its result does not depend on what the other rows hold.
@@ -109,7 +110,8 @@ class Edit:
 
 class Request:
     """One generation request: the condition (``xf_out`` [Nt, Dt], the text encoder's output -- or ``text``, encoded on submit),
-    ``length`` frames (1 .. the batcher's ``frames``), ``seed`` in [0, 2^64) and optionally a control condition ``c`` [Tc, Fc].
+    ``length`` frames (1 .. the batcher's ``frames``; longer in a ``ContinuousBatcher`` with ``overlap=``), ``seed`` in [0, 2^64) and
+    optionally a control condition ``c`` [Tc, Fc].
     ``guidance_scale``: the request's own classifier-free guidance scale (``ContinuousBatcher``; None: the model's).
     ``edit``: an ``Edit`` -- the frames / channels of the result that are given (at most ``length`` frames)."""
 
@@ -144,6 +146,21 @@ def _check_edit(model, request):
         C = model.model.dims['input_feats']
         if request.edit.feats != C:
             raise ValueError(f'the edit has {request.edit.feats} channels, the model {C}')
+
+
+def plan_windows(length, frames, overlap):
+    """The windows of a request of ``length`` frames in a batcher of ``frames`` with ``overlap`` shared frames:
+    ``[(first_frame, window length)]``.  Up to ``frames`` it is one window; beyond that ``W = ceil((length - overlap) / stride)``
+    windows, ``stride = frames - overlap``, window j at ``j * stride`` with ``min(frames, length - j * stride)`` frames -- the last one
+    may be ragged, its length in ``(overlap, frames]``."""
+    F, T, ov = int(length), int(frames), int(overlap)
+    if not 0 < 2 * ov <= T:
+        raise ValueError(f'overlap={overlap!r}: an integer with 0 < 2 overlap <= frames ({T})')
+    if F <= T:
+        return [(0, F)]
+    stride = T - ov
+    W = -((ov - F) // stride)                     # ceil((F - ov) / stride)
+    return [(j * stride, min(T, F - j * stride)) for j in range(W)]
 
 
 class RequestBatcher:
@@ -302,9 +319,27 @@ class ContinuousBatcher:
                                    be uploaded) while a running row carries an edit or a table is set
       ``clear_edits()``                       -- no running row carries an edit any more (only ever called after such a ``condition``)
       ``advance(pos [n][B], scales [B])``     -- n steps, row b of step k at walk position ``pos[k][b]`` (schedule index steps-1-pos)
-      ``result()`` -> [B, frames, C]          -- the rows as they stand, post-processed."""
+      ``result()`` -> [B, frames, C]          -- the rows as they stand, post-processed.
 
-    def __init__(self, model, batch, frames, sampler='ddim', steps=None, capacity_factor=0, eta=0.0, order=2, runner=None):
+    Long requests (``overlap=``).  Without ``overlap`` a request longer than ``frames`` is a ``ValueError``, as
+    ever.  With it (``0 < 2 overlap <= frames``; ``seam_weights``: the right window's share per shared frame, default
+    ``(f + 1) / (overlap + 1)``) such a request is planned into ``W`` windows (``plan_windows``), takes the ``W`` lowest open rows --
+    they need not be contiguous -- and walks as ONE request: its rows are admitted, advance and retire together, the shared frames of
+    neighbouring windows are blended after every denoiser call (``set_seam_rows``), and its noise is one field over its global frames
+    (x_T = draw 0, step k = draw 1 + k of its seed), so the result does not depend on the rows it lands in.  ``xf_out`` is repeated per
+    window; a control condition ``c`` [length * r, Fc] is sliced per window by its ``r`` rows per frame.  The result is the stitched
+    motion [length, C]: the first ``stride`` frames of every window but the last, then the last window's valid frames.
+    Admission is then strict FIFO: the head of the queue waits until ``W`` rows are open (and, a control request, until the batch is
+    empty) and nothing overtakes it -- no request starves, but a short request can wait behind a long one.  ``W > batch`` and an
+    ``edit`` on a request longer than ``frames`` are ``ValueError`` at ``submit()``; a long request waits while a running row carries
+    an edit and a request with an edit waits while a long request runs (the two tables exclude each other in the library).
+    The runner sees two more calls, both only while long requests are involved: ``condition(..., first_frames=[...] * B)`` (the global
+    frame of every row's frame 0; a fresh row's x_T is its part of draw 0 of the request's field) and, after every admission and every
+    retirement of a long request, ``seams(right [B], first_frame [B])`` with the table as it now stands, or ``clear_seams()`` once no
+    long request runs."""
+
+    def __init__(self, model, batch, frames, sampler='ddim', steps=None, capacity_factor=0, eta=0.0, order=2, runner=None, overlap=None,
+                 seam_weights=None):
         if sampler not in SAMPLERS:
             raise ValueError(f'sampler {sampler!r}: one of {SAMPLERS}')
         if int(batch) < 1 or int(frames) < 1:
@@ -316,11 +351,24 @@ class ContinuousBatcher:
         self.model, self.batch, self.frames = model, int(batch), int(frames)
         self.sampler, self.steps, self.capacity_factor = sampler, None if steps is None else int(steps), float(capacity_factor)
         self.eta, self.order = float(eta), int(order)
+        if overlap is None:
+            if seam_weights is not None:
+                raise ValueError('seam_weights without overlap')
+        else:
+            if isinstance(overlap, bool) or int(overlap) != overlap or not 0 < 2 * int(overlap) <= self.frames:
+                raise ValueError(f'overlap={overlap!r}: an integer with 0 < 2 overlap <= frames ({self.frames})')
+            overlap = int(overlap)
+            if seam_weights is not None:
+                seam_weights = [float(v) for v in seam_weights]
+                if len(seam_weights) != overlap or not all(0.0 <= v <= 1.0 for v in seam_weights):
+                    raise ValueError(f'seam_weights: {overlap} numbers in [0, 1]')
+        self.overlap, self.seam_weights = overlap, seam_weights
+        self._seams_on = False                        # the runner holds a row seam table
         self.runner = runner if runner is not None else _RowsRunner(self)
         self.walk = int(self.runner.steps)            # steps of one request's walk
         if self.walk < 1:
             raise ValueError(f'the schedule has {self.walk} steps')
-        self._rows = [None] * self.batch              # per row: None (open) or [handle, Request, walk position]
+        self._rows = [None] * self.batch              # per row: None (open) or [handle, Request, walk position, window of the request]
         self._pending = []
         self._done = {}
         self._next = 0
@@ -336,7 +384,15 @@ class ContinuousBatcher:
         if not isinstance(request, Request):
             raise ValueError('submit() takes a Request')
         if request.length > self.frames:
-            raise ValueError(f'request of {request.length} frames in a batcher of {self.frames}')
+            if self.overlap is None:
+                raise ValueError(f'request of {request.length} frames in a batcher of {self.frames}')
+            if request.edit is not None:
+                raise ValueError(f'an edit on a request of {request.length} frames, longer than the batcher\'s {self.frames}: edits on long requests are not served')
+            W = len(plan_windows(request.length, self.frames, self.overlap))
+            if W > self.batch:
+                raise ValueError(f'request of {request.length} frames is {W} windows of {self.frames} (overlap {self.overlap}) in a batcher of {self.batch} rows')
+            if request.c is not None and request.c.shape[0] % request.length:
+                raise ValueError(f'the control condition has {request.c.shape[0]} rows for {request.length} frames: a whole number of rows per frame')
         _check_edit(self.model, request)
         if request.xf_out is None:
             xf = self.model.model.encode_text([request.text], None, None)[0]
@@ -352,9 +408,37 @@ class ContinuousBatcher:
         """handles of the running rows (None: an open row)"""
         return [None if r is None else r[0] for r in self._rows]
 
-    @staticmethod
-    def _group(r):
-        return None if r.c is None else tuple(r.c.shape)
+    def _group(self, r):
+        """the shape of one row's control condition (None: no control); the windows of a long request hold ``frames`` frames of it"""
+        if r.c is None:
+            return None
+        if r.length > self.frames:
+            return (self.frames * (r.c.shape[0] // r.length), int(r.c.shape[1]))
+        return tuple(r.c.shape)
+
+    def _windows(self, r):
+        return plan_windows(r.length, self.frames, self.overlap) if r.length > self.frames else [(0, r.length)]
+
+    def _admit_fifo(self, group):
+        """``_admit`` with ``overlap`` set: strict FIFO, the head of the queue takes the lowest open rows or everyone waits"""
+        fresh = []
+        while self._pending:
+            handle, r = self._pending[0]
+            if self._group(r) != group:
+                break
+            long_runs = any(q is not None and q[1].length > self.frames for q in self._rows)
+            edit_runs = self._edit_on or any(q is not None and q[1].edit is not None for q in self._rows)
+            if (r.length > self.frames and edit_runs) or (r.edit is not None and long_runs):
+                break                                 # the edit table and the row seam table exclude each other
+            wins = self._windows(r)
+            open_rows = [b for b in range(self.batch) if self._rows[b] is None]
+            if len(open_rows) < len(wins):
+                break
+            self._pending.pop(0)
+            for j, b in enumerate(open_rows[:len(wins)]):
+                self._rows[b] = [handle, r, 0, j]
+                fresh.append(b)
+        return fresh
 
     def _admit(self):
         """step 1 of a round; -> the rows that took a new request"""
@@ -365,6 +449,8 @@ class ContinuousBatcher:
         group = self._group(running[0][1]) if running else self._group(self._pending[0][1])
         if group is not None and running:
             return fresh                              # control requests start in an empty batch only
+        if self.overlap is not None:
+            return self._admit_fifo(group)
         for b in range(self.batch):
             if self._rows[b] is not None:
                 continue
@@ -372,7 +458,7 @@ class ContinuousBatcher:
             if k is None:
                 break
             handle, r = self._pending.pop(k)
-            self._rows[b] = [handle, r, 0]
+            self._rows[b] = [handle, r, 0, 0]
             fresh.append(b)
         return fresh
 
@@ -385,20 +471,60 @@ class ContinuousBatcher:
         else:                                         # a retired row that stays open takes the dummy now
             flags = [f or (self._rows[b] is None and self._stale[b]) for b, f in enumerate(flags)]
         xf = torch.stack([r[1].xf_out if r is not None else torch.zeros_like(first.xf_out) for r in self._rows])
-        lengths = [r[1].length if r is not None else self.frames for r in self._rows]
+        wins = [self._windows(r[1])[r[3]] if r is not None else (0, self.frames) for r in self._rows]      # (first frame, frames) per row
+        lengths = [n for _, n in wins]
         seeds = [r[1].seed if r is not None else DUMMY_SEED for r in self._rows]
         c = None
         if first.c is not None:
-            c = torch.stack([r[1].c if r is not None else torch.zeros_like(first.c) for r in self._rows])
+            c = torch.stack([self._row_control(r, wins[b], first) for b, r in enumerate(self._rows)])
         edits = [r[1].edit if r is not None else None for r in self._rows]
+        long_rows = any(r is not None and r[1].length > self.frames for r in self._rows)
         if self._edit_on or any(e is not None for e in edits):
             self.runner.condition(xf, lengths, seeds, flags, c, edits=edits)
             self._edit_on = True
             self._settle_edits()
+        elif long_rows:
+            self.runner.condition(xf, lengths, seeds, flags, c, first_frames=[f for f, _ in wins])
         else:
             self.runner.condition(xf, lengths, seeds, flags, c)
         self._conditioned = True
         self._stale = [False] * self.batch
+        if any(self._rows[b] is not None and self._rows[b][1].length > self.frames for b in fresh):
+            self._send_seams()
+
+    def _row_control(self, r, win, first):
+        """the control condition of one row: the request's, the rows of a long request's window (zero rows behind a ragged last
+        window), or zeros for an open row"""
+        shape = self._group(first)
+        if r is None:
+            return torch.zeros(shape, dtype=first.c.dtype)
+        c = r[1].c
+        if r[1].length <= self.frames:
+            return c
+        per = c.shape[0] // r[1].length
+        out = torch.zeros(shape, dtype=c.dtype)
+        out[:win[1] * per] = c[win[0] * per:(win[0] + win[1]) * per]
+        return out
+
+    def _send_seams(self):
+        """the row seam table as the rows now stand (after an admission or a retirement of a long request), or none"""
+        by_handle = {}
+        for b, r in enumerate(self._rows):
+            if r is not None and r[1].length > self.frames:
+                by_handle.setdefault(r[0], {})[r[3]] = b
+        if not by_handle:
+            if self._seams_on:
+                self.runner.clear_seams()
+                self._seams_on = False
+            return
+        right, first = [-1] * self.batch, [0] * self.batch
+        stride = self.frames - self.overlap
+        for rows in by_handle.values():
+            for j, b in rows.items():
+                right[b] = rows.get(j + 1, -1)
+                first[b] = j * stride
+        self.runner.seams(right, first)
+        self._seams_on = True
 
     def _settle_edits(self):
         """clear the runner's table once no running row carries an edit"""
@@ -422,6 +548,7 @@ class ContinuousBatcher:
         self.runner.advance(pos, scales)
         self.ticks += n
         out = None
+        parts = {}                                    # handle of a retiring long request -> (its length, {window: its frames})
         for b, r in enumerate(self._rows):
             if r is None:
                 continue
@@ -429,12 +556,25 @@ class ContinuousBatcher:
             if r[2] == self.walk:
                 if out is None:
                     out = self.runner.result()
-                self._done[r[0]] = out[b, :r[1].length].clone()
+                if r[1].length > self.frames:         # (the rows of a request were admitted together: they all retire in this round)
+                    parts.setdefault(r[0], (r[1].length, {}))[1][r[3]] = out[b]
+                else:
+                    self._done[r[0]] = out[b, :r[1].length].clone()
                 self.finished_at[r[0]] = self.ticks
                 self._rows[b] = None
                 self._stale[b] = True
+        for handle, (length, wins) in parts.items():
+            self._done[handle] = self._stitch([wins[j] for j in range(len(wins))], length)
+        if parts:
+            self._send_seams()
         self._settle_edits()
         return n
+
+    def _stitch(self, wins, length):
+        """the windows of one request [frames, C] each, in order -> [length, C]: the first ``stride`` frames of every window but the
+        last, then the last window's valid frames"""
+        stride = self.frames - self.overlap
+        return torch.cat([w[:stride] for w in wins[:-1]] + [wins[-1]])[:length].clone()
 
     def run(self):
         """Tick until the queue and the rows are empty; -> ``poll()``."""
@@ -463,7 +603,7 @@ class _RowsRunner:
         self.ctx, self.x, self.group = None, None, ()
         self._coefs = {}                              # scale -> the StepCoefs of a whole walk, by walk position
 
-    def condition(self, xf_out, lengths, seeds, fresh, c, edits=None):
+    def condition(self, xf_out, lengths, seeds, fresh, c, edits=None, first_frames=None):
         from . import lib as _lib
         from .engine import _ptr, _stream
         o, net = self.o, self.o.model.model
@@ -486,10 +626,26 @@ class _RowsRunner:
         if edits is not None:
             self._upload_edits(edits, fresh, dev)
         self.ctx.set_row_seeds(seeds)
+        # x_T of a fresh row: its frames of draw 0 of its seed's field (a short request, or window 0: elements [0, T C)).  The field is
+        # a function of the seed alone, so it is drawn once per seed, as far as the last fresh window reaches, and gathered
+        first = [0] * B if first_frames is None else [int(v) for v in first_frames]
+        reach = {}
         for b, f in enumerate(fresh):
-            if f:                                     # x_T of the row: draw 0 of its own stream
-                _lib.check(self.ctx.lib.mc_op_philox_normal(_ptr(self.x[b]), None, T * C, int(seeds[b]) & (2 ** 64 - 1), 0, _stream()),
-                           'mc_op_philox_normal')
+            if f:
+                reach[seeds[b]] = max(reach.get(seeds[b], 0), first[b] + T)
+        for seed, frames in reach.items():
+            z = torch.empty(frames, C, device=dev)
+            _lib.check(self.ctx.lib.mc_op_philox_normal(_ptr(z), None, z.numel(), int(seed) & (2 ** 64 - 1), 0, _stream()), 'mc_op_philox_normal')
+            for b, f in enumerate(fresh):
+                if f and seeds[b] == seed:
+                    self.x[b] = z[first[b]:first[b] + T]
+
+    def seams(self, right, first_frame):
+        self.ctx.set_seam_rows(right, first_frame, self.o.overlap, self.o.seam_weights)
+
+    def clear_seams(self):
+        if self.ctx is not None:
+            self.ctx.clear_seam_rows()
 
     def _upload_edits(self, edits, fresh, dev):
         """the tables of the rows with ``fresh[b]``: the row's edit in model space, or nothing kept.  Into a context that holds no table

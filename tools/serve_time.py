@@ -19,7 +19,12 @@ after one warm-up:
             alternated in one process: (a) no edit table, (b) a table whose keep bytes are all zero, (c) a table with 25 % of the
             elements kept; and mc_ctx_set_edit_rows for one fresh row beside mc_ctx_set_condition_rows
 
-usage: serve_time.py [--small] [--batch B] [--requests R] [--steps N] [--reps K] [--only routing,noise,batcher,rows,arrivals,edits]
+  long       one mc_sample_rows tick (DDIM eta 0.5, capacity factor 0, noise drawn from the seed table) without a
+            row seam table and with one of B / 8 chains of 8 windows, alternated in one process, and mc_ctx_set_seam_rows itself; then
+            the arrival list LONG_ARRIVALS, which mixes short requests and requests of 2 .. 8 windows, through
+            serve.ContinuousBatcher(overlap=), beside its long requests alone through longform.sample_long_coupled batches
+
+usage: serve_time.py [--small] [--batch B] [--requests R] [--steps N] [--reps K] [--only routing,noise,batcher,rows,arrivals,edits,long]
   --small: the reduced test config (24 frames) instead of the 0.125b architecture (196 frames)"""
 import argparse
 import os
@@ -42,6 +47,7 @@ p.add_argument('--requests', type=int, default=16)
 p.add_argument('--steps', type=int, default=50)
 p.add_argument('--reps', type=int, default=3)
 p.add_argument('--only', default='routing,noise,batcher')
+p.add_argument('--skip_arrivals', action='store_true', help='--only long: the tick arms alone (a kernel trace of them)')
 # request i arrives at tick ARRIVALS[i]: a burst, a trickle one step apart, a lull, a second burst that overfills B = 16, stragglers
 ARRIVALS = [0, 0, 0, 0, 1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 15, 20, 26, 33, 41, 50, 70, 70, 70, 70, 70, 70, 70, 70, 70, 70, 70, 70, 70, 70, 70, 70,
             70, 70, 71, 73, 76, 80, 85, 91, 98, 120, 150, 151]
@@ -255,4 +261,123 @@ if 'arrivals' in only:
         lat = box['lat']
         print(f'{R} arrivals, {a.steps}-step DDIM, B={B}, {name:17s}: median {med * 1e3:8.1f} ms = {R / med:7.2f} requests/s   '
               f'(min {lo * 1e3:8.1f}, max {hi * 1e3:8.1f} ms);  ticks to completion: mean {sum(lat) / len(lat):6.1f}, max {max(lat)}', flush=True)
+if 'long' in only:
+    # (a) one tick with and without a row seam table: B rows as B / 8 chains of 8 windows, chain c on rows c, c + B/8, c + 2 B/8, ...
+    ov = T // 7 if not a.small else 6
+    stride = T - ov
+    x, xf, mask, _ = inputs(B)
+    mask[:] = 1
+    dd = build_diffusion(dict(schedule, respace=f'ddim{a.steps}'))
+    ctx = arch.model.native.context(B, T, max_steps=a.steps)
+    ctx.set_capacity_factor(0)
+    ctx.set_timesteps(dd.timestep_map)
+    ctx.set_condition(xf, mask)
+    nch = max(B // 8, 1)
+    ctx.set_row_seeds([100 + b % nch for b in range(B)])
+    step = a.steps // 2
+    ck = dd.step_coefs(step, 'ddim', arch.model.cfg_scale, 0.5)
+    right = [b + nch if b + nch < B else -1 for b in range(B)]
+    first = [(b // nch) * stride for b in range(B)]
+    xd = x.clone()
+    tick = lambda: ctx.sample_rows(xd, [[step] * B], [[ck] * B], draws=[[1] * B])
+
+    def version(table):
+        if table:
+            ctx.set_seam_rows(right, first, ov)
+        else:
+            ctx.clear_seam_rows()
+        return median_of(lambda: events_ms(tick, 5))
+    # (c) the whole-batch path of section 4m at the same shape: mc_sample_step under mc_ctx_set_seams, nch sequences of adjacent windows
+    noise1 = torch.randn(B, T, C, device='cuda')
+    per = B // nch
+    first_adj = [(b // per) * (per * T + T) + (b % per) * stride for b in range(B)]
+
+    def whole_batch():
+        ctx.clear_seam_rows()
+        ctx.set_seams(first_adj, ov)
+        try:
+            return median_of(lambda: events_ms(lambda: ctx.sample_step(xd, step, ck, noise1, x_prev=xd), 5))
+        finally:
+            ctx.clear_seams()
+    arms = {'(a) mc_sample_rows tick, no table': lambda: version(False),
+            f'(b) ... {nch} chains of {B // nch} windows': lambda: version(True),
+            '(c) mc_sample_step, mc_ctx_set_seams': whole_batch,
+            'mc_ctx_set_seam_rows': lambda: median_of(lambda: events_ms(lambda: ctx.set_seam_rows(right, first, ov), 5))}
+    for name in list(arms) * 2:                    # (the comparison twice, alternated: the spread of equal settings is the machine's drift)
+        med, lo, hi = arms[name]()
+        print(f'B={B} {name:38s}: median {med:8.3f} ms   min {lo:8.3f}   max {hi:8.3f}   (5 calls per run)', flush=True)
+    ctx.clear_seam_rows()
+    ctx.close()
+if 'long' in only and not a.skip_arrivals:
+    ov = T // 7 if not a.small else 6
+    stride = T - ov
+
+    # (b) a fixed arrival list that mixes short requests (windows = 1) and requests of 2 .. 8 windows, through ContinuousBatcher(overlap=);
+    # beside it the list's long requests alone through longform.sample_long_coupled batches (idle -> whatever has arrived, whole
+    # sequences up to B windows, its whole walk): the only way such a request could run before
+    from motioncraft_amd import longform
+    LONG_ARRIVALS = [(0, 1), (0, 3), (1, 1), (2, 1), (4, 2), (5, 1), (8, 4), (10, 1), (12, 1), (20, 8), (21, 1), (30, 2), (30, 1), (45, 3),
+                     (60, 1), (70, 4), (70, 1), (70, 1), (90, 2)]
+    g = torch.Generator().manual_seed(4)
+    lreqs = []
+    for i, (_, w) in enumerate(LONG_ARRIVALS):
+        n = int(torch.randint(T // 3, T + 1, (1,), generator=g)) if w == 1 else T + (w - 1) * stride
+        lreqs.append(Request(length=n, seed=700 + i, xf_out=torch.nn.functional.layer_norm(torch.randn(dims['Nt'], dims['Dt'], generator=g), (dims['Dt'],)).cuda()))
+    R = len(lreqs)
+    longs = [i for i, (_, w) in enumerate(LONG_ARRIVALS) if w > 1]
+
+    def replay_mixed():
+        bt = ContinuousBatcher(arch, batch=B, frames=T, sampler='ddim', steps=a.steps, overlap=ov)
+        k, done, lat = 0, 0, {}
+        while done < R:
+            while k < R and LONG_ARRIVALS[k][0] <= bt.ticks:
+                bt.submit(lreqs[k])
+                k += 1
+            if bt.tick() == 0:
+                bt.ticks = LONG_ARRIVALS[k][0]      # idle: the clock jumps to the next arrival
+            for h in bt.poll():
+                lat[h] = bt.finished_at[h] - LONG_ARRIVALS[h][0]
+                done += 1
+        return [lat[i] for i in longs], [lat[i] for i in range(R) if i not in longs]
+
+    def replay_coupled():
+        old, arch.inference_type = arch.inference_type, 'ddim'
+        tick_, k, waiting, lat = 0, 0, [], []
+        try:
+            while k < len(longs) or waiting:
+                while k < len(longs) and LONG_ARRIVALS[longs[k]][0] <= tick_:
+                    waiting.append(longs[k])
+                    k += 1
+                if not waiting:
+                    tick_ = LONG_ARRIVALS[longs[k]][0]
+                    continue
+                part, used = [], 0
+                while waiting and used + LONG_ARRIVALS[waiting[0]][1] <= B:
+                    used += LONG_ARRIVALS[waiting[0]][1]
+                    part.append(waiting.pop(0))
+                longform.sample_long_coupled(arch, [lreqs[i].length for i in part], T, ov, text=['a'] * len(part), input_dim=C,
+                                             condition_kwargs=dict(xf_out=torch.stack([lreqs[i].xf_out for i in part])),
+                                             inference_kwargs=dict(capacity_factor=0), max_batch=B, shard=False)
+                tick_ += a.steps
+                lat += [tick_ - LONG_ARRIVALS[i][0] for i in part]
+        finally:
+            arch.inference_type = old
+        return lat, []
+
+    for name, fn in (('ContinuousBatcher(overlap), all requests', replay_mixed), ('sample_long_coupled, the long ones alone', replay_coupled)) * 2:
+        box = {}
+
+        def run():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            box['lat'] = fn()
+            torch.cuda.synchronize()
+            return time.perf_counter() - t0
+        med, lo, hi = median_of(run)
+        ll, ls = box['lat']
+        nreq = len(ll) + len(ls)
+        short = f'; short: mean {sum(ls) / len(ls):6.1f}, max {max(ls)}' if ls else ''
+        print(f'{nreq} arrivals ({len(ll)} long, overlap {ov}), {a.steps}-step DDIM, B={B}, {name:42s}: median {med * 1e3:8.1f} ms = '
+              f'{nreq / med:7.2f} requests/s   (min {lo * 1e3:8.1f}, max {hi * 1e3:8.1f} ms);  ticks to completion, long: mean '
+              f'{sum(ll) / len(ll):6.1f}, max {max(ll)}{short}', flush=True)
 arch.model.release()
