@@ -190,7 +190,7 @@ int denoise_impl(mc_ctx* c, const float* x_t, int32_t step, float* out2_dev, int
 SamplerCoefs to_coefs(const mc_step_coefs* k);
 
 // x0 of a sampler step as denoise_combined leaves it: one array, or the two partial products of the folded tail (b != null), which the
-// sampler kernels add.  Their call pattern:  mc_launch_sampler_*(x_t, x0.a, x0.second(), ..., x0.coefs(k), ...)
+// sampler kernels add.  In a SamplerForm:  out_text = x0.a, out_none = x0.second(), c = x0.coefs(k)
 struct X0Parts {
     const float *a = nullptr, *b = nullptr;
     const float* second() const { return b ? b : a; }

@@ -46,67 +46,62 @@ struct SamplerCoefs {
     float sqrt_recip, sqrt_recipm1, ab, ab_prev, eta;   // ddim
     float nonzero;     // 0 at i == 0
 };
-// x_prev = sampler(x_t, x0 = text_coef*out_text + none_coef*out_none, noise); optionally also writes x0
-// table != nullptr (graph replay): the step's coefficients are table[*step_ptr]; only text_coef / none_coef of `c` are used
+// ---- the sampler update family (mc_kernels.hip): one launcher, the form described by what SamplerForm sets ----
 // rng (with noise == nullptr): the noise is drawn inside the kernel, Philox4x32-10 keyed by the seed, counter (element / 4, draw index)
 struct RngArgs { uint32_t seed_lo = 0, seed_hi = 0, draw_lo = 0, draw_hi = 0; };
 // pad (mc_sample_loop): x_prev is also written as rows of Cp floats into xpad (the next step's pose-encoder GEMM operand; the pad
 // columns are not touched)
 struct PadOut { float* xpad = nullptr; int C = 0, Cp = 0; };
-// rows (with rng, noise == nullptr): every row of TC elements draws from its own stream -- key keys[2 b] | keys[2 b + 1] << 32, counter
+// keys (drawn noise): every row of TC elements draws from its own stream -- key keys[2 b] | keys[2 b + 1] << 32, counter
 // (row-local element / 4, draw index); rng's seed is ignored (mc_ctx_set_row_seeds)
 struct RowKeys { const uint32_t* keys = nullptr; int TC = 0; };
 // Per-row schedules (mc_sample_rows): device tables of one tick -- step[B] schedule indices, coefs[B], draw[B]
 // Philox draw numbers (read only with in-kernel noise).  Row r of a [B T]- or [2 B T]-row operand belongs to request row (r / T) % B.
 struct RowTab { const int* step = nullptr; const SamplerCoefs* coefs = nullptr; const uint64_t* draw = nullptr; int B = 0, T = 0; };
-int mc_launch_sampler_update(const float* x_t, const float* out_text, const float* out_none,
-                             const float* noise, float* x_prev, float* x0_out, long n,
-                             SamplerCoefs c, hipStream_t s, const SamplerCoefs* table = nullptr, const int* step_ptr = nullptr,
-                             const RngArgs* rng = nullptr, const PadOut* pad = nullptr, const RowKeys* rows = nullptr);
-// mode 2 (multistep): x_prev = c.c2 x_t + c.c1 x0 + c.eta x0_hist;  x0_hist <- x0 (in-out [n], read only when c.eta != 0); no noise.
-// table / step_ptr / pad as above
-int mc_launch_sampler_multistep(const float* x_t, const float* out_text, const float* out_none, float* x0_hist, float* x_prev,
-                                float* x0_out, long n, SamplerCoefs c, hipStream_t s, const SamplerCoefs* table = nullptr,
-                                const int* step_ptr = nullptr, const PadOut* pad = nullptr);
-// The two updates with the coefficients of element e from rt.coefs[e / TC] (modes 0 / 1, or mode 2: one mode per launch, the caller
-// checks); x0 = tc out_text + nc out_none.  noise == nullptr: drawn in the kernel from the rows' keys at draw rt.draw[row].  A flat
-// group of four that straddles two rows takes each element's own row's entry.
-int mc_launch_sampler_update_rows(const float* x_t, const float* out_text, const float* out_none, const float* noise, float* x_prev,
-                                  float* x0_out, long n, float tc, float nc, const RowTab& rt, int TC, hipStream_t s,
-                                  const RowKeys* keys = nullptr, const PadOut* pad = nullptr);
-int mc_launch_sampler_multistep_rows(const float* x_t, const float* out_text, const float* out_none, float* x0_hist, float* x_prev,
-                                     float* x0_out, long n, float tc, float nc, const RowTab& rt, int TC, hipStream_t s,
-                                     const PadOut* pad = nullptr);
-// The two row updates with a kept region (mc_ctx_set_edit_rows): gt [B][TC] floats and keep [B][TC] bytes on the
-// device; where keep != 0, x0 = gt (a select) and, in mode 1, x_prev = sqrt(ab_prev) gt + sqrt(1 - ab_prev) z2 with z2 read from gt_noise
-// (beside a noise tensor) or drawn from the rows' keys at draw rt.draw[row] ^ 2^63 (noise == nullptr).  kword is the launcher's (the keep
-// table is 4-byte aligned: whole groups read their four bytes as one word).  All-zero keep bytes give the row kernels' bits.
+// A kept region (mc_ctx_set_edit_rows, section 4p): gt [B][TC] floats and keep [B][TC] bytes on the device; where keep != 0, x0 = gt (a
+// select) and, in mode 1, x_prev = sqrt(ab_prev) gt + sqrt(1 - ab_prev) z2 with z2 read from gt_noise (beside a noise tensor) or drawn
+// from the rows' keys at draw rt.draw[row] ^ 2^63.  kword is the launcher's (the keep table is 4-byte aligned: whole groups read their
+// four bytes as one word).  All-zero keep bytes give the plain row forms' bits.
 struct EditTab { const float* gt = nullptr; const uint8_t* keep = nullptr; const float* gt_noise = nullptr; int kword = 0; };
-int mc_launch_sampler_edit_rows(const float* x_t, const float* out_text, const float* out_none, const float* noise, EditTab et, float* x_prev,
-                                float* x0_out, long n, float tc, float nc, const RowTab& rt, int TC, int mode, hipStream_t s,
-                                const RowKeys* keys = nullptr, const PadOut* pad = nullptr);      // mode: the table's (0 or 1)
-int mc_launch_sampler_multistep_edit_rows(const float* x_t, const float* out_text, const float* out_none, float* x0_hist, EditTab et,
-                                          float* x_prev, float* x0_out, long n, float tc, float nc, const RowTab& rt, int TC, hipStream_t s,
-                                          const PadOut* pad = nullptr);
-// Seam-coupled update of B windows [B][T][C] (sampler_seam_k, all three modes): flags [B] ints on the device, bit 0 = the row shares
-// its first `ov` frames with the last `ov` of row b - 1, bit 1 = its last `ov` with the first of row b + 1 (the caller guarantees bit 1
-// of row b goes with bit 0 of row b + 1 and is clear on row B - 1); w [ov] = the right window's weight per shared frame; 0 < 2 ov <= T.
-// Modes 0 / 1: noise or rng as above (a seam element takes the LEFT row's draw); mode 2: x0_hist in-out, no noise.  No graph table.
+// The batch as one sequence of seam-coupled windows [B][T][C] (section 4l): flags [B] ints on the device, bit 0 = the row shares its
+// first `ov` frames with the last `ov` of row b - 1, bit 1 = its last `ov` with the first of row b + 1 (the caller guarantees bit 1 of
+// row b goes with bit 0 of row b + 1 and is clear on row B - 1); w [ov] = the right window's weight per shared frame; 0 < 2 ov <= T.
+// A seam element takes the LEFT row's noise / history.
 struct SeamTab { const int* flags = nullptr; const float* w = nullptr; int T = 0, C = 0, ov = 0; };
-int mc_launch_sampler_seam(const float* x_t, const float* out_text, const float* out_none, const float* noise, float* x0_hist,
-                           float* x_prev, float* x0_out, int B, SamplerCoefs c, const SeamTab& st, hipStream_t s,
-                           const RngArgs* rng = nullptr, const PadOut* pad = nullptr, const RowKeys* rows = nullptr);
-// Seam-coupled update in the per-row path (sampler_seam_rows_k; all three modes, `mode` the launch's one): the
-// rows update of mc_launch_sampler_update_rows / _multistep_rows with sampler_seam_k's blend between row b and row rows[b].right (ANY
-// row, or -1).  rows [B] and w [ov] on the device; the caller guarantees what mc_ctx_set_seam_rows checks (has_left of a row that is
-// some row's right neighbour and of no other, first frames a stride apart along a chain, equal coefficient entries on both rows of a
-// seam).  noise == nullptr (modes 0 / 1): drawn from keys[b] at draw rt.draw[b], counter ((first_frame[b] C + row-local element) / 4,
-// draw) -- the request-global counter rule.  n = B T C < 2^31 and T C >= 4.
+// Seam-coupled windows among per-row schedules (section 4q): the blend between row b and row rows[b].right (ANY row, or -1).  rows [B]
+// and w [ov] on the device; the caller guarantees what mc_ctx_set_seam_rows checks (has_left of a row that is some row's right
+// neighbour and of no other, first frames a stride apart along a chain, equal coefficient entries on both rows of a seam).  Drawn
+// noise takes counter ((first_frame[b] C + row-local element) / 4, draw): the request-global counter rule.  n < 2^31 and T C >= 4.
 struct alignas(16) SeamRow { int right, has_left, first_frame, pad; };      // (16-byte aligned: a row's entry is one vector load)
 struct SeamRowsTab { const SeamRow* rows = nullptr; const float* w = nullptr; int T = 0, C = 0, ov = 0; };
-int mc_launch_sampler_seam_rows(const float* x_t, const float* out_text, const float* out_none, const float* noise, float* x0_hist,
-                                float* x_prev, float* x0_out, float tc, float nc, const RowTab& rt, const SeamRowsTab& st, int mode,
-                                hipStream_t s, const RowKeys* keys = nullptr, const PadOut* pad = nullptr);
+// x_prev [n] = update(x_t, x0 = text_coef out_text + none_coef out_none, noise | history); optionally also writes x0.  One mode per
+// launch (`mode`): 0 / 1 take noise (the tensor, or drawn where it is null), 2 the in-out history x0_hist (x_prev = c2 x_t + c1 x0 +
+// eta x0_hist; x0_hist <- x0) and no noise.  x_prev may alias x_t.  What is set picks the kernel:
+//   nothing more      sampler_update_k / sampler_multistep_k: the entry `c`; table (graph replay): the entry is table[*step_ptr], only
+//                     text_coef / none_coef of `c` are used; drawn noise from rng, keyed per row where keys is set
+//   rt                sampler_update_rows_k / sampler_multistep_rows_k: element e under rt->coefs[e / TC] with c's text_coef / none_coef;
+//                     drawn noise from keys at draw rt->draw[row] (no rng)
+//   rt + edit         sampler_edit_rows_k / sampler_multistep_edit_rows_k
+//   rt + seam_rows    sampler_seam_rows_k
+//   seam              sampler_seam_k (the entry `c`; noise as in the first form)
+// Nothing else is a form: an edit table beside a seam table, a graph table beside rt or a seam table are refused.
+struct SamplerForm {
+    const float *x_t = nullptr, *out_text = nullptr, *out_none = nullptr, *noise = nullptr;
+    float *x0_hist = nullptr, *x_prev = nullptr, *x0_out = nullptr;
+    long n = 0;
+    int mode = 0, TC = 0;                  // TC: elements per row (with rt; the seam forms take T C of their table)
+    SamplerCoefs c = SamplerCoefs();
+    const SamplerCoefs* table = nullptr;
+    const int* step_ptr = nullptr;
+    const RngArgs* rng = nullptr;
+    const RowKeys* keys = nullptr;
+    const PadOut* pad = nullptr;
+    const RowTab* rt = nullptr;
+    const EditTab* edit = nullptr;
+    const SeamTab* seam = nullptr;
+    const SeamRowsTab* seam_rows = nullptr;
+};
+int mc_launch_sampler(const SamplerForm& f, hipStream_t s);
 // out [B][rk.TC] = draw rng.draw_* of every row's own stream (rng's seed is ignored)
 int mc_launch_philox_rows_fill(float* out, int B, RowKeys rk, RngArgs rng, hipStream_t s);
 // out[n] = the normals / bits[n] = the raw 32-bit words of draw `rng` (either may be null)

@@ -1195,141 +1195,87 @@ int mc_launch_softmax_rows_small(const float* W, float* out, int rows, int cols,
     return MC_OK;
 }
 
-int mc_launch_sampler_update(const float* x_t, const float* out_text, const float* out_none, const float* noise, float* x_prev, float* x0_out, long n,
-                             SamplerCoefs c, hipStream_t s, const SamplerCoefs* table, const int* step_ptr, const RngArgs* rng, const PadOut* pad,
-                             const RowKeys* rows) {
-    MC_REQUIRE(noise || rng, "sampler update: neither a noise tensor nor a Philox draw given");
-    MC_REQUIRE(!rows || (rows->keys && rows->TC > 0 && n % rows->TC == 0), "sampler update: row keys for rows of %d elements, %ld in all", rows ? rows->TC : 0, n);
-    // float4 path when every stream is 16-byte aligned (torch / workspace allocations are; out2 + B*T*C or noise + k*n need not be:
-    // C = 263 / 251 / 322 with an odd B*T) -- otherwise the element-wise form of the same kernel (same groups, same Philox counters)
-    const bool vec = ((uintptr_t)x_t | (uintptr_t)out_text | (uintptr_t)out_none | (uintptr_t)x_prev | (uintptr_t)x0_out | (uintptr_t)noise) % 16 == 0;
-    int blocks = cdiv((n + 3) / 4, 256);
+// The sampler family's one launcher: every check, the vector rule, the grid and the RNG x VEC selection stated once.
+namespace {
+template <class F> void with_bool(bool v, F&& f) { if (v) f(std::true_type{}); else f(std::false_type{}); }
+}  // namespace
+int mc_launch_sampler(const SamplerForm& f, hipStream_t s) {
+    const bool ms = f.mode == 2, rows = f.rt != nullptr, seam = f.seam || f.seam_rows;
+    const char* const form = f.seam_rows ? "seam rows" : f.seam ? "seam" : f.edit ? "edited rows" : rows ? "rows" : "uniform";
+    MC_REQUIRE(f.x_t && f.out_text && f.out_none && f.x_prev && (f.n >= 0 || !ms), "sampler update (%s): null operand", form);
+    MC_REQUIRE(f.mode >= 0 && f.mode <= 2, "sampler update (%s): unknown sampler mode %d", form, f.mode);
+    MC_REQUIRE((!f.edit || (rows && !seam)) && (!f.seam_rows || rows) && (!f.seam || (!rows && !f.seam_rows)) && (!f.table || (!rows && !seam)),
+               "sampler update (%s): no such form", form);
+    MC_REQUIRE(!ms || rows || f.table || f.c.mode == 2, "sampler update (%s): coefficients of mode %d in a launch of mode 2", form, f.c.mode);
+    // rows of TC elements
+    int TC = f.TC, C = 0;
+    if (seam) {
+        const int T = f.seam ? f.seam->T : f.seam_rows->T, ov = f.seam ? f.seam->ov : f.seam_rows->ov;
+        C = f.seam ? f.seam->C : f.seam_rows->C;
+        MC_REQUIRE(f.seam ? f.seam->flags && f.seam->w : f.seam_rows->rows && f.seam_rows->w, "sampler update (%s): no seam table", form);
+        MC_REQUIRE(T > 0 && C > 0 && ov > 0 && 2 * ov <= T, "sampler update (%s): overlap %d outside (0, %d / 2]", form, ov, T);
+        MC_REQUIRE((long)T * C <= 0x7fffffffL, "sampler update (%s): a window of %d x %d floats", form, T, C);
+        TC = T * C;
+        MC_REQUIRE(f.n % TC == 0, "sampler update (%s): %ld elements are no whole windows of %d", form, f.n, TC);
+        MC_REQUIRE(!f.seam_rows || (f.n <= 0x7fffffffL && TC >= 4), "sampler update (%s): %ld floats in rows of %d (the kernel indexes in 32 bits; a row holds at least 4)", form, f.n, TC);
+    }
+    MC_REQUIRE(!rows || (f.rt->coefs && f.rt->B > 0 && TC > 0 && f.n == (long)f.rt->B * TC), "sampler update (%s): %ld elements for %d rows of %d", form, f.n,
+               rows ? f.rt->B : 0, TC);
+    // noise (modes 0 / 1): the tensor, or drawn -- from rng (keyed per row where keys is set), under per-row schedules from keys at rt->draw
+    const bool drawn = !ms && !f.noise;
+    MC_REQUIRE(!f.keys || (f.keys->keys && f.keys->TC > 0 && (rows || seam ? f.keys->TC == TC : f.n % f.keys->TC == 0)),
+               "sampler update (%s): row keys for rows of %d elements, %ld in all", form, f.keys ? f.keys->TC : 0, f.n);
+    MC_REQUIRE(!drawn || rows || f.rng, "sampler update (%s): neither a noise tensor nor a Philox draw given", form);
+    MC_REQUIRE(!drawn || !rows || (f.keys && f.rt->draw), "sampler update (%s): no noise tensor, and no seed table / draw numbers", form);
+    // the history (mode 2)
+    float* const hist = ms ? f.x0_hist : nullptr;
+    MC_REQUIRE(!ms || hist, "sampler update (%s): mode 2 without a history buffer", form);
+    MC_REQUIRE(!ms || (hist != f.x_t && hist != f.x_prev && hist != f.x0_out && hist != f.out_text && hist != f.out_none && (!f.edit || hist != f.edit->gt)),
+               "sampler update (%s): the history buffer aliases another operand", form);
+    EditTab et = f.edit ? *f.edit : EditTab();
+    if (f.edit) {
+        MC_REQUIRE(et.gt && et.keep, "sampler update (%s): no gt / keep table", form);
+        if (drawn || f.mode != 1) et.gt_noise = nullptr;      // (both noises come from the rows' streams; modes 0 and 2 take no second one)
+        MC_REQUIRE(f.mode != 1 || drawn || et.gt_noise, "sampler update (%s): mode 1 beside a noise tensor needs the kept region's noise tensor", form);
+        et.kword = (uintptr_t)et.keep % 4 == 0 ? 1 : 0;
+    }
+    const PadOut po = f.pad ? *f.pad : PadOut();
+    MC_REQUIRE(!po.xpad || (po.C > 0 && po.Cp >= po.C && (!seam || po.C == C)), "sampler update (%s): bad padded-copy shape", form);
+    if (f.n <= 0) return MC_OK;
+    // the vector rule: f32x4 loads / stores when every stream the form reads or writes is 16-byte aligned (torch / workspace allocations
+    // are; out2 + B*T*C or noise + k*n need not be: C = 263 / 251 / 322 with an odd B*T) -- otherwise the element form of the same
+    // kernel (same groups, same Philox counters)
+    const bool vec = ((uintptr_t)f.x_t | (uintptr_t)f.out_text | (uintptr_t)f.out_none | (uintptr_t)f.x_prev | (uintptr_t)f.x0_out |
+                      (uintptr_t)(ms ? hist : f.noise) | (uintptr_t)et.gt | (uintptr_t)et.gt_noise) % 16 == 0;
+    int blocks = cdiv((f.n + 3) / 4, 256);
     if (blocks > 2048) blocks = 2048;
-    if (blocks < 1) blocks = 1;
-    const bool dev_rng = rng && !noise;
-    const RngArgs ra = dev_rng ? *rng : RngArgs();
-    const PadOut po = pad ? *pad : PadOut();
-    MC_REQUIRE(!po.xpad || (po.C > 0 && po.Cp >= po.C), "sampler update: bad padded-copy shape");
-#define MC_SU(R, V) hipLaunchKernelGGL((sampler_update_k<R, V>), dim3(blocks), dim3(256), 0, s, x_t, out_text, out_none, noise, x_prev, x0_out, n, c, table, step_ptr, ra, po)
-    if (dev_rng && rows) {        // the rows' own streams (same kernel, RowNoise draw)
-        const RowNoise rn{ra, *rows};
-        if (vec) hipLaunchKernelGGL((sampler_update_k<true, true, RowNoise>), dim3(blocks), dim3(256), 0, s, x_t, out_text, out_none, noise, x_prev, x0_out, n, c, table, step_ptr, rn, po);
-        else hipLaunchKernelGGL((sampler_update_k<true, false, RowNoise>), dim3(blocks), dim3(256), 0, s, x_t, out_text, out_none, noise, x_prev, x0_out, n, c, table, step_ptr, rn, po);
-    } else if (dev_rng) { if (vec) MC_SU(true, true); else MC_SU(true, false); }
-    else { if (vec) MC_SU(false, true); else MC_SU(false, false); }
-#undef MC_SU
+    const RngArgs ra = drawn && f.rng ? *f.rng : RngArgs();
+    const RowKeys rk{drawn && f.keys ? f.keys->keys : nullptr, TC};
+    const RowNoise rn{ra, f.keys ? *f.keys : RowKeys()};
+    const bool row_noise = drawn && f.keys;            // (uniform entries: the rows' own streams at the call's draw)
+    const float tc = f.c.text_coef, nc = f.c.none_coef;
+#define MC_GO(K, ...) hipLaunchKernelGGL(K, dim3(blocks), dim3(256), 0, s, f.x_t, f.out_text, f.out_none, __VA_ARGS__)
+    with_bool(vec, [&](auto vec_t) {
+        constexpr bool V = decltype(vec_t)::value;
+        with_bool(drawn, [&](auto drawn_t) {
+            constexpr bool R = decltype(drawn_t)::value;
+            if (f.seam_rows) MC_GO((sampler_seam_rows_k<R, V>), f.noise, hist, f.x_prev, f.x0_out, (uint32_t)f.n, tc, nc, f.rt->coefs, rk, f.rt->draw, *f.seam_rows, ms ? 1 : 0, po);
+            else if (f.seam && row_noise) MC_GO((sampler_seam_k<true, V, RowNoise>), f.noise, hist, f.x_prev, f.x0_out, f.n, f.c, *f.seam, rn, po);
+            else if (f.seam) MC_GO((sampler_seam_k<R, V>), f.noise, hist, f.x_prev, f.x0_out, f.n, f.c, *f.seam, ra, po);
+            else if (f.edit && ms) MC_GO((sampler_multistep_edit_rows_k<V>), hist, et, f.x_prev, f.x0_out, f.n, tc, nc, f.rt->coefs, TC, po);
+            else if (f.edit) MC_GO((sampler_edit_rows_k<R, V>), f.noise, et, f.x_prev, f.x0_out, f.n, tc, nc, f.rt->coefs, rk, f.rt->draw, po);
+            else if (rows && ms) MC_GO((sampler_multistep_rows_k<V>), hist, f.x_prev, f.x0_out, f.n, tc, nc, f.rt->coefs, TC, po);
+            else if (rows) MC_GO((sampler_update_rows_k<R, V>), f.noise, f.x_prev, f.x0_out, f.n, tc, nc, f.rt->coefs, rk, f.rt->draw, po);
+            else if (ms) MC_GO((sampler_multistep_k<V>), hist, f.x_prev, f.x0_out, f.n, f.c, f.table, f.step_ptr, po);
+            else if (row_noise) MC_GO((sampler_update_k<true, V, RowNoise>), f.noise, f.x_prev, f.x0_out, f.n, f.c, f.table, f.step_ptr, rn, po);
+            else MC_GO((sampler_update_k<R, V>), f.noise, f.x_prev, f.x0_out, f.n, f.c, f.table, f.step_ptr, ra, po);
+        });
+    });
+#undef MC_GO
     MC_LAUNCH_CHECK();
     return MC_OK;
 }
 
-int mc_launch_sampler_multistep(const float* x_t, const float* out_text, const float* out_none, float* x0_hist, float* x_prev, float* x0_out, long n,
-                                SamplerCoefs c, hipStream_t s, const SamplerCoefs* table, const int* step_ptr, const PadOut* pad) {
-    MC_REQUIRE(x_t && out_text && out_none && x0_hist && x_prev && n >= 0, "multistep update: null operand");
-    MC_REQUIRE(table || c.mode == 2, "multistep update: coefficients of mode %d", c.mode);
-    MC_REQUIRE(x0_hist != x_t && x0_hist != x_prev && x0_hist != x0_out && x0_hist != out_text && x0_hist != out_none,
-               "multistep update: the history buffer aliases another operand");
-    if (n == 0) return MC_OK;
-    const bool vec = ((uintptr_t)x_t | (uintptr_t)out_text | (uintptr_t)out_none | (uintptr_t)x_prev | (uintptr_t)x0_out | (uintptr_t)x0_hist) % 16 == 0;
-    int blocks = cdiv((n + 3) / 4, 256);
-    if (blocks > 2048) blocks = 2048;
-    const PadOut po = pad ? *pad : PadOut();
-    MC_REQUIRE(!po.xpad || (po.C > 0 && po.Cp >= po.C), "multistep update: bad padded-copy shape");
-    if (vec) hipLaunchKernelGGL((sampler_multistep_k<true>), dim3(blocks), dim3(256), 0, s, x_t, out_text, out_none, x0_hist, x_prev, x0_out, n, c, table, step_ptr, po);
-    else hipLaunchKernelGGL((sampler_multistep_k<false>), dim3(blocks), dim3(256), 0, s, x_t, out_text, out_none, x0_hist, x_prev, x0_out, n, c, table, step_ptr, po);
-    MC_LAUNCH_CHECK();
-    return MC_OK;
-}
-
-// the per-row forms: the same vector rule, grids and PadOut checks as the two launchers above
-int mc_launch_sampler_update_rows(const float* x_t, const float* out_text, const float* out_none, const float* noise, float* x_prev,
-                                  float* x0_out, long n, float tc, float nc, const RowTab& rt, int TC, hipStream_t s, const RowKeys* keys,
-                                  const PadOut* pad) {
-    MC_REQUIRE(x_t && out_text && out_none && x_prev && rt.coefs && rt.B > 0 && TC > 0 && n == (long)rt.B * TC,
-               "row sampler update: %ld elements for %d rows of %d", n, rt.B, TC);
-    const bool dev_rng = !noise;
-    MC_REQUIRE(!dev_rng || (keys && keys->keys && keys->TC == TC && rt.draw), "row sampler update: no noise tensor, and no seed table / draw numbers");
-    const bool vec = ((uintptr_t)x_t | (uintptr_t)out_text | (uintptr_t)out_none | (uintptr_t)x_prev | (uintptr_t)x0_out | (uintptr_t)noise) % 16 == 0;
-    int blocks = cdiv((n + 3) / 4, 256);
-    if (blocks > 2048) blocks = 2048;
-    if (blocks < 1) blocks = 1;
-    const PadOut po = pad ? *pad : PadOut();
-    MC_REQUIRE(!po.xpad || (po.C > 0 && po.Cp >= po.C), "row sampler update: bad padded-copy shape");
-    const RowKeys rk{dev_rng ? keys->keys : nullptr, TC};
-#define MC_SUR(R, V) hipLaunchKernelGGL((sampler_update_rows_k<R, V>), dim3(blocks), dim3(256), 0, s, x_t, out_text, out_none, noise, x_prev, x0_out, n, tc, nc, rt.coefs, rk, rt.draw, po)
-    if (dev_rng) { if (vec) MC_SUR(true, true); else MC_SUR(true, false); }
-    else { if (vec) MC_SUR(false, true); else MC_SUR(false, false); }
-#undef MC_SUR
-    MC_LAUNCH_CHECK();
-    return MC_OK;
-}
-
-int mc_launch_sampler_multistep_rows(const float* x_t, const float* out_text, const float* out_none, float* x0_hist, float* x_prev,
-                                     float* x0_out, long n, float tc, float nc, const RowTab& rt, int TC, hipStream_t s, const PadOut* pad) {
-    MC_REQUIRE(x_t && out_text && out_none && x0_hist && x_prev && rt.coefs && rt.B > 0 && TC > 0 && n == (long)rt.B * TC,
-               "row multistep update: %ld elements for %d rows of %d", n, rt.B, TC);
-    MC_REQUIRE(x0_hist != x_t && x0_hist != x_prev && x0_hist != x0_out && x0_hist != out_text && x0_hist != out_none,
-               "row multistep update: the history buffer aliases another operand");
-    const bool vec = ((uintptr_t)x_t | (uintptr_t)out_text | (uintptr_t)out_none | (uintptr_t)x_prev | (uintptr_t)x0_out | (uintptr_t)x0_hist) % 16 == 0;
-    int blocks = cdiv((n + 3) / 4, 256);
-    if (blocks > 2048) blocks = 2048;
-    const PadOut po = pad ? *pad : PadOut();
-    MC_REQUIRE(!po.xpad || (po.C > 0 && po.Cp >= po.C), "row multistep update: bad padded-copy shape");
-    if (vec) hipLaunchKernelGGL((sampler_multistep_rows_k<true>), dim3(blocks), dim3(256), 0, s, x_t, out_text, out_none, x0_hist, x_prev, x0_out, n, tc, nc, rt.coefs, TC, po);
-    else hipLaunchKernelGGL((sampler_multistep_rows_k<false>), dim3(blocks), dim3(256), 0, s, x_t, out_text, out_none, x0_hist, x_prev, x0_out, n, tc, nc, rt.coefs, TC, po);
-    MC_LAUNCH_CHECK();
-    return MC_OK;
-}
-
-// the edited forms: the same grids and checks; gt (and gt_noise where it is read) join the vector rule
-int mc_launch_sampler_edit_rows(const float* x_t, const float* out_text, const float* out_none, const float* noise, EditTab et, float* x_prev,
-                                float* x0_out, long n, float tc, float nc, const RowTab& rt, int TC, int mode, hipStream_t s,
-                                const RowKeys* keys, const PadOut* pad) {
-    MC_REQUIRE(x_t && out_text && out_none && x_prev && rt.coefs && rt.B > 0 && TC > 0 && n == (long)rt.B * TC,
-               "edited row sampler update: %ld elements for %d rows of %d", n, rt.B, TC);
-    MC_REQUIRE(et.gt && et.keep, "edited row sampler update: no gt / keep table");
-    const bool dev_rng = !noise;
-    MC_REQUIRE(!dev_rng || (keys && keys->keys && keys->TC == TC && rt.draw), "edited row sampler update: no noise tensor, and no seed table / draw numbers");
-    MC_REQUIRE(mode == 0 || mode == 1, "edited row sampler update: mode %d (0 or 1: the table's one mode)", mode);
-    if (dev_rng || mode == 0) et.gt_noise = nullptr;      // (both noises come from the rows' streams; mode 0 draws no second one)
-    MC_REQUIRE(mode == 0 || dev_rng || et.gt_noise, "edited row sampler update: mode 1 beside a noise tensor needs the kept region's noise tensor");
-    const bool vec = ((uintptr_t)x_t | (uintptr_t)out_text | (uintptr_t)out_none | (uintptr_t)x_prev | (uintptr_t)x0_out | (uintptr_t)noise |
-                      (uintptr_t)et.gt | (uintptr_t)et.gt_noise) % 16 == 0;
-    et.kword = (uintptr_t)et.keep % 4 == 0 ? 1 : 0;
-    int blocks = cdiv((n + 3) / 4, 256);
-    if (blocks > 2048) blocks = 2048;
-    if (blocks < 1) blocks = 1;
-    const PadOut po = pad ? *pad : PadOut();
-    MC_REQUIRE(!po.xpad || (po.C > 0 && po.Cp >= po.C), "edited row sampler update: bad padded-copy shape");
-    const RowKeys rk{dev_rng ? keys->keys : nullptr, TC};
-#define MC_SER(R, V) hipLaunchKernelGGL((sampler_edit_rows_k<R, V>), dim3(blocks), dim3(256), 0, s, x_t, out_text, out_none, noise, et, x_prev, x0_out, n, tc, nc, rt.coefs, rk, rt.draw, po)
-    if (dev_rng) { if (vec) MC_SER(true, true); else MC_SER(true, false); }
-    else { if (vec) MC_SER(false, true); else MC_SER(false, false); }
-#undef MC_SER
-    MC_LAUNCH_CHECK();
-    return MC_OK;
-}
-
-int mc_launch_sampler_multistep_edit_rows(const float* x_t, const float* out_text, const float* out_none, float* x0_hist, EditTab et,
-                                          float* x_prev, float* x0_out, long n, float tc, float nc, const RowTab& rt, int TC, hipStream_t s,
-                                          const PadOut* pad) {
-    MC_REQUIRE(x_t && out_text && out_none && x0_hist && x_prev && rt.coefs && rt.B > 0 && TC > 0 && n == (long)rt.B * TC,
-               "edited row multistep update: %ld elements for %d rows of %d", n, rt.B, TC);
-    MC_REQUIRE(et.gt && et.keep, "edited row multistep update: no gt / keep table");
-    MC_REQUIRE(x0_hist != x_t && x0_hist != x_prev && x0_hist != x0_out && x0_hist != out_text && x0_hist != out_none && x0_hist != et.gt,
-               "edited row multistep update: the history buffer aliases another operand");
-    const bool vec = ((uintptr_t)x_t | (uintptr_t)out_text | (uintptr_t)out_none | (uintptr_t)x_prev | (uintptr_t)x0_out | (uintptr_t)x0_hist |
-                      (uintptr_t)et.gt) % 16 == 0;
-    et.kword = (uintptr_t)et.keep % 4 == 0 ? 1 : 0;
-    et.gt_noise = nullptr;
-    int blocks = cdiv((n + 3) / 4, 256);
-    if (blocks > 2048) blocks = 2048;
-    const PadOut po = pad ? *pad : PadOut();
-    MC_REQUIRE(!po.xpad || (po.C > 0 && po.Cp >= po.C), "edited row multistep update: bad padded-copy shape");
-    if (vec) hipLaunchKernelGGL((sampler_multistep_edit_rows_k<true>), dim3(blocks), dim3(256), 0, s, x_t, out_text, out_none, x0_hist, et, x_prev, x0_out, n, tc, nc, rt.coefs, TC, po);
-    else hipLaunchKernelGGL((sampler_multistep_edit_rows_k<false>), dim3(blocks), dim3(256), 0, s, x_t, out_text, out_none, x0_hist, et, x_prev, x0_out, n, tc, nc, rt.coefs, TC, po);
-    MC_LAUNCH_CHECK();
-    return MC_OK;
-}
 
 int mc_launch_axpby_rows(const float* x, const float* y, const RowTab& rt, int D, float* out, long n, hipStream_t s) {
     MC_REQUIRE(rt.coefs && rt.B > 0 && rt.T > 0 && D > 0, "axpby rows: no coefficient table");
@@ -1348,73 +1294,6 @@ int mc_launch_axpby_pair_rows(const float* x0, const float* y0, float* out0, con
     int blocks = cdiv(n, 256);
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(axpby_pair_rows_k, dim3(blocks, 2), dim3(256), 0, s, AxpbySet{x0, y0, out0}, AxpbySet{x1, y1, out1}, rt.coefs, D, rt.T, rt.B, n);
-    MC_LAUNCH_CHECK();
-    return MC_OK;
-}
-
-int mc_launch_sampler_seam(const float* x_t, const float* out_text, const float* out_none, const float* noise, float* x0_hist, float* x_prev,
-                           float* x0_out, int B, SamplerCoefs c, const SeamTab& st, hipStream_t s, const RngArgs* rng, const PadOut* pad,
-                           const RowKeys* rows) {
-    MC_REQUIRE(!rows || (rows->keys && rows->TC == st.T * st.C), "seam update: row keys for rows of %d elements, windows of %d", rows ? rows->TC : 0, st.T * st.C);
-    MC_REQUIRE(x_t && out_text && out_none && x_prev && st.flags && st.w && B >= 0, "seam update: null operand");
-    MC_REQUIRE(st.T > 0 && st.C > 0 && st.ov > 0 && 2 * st.ov <= st.T, "seam update: overlap %d outside (0, %d / 2]", st.ov, st.T);
-    MC_REQUIRE((long)st.T * st.C <= 0x7fffffffL, "seam update: a window of %d x %d floats", st.T, st.C);
-    MC_REQUIRE(c.mode >= 0 && c.mode <= 2, "seam update: unknown sampler mode %d", c.mode);
-    const bool ms = c.mode == 2;
-    MC_REQUIRE(ms || noise || rng, "seam update: neither a noise tensor nor a Philox draw given");
-    MC_REQUIRE(!ms || x0_hist, "seam update: mode 2 without a history buffer");
-    MC_REQUIRE(!ms || (x0_hist != x_t && x0_hist != x_prev && x0_hist != x0_out && x0_hist != out_text && x0_hist != out_none),
-               "seam update: the history buffer aliases another operand");
-    const long n = (long)B * st.T * st.C;
-    if (n == 0) return MC_OK;
-    const bool vec = ((uintptr_t)x_t | (uintptr_t)out_text | (uintptr_t)out_none | (uintptr_t)x_prev | (uintptr_t)x0_out |
-                      (uintptr_t)(ms ? nullptr : noise) | (uintptr_t)(ms ? x0_hist : nullptr)) % 16 == 0;
-    int blocks = cdiv((n + 3) / 4, 256);
-    if (blocks > 2048) blocks = 2048;
-    const bool dev_rng = !ms && rng && !noise;
-    const RngArgs ra = dev_rng ? *rng : RngArgs();
-    const PadOut po = pad ? *pad : PadOut();
-    MC_REQUIRE(!po.xpad || (po.C == st.C && po.Cp >= po.C), "seam update: bad padded-copy shape");
-#define MC_SS(R, V) hipLaunchKernelGGL((sampler_seam_k<R, V>), dim3(blocks), dim3(256), 0, s, x_t, out_text, out_none, noise, x0_hist, x_prev, x0_out, n, c, st, ra, po)
-    if (dev_rng && rows) {        // a seam element takes the LEFT row's key and its row-local counter (its owner is the left row's thread)
-        const RowNoise rn{ra, *rows};
-        if (vec) hipLaunchKernelGGL((sampler_seam_k<true, true, RowNoise>), dim3(blocks), dim3(256), 0, s, x_t, out_text, out_none, noise, x0_hist, x_prev, x0_out, n, c, st, rn, po);
-        else hipLaunchKernelGGL((sampler_seam_k<true, false, RowNoise>), dim3(blocks), dim3(256), 0, s, x_t, out_text, out_none, noise, x0_hist, x_prev, x0_out, n, c, st, rn, po);
-    } else if (dev_rng) { if (vec) MC_SS(true, true); else MC_SS(true, false); }
-    else { if (vec) MC_SS(false, true); else MC_SS(false, false); }
-#undef MC_SS
-    MC_LAUNCH_CHECK();
-    return MC_OK;
-}
-
-int mc_launch_sampler_seam_rows(const float* x_t, const float* out_text, const float* out_none, const float* noise, float* x0_hist,
-                                float* x_prev, float* x0_out, float tc, float nc, const RowTab& rt, const SeamRowsTab& st, int mode,
-                                hipStream_t s, const RowKeys* keys, const PadOut* pad) {
-    MC_REQUIRE(x_t && out_text && out_none && x_prev && rt.coefs && rt.B > 0 && st.rows && st.w, "seam rows update: null operand");
-    MC_REQUIRE(st.T > 0 && st.C > 0 && st.ov > 0 && 2 * st.ov <= st.T, "seam rows update: overlap %d outside (0, %d / 2]", st.ov, st.T);
-    MC_REQUIRE(mode >= 0 && mode <= 2, "seam rows update: unknown sampler mode %d", mode);
-    const long nl = (long)rt.B * st.T * st.C, TCl = (long)st.T * st.C;
-    MC_REQUIRE(nl <= 0x7fffffffL && TCl >= 4, "seam rows update: %d rows of %d x %d floats (the kernel indexes in 32 bits; a row holds at least 4)", rt.B, st.T, st.C);
-    const int TC = (int)TCl;
-    const bool ms = mode == 2;
-    const bool dev_rng = !ms && !noise;
-    MC_REQUIRE(!dev_rng || (keys && keys->keys && keys->TC == TC && rt.draw), "seam rows update: no noise tensor, and no seed table / draw numbers");
-    MC_REQUIRE(!ms || x0_hist, "seam rows update: mode 2 without a history buffer");
-    MC_REQUIRE(!ms || (x0_hist != x_t && x0_hist != x_prev && x0_hist != x0_out && x0_hist != out_text && x0_hist != out_none),
-               "seam rows update: the history buffer aliases another operand");
-    const bool vec = ((uintptr_t)x_t | (uintptr_t)out_text | (uintptr_t)out_none | (uintptr_t)x_prev | (uintptr_t)x0_out |
-                      (uintptr_t)(ms ? nullptr : noise) | (uintptr_t)(ms ? x0_hist : nullptr)) % 16 == 0;
-    const uint32_t n = (uint32_t)nl;
-    int blocks = cdiv((nl + 3) / 4, 256);
-    if (blocks > 2048) blocks = 2048;
-    const PadOut po = pad ? *pad : PadOut();
-    MC_REQUIRE(!po.xpad || (po.C == st.C && po.Cp >= po.C), "seam rows update: bad padded-copy shape");
-    const RowKeys rk{dev_rng ? keys->keys : nullptr, TC};
-    float* const hist = ms ? x0_hist : nullptr;
-#define MC_SSR(R, V) hipLaunchKernelGGL((sampler_seam_rows_k<R, V>), dim3(blocks), dim3(256), 0, s, x_t, out_text, out_none, noise, hist, x_prev, x0_out, n, tc, nc, rt.coefs, rk, rt.draw, st, ms ? 1 : 0, po)
-    if (dev_rng) { if (vec) MC_SSR(true, true); else MC_SSR(true, false); }
-    else { if (vec) MC_SSR(false, true); else MC_SSR(false, false); }
-#undef MC_SSR
     MC_LAUNCH_CHECK();
     return MC_OK;
 }

@@ -1193,7 +1193,10 @@ int mc_sample_step_seeded(mc_ctx* c, float* x_t, int32_t step, const mc_step_coe
     X0Parts p;
     if (int r = denoise_combined(c, x_t, step, k, stream, &p, &a)) return r;
     const long n = (long)c->B * c->T * c->m->cfg.input_feats;
-    return mc_launch_sampler_update(x_t, p.a, p.second(), noise, x_prev, x0, n, p.coefs(k), (hipStream_t)stream);
+    SamplerForm f;
+    f.x_t = x_t; f.out_text = p.a; f.out_none = p.second(); f.noise = noise; f.x_prev = x_prev; f.x0_out = x0; f.n = n;
+    f.c = p.coefs(k); f.mode = MC_SAMPLER_DDPM;          // (multistep is refused above: sampler_update_k, which reads the entry's own mode)
+    return mc_launch_sampler(f, (hipStream_t)stream);
 }
 
 int mc_sample_step_inpaint(mc_ctx* c, const float* x_t, int32_t step, const mc_step_coefs* k, const float* noise,
@@ -1426,29 +1429,86 @@ int mc_op_temporal_attention(const float* mf, const float* tf, const float* mask
     return MC_ERR_ARG;
 }
 
+// ---- the sampler family as context-free ops (tests, tools): every form through mc_launch_sampler ----
+static SamplerForm op_form(const float* x_t, const float* ot, const float* on, const float* noise, float* x0_hist, float* x_prev, float* x0, long n,
+                           const mc_step_coefs* k) {
+    SamplerForm f;
+    f.x_t = x_t; f.out_text = ot; f.out_none = on; f.x_prev = x_prev; f.x0_out = x0; f.n = n;
+    f.c = to_coefs(k);
+    f.mode = k->mode;
+    if (is_multistep(k)) f.x0_hist = x0_hist; else f.noise = noise;
+    return f;
+}
+
 int mc_op_sampler_update(const float* x_t, const float* ot, const float* on, const float* noise, float* x_prev, float* x0,
                          int64_t n, const mc_step_coefs* k, void* stream) {
     MC_REQUIRE(x_t && ot && on && noise && x_prev && k, "null argument");
-    return mc_launch_sampler_update(x_t, ot, on, noise, x_prev, x0, n, to_coefs(k), (hipStream_t)stream);
+    SamplerForm f = op_form(x_t, ot, on, noise, nullptr, x_prev, x0, n, k);
+    f.noise = noise; f.mode = MC_SAMPLER_DDPM;          // (this entry is sampler_update_k whatever k->mode says: the kernel reads the entry's own mode)
+    return mc_launch_sampler(f, (hipStream_t)stream);
 }
 
 int mc_op_sampler_multistep(const float* x_t, const float* ot, const float* on, float* x0_hist, float* x_prev, float* x0, int64_t n,
                             const mc_step_coefs* k, void* stream) {
     MC_REQUIRE(x_t && ot && on && x0_hist && x_prev && k && n >= 0, "bad argument");
     MC_REQUIRE(is_multistep(k), "mc_op_sampler_multistep: coefficients of mode %d (MC_SAMPLER_MULTISTEP = 2 expected)", k->mode);
-    return mc_launch_sampler_multistep(x_t, ot, on, x0_hist, x_prev, x0, n, to_coefs(k), (hipStream_t)stream);
+    return mc_launch_sampler(op_form(x_t, ot, on, nullptr, x0_hist, x_prev, x0, n, k), (hipStream_t)stream);
 }
 
-// ---- the per-row kernel forms as context-free ops (tests): the coefficient table is a temporary device copy, so both synchronise ----
-static int rows_tab_upload(const mc_step_coefs* coefs, int B, SamplerCoefs** dev, hipStream_t s) {
-    std::vector<SamplerCoefs> tab((size_t)B);
-    for (int b = 0; b < B; ++b) tab[b] = to_coefs(&coefs[b]);
-    MC_HIP(hipMalloc((void**)dev, sizeof(SamplerCoefs) * B));
-    if (hipMemcpyAsync(*dev, tab.data(), sizeof(SamplerCoefs) * B, hipMemcpyHostToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
-        (void)hipFree(*dev);
-        mc_set_error("row coefficient table upload failed");
+// A temporary device table of an op entry: uploaded before the launch, given back on every path once the stream has drained (the
+// launch reads it), so the ops that take one synchronise.
+}  // extern "C"
+namespace {
+struct TempTable {
+    void* p = nullptr;
+    hipStream_t s;
+    explicit TempTable(hipStream_t s_) : s(s_) {}
+    TempTable(const TempTable&) = delete;
+    TempTable& operator=(const TempTable&) = delete;
+    ~TempTable() {
+        (void)hipStreamSynchronize(s);
+        if (p) (void)hipFree(p);
+    }
+    int alloc(size_t bytes, const char* what) {
+        if (hipMalloc(&p, bytes) == hipSuccess) return MC_OK;
+        p = nullptr;
+        mc_set_error("%s: temporary table allocation failed", what);
         return MC_ERR_HIP;
     }
+    int upload(const void* host, size_t bytes, const char* what, const void* more = nullptr, size_t more_bytes = 0) {      // (`more`: a second piece right behind the first)
+        if (int r = alloc(bytes + more_bytes, what)) return r;
+        if (hipMemcpyAsync(p, host, bytes, hipMemcpyHostToDevice, s) == hipSuccess &&
+            (!more_bytes || hipMemcpyAsync(static_cast<char*>(p) + bytes, more, more_bytes, hipMemcpyHostToDevice, s) == hipSuccess) &&
+            hipStreamSynchronize(s) == hipSuccess) return MC_OK;
+        mc_set_error("%s: temporary table upload failed", what);
+        return MC_ERR_HIP;
+    }
+};
+}  // namespace
+extern "C" {
+// the per-row forms: one mode per call ...
+static int rows_one_mode(const char* what, const mc_step_coefs* coefs, int B) {
+    for (int b = 0; b < B; ++b) {
+        if (int r = check_mode(&coefs[b])) return r;
+        MC_REQUIRE(coefs[b].mode == coefs[0].mode, "%s: row %d in mode %d beside mode %d (one mode per call)", what, b, coefs[b].mode, coefs[0].mode);
+    }
+    return MC_OK;
+}
+// ... their coefficient table rt->coefs [B] ...
+static int rows_tab_upload(const char* what, const mc_step_coefs* coefs, int B, TempTable* t, RowTab* rt) {
+    std::vector<SamplerCoefs> tab((size_t)B);
+    for (int b = 0; b < B; ++b) tab[b] = to_coefs(&coefs[b]);
+    if (int r = t->upload(tab.data(), sizeof(SamplerCoefs) * B, what)) return r;
+    rt->coefs = static_cast<const SamplerCoefs*>(t->p);
+    return MC_OK;
+}
+// ... and, for noise drawn in the kernel, [B] keys | [B] draw numbers (rk->keys, rt->draw)
+static int rows_keys_upload(const char* what, const uint64_t* seeds, const uint64_t* draw, int B, int TC, TempTable* t, RowTab* rt, RowKeys* rk) {
+    std::vector<uint64_t> h((size_t)2 * B);
+    for (int b = 0; b < B; ++b) { h[b] = seeds[b]; h[(size_t)B + b] = draw[b]; }
+    if (int r = t->upload(h.data(), sizeof(uint64_t) * 2 * B, what)) return r;
+    rk->keys = static_cast<const uint32_t*>(t->p); rk->TC = TC;
+    rt->draw = static_cast<const uint64_t*>(t->p) + B;
     return MC_OK;
 }
 
@@ -1463,15 +1523,14 @@ int mc_op_gemm_tail_rows(const float* h, const float* a, const float* w, const f
     if (!o) return MC_ERR_ARG;
     RowTab rt;
     rt.B = M / T; rt.T = T;
-    SamplerCoefs* tab = nullptr;
+    TempTable tab(s), scratch(s);
     int r;
-    if ((r = rows_tab_upload(coefs, rt.B, &tab, s))) return r;
-    rt.coefs = tab;
-    float* comb = nullptr;
+    if ((r = rows_tab_upload("gemm_tail_rows", coefs, rt.B, &tab, &rt))) return r;
     if (variant == 3) {
         // the small-batch form of denoise_combined: h_c | a_c by axpby_pair_rows_k, then the two skinny products as one grouped GEMM
         const long MK = (long)M * K;
-        if (hipMalloc((void**)&comb, sizeof(float) * 2 * MK) != hipSuccess) { (void)hipFree(tab); mc_set_error("gemm_tail_rows: scratch allocation failed"); return MC_ERR_HIP; }
+        if ((r = scratch.alloc(sizeof(float) * 2 * MK, "gemm_tail_rows"))) return r;
+        float* const comb = static_cast<float*>(scratch.p);
         r = mc_launch_axpby_pair_rows(h, h + MK, comb, a, a + MK, comb + MK, rt, K, MK, s);
         GemmArgs t;
         mc_gemm_opts(*o, t);
@@ -1484,7 +1543,7 @@ int mc_op_gemm_tail_rows(const float* h, const float* a, const float* w, const f
         TailArgs t;
         t.H = h; t.Af = a; t.half = (long)M * K; t.lda = K; t.W = w; t.ldw = K; t.w_gstride = (long)N * K; t.bias = bias; t.b_gstride = N;
         t.C = cdev; t.ldc = N; t.M = M; t.N = N; t.K = K; t.C2 = c2dev;
-        t.coef_table = reinterpret_cast<const float*>(tab) + offsetof(SamplerCoefs, text_coef) / sizeof(float);
+        t.coef_table = reinterpret_cast<const float*>(rt.coefs) + offsetof(SamplerCoefs, text_coef) / sizeof(float);
         t.coef_stride = sizeof(SamplerCoefs) / sizeof(float);
         t.rows_T = T; t.rows_B = rt.B;
         t.tune = variant == 1 ? ((int)o->gemm_tune & ~kTuneTail2) : ((int)o->gemm_tune | kTuneTail2);
@@ -1495,9 +1554,6 @@ int mc_op_gemm_tail_rows(const float* h, const float* a, const float* w, const f
         if (r == MC_OK) r = mc_launch_gemm_tail(t, s);
         if (r == MC_OK && mc_gemm_tail_two_outputs(t)) r = mc_launch_axpby(cdev, c2dev, 1.f, 1.f, cdev, (long)M * N, s);
     }
-    (void)hipStreamSynchronize(s);                   // (the table and the scratch are temporaries)
-    (void)hipFree(tab);
-    if (comb) (void)hipFree(comb);
     return r;
 }
 
@@ -1505,24 +1561,17 @@ int mc_op_sampler_rows(const float* x_t, const float* ot, const float* on, const
                        int32_t B, int32_t TC, const mc_step_coefs* coefs, void* stream) {
     MC_REQUIRE(x_t && ot && on && x_prev && coefs && B >= 1 && TC >= 1, "mc_op_sampler_rows: bad argument");
     int r;
-    for (int b = 0; b < B; ++b) {
-        if ((r = check_mode(&coefs[b]))) return r;
-        MC_REQUIRE(coefs[b].mode == coefs[0].mode, "mc_op_sampler_rows: row %d in mode %d beside mode %d (one mode per call)", b, coefs[b].mode, coefs[0].mode);
-    }
-    const bool ms = is_multistep(&coefs[0]);
-    MC_REQUIRE(ms ? x0_hist != nullptr : noise != nullptr, "mc_op_sampler_rows: mode 2 needs x0_hist_dev, the other modes noise_dev");
+    if ((r = rows_one_mode("mc_op_sampler_rows", coefs, B))) return r;
+    MC_REQUIRE(is_multistep(&coefs[0]) ? x0_hist != nullptr : noise != nullptr, "mc_op_sampler_rows: mode 2 needs x0_hist_dev, the other modes noise_dev");
     hipStream_t s = (hipStream_t)stream;
     RowTab rt;
     rt.B = B; rt.T = 1;
-    SamplerCoefs* tab = nullptr;
-    if ((r = rows_tab_upload(coefs, B, &tab, s))) return r;
-    rt.coefs = tab;
-    const long n = (long)B * TC;
-    r = ms ? mc_launch_sampler_multistep_rows(x_t, ot, on, x0_hist, x_prev, x0, n, 1.f, 1.f, rt, TC, s)
-           : mc_launch_sampler_update_rows(x_t, ot, on, noise, x_prev, x0, n, 1.f, 1.f, rt, TC, s);
-    (void)hipStreamSynchronize(s);
-    (void)hipFree(tab);
-    return r;
+    TempTable tab(s);
+    if ((r = rows_tab_upload("mc_op_sampler_rows", coefs, B, &tab, &rt))) return r;
+    SamplerForm f = op_form(x_t, ot, on, noise, x0_hist, x_prev, x0, (long)B * TC, &coefs[0]);
+    f.c.text_coef = f.c.none_coef = 1.f;
+    f.rt = &rt; f.TC = TC;
+    return mc_launch_sampler(f, s);
 }
 
 int mc_op_sampler_edit_rows(const float* x_t, const float* ot, const float* on, const float* noise, const float* gt_noise, const float* gt,
@@ -1530,10 +1579,7 @@ int mc_op_sampler_edit_rows(const float* x_t, const float* ot, const float* on, 
                             int32_t TC, const mc_step_coefs* coefs, void* stream) {
     MC_REQUIRE(x_t && ot && on && gt && keep && x_prev && coefs && B >= 1 && TC >= 1, "mc_op_sampler_edit_rows: bad argument");
     int r;
-    for (int b = 0; b < B; ++b) {
-        if ((r = check_mode(&coefs[b]))) return r;
-        MC_REQUIRE(coefs[b].mode == coefs[0].mode, "mc_op_sampler_edit_rows: row %d in mode %d beside mode %d (one mode per call)", b, coefs[b].mode, coefs[0].mode);
-    }
+    if ((r = rows_one_mode("mc_op_sampler_edit_rows", coefs, B))) return r;
     const bool ms = is_multistep(&coefs[0]);
     const bool dev_rng = seeds != nullptr || draw != nullptr;
     if (ms) MC_REQUIRE(x0_hist && !noise && !gt_noise && !dev_rng, "mc_op_sampler_edit_rows: mode 2 needs x0_hist_dev and takes no noise");
@@ -1545,32 +1591,17 @@ int mc_op_sampler_edit_rows(const float* x_t, const float* ot, const float* on, 
     hipStream_t s = (hipStream_t)stream;
     RowTab rt;
     rt.B = B; rt.T = 1;
-    SamplerCoefs* tab = nullptr;
-    if ((r = rows_tab_upload(coefs, B, &tab, s))) return r;
-    rt.coefs = tab;
-    uint64_t* kd = nullptr;               // [B] keys | [B] draw numbers
-    if (dev_rng) {
-        std::vector<uint64_t> h((size_t)2 * B);
-        for (int b = 0; b < B; ++b) { h[b] = seeds[b]; h[(size_t)B + b] = draw[b]; }
-        if (hipMalloc((void**)&kd, sizeof(uint64_t) * 2 * B) != hipSuccess ||
-            hipMemcpyAsync(kd, h.data(), sizeof(uint64_t) * 2 * B, hipMemcpyHostToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
-            if (kd) (void)hipFree(kd);
-            (void)hipFree(tab);
-            mc_set_error("mc_op_sampler_edit_rows: seed table upload failed");
-            return MC_ERR_HIP;
-        }
-        rt.draw = kd + B;
-    }
+    RowKeys rk;
+    TempTable tab(s), kd(s);
+    if ((r = rows_tab_upload("mc_op_sampler_edit_rows", coefs, B, &tab, &rt))) return r;
+    if (dev_rng && (r = rows_keys_upload("mc_op_sampler_edit_rows", seeds, draw, B, TC, &kd, &rt, &rk))) return r;
     EditTab et;
     et.gt = gt; et.keep = keep; et.gt_noise = gt_noise;
-    const RowKeys rk{reinterpret_cast<const uint32_t*>(kd), TC};
-    const long n = (long)B * TC;
-    r = ms ? mc_launch_sampler_multistep_edit_rows(x_t, ot, on, x0_hist, et, x_prev, x0, n, 1.f, 1.f, rt, TC, s)
-           : mc_launch_sampler_edit_rows(x_t, ot, on, noise, et, x_prev, x0, n, 1.f, 1.f, rt, TC, coefs[0].mode, s, dev_rng ? &rk : nullptr);
-    (void)hipStreamSynchronize(s);
-    (void)hipFree(tab);
-    if (kd) (void)hipFree(kd);
-    return r;
+    SamplerForm f = op_form(x_t, ot, on, noise, x0_hist, x_prev, x0, (long)B * TC, &coefs[0]);
+    f.c.text_coef = f.c.none_coef = 1.f;
+    f.rt = &rt; f.TC = TC; f.edit = &et;
+    if (dev_rng) f.keys = &rk;
+    return mc_launch_sampler(f, s);
 }
 
 int mc_op_sampler_seam(const float* x_t, const float* ot, const float* on, const float* noise, uint64_t seed, uint64_t draw, float* x0_hist,
@@ -1586,21 +1617,16 @@ int mc_op_sampler_seam(const float* x_t, const float* ot, const float* on, const
     std::vector<float> wt;
     if ((r = seam_plan("mc_op_sampler_seam", B, T, overlap, first_frame, weight, &flags, &wt))) return r;
     hipStream_t s = (hipStream_t)stream;
-    int* tab = nullptr;
-    MC_HIP(hipMalloc((void**)&tab, sizeof(int) * ((size_t)B + overlap)));
+    // one temporary block: [B] flags | [overlap] weights
+    TempTable tab(s);
+    if ((r = tab.upload(flags.data(), sizeof(int) * B, "mc_op_sampler_seam", wt.data(), sizeof(float) * overlap))) return r;
     SeamTab st;
-    st.flags = tab; st.w = reinterpret_cast<const float*>(tab + B); st.T = T; st.C = C; st.ov = overlap;
-    r = MC_OK;
-    if (hipMemcpyAsync(tab, flags.data(), sizeof(int) * B, hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipMemcpyAsync(tab + B, wt.data(), sizeof(float) * overlap, hipMemcpyHostToDevice, s) != hipSuccess) {
-        mc_set_error("mc_op_sampler_seam: table upload failed");
-        r = MC_ERR_HIP;
-    }
+    st.flags = static_cast<const int*>(tab.p); st.w = reinterpret_cast<const float*>(st.flags + B); st.T = T; st.C = C; st.ov = overlap;
     const RngArgs rng = rng_args(seed, draw);
-    if (r == MC_OK) r = mc_launch_sampler_seam(x_t, ot, on, noise, ms ? x0_hist : nullptr, x_prev, x0, B, to_coefs(k), st, s, noise ? nullptr : &rng);
-    (void)hipStreamSynchronize(s);                   // (the table is a temporary)
-    (void)hipFree(tab);
-    return r;
+    SamplerForm f = op_form(x_t, ot, on, noise, x0_hist, x_prev, x0, (long)B * T * C, k);
+    f.seam = &st;
+    if (!noise) f.rng = &rng;
+    return mc_launch_sampler(f, s);
 }
 
 int mc_op_sampler_seam_rows(const float* x_t, const float* ot, const float* on, const float* noise, const uint64_t* seeds, const uint64_t* draw,
@@ -1608,10 +1634,7 @@ int mc_op_sampler_seam_rows(const float* x_t, const float* ot, const float* on, 
                             const int32_t* first_frame, const float* weight, const mc_step_coefs* coefs, void* stream) {
     MC_REQUIRE(x_t && ot && on && x_prev && coefs && B >= 1 && C >= 1, "mc_op_sampler_seam_rows: bad argument");
     int r;
-    for (int b = 0; b < B; ++b) {
-        if ((r = check_mode(&coefs[b]))) return r;
-        MC_REQUIRE(coefs[b].mode == coefs[0].mode, "mc_op_sampler_seam_rows: row %d in mode %d beside mode %d (one mode per call)", b, coefs[b].mode, coefs[0].mode);
-    }
+    if ((r = rows_one_mode("mc_op_sampler_seam_rows", coefs, B))) return r;
     const bool ms = is_multistep(&coefs[0]);
     const bool dev_rng = seeds != nullptr || draw != nullptr;
     if (ms) MC_REQUIRE(x0_hist && !noise && !dev_rng, "mc_op_sampler_seam_rows: mode 2 needs x0_hist_dev and takes no noise");
@@ -1631,34 +1654,19 @@ int mc_op_sampler_seam_rows(const float* x_t, const float* ot, const float* on, 
     hipStream_t s = (hipStream_t)stream;
     RowTab rt;
     rt.B = B; rt.T = 1;
-    SamplerCoefs* tab = nullptr;
-    if ((r = rows_tab_upload(coefs, B, &tab, s))) return r;
-    rt.coefs = tab;
-    // one temporary block: [B] SeamRow | [overlap] weights (padded to 16 bytes) | [B] keys | [B] draw numbers
-    const size_t wq = ((size_t)overlap + 3) / 4, nq = (size_t)B + wq + (dev_rng ? (size_t)B : 0);
-    std::vector<SeamRow> h(nq, SeamRow{0, 0, 0, 0});
-    memcpy(h.data(), rows.data(), sizeof(SeamRow) * B);
-    memcpy(h.data() + B, wt.data(), sizeof(float) * overlap);
-    uint64_t* hk = reinterpret_cast<uint64_t*>(h.data() + B + wq);
-    if (dev_rng) for (int b = 0; b < B; ++b) { hk[b] = seeds[b]; hk[(size_t)B + b] = draw[b]; }
-    SeamRow* blk = nullptr;
-    if (hipMalloc((void**)&blk, sizeof(SeamRow) * nq) != hipSuccess ||
-        hipMemcpyAsync(blk, h.data(), sizeof(SeamRow) * nq, hipMemcpyHostToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
-        if (blk) (void)hipFree(blk);
-        (void)hipFree(tab);
-        mc_set_error("mc_op_sampler_seam_rows: table upload failed");
-        return MC_ERR_HIP;
-    }
+    RowKeys rk;
+    TempTable tab(s), blk(s), kd(s);
+    if ((r = rows_tab_upload("mc_op_sampler_seam_rows", coefs, B, &tab, &rt))) return r;
+    if (dev_rng && (r = rows_keys_upload("mc_op_sampler_seam_rows", seeds, draw, B, (int)((long)T * C), &kd, &rt, &rk))) return r;
+    // one temporary block: [B] SeamRow | [overlap] weights
+    if ((r = blk.upload(rows.data(), sizeof(SeamRow) * B, "mc_op_sampler_seam_rows", wt.data(), sizeof(float) * overlap))) return r;
     SeamRowsTab st;
-    st.rows = blk; st.w = reinterpret_cast<const float*>(blk + B); st.T = T; st.C = C; st.ov = overlap;
-    const uint64_t* kd = reinterpret_cast<const uint64_t*>(blk + B + wq);
-    if (dev_rng) rt.draw = kd + B;
-    const RowKeys rk{reinterpret_cast<const uint32_t*>(kd), (int)((long)T * C)};
-    r = mc_launch_sampler_seam_rows(x_t, ot, on, noise, ms ? x0_hist : nullptr, x_prev, x0, 1.f, 1.f, rt, st, coefs[0].mode, s, dev_rng ? &rk : nullptr);
-    (void)hipStreamSynchronize(s);                   // (the tables are temporaries)
-    (void)hipFree(tab);
-    (void)hipFree(blk);
-    return r;
+    st.rows = static_cast<const SeamRow*>(blk.p); st.w = reinterpret_cast<const float*>(st.rows + B); st.T = T; st.C = C; st.ov = overlap;
+    SamplerForm f = op_form(x_t, ot, on, noise, x0_hist, x_prev, x0, (long)B * T * C, &coefs[0]);
+    f.c.text_coef = f.c.none_coef = 1.f;
+    f.rt = &rt; f.seam_rows = &st;
+    if (dev_rng) f.keys = &rk;
+    return mc_launch_sampler(f, s);
 }
 
 }  // extern "C"

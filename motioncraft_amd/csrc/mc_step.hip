@@ -833,61 +833,53 @@ int denoise_combined(mc_ctx* c, const float* x_t, int32_t step, const mc_step_co
     return dense(c, c->z2, D, c->dec_w, D, c->dec_b, nullptr, 0, c->out2, C, BT, C, D, ACT_NONE, s);
 }
 
-// The sampler update behind denoise_combined: ONE place picks the kernel by mode for the per-step entry, the fused loop and the captured
-// step.  Under capture the coefficients (the mode among them) come from the device table at replay, so the kernel is picked from what
-// mc_ctx_graph_capture found in the table (all mode 2 or none of it), not from the step-0 entry `k`.
+// The sampler update behind denoise_combined, for the per-step entry, the fused loop and the captured step: gathers what the context
+// has set into ONE description of the form (mc_launch_sampler picks the kernel).  Under capture the coefficients (the mode among
+// them) come from the device table at replay, so the mode is what mc_ctx_graph_capture found in the table (all mode 2 or none of it),
+// not the step-0 entry `k`'s.  Per-row schedules (one mode per call, checked by mc_sample_rows) go with no graph and no whole-batch
+// seam table, an edit table with no row seam table.
 int sampler_update(mc_ctx* c, const float* x_t, const X0Parts& x0p, const mc_step_coefs* k, const float* noise, float* x_prev, float* x0,
                    hipStream_t s, const RngArgs* rng, const PadOut* pad) {
-    const long n = (long)c->B * c->T * c->m->cfg.input_feats;
-    const SamplerCoefs* table = c->graph_mode ? c->gcoefs : nullptr;
-    const int* step_ptr = c->graph_mode ? c->gstep : nullptr;
+    if (c->rows_mode && (c->graph_mode || c->seam_ov > 0)) { mc_set_error("per-row sampler update under graph capture or with a seam table set"); return MC_ERR_STATE; }
+    if (c->rows_mode && c->seam_rows_ov > 0 && c->edit_set) { mc_set_error("per-row sampler update with a row seam table and an edit table set"); return MC_ERR_STATE; }
+    if (c->seam_ov > 0 && c->graph_mode) { mc_set_error("sampler update under graph capture with a seam table set"); return MC_ERR_STATE; }
     const bool multistep = c->graph_mode ? c->graph_multistep : k->mode == MC_SAMPLER_MULTISTEP;
+    const int C = c->m->cfg.input_feats;
+    SamplerForm f;
+    f.x_t = x_t; f.out_text = x0p.a; f.out_none = x0p.second(); f.x_prev = x_prev; f.x0_out = x0;
+    f.n = (long)c->B * c->T * C;
+    f.c = x0p.coefs(k);
+    f.mode = c->graph_mode ? (multistep ? (int)MC_SAMPLER_MULTISTEP : (int)MC_SAMPLER_DDPM) : k->mode;      // (under capture only "2 or not" is read)
+    f.pad = pad;
+    MC_REQUIRE(!multistep || c->x0_hist, "multistep update without a history buffer");
+    if (multistep) f.x0_hist = c->x0_hist;
+    else f.noise = noise;
     // a seed table (mc_ctx_set_row_seeds): an in-kernel draw takes every row's own key; a noise tensor is read as it is
-    const RowKeys rk{reinterpret_cast<const uint32_t*>(c->row_seeds), (int)(n / c->B)};
-    const RowKeys* rows = c->row_seeds_set && rng && !noise ? &rk : nullptr;
-    if (c->rows_mode) {          // per-row schedules: the two row kernels (one mode per call, checked by mc_sample_rows; no graph, no seams)
-        if (c->graph_mode || c->seam_ov > 0) { mc_set_error("per-row sampler update under graph capture or with a seam table set"); return MC_ERR_STATE; }
-        const SamplerCoefs u = x0p.coefs(k);
-        if (c->seam_rows_ov > 0) {       // windows of long requests among the rows (mc_ctx_set_seam_rows): one kernel for every mode
-            if (c->edit_set) { mc_set_error("per-row sampler update with a row seam table and an edit table set"); return MC_ERR_STATE; }
-            MC_REQUIRE(multistep || noise || c->row_seeds_set, "per-row sampler update without a noise tensor needs a seed table (mc_ctx_set_row_seeds)");
-            MC_REQUIRE(!multistep || c->x0_hist, "multistep update without a history buffer");
-            SeamRowsTab st;
-            st.rows = c->seam_rows_tab; st.w = reinterpret_cast<const float*>(c->seam_rows_tab + c->B);
-            st.T = c->T; st.C = c->m->cfg.input_feats; st.ov = c->seam_rows_ov;
-            return mc_launch_sampler_seam_rows(x_t, x0p.a, x0p.second(), multistep ? nullptr : noise, multistep ? c->x0_hist : nullptr, x_prev, x0,
-                                               u.text_coef, u.none_coef, c->rowtab, st, k->mode, s, noise || multistep ? nullptr : &rk, pad);
-        }
-        if (c->edit_set) {       // a kept region (mc_ctx_set_edit_rows): the edit kernels, the same forms otherwise
-            EditTab et;
+    const RowKeys rk{reinterpret_cast<const uint32_t*>(c->row_seeds), c->T * C};
+    const bool drawn = !multistep && !noise;
+    if (c->row_seeds_set && drawn && (rng || c->rows_mode)) f.keys = &rk;
+    EditTab et;
+    SeamTab st;
+    SeamRowsTab sr;
+    if (c->rows_mode) {
+        MC_REQUIRE(!drawn || c->row_seeds_set, "per-row sampler update without a noise tensor needs a seed table (mc_ctx_set_row_seeds)");
+        f.rt = &c->rowtab; f.TC = rk.TC;
+        if (c->seam_rows_ov > 0) {       // windows of long requests among the rows (mc_ctx_set_seam_rows)
+            sr.rows = c->seam_rows_tab; sr.w = reinterpret_cast<const float*>(c->seam_rows_tab + c->B);
+            sr.T = c->T; sr.C = C; sr.ov = c->seam_rows_ov;
+            f.seam_rows = &sr;
+        } else if (c->edit_set) {        // a kept region (mc_ctx_set_edit_rows)
+            MC_REQUIRE(multistep || !noise || k->mode == MC_SAMPLER_DDPM, "edited rows in mode 1 draw the kept region's noise from the seed table: no noise tensor");
             et.gt = c->edit_gt; et.keep = c->edit_keep;
-            if (!multistep) {
-                MC_REQUIRE(noise || c->row_seeds_set, "per-row sampler update without a noise tensor needs a seed table (mc_ctx_set_row_seeds)");
-                MC_REQUIRE(!noise || k->mode == MC_SAMPLER_DDPM, "edited rows in mode 1 draw the kept region's noise from the seed table: no noise tensor");
-                return mc_launch_sampler_edit_rows(x_t, x0p.a, x0p.second(), noise, et, x_prev, x0, n, u.text_coef, u.none_coef, c->rowtab, rk.TC,
-                                                   k->mode, s, noise ? nullptr : &rk, pad);
-            }
-            MC_REQUIRE(c->x0_hist, "multistep update without a history buffer");
-            return mc_launch_sampler_multistep_edit_rows(x_t, x0p.a, x0p.second(), c->x0_hist, et, x_prev, x0, n, u.text_coef, u.none_coef, c->rowtab,
-                                                         rk.TC, s, pad);
+            f.edit = &et;
         }
-        if (!multistep) {
-            MC_REQUIRE(noise || c->row_seeds_set, "per-row sampler update without a noise tensor needs a seed table (mc_ctx_set_row_seeds)");
-            return mc_launch_sampler_update_rows(x_t, x0p.a, x0p.second(), noise, x_prev, x0, n, u.text_coef, u.none_coef, c->rowtab, rk.TC, s,
-                                                 noise ? nullptr : &rk, pad);
-        }
-        MC_REQUIRE(c->x0_hist, "multistep update without a history buffer");
-        return mc_launch_sampler_multistep_rows(x_t, x0p.a, x0p.second(), c->x0_hist, x_prev, x0, n, u.text_coef, u.none_coef, c->rowtab, rk.TC, s, pad);
+    } else {
+        f.rng = rng;
+        if (c->seam_ov > 0) {            // the batch as coupled windows (mc_ctx_set_seams)
+            st.flags = c->seam_tab; st.w = reinterpret_cast<const float*>(c->seam_tab + c->B);
+            st.T = c->T; st.C = C; st.ov = c->seam_ov;
+            f.seam = &st;
+        } else if (c->graph_mode) { f.table = c->gcoefs; f.step_ptr = c->gstep; }
     }
-    if (c->seam_ov > 0) {        // coupled windows: one kernel for every mode (no graph table: capture is refused while the seam table is set)
-        if (c->graph_mode) { mc_set_error("sampler update under graph capture with a seam table set"); return MC_ERR_STATE; }
-        MC_REQUIRE(!multistep || c->x0_hist, "multistep update without a history buffer");
-        SeamTab st;
-        st.flags = c->seam_tab; st.w = reinterpret_cast<const float*>(c->seam_tab + c->B);
-        st.T = c->T; st.C = c->m->cfg.input_feats; st.ov = c->seam_ov;
-        return mc_launch_sampler_seam(x_t, x0p.a, x0p.second(), noise, multistep ? c->x0_hist : nullptr, x_prev, x0, c->B, x0p.coefs(k), st, s, rng, pad, rows);
-    }
-    if (!multistep) return mc_launch_sampler_update(x_t, x0p.a, x0p.second(), noise, x_prev, x0, n, x0p.coefs(k), s, table, step_ptr, rng, pad, rows);
-    MC_REQUIRE(c->x0_hist, "multistep update without a history buffer");
-    return mc_launch_sampler_multistep(x_t, x0p.a, x0p.second(), c->x0_hist, x_prev, x0, n, x0p.coefs(k), s, table, step_ptr, pad);
+    return mc_launch_sampler(f, s);
 }

@@ -452,6 +452,71 @@ def test_seam_kernel_takes_the_left_rows_key(natives):
         ctx.close()
 
 
+# ---- 7b. every drawn-noise form of the sampler update at both operand alignments -------------------
+@pytest.mark.parametrize('Bn', [3, 4], ids=['odd_elements', 'whole_vectors'])
+def test_drawn_noise_forms_equal_the_forms_fed_their_draws_at_both_alignments(natives, Bn):
+    """C = 263, T = 7 (T C = 1841 is odd: flat groups of four straddle every row boundary; at B = 3 the element count is odd too, so the
+    second partial product of the decoder tail is off 16-byte alignment and n % 4 == 3 leaves a ragged last group; at B = 4 every operand
+    is aligned).  Two fused steps, modes 0 and 1, without and with a seam table (overlap 3, first frames 0, 4, 8, ..): the loop that draws
+    in the kernel -- from the call's stream, and from the rows' keys -- equals the loop fed the same normals as a tensor
+    (mc_op_philox_normal / mc_ctx_draw_rows), bit for bit; one tick of per-row schedules at mixed steps and draw numbers likewise.
+    This pins the NOISE path only (which key, which counter, which draw number, the left row's element on a seam).  It depends on the
+    op tests for the rest: the tensor-fed forms it compares with are held against fp64, with guard sentinels around every output, by
+    test_seam_op, test_seam_rows_op, test_per_row_sampler_kernels_vs_fp64 and test_multistep_op_vs_fp64 at the same C and T; a context
+    owns its buffers, so a store outside an output cannot show here.  No op entry draws from row keys under a seam table."""
+    lib, ptr, stream = _lib()
+    dims, _, nm = natives('C263_T23')
+    Tn, C, ov = 7, dims['input_feats'], 3
+    assert C == 263
+    n, TC = Bn * Tn * C, Tn * C
+    d = _diffusion('ddim4')
+    seeds = (SEEDS + [77])[:Bn]
+    ff = [b * (Tn - ov) for b in range(Bn)]
+    z = torch.randn(ff[-1] + Tn, C, generator=torch.Generator().manual_seed(68))
+    x_T = torch.stack([z[f:f + Tn] for f in ff]).cuda()                       # equal on shared frames
+    _, xf, mask = synth_inputs(dims, Bn, Tn, seed=67)
+    idx = [3, 2]
+
+    def normals(count, seed, draw):
+        out = torch.empty(count, device='cuda')
+        assert lib.mc_op_philox_normal(ptr(out), None, count, seed & (2 ** 64 - 1), draw, stream()) == 0, lib.mc_last_error()
+        return out
+
+    ctx = nm.context(Bn, Tn, max_steps=4)
+    try:
+        ctx.set_timesteps(d.timestep_map)
+        ctx.set_condition(xf.cuda(), mask.cuda())
+        for mode, eta in (('ddpm', 0.0), ('ddim', 0.5)):
+            coefs = [d.step_coefs(i, mode, dims['scale'], eta) for i in idx]
+            for seam in (False, True):
+                if seam:
+                    ctx.set_seams(ff, ov)
+                ctx.clear_row_seeds()
+                got = ctx.sample_loop(x_T.clone(), idx, coefs, noise=None, seed=99, draw0=1).clone()
+                fed = ctx.sample_loop(x_T.clone(), idx, coefs, noise=torch.stack([normals(n, 99, 1 + k).view(Bn, Tn, C) for k in range(2)])).clone()
+                assert torch.equal(got, fed) and bool(torch.isfinite(got).all()), (mode, seam, 'call stream', float((got - fed).abs().max()))
+                ctx.set_row_seeds(seeds)
+                keyed = ctx.sample_loop(x_T.clone(), idx, coefs, noise=None, draw0=1).clone()
+                fed = ctx.sample_loop(x_T.clone(), idx, coefs, noise=torch.stack([ctx.draw_rows(1 + k) for k in range(2)])).clone()
+                assert torch.equal(keyed, fed) and bool(torch.isfinite(keyed).all()), (mode, seam, 'row keys', float((keyed - fed).abs().max()))
+                assert not torch.equal(keyed, got)
+                if seam:
+                    flags = S.plan_flags(ff, Tn, ov)
+                    assert S.seams_equal(got.cpu().numpy(), flags, ov) and S.seams_equal(keyed.cpu().numpy(), flags, ov)
+                    ctx.clear_seams()
+            # per-row schedules: row b at its own step and draw number
+            st = [[3, 2, 1, 3][b] for b in range(Bn)]
+            dr = [[1, 5, 2 ** 63 + 2, 9][b] for b in range(Bn)]
+            cf = [d.step_coefs(s, mode, dims['scale'], eta) for s in st]
+            rows_got = ctx.sample_rows(x_T.clone(), [st], [cf], draws=[dr]).clone()
+            nz = torch.stack([normals(TC, seeds[b], dr[b]).view(Tn, C) for b in range(Bn)])
+            rows_fed = ctx.sample_rows(x_T.clone(), [st], [cf], noise=nz[None]).clone()
+            assert torch.equal(rows_got, rows_fed) and bool(torch.isfinite(rows_got).all()), (mode, 'rows', float((rows_got - rows_fed).abs().max()))
+        torch.cuda.synchronize()
+    finally:
+        ctx.close()
+
+
 # ---- 8. state rules -------------------------------------------------------------------------------
 def test_capacity_factor_state_rules(natives):
     """cf < 0 -> MC_ERR_ARG (1); a denoiser call after the setting without a new condition fails as on a fresh context; with a captured
