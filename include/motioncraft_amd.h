@@ -372,6 +372,24 @@ int mc_ctx_set_edit_rows(mc_ctx* c, const float* gt_dev, const uint8_t* keep_dev
 int mc_ctx_set_seam_rows(mc_ctx* c, int32_t overlap, const int32_t* right_host, const int32_t* first_frame_host, const float* weight_host,
                          void* stream);
 
+/* Kept regions on long requests: one switch per context under which the edit table and the row seam table may
+ * be set side by side.  Off (the default), each setter refuses the other's table exactly as described above.  On:
+ * mc_ctx_set_edit_rows beside a row seam table and mc_ctx_set_seam_rows beside an edit table are accepted, and mc_sample_rows runs
+ * with both set.  For an element of a window row the order is 4q's blend, then 4p's select:
+ *     x0m = the CFG-combined prediction;   the seam's owner (the left row's tail element): x0m = w x0_right + (1 - w) x0m
+ *     x0 = keep ? gt : x0m;   the update of mc_ctx_set_edit_rows on that x0 (mode 1: x_prev = sqrt(ab_prev) gt + sqrt(1 - ab_prev) z2)
+ * and the owner stores x_prev, x0, the history and the next step's operand to both copies of a shared element.  The owner reads ITS
+ * OWN keep / gt entry; the entry of the head copy (the right row's first `overlap` frames, where it has a left neighbour) is never
+ * read into a result.  The tables arrive as device pointers, so the library cannot check that the two copies agree: the caller
+ * uploads equal keep / gt for both copies of a shared frame (serve.ContinuousBatcher cuts both from one request-global edit).
+ * The step noise is the request-global field of mc_ctx_set_seam_rows; z2 is the same field at draw number draw ^ 2^63, so both copies
+ * of a shared frame have one z2 and a row at first_frame 0 draws what it draws under mc_ctx_set_edit_rows alone.
+ * Still MC_ERR_STATE / MC_ERR_ARG with the switch on, the context unchanged: either setter beside a captured graph or the whole-batch
+ * seam table of mc_ctx_set_seams; every entry without a rows form while a table is set; mc_sample_rows in mode 1 with noise_dev !=
+ * NULL beside an edit table; the seam-pair checks of mc_sample_rows.  Switching off while both tables are set is MC_ERR_STATE.  The
+ * switch touches no table and no multistep history flag. */
+int mc_ctx_set_long_edits(mc_ctx* c, int32_t on);
+
 /* hipGraph replay of mc_sample_step (BASELINE.json configs[4] "hipGraph-captured 50-step DDIM"): ONE graph serves every step
  * of the schedule -- the step index is a device-side integer, the FiLM tables and the sampler coefficients are addressed
  * with it inside the kernels, no host sync or per-step H2D copy (SURVEY.md section 3.1 lists the reference's per-step
@@ -551,6 +569,15 @@ int mc_op_sampler_seam_rows(const float* x_t_dev, const float* out_text_dev, con
                             const uint64_t* seeds_host, const uint64_t* draw_host, float* x0_hist_dev, float* x_prev_dev, float* x0_dev,
                             int32_t B, int32_t T, int32_t C, int32_t overlap, const int32_t* right_host, const int32_t* first_frame_host,
                             const float* weight_host, const mc_step_coefs* coefs_host, void* stream);
+/* mc_op_sampler_seam_rows with a kept region (sampler_seam_edit_rows_k; see mc_ctx_set_long_edits): gt_dev [B,T,C] floats, keep_dev
+ * [B,T,C] bytes, and the noise sources of mc_op_sampler_edit_rows -- noise_dev (mode 1: with gt_noise_dev), or seeds_host + draw_host,
+ * both noises then drawn from the request-global field at draws draw_host[b] and draw_host[b] ^ 2^63.  The keep / gt / gt_noise
+ * entries of the head copy of a shared element are never read into a result.  Synchronises. */
+int mc_op_sampler_seam_edit_rows(const float* x_t_dev, const float* out_text_dev, const float* out_none_dev, const float* noise_dev,
+                                 const float* gt_noise_dev, const float* gt_dev, const uint8_t* keep_dev, const uint64_t* seeds_host,
+                                 const uint64_t* draw_host, float* x0_hist_dev, float* x_prev_dev, float* x0_dev, int32_t B, int32_t T,
+                                 int32_t C, int32_t overlap, const int32_t* right_host, const int32_t* first_frame_host,
+                                 const float* weight_host, const mc_step_coefs* coefs_host, void* stream);
 
 /* Result post-processing of the 322-d motion.  pred_dev [B,T,322] normalised; lengths_dev [B]
  * int32 valid frames (NULL = T); mean/std_dev [322] fp64; taps_dev [4][MC_POST_MAXTAP] fp64 = normalised Gaussian

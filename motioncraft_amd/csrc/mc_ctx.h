@@ -168,6 +168,9 @@ struct mc_ctx {
     int seam_rows_ov = 0;
     std::vector<int> seam_rows_right;
     std::vector<uint64_t> row_seeds_host;
+    // kept regions on long requests (mc_ctx_set_long_edits): off, the edit table and the row seam table refuse
+    // each other; on, both may be set and sampler_update launches sampler_seam_edit_rows_k in rows mode
+    bool long_edits = false;
     int prec = MC_PREC_F32;     // MFMA operand precision of the per-step GEMM-shaped kernels (mc_ctx_set_precision)
     int* cap_idx = nullptr;      // [NL][2N] routing capture (tests): expert ids ...
     float* cap_w = nullptr;      // ... and combine weights (0 = dropped) of every layer
@@ -204,7 +207,8 @@ int denoise_combined(mc_ctx* c, const float* x_t, int32_t step, const mc_step_co
 // the sampler update behind denoise_combined, its kernel picked by the step's mode (under capture: by the graph's table) -- sampler_update_k
 // (modes 0 / 1; noise or rng) or sampler_multistep_k (mode 2; x0_hist must be allocated, the caller keeps the history-valid flag); with
 // a seam table set (mc_ctx_set_seams) sampler_seam_k in every mode; in rows mode the row kernels, the edit kernels under an edit table,
-// or sampler_seam_rows_k in every mode under a row seam table (mc_ctx_set_seam_rows)
+// or sampler_seam_rows_k in every mode under a row seam table (mc_ctx_set_seam_rows), sampler_seam_edit_rows_k under both tables
+// (mc_ctx_set_long_edits)
 int sampler_update(mc_ctx* c, const float* x_t, const X0Parts& x0p, const mc_step_coefs* k, const float* noise, float* x_prev, float* x0,
                    hipStream_t s, const RngArgs* rng = nullptr, const PadOut* pad = nullptr);
 #pragma GCC visibility pop

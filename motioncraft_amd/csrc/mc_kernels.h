@@ -83,8 +83,11 @@ struct SeamRowsTab { const SeamRow* rows = nullptr; const float* w = nullptr; in
 //                     drawn noise from keys at draw rt->draw[row] (no rng)
 //   rt + edit         sampler_edit_rows_k / sampler_multistep_edit_rows_k
 //   rt + seam_rows    sampler_seam_rows_k
+//   rt + seam_rows + edit   sampler_seam_edit_rows_k (section 4s): the select behind the blend; a seam's owner reads its own keep / gt /
+//                     gt_noise element -- the entries of the head copy of a shared element are never used for an output, so the caller
+//                     keeps the two copies equal (the kernel cannot check device tables)
 //   seam              sampler_seam_k (the entry `c`; noise as in the first form)
-// Nothing else is a form: an edit table beside a seam table, a graph table beside rt or a seam table are refused.
+// Nothing else is a form: an edit table beside the whole-batch seam table, a graph table beside rt or a seam table are refused.
 struct SamplerForm {
     const float *x_t = nullptr, *out_text = nullptr, *out_none = nullptr, *noise = nullptr;
     float *x0_hist = nullptr, *x_prev = nullptr, *x0_out = nullptr;

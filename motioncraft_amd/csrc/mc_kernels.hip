@@ -942,6 +942,140 @@ __global__ __launch_bounds__(256) void sampler_seam_rows_k(const float* x_t, con
     }
 }
 
+// ---- kept regions on seam-coupled rows (mc_ctx_set_long_edits) ----
+// sampler_seam_rows_k's blend and ownership with sampler_edit_rows_k's select behind it, nothing new beyond their order:
+//   x0m = cfg_elem(..);  the seam's owner: x0m = fmaf(w, x0_right, (1 - w) x0m);  x0 = keep ? gt : x0m  (a select AFTER the blend)
+//   modes 0 / 1: sampler_elem on x0, in mode 1 x_prev = edit_renoise(gt, z2) where kept;  mode 2: multistep_elem, hist <- x0
+// The owner reads ITS OWN keep / gt (and noise / gt_noise element) and stores x_prev, x0_out, the history and xpad to both copies of a
+// shared element; the head copy's keep / gt entries are never used for an output (its thread skips the element).  gt where keep == 0
+// reaches no output.  Noise (RNG): the request-global field of philox_rows4g for both draws, z2 at draw[b] ^ MC_EDIT_DRAW_FLIP, drawn in
+// mode 1 only and only for groups whose keep word is non-zero -- both copies of a shared frame would draw the same z2, and a row with
+// first_frame 0 draws what sampler_edit_rows_k draws.  One kernel for the three modes (launch-uniform `mode`).  Flat groups of four,
+// 32-bit index arithmetic, VEC rule, straddle rule and PadOut as in sampler_seam_rows_k: groups that touch no overlap region keep f32x4
+// loads and stores (keep bytes: one 32-bit load; gt / z2 only behind a non-zero word), the others go element by element.  All-zero
+// keep bytes give sampler_seam_rows_k's bits; a table without neighbours at first_frame 0 gives the two edit kernels'.  No LDS, no
+// atomics.  philox_rows4g with the draw number flipped is a sibling of its own: philox_rows4g keeps its instruction stream.
+__device__ __forceinline__ f32x4 philox_rows4gx(uint32_t i, uint32_t n, RowKeys rk, const uint64_t* __restrict__ draw,
+                                                const SeamRow* __restrict__ rows, int C, int first0, uint64_t flip) {
+    uint32_t b = i / (uint32_t)rk.TC;
+    int r = (int)(i - b * (uint32_t)rk.TC);
+    RngArgs rng;
+    f32x4 z = {0.f, 0.f, 0.f, 0.f}, cur = z;
+    long cb = -1, cc = -1;
+    long g = (long)first0 * C + r;
+    for (int j = 0; j < 4 && i + j < n; ++j) {
+        if ((long)b != cb || (g >> 2) != cc) {
+            cb = b; cc = g >> 2;
+            const uint64_t dr = draw[b] ^ flip;
+            rng.seed_lo = rk.keys[2 * b]; rng.seed_hi = rk.keys[2 * b + 1];
+            rng.draw_lo = (uint32_t)dr; rng.draw_hi = (uint32_t)(dr >> 32);
+            cur = philox_normal4(cc, rng);
+        }
+        const int l = (int)(g & 3);
+        z[j] = l == 0 ? cur[0] : l == 1 ? cur[1] : l == 2 ? cur[2] : cur[3];
+        ++g;
+        if (++r == rk.TC) { r = 0; ++b; if (i + j + 1 < n) g = (long)rows[b].first_frame * C; }
+    }
+    return z;
+}
+
+template <bool RNG, bool VEC>
+__global__ __launch_bounds__(256) void sampler_seam_edit_rows_k(const float* x_t, const float* __restrict__ o_text,
+                                                                const float* __restrict__ o_none, const float* __restrict__ noise,
+                                                                float* hist, EditTab et, float* x_prev, float* x0_out, uint32_t n, float tc,
+                                                                float nc, const SamplerCoefs* __restrict__ tab, RowKeys rk,
+                                                                const uint64_t* __restrict__ draw, SeamRowsTab st, int mode, PadOut po) {
+    const bool ms = mode == 2, m1 = mode == 1;
+    const int TC = rk.TC, headC = st.ov * st.C, tailC = (st.T - st.ov) * st.C;
+    const uint32_t ngroups = (n + 3) >> 2;
+    for (uint32_t gi = blockIdx.x * blockDim.x + threadIdx.x; gi < ngroups; gi += gridDim.x * blockDim.x) {
+        const uint32_t i = gi * 4;
+        uint32_t b = i / (uint32_t)TC;
+        int r = (int)(i - b * (uint32_t)TC);
+        const bool whole = i + 4 <= n;
+        SeamRow sr = st.rows[b];
+        bool any = (sr.has_left && r < headC) || (sr.right >= 0 && (r + 3 >= tailC));      // (as in sampler_seam_rows_k)
+        if (whole && r + 4 > TC) {
+            const SeamRow s1 = st.rows[b + 1];
+            any = any || s1.has_left || (s1.right >= 0 && r + 3 - TC >= tailC);
+        }
+        SamplerCoefs c = row_coefs(tab, b, tc, nc);
+        SamplerDerived d = sampler_derive(c);
+        const uint32_t kw = keep4(et.keep, i, n, et.kword);
+        const bool renoise = kw != 0 && m1;
+        f32x4 nz = {0.f, 0.f, 0.f, 0.f}, z2 = nz;
+        if constexpr (RNG) {
+            if (!ms) nz = philox_rows4gx(i, n, rk, draw, st.rows, st.C, sr.first_frame, 0);
+            if (renoise) z2 = philox_rows4gx(i, n, rk, draw, st.rows, st.C, sr.first_frame, MC_EDIT_DRAW_FLIP);
+        }
+        if (VEC && whole && !any) {
+            const f32x4 x = *reinterpret_cast<const f32x4*>(x_t + i);
+            const f32x4 a = *reinterpret_cast<const f32x4*>(o_text + i), bb = *reinterpret_cast<const f32x4*>(o_none + i);
+            f32x4 hv = {0.f, 0.f, 0.f, 0.f}, g = hv;
+            if (ms) hv = *reinterpret_cast<const f32x4*>(hist + i);
+            else if constexpr (!RNG) {
+                nz = *reinterpret_cast<const f32x4*>(noise + i);
+                if (renoise) z2 = *reinterpret_cast<const f32x4*>(et.gt_noise + i);
+            }
+            if (kw) g = *reinterpret_cast<const f32x4*>(et.gt + i);
+            f32x4 out, x0v;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const bool k = kept(kw, j);
+                const float x0m = cfg_elem(a[j], bb[j], c);
+                x0v[j] = k ? g[j] : x0m;
+                const float o = ms ? multistep_elem(x[j], x0v[j], c.eta != 0.f ? hv[j] : 0.f, c.c2, c.c1, c.eta) : sampler_elem(x[j], x0v[j], nz[j], c, d);
+                out[j] = (k && m1) ? edit_renoise(g[j], z2[j], c, d) : o;
+                if (j < 3 && ++r == TC) { r = 0; ++b; c = row_coefs(tab, b, tc, nc); d = sampler_derive(c); }
+            }
+            *reinterpret_cast<f32x4*>(x_prev + i) = out;
+            if (ms) *reinterpret_cast<f32x4*>(hist + i) = x0v;
+            if (x0_out) *reinterpret_cast<f32x4*>(x0_out + i) = x0v;
+            if (po.xpad) {
+                uint32_t row = i / (uint32_t)po.C;
+                int col = (int)(i - row * (uint32_t)po.C);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    po.xpad[(long)row * po.Cp + col] = out[j];
+                    if (++col == po.C) { col = 0; ++row; }
+                }
+            }
+        } else {
+            for (int j = 0; j < 4 && i + j < n; ++j) {
+                const uint32_t e = i + j;
+                if (!(sr.has_left && r < headC)) {               // (head: written by the left neighbour's tail thread, its keep / gt unused)
+                    const bool k = kept(kw, j);
+                    const float gj = k ? et.gt[e] : 0.f;
+                    float x0 = cfg_elem(o_text[e], o_none[e], c);
+                    long er = -1;
+                    if (sr.right >= 0 && r >= tailC) {           // the seam's owner: (right[b], f, ch)
+                        er = (long)e + ((long)sr.right - (long)b) * TC - tailC;
+                        const float w = st.w[(r - tailC) / st.C];
+                        const float x0r = cfg_elem(o_text[er], o_none[er], c);
+                        x0 = fmaf(w, x0r, __fmul_rn(__fsub_rn(1.f, w), x0));
+                    }
+                    x0 = k ? gj : x0;                            // the select, after the blend
+                    float o;
+                    if (ms) o = multistep_elem(x_t[e], x0, c.eta != 0.f ? hist[e] : 0.f, c.c2, c.c1, c.eta);
+                    else o = sampler_elem(x_t[e], x0, RNG ? nz[j] : noise[e], c, d);
+                    if (k && m1) o = edit_renoise(gj, RNG ? z2[j] : et.gt_noise[e], c, d);
+                    x_prev[e] = o;
+                    if (ms) hist[e] = x0;
+                    if (x0_out) x0_out[e] = x0;
+                    if (po.xpad) po.xpad[(long)(e / (uint32_t)po.C) * po.Cp + e % (uint32_t)po.C] = o;
+                    if (er >= 0) {
+                        x_prev[er] = o;
+                        if (ms) hist[er] = x0;
+                        if (x0_out) x0_out[er] = x0;
+                        if (po.xpad) po.xpad[er / po.C * po.Cp + er % po.C] = o;
+                    }
+                }
+                if (e + 1 < n && ++r == TC) { r = 0; ++b; sr = st.rows[b]; c = row_coefs(tab, b, tc, nc); d = sampler_derive(c); }
+            }
+        }
+    }
+}
+
 // the same draws written to memory (tests; callers that want the loop's noise stream)
 __global__ __launch_bounds__(256) void philox_fill_k(float* __restrict__ out, uint32_t* __restrict__ bits, long n, RngArgs rng) {
     const long ngroups = (n + 3) >> 2;
@@ -1201,10 +1335,10 @@ template <class F> void with_bool(bool v, F&& f) { if (v) f(std::true_type{}); e
 }  // namespace
 int mc_launch_sampler(const SamplerForm& f, hipStream_t s) {
     const bool ms = f.mode == 2, rows = f.rt != nullptr, seam = f.seam || f.seam_rows;
-    const char* const form = f.seam_rows ? "seam rows" : f.seam ? "seam" : f.edit ? "edited rows" : rows ? "rows" : "uniform";
+    const char* const form = f.seam_rows ? (f.edit ? "edited seam rows" : "seam rows") : f.seam ? "seam" : f.edit ? "edited rows" : rows ? "rows" : "uniform";
     MC_REQUIRE(f.x_t && f.out_text && f.out_none && f.x_prev && (f.n >= 0 || !ms), "sampler update (%s): null operand", form);
     MC_REQUIRE(f.mode >= 0 && f.mode <= 2, "sampler update (%s): unknown sampler mode %d", form, f.mode);
-    MC_REQUIRE((!f.edit || (rows && !seam)) && (!f.seam_rows || rows) && (!f.seam || (!rows && !f.seam_rows)) && (!f.table || (!rows && !seam)),
+    MC_REQUIRE((!f.edit || (rows && !f.seam)) && (!f.seam_rows || rows) && (!f.seam || (!rows && !f.seam_rows)) && (!f.table || (!rows && !seam)),
                "sampler update (%s): no such form", form);
     MC_REQUIRE(!ms || rows || f.table || f.c.mode == 2, "sampler update (%s): coefficients of mode %d in a launch of mode 2", form, f.c.mode);
     // rows of TC elements
@@ -1259,7 +1393,8 @@ int mc_launch_sampler(const SamplerForm& f, hipStream_t s) {
         constexpr bool V = decltype(vec_t)::value;
         with_bool(drawn, [&](auto drawn_t) {
             constexpr bool R = decltype(drawn_t)::value;
-            if (f.seam_rows) MC_GO((sampler_seam_rows_k<R, V>), f.noise, hist, f.x_prev, f.x0_out, (uint32_t)f.n, tc, nc, f.rt->coefs, rk, f.rt->draw, *f.seam_rows, ms ? 1 : 0, po);
+            if (f.seam_rows && f.edit) MC_GO((sampler_seam_edit_rows_k<R, V>), f.noise, hist, et, f.x_prev, f.x0_out, (uint32_t)f.n, tc, nc, f.rt->coefs, rk, f.rt->draw, *f.seam_rows, f.mode, po);
+            else if (f.seam_rows) MC_GO((sampler_seam_rows_k<R, V>), f.noise, hist, f.x_prev, f.x0_out, (uint32_t)f.n, tc, nc, f.rt->coefs, rk, f.rt->draw, *f.seam_rows, ms ? 1 : 0, po);
             else if (f.seam && row_noise) MC_GO((sampler_seam_k<true, V, RowNoise>), f.noise, hist, f.x_prev, f.x0_out, f.n, f.c, *f.seam, rn, po);
             else if (f.seam) MC_GO((sampler_seam_k<R, V>), f.noise, hist, f.x_prev, f.x0_out, f.n, f.c, *f.seam, ra, po);
             else if (f.edit && ms) MC_GO((sampler_multistep_edit_rows_k<V>), hist, et, f.x_prev, f.x0_out, f.n, tc, nc, f.rt->coefs, TC, po);

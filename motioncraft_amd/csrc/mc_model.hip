@@ -746,7 +746,7 @@ int mc_ctx_set_seam_rows(mc_ctx* c, int32_t overlap, const int32_t* right, const
         mc_set_error("mc_ctx_set_seam_rows: the context holds a captured graph (mc_ctx_graph_release first): row steps are not replayed");
         return MC_ERR_STATE;
     }
-    if (int re = edit_refuse(c, "mc_ctx_set_seam_rows")) return re;
+    if (!c->long_edits) { if (int re = edit_refuse(c, "mc_ctx_set_seam_rows")) return re; }
     if (int rs = seam_refuse(c, "mc_ctx_set_seam_rows")) return rs;
     std::vector<SeamRow> rows;
     std::vector<float> wt;
@@ -1076,7 +1076,7 @@ int mc_ctx_set_edit_rows(mc_ctx* c, const float* gt, const uint8_t* keep, const 
         return MC_ERR_STATE;
     }
     if (c->seam_ov > 0) { mc_set_error("mc_ctx_set_edit_rows: the context has a seam table set (mc_ctx_set_seams): clear it with overlap = 0"); return MC_ERR_STATE; }
-    if (int rq = seam_rows_refuse(c, "mc_ctx_set_edit_rows")) return rq;
+    if (!c->long_edits) { if (int rq = seam_rows_refuse(c, "mc_ctx_set_edit_rows")) return rq; }
     const size_t TC = (size_t)c->T * c->m->cfg.input_feats, n = (size_t)c->B * TC;
     hipStream_t s = (hipStream_t)stream;
     int r;
@@ -1097,6 +1097,18 @@ int mc_ctx_set_edit_rows(mc_ctx* c, const float* gt, const uint8_t* keep, const 
         b = e;
     }
     c->edit_set = true;
+    return MC_OK;
+}
+
+// Kept regions on long requests: the one switch under which the edit table and the row seam table may be set
+// side by side.  Off (the default) each refuses the other as ever.  No table, no history flag is touched.
+int mc_ctx_set_long_edits(mc_ctx* c, int32_t on) {
+    MC_REQUIRE(c, "null context");
+    if (!on && c->edit_set && c->seam_rows_ov > 0) {
+        mc_set_error("mc_ctx_set_long_edits: the context has an edit table and a row seam table set: clear one of them first");
+        return MC_ERR_STATE;
+    }
+    c->long_edits = on != 0;
     return MC_OK;
 }
 
@@ -1665,6 +1677,50 @@ int mc_op_sampler_seam_rows(const float* x_t, const float* ot, const float* on, 
     SamplerForm f = op_form(x_t, ot, on, noise, x0_hist, x_prev, x0, (long)B * T * C, &coefs[0]);
     f.c.text_coef = f.c.none_coef = 1.f;
     f.rt = &rt; f.seam_rows = &st;
+    if (dev_rng) f.keys = &rk;
+    return mc_launch_sampler(f, s);
+}
+
+// mc_op_sampler_seam_rows with a kept region (sampler_seam_edit_rows_k): the noise sources follow mc_op_sampler_edit_rows
+int mc_op_sampler_seam_edit_rows(const float* x_t, const float* ot, const float* on, const float* noise, const float* gt_noise, const float* gt,
+                                 const uint8_t* keep, const uint64_t* seeds, const uint64_t* draw, float* x0_hist, float* x_prev, float* x0,
+                                 int32_t B, int32_t T, int32_t C, int32_t overlap, const int32_t* right, const int32_t* first_frame,
+                                 const float* weight, const mc_step_coefs* coefs, void* stream) {
+    MC_REQUIRE(x_t && ot && on && gt && keep && x_prev && coefs && B >= 1 && C >= 1, "mc_op_sampler_seam_edit_rows: bad argument");
+    int r;
+    if ((r = rows_one_mode("mc_op_sampler_seam_edit_rows", coefs, B))) return r;
+    const bool ms = is_multistep(&coefs[0]);
+    const bool dev_rng = seeds != nullptr || draw != nullptr;
+    if (ms) MC_REQUIRE(x0_hist && !noise && !gt_noise && !dev_rng, "mc_op_sampler_seam_edit_rows: mode 2 needs x0_hist_dev and takes no noise");
+    else {
+        MC_REQUIRE(!dev_rng || (seeds && draw && !noise && !gt_noise), "mc_op_sampler_seam_edit_rows: (seeds_host, draw_host) come together and exclude the noise tensors");
+        MC_REQUIRE(dev_rng || noise, "mc_op_sampler_seam_edit_rows: modes 0 / 1 need noise_dev, or (seeds_host, draw_host)");
+        MC_REQUIRE(dev_rng || coefs[0].mode == MC_SAMPLER_DDPM || gt_noise, "mc_op_sampler_seam_edit_rows: mode 1 beside noise_dev needs gt_noise_dev");
+    }
+    std::vector<SeamRow> rows;
+    std::vector<float> wt;
+    if ((r = seam_rows_plan("mc_op_sampler_seam_edit_rows", B, T, overlap, right, first_frame, weight, &rows, &wt))) return r;
+    for (int b = 0; b < B; ++b) {
+        const int rb = right[b];
+        if (rb < 0) continue;
+        MC_REQUIRE(memcmp(&coefs[b], &coefs[rb], sizeof(mc_step_coefs)) == 0, "mc_op_sampler_seam_edit_rows: rows %d and %d share a seam but not their coefficients", b, rb);
+        MC_REQUIRE(!dev_rng || (seeds[b] == seeds[rb] && draw[b] == draw[rb]), "mc_op_sampler_seam_edit_rows: rows %d and %d share a seam but not their seed / draw number", b, rb);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    RowTab rt;
+    rt.B = B; rt.T = 1;
+    RowKeys rk;
+    TempTable tab(s), blk(s), kd(s);
+    if ((r = rows_tab_upload("mc_op_sampler_seam_edit_rows", coefs, B, &tab, &rt))) return r;
+    if (dev_rng && (r = rows_keys_upload("mc_op_sampler_seam_edit_rows", seeds, draw, B, (int)((long)T * C), &kd, &rt, &rk))) return r;
+    if ((r = blk.upload(rows.data(), sizeof(SeamRow) * B, "mc_op_sampler_seam_edit_rows", wt.data(), sizeof(float) * overlap))) return r;
+    SeamRowsTab st;
+    st.rows = static_cast<const SeamRow*>(blk.p); st.w = reinterpret_cast<const float*>(st.rows + B); st.T = T; st.C = C; st.ov = overlap;
+    EditTab et;
+    et.gt = gt; et.keep = keep; et.gt_noise = gt_noise;
+    SamplerForm f = op_form(x_t, ot, on, noise, x0_hist, x_prev, x0, (long)B * T * C, &coefs[0]);
+    f.c.text_coef = f.c.none_coef = 1.f;
+    f.rt = &rt; f.seam_rows = &st; f.edit = &et;
     if (dev_rng) f.keys = &rk;
     return mc_launch_sampler(f, s);
 }

@@ -837,11 +837,11 @@ int denoise_combined(mc_ctx* c, const float* x_t, int32_t step, const mc_step_co
 // has set into ONE description of the form (mc_launch_sampler picks the kernel).  Under capture the coefficients (the mode among
 // them) come from the device table at replay, so the mode is what mc_ctx_graph_capture found in the table (all mode 2 or none of it),
 // not the step-0 entry `k`'s.  Per-row schedules (one mode per call, checked by mc_sample_rows) go with no graph and no whole-batch
-// seam table, an edit table with no row seam table.
+// seam table, an edit table with no row seam table unless the context's long-edits switch is on (mc_ctx_set_long_edits).
 int sampler_update(mc_ctx* c, const float* x_t, const X0Parts& x0p, const mc_step_coefs* k, const float* noise, float* x_prev, float* x0,
                    hipStream_t s, const RngArgs* rng, const PadOut* pad) {
     if (c->rows_mode && (c->graph_mode || c->seam_ov > 0)) { mc_set_error("per-row sampler update under graph capture or with a seam table set"); return MC_ERR_STATE; }
-    if (c->rows_mode && c->seam_rows_ov > 0 && c->edit_set) { mc_set_error("per-row sampler update with a row seam table and an edit table set"); return MC_ERR_STATE; }
+    if (c->rows_mode && c->seam_rows_ov > 0 && c->edit_set && !c->long_edits) { mc_set_error("per-row sampler update with a row seam table and an edit table set"); return MC_ERR_STATE; }
     if (c->seam_ov > 0 && c->graph_mode) { mc_set_error("sampler update under graph capture with a seam table set"); return MC_ERR_STATE; }
     const bool multistep = c->graph_mode ? c->graph_multistep : k->mode == MC_SAMPLER_MULTISTEP;
     const int C = c->m->cfg.input_feats;
@@ -868,7 +868,8 @@ int sampler_update(mc_ctx* c, const float* x_t, const X0Parts& x0p, const mc_ste
             sr.rows = c->seam_rows_tab; sr.w = reinterpret_cast<const float*>(c->seam_rows_tab + c->B);
             sr.T = c->T; sr.C = C; sr.ov = c->seam_rows_ov;
             f.seam_rows = &sr;
-        } else if (c->edit_set) {        // a kept region (mc_ctx_set_edit_rows)
+        }
+        if (c->edit_set) {               // a kept region (mc_ctx_set_edit_rows); beside a row seam table under mc_ctx_set_long_edits
             MC_REQUIRE(multistep || !noise || k->mode == MC_SAMPLER_DDPM, "edited rows in mode 1 draw the kept region's noise from the seed table: no noise tensor");
             et.gt = c->edit_gt; et.keep = c->edit_keep;
             f.edit = &et;

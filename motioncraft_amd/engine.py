@@ -75,6 +75,7 @@ class NativeContext:
         self.row_seeds = None          # the rows' Philox keys while a seed table is set (set_row_seeds)
         self.edit_rows = False         # an edit table is set (set_edit_rows); read by serve: the first upload after a clear sends every row
         self.seam_rows = None          # dict(right, first_frame, overlap) while a row seam table is set (set_seam_rows)
+        self.long_edits = False        # the two tables may be set side by side (set_long_edits)
 
     @property
     def workspace_bytes(self):
@@ -367,6 +368,14 @@ class NativeContext:
     def clear_seam_rows(self):
         _lib.check(self.lib.mc_ctx_set_seam_rows(self.handle, 0, None, None, None, _stream()), 'mc_ctx_set_seam_rows')
         self.seam_rows = None
+
+    def set_long_edits(self, on=True):
+        """Let the edit table and the row seam table be set side by side (mc_ctx_set_long_edits): kept regions
+        on the windows of long requests.  Off (the default) the two setters refuse each other.  On, ``sample_rows`` blends a shared
+        frame's two x0 predictions and then takes x0 = gt where the OWNER's (the left row's) keep byte is set: upload equal ``keep`` /
+        ``gt`` for both copies of a shared frame.  Switching off while both tables are set raises."""
+        _lib.check(self.lib.mc_ctx_set_long_edits(self.handle, 1 if on else 0), 'mc_ctx_set_long_edits')
+        self.long_edits = bool(on)
 
     def set_capacity_factor(self, cf):
         """Capacity factor of every MoE of this context (mc_ctx_set_capacity_factor): > 0 tutel's formula with it, 0 = no (token,

@@ -94,8 +94,13 @@ class Edit:
         keep[torch.tensor(rows)[:, None], torch.tensor(cols)[None, :]] = True
         return cls(motion, keep)
 
-    def tables(self, frames, pre_process=None):
-        """-> (gt [frames, C] float32 in model space, keep [frames, C] uint8) on the CPU: frames past the edit's are free"""
+    def tables(self, frames, pre_process=None, first_frame=0):
+        """-> (gt [frames, C] float32 in model space, keep [frames, C] uint8) on the CPU: frames past the edit's are free.
+        ``first_frame``: the window form -- the slice of the edit that starts at that frame of the request, for
+        the row that shows frames ``[first_frame, first_frame + frames)``; two windows that share a frame get equal entries for it."""
+        if isinstance(first_frame, bool) or int(first_frame) != first_frame or int(first_frame) < 0:
+            raise ValueError(f'first_frame must be a non-negative integer, got {first_frame!r}')
+        first = int(first_frame)
         motion = self.motion.detach().float().cpu()
         keep = self.keep.cpu()
         motion = torch.where(keep, motion, torch.zeros_like(motion))          # (what is not given never reaches the device)
@@ -103,8 +108,9 @@ class Edit:
             motion = pre_process(motion)
         gt = torch.zeros(frames, self.feats)
         kp = torch.zeros(frames, self.feats, dtype=torch.uint8)
-        gt[:self.frames] = motion
-        kp[:self.frames] = keep.to(torch.uint8)
+        n = max(0, min(self.frames - first, frames))
+        gt[:n] = motion[first:first + n]
+        kp[:n] = keep[first:first + n].to(torch.uint8)
         return gt, kp
 
 
@@ -336,10 +342,17 @@ class ContinuousBatcher:
     The runner sees two more calls, both only while long requests are involved: ``condition(..., first_frames=[...] * B)`` (the global
     frame of every row's frame 0; a fresh row's x_T is its part of draw 0 of the request's field) and, after every admission and every
     retirement of a long request, ``seams(right [B], first_frame [B])`` with the table as it now stands, or ``clear_seams()`` once no
-    long request runs."""
+    long request runs.
+
+    Edits on long requests (``long_edits=True``, needs ``overlap=``).  ``submit()`` then takes an ``Edit`` on a
+    request longer than ``frames`` (keyframes over the whole sequence, a given opening, given body parts), and neither kind of
+    request waits for the other: the context holds both tables (``set_long_edits``).  Every window row is uploaded at admission with
+    its slice of the request's edit (``Edit.tables(frames, pre_process, first_frame)``), so the two copies of a shared frame carry
+    equal entries; the runner's ``condition`` then gets ``edits=`` and ``first_frames=`` in one call.  At the end of the walk the kept
+    elements of the stitched result are the given ones.  With ``long_edits=False`` nothing of this changes anything."""
 
     def __init__(self, model, batch, frames, sampler='ddim', steps=None, capacity_factor=0, eta=0.0, order=2, runner=None, overlap=None,
-                 seam_weights=None):
+                 seam_weights=None, long_edits=False):
         if sampler not in SAMPLERS:
             raise ValueError(f'sampler {sampler!r}: one of {SAMPLERS}')
         if int(batch) < 1 or int(frames) < 1:
@@ -362,7 +375,9 @@ class ContinuousBatcher:
                 seam_weights = [float(v) for v in seam_weights]
                 if len(seam_weights) != overlap or not all(0.0 <= v <= 1.0 for v in seam_weights):
                     raise ValueError(f'seam_weights: {overlap} numbers in [0, 1]')
-        self.overlap, self.seam_weights = overlap, seam_weights
+        if long_edits and overlap is None:
+            raise ValueError('long_edits without overlap: edits on long requests need the windows of overlap=')
+        self.overlap, self.seam_weights, self.long_edits = overlap, seam_weights, bool(long_edits)
         self._seams_on = False                        # the runner holds a row seam table
         self.runner = runner if runner is not None else _RowsRunner(self)
         self.walk = int(self.runner.steps)            # steps of one request's walk
@@ -386,7 +401,7 @@ class ContinuousBatcher:
         if request.length > self.frames:
             if self.overlap is None:
                 raise ValueError(f'request of {request.length} frames in a batcher of {self.frames}')
-            if request.edit is not None:
+            if request.edit is not None and not self.long_edits:
                 raise ValueError(f'an edit on a request of {request.length} frames, longer than the batcher\'s {self.frames}: edits on long requests are not served')
             W = len(plan_windows(request.length, self.frames, self.overlap))
             if W > self.batch:
@@ -428,8 +443,8 @@ class ContinuousBatcher:
                 break
             long_runs = any(q is not None and q[1].length > self.frames for q in self._rows)
             edit_runs = self._edit_on or any(q is not None and q[1].edit is not None for q in self._rows)
-            if (r.length > self.frames and edit_runs) or (r.edit is not None and long_runs):
-                break                                 # the edit table and the row seam table exclude each other
+            if not self.long_edits and ((r.length > self.frames and edit_runs) or (r.edit is not None and long_runs)):
+                break                                 # the edit table and the row seam table exclude each other (without long_edits)
             wins = self._windows(r)
             open_rows = [b for b in range(self.batch) if self._rows[b] is None]
             if len(open_rows) < len(wins):
@@ -480,7 +495,10 @@ class ContinuousBatcher:
         edits = [r[1].edit if r is not None else None for r in self._rows]
         long_rows = any(r is not None and r[1].length > self.frames for r in self._rows)
         if self._edit_on or any(e is not None for e in edits):
-            self.runner.condition(xf, lengths, seeds, flags, c, edits=edits)
+            if long_rows:                             # (long_edits: every row's slice of its request's edit starts at its first frame)
+                self.runner.condition(xf, lengths, seeds, flags, c, edits=edits, first_frames=[f for f, _ in wins])
+            else:
+                self.runner.condition(xf, lengths, seeds, flags, c, edits=edits)
             self._edit_on = True
             self._settle_edits()
         elif long_rows:
@@ -619,12 +637,14 @@ class _RowsRunner:
             kw = dict(xf_out=xf_out.to(dev), motion_mask=mask, c=c, capacity_factor=o.capacity_factor)
             self.ctx = net.sampling_context(B, T, self.diffusion.timestep_map, kw, dev)
             self.group = group
+            if self.ctx.long_edits != bool(getattr(o, 'long_edits', False)):      # (the context is the model's cached one)
+                self.ctx.set_long_edits(not self.ctx.long_edits)
             if self.x is None:
                 self.x = torch.zeros(B, T, C, device=dev)
         else:
             self.ctx.set_condition_rows(xf_out.to(dev), mask, fresh)
         if edits is not None:
-            self._upload_edits(edits, fresh, dev)
+            self._upload_edits(edits, fresh, dev, first_frames)
         self.ctx.set_row_seeds(seeds)
         # x_T of a fresh row: its frames of draw 0 of its seed's field (a short request, or window 0: elements [0, T C)).  The field is
         # a function of the seed alone, so it is drawn once per seed, as far as the last fresh window reaches, and gathered
@@ -647,8 +667,9 @@ class _RowsRunner:
         if self.ctx is not None:
             self.ctx.clear_seam_rows()
 
-    def _upload_edits(self, edits, fresh, dev):
-        """the tables of the rows with ``fresh[b]``: the row's edit in model space, or nothing kept.  Into a context that holds no table
+    def _upload_edits(self, edits, fresh, dev, first_frames=None):
+        """the tables of the rows with ``fresh[b]``: the row's edit in model space (the window of a long request: the slice that starts
+        at its first frame), or nothing kept.  Into a context that holds no table
         (the first edit, or the first after a clear) EVERY row is uploaded, each with its own edit or nothing kept: whatever
         an earlier table left on a row that now runs a request without an edit must not come back with the flag."""
         o, net = self.o, self.o.model.model
@@ -658,7 +679,7 @@ class _RowsRunner:
         keep = torch.zeros(B, T, C, dtype=torch.uint8)
         for b, e in enumerate(edits):
             if e is not None and (fresh[b] or every):
-                gt[b], keep[b] = e.tables(T, net.pre_process)
+                gt[b], keep[b] = e.tables(T, net.pre_process, 0 if first_frames is None else int(first_frames[b]))
         self.ctx.set_edit_rows(gt.to(dev), keep.to(dev), None if every else fresh)
 
     def clear_edits(self):

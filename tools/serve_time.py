@@ -24,7 +24,11 @@ after one warm-up:
             the arrival list LONG_ARRIVALS, which mixes short requests and requests of 2 .. 8 windows, through
             serve.ContinuousBatcher(overlap=), beside its long requests alone through longform.sample_long_coupled batches
 
-usage: serve_time.py [--small] [--batch B] [--requests R] [--steps N] [--reps K] [--only routing,noise,batcher,rows,arrivals,edits,long]
+  long_edits the long arm's tick with the row seam table AND an edit table (sampler_seam_edit_rows_k; keep bytes all
+            zero, and 25 % kept) against the table alone and no table, alternated in one process
+
+usage: serve_time.py [--small] [--batch B] [--requests R] [--steps N] [--reps K]
+                     [--only routing,noise,batcher,rows,arrivals,edits,long,long_edits]
   --small: the reduced test config (24 frames) instead of the 0.125b architecture (196 frames)"""
 import argparse
 import os
@@ -380,4 +384,52 @@ if 'long' in only and not a.skip_arrivals:
         print(f'{nreq} arrivals ({len(ll)} long, overlap {ov}), {a.steps}-step DDIM, B={B}, {name:42s}: median {med * 1e3:8.1f} ms = '
               f'{nreq / med:7.2f} requests/s   (min {lo * 1e3:8.1f}, max {hi * 1e3:8.1f} ms);  ticks to completion, long: mean '
               f'{sum(ll) / len(ll):6.1f}, max {max(ll)}{short}', flush=True)
+if 'long_edits' in only:
+    #  one tick with both tables set (sampler_seam_edit_rows_k) against the same tick with the row seam table alone
+    # (sampler_seam_rows_k) and with no table (sampler_update_rows_k), alternated in one process; the chains are those of the long arm
+    ov = T // 7 if not a.small else 6
+    stride = T - ov
+    x, xf, mask, _ = inputs(B)
+    mask[:] = 1
+    dd = build_diffusion(dict(schedule, respace=f'ddim{a.steps}'))
+    ctx = arch.model.native.context(B, T, max_steps=a.steps)
+    ctx.set_capacity_factor(0)
+    ctx.set_timesteps(dd.timestep_map)
+    ctx.set_condition(xf, mask)
+    ctx.set_long_edits(True)
+    nch = max(B // 8, 1)
+    ctx.set_row_seeds([100 + b % nch for b in range(B)])
+    step = a.steps // 2
+    ck = dd.step_coefs(step, 'ddim', arch.model.cfg_scale, 0.5)
+    right = [b + nch if b + nch < B else -1 for b in range(B)]
+    first = [(b // nch) * stride for b in range(B)]
+    g = torch.Generator().manual_seed(5)
+    gt = torch.randn(B, T, C, generator=g).cuda()
+    keep0 = torch.zeros(B, T, C, dtype=torch.uint8, device='cuda')
+    # 25 % kept, cut per chain from one request-global mask so that both copies of a shared frame agree
+    glob = torch.rand(nch, (B // nch - 1) * stride + T, C, generator=g) < 0.25
+    keep25 = torch.stack([glob[b % nch, first[b]:first[b] + T] for b in range(B)]).to(torch.uint8).cuda()
+    xd = x.clone()
+    tick = lambda: ctx.sample_rows(xd, [[step] * B], [[ck] * B], draws=[[1] * B])
+
+    def version(table, keep):
+        if table:
+            ctx.set_seam_rows(right, first, ov)
+        else:
+            ctx.clear_seam_rows()
+        if keep is None:
+            ctx.clear_edit_rows()
+        else:
+            ctx.set_edit_rows(gt, keep)
+        return median_of(lambda: events_ms(tick, 5))
+    arms = {'(a) mc_sample_rows tick, no table': lambda: version(False, None),
+            f'(b) ... {nch} chains of {B // nch} windows': lambda: version(True, None),
+            '(c) ... chains + keep all zero': lambda: version(True, keep0),
+            '(d) ... chains + 25 % kept': lambda: version(True, keep25)}
+    for name in list(arms) * 3:                    # (three rounds, alternated: the spread of equal settings is the machine's drift)
+        med, lo, hi = arms[name]()
+        print(f'B={B} {name:38s}: median {med:8.3f} ms   min {lo:8.3f}   max {hi:8.3f}   (5 calls per run)', flush=True)
+    ctx.clear_seam_rows()
+    ctx.clear_edit_rows()
+    ctx.close()
 arch.model.release()
