@@ -10,13 +10,17 @@ schedule ``mogen/models/utils/scheduler.py:178-208``) is covered too.  ``dpm_sol
 ``logsnr_timesteps``) is this project's own: the reference has no second-order sampler.  Training losses, learned variances and
 cond_fn guidance are outside this path and raise loudly.
 """
+import contextlib
 import enum
+import itertools
 import math
 
 import numpy as np
 import torch
 
 from . import lib as _lib
+
+FUSED_NOISE_CHUNK_BYTES = 512 << 20     # the fused loop with step_noise gathers the draws into [steps, B, T, C] chunks of at most this
 
 
 class ModelMeanType(enum.Enum):
@@ -162,10 +166,13 @@ class GaussianDiffusion:
                              "architecture with cfg.model['opt'] = args as the reference tools do")
         return dict(keep=keep.to(device).contiguous(), gt=y['gt'].to(device=device, dtype=torch.float32).contiguous())
 
+    def _cfg_weight(self, i, scale):
+        """the text branch's share of the classifier-free combination at spaced index i (the other branch gets 1 - w)"""
+        return (1 - (1000 - int(self.timestep_map[i])) / 1000) * scale + 1
+
     def step_coefs(self, i, mode, scale, eta=0.0):
         """fp64 tables -> fp32 scalars exactly like _extract_into_tensor(...).float()."""
-        t_orig = self.timestep_map[i]
-        w = (1 - (1000 - int(t_orig)) / 1000) * scale + 1
+        w = self._cfg_weight(i, scale)
         c = _lib.StepCoefs()
         c.mode = 0 if mode == 'ddpm' else 1
         c.text_coef, c.none_coef = w, 1 - w
@@ -193,8 +200,7 @@ class GaussianDiffusion:
         out, h_prev = [], None
         for i in indices:
             i = int(i)
-            t_orig = self.timestep_map[i]
-            w = (1 - (1000 - int(t_orig)) / 1000) * scale + 1
+            w = self._cfg_weight(i, scale)
             c = _lib.StepCoefs()
             c.mode = _lib.MC_SAMPLER_MULTISTEP
             c.text_coef, c.none_coef = w, 1 - w
@@ -249,60 +255,47 @@ class GaussianDiffusion:
         from .engine import check_seeds
         return check_seeds(seeds, shape[0])
 
-    def _loop(self, mode, model, shape, noise, model_kwargs, device, progress, eta, step_noise, generator,
-              num_steps=None, trajectory=None, pre_seq=None, transl_req=None, graph=False, fused=True, seeds=None):
-        """the walk of ``_walk``; with ``model_kwargs['seams']`` the context's seam table is set before it and cleared after it, whatever
-        happens in between (per-step and fused path alike: the library picks the coupled update wherever a table is set); the seed
-        table of ``seeds`` likewise"""
-        seams = self._seams_of(model_kwargs, graph, pre_seq, transl_req)
-        seeds = self._seeds_of(seeds, shape, noise, step_noise, generator, transl_req)
-        if seeds is not None:
-            held, seeded = [], []
-            try:
-                return self._walk(mode, model, shape, noise, model_kwargs, device, progress, eta, step_noise, generator, num_steps,
-                                  trajectory, pre_seq, transl_req, graph, fused, seams=seams, seam_held=held, seeds=seeds, seed_held=seeded)
-            finally:
-                for ctx in held:
-                    ctx.clear_seams()
-                for ctx in seeded:
-                    ctx.clear_row_seeds()
-        if seams is None:
-            return self._walk(mode, model, shape, noise, model_kwargs, device, progress, eta, step_noise, generator, num_steps,
-                              trajectory, pre_seq, transl_req, graph, fused)
-        held = []
-        try:
-            return self._walk(mode, model, shape, noise, model_kwargs, device, progress, eta, step_noise, generator, num_steps,
-                              trajectory, pre_seq, transl_req, graph, fused, seams=seams, seam_held=held)
-        finally:
-            for ctx in held:
-                ctx.clear_seams()
-
-    def _walk(self, mode, model, shape, noise, model_kwargs, device, progress, eta, step_noise, generator,
-              num_steps=None, trajectory=None, pre_seq=None, transl_req=None, graph=False, fused=True, seams=None, seam_held=None,
-              seeds=None, seed_held=None):
-        if model_kwargs is None:
-            model_kwargs = {}
-        if not isinstance(shape, (tuple, list)):
+    # ---- the walk: one description of the call, one context, one table guard, one x_T, one step loop -------------
+    def _sample(self, run):
+        """The walk of one public call.  With ``model_kwargs['seams']`` the context's seam table is set before it and cleared after
+        it, whatever happens in between (per-step and fused path alike: the library picks the coupled update wherever a table is set);
+        the seed table of ``seeds`` likewise."""
+        if run.model_kwargs is None:
+            run.model_kwargs = {}
+        if not isinstance(run.shape, (tuple, list)):
             raise AssertionError('shape must be a tuple or list')
-        B, T, C = shape
-        if device is None:
-            device = torch.device('cuda', torch.cuda.current_device())
-        inp = self._inpaint_operands(mode, model_kwargs, shape, device)
-        ctx = model.sampling_context(B, T, self.timestep_map, model_kwargs, device)
-        if seams is not None:
-            seam_held.append(ctx)
-            ctx.set_seams(**seams)
-        if seeds is not None:
-            seed_held.append(ctx)
-            ctx.set_row_seeds(seeds)
-            img = ctx.draw_rows(0)                                            # x_T: draw 0 of every row
-        elif noise is not None:
-            img = noise.to(device=device, dtype=torch.float32).contiguous().clone()
-        else:
-            img = torch.randn(*shape, device=device, generator=generator)
-        # the schedule: (i, True) = denoise at spaced index i, (i, False) = forward "undo" step with beta[i]
-        if inp is not None and mode == 'ddim' and not getattr(self.opt, 'no_repaint', False):
-            if num_steps is not None:
+        B, T, C = run.shape
+        if run.device is None:
+            run.device = torch.device('cuda', torch.cuda.current_device())
+        inp = None if run.mode == 'dpmpp' else self._inpaint_operands(run.mode, run.model_kwargs, run.shape, run.device)
+        ctx = run.model.sampling_context(B, T, self.timestep_map, run.model_kwargs, run.device)
+        with _tables(ctx, run.seams, run.seeds):
+            img = self._walk(ctx, run, inp, self._x_T(ctx, run))
+            if getattr(ctx, 'uses_coop_routing', False):
+                ctx.check()            # one sync after the last step: a timed-out grid barrier of the routing kernel raises here
+        return img
+
+    @staticmethod
+    def _x_T(ctx, run):
+        if run.seeds is not None:
+            return ctx.draw_rows(0)                                           # draw 0 of every row's own stream
+        if run.noise is not None:
+            return run.noise.to(device=run.device, dtype=torch.float32).contiguous().clone()
+        return torch.randn(*run.shape, device=run.device, generator=run.generator)
+
+    def _coefs(self, run, indices):
+        """the ``StepCoefs`` at the schedule indices ``indices``.  k1 of a multistep step belongs to the walk: those are picked from the
+        coefficients of the whole descent, so a truncated run is a prefix of it"""
+        scale = run.model.cfg_scale
+        if run.mode == 'dpmpp':
+            whole = self.multistep_coefs(range(self.num_timesteps - 1, -1, -1), scale, run.order)[::-1]
+            return [whole[i] for i in indices]
+        return [self.step_coefs(i, run.mode, scale, run.eta) for i in indices]
+
+    def _plan(self, run, inp):
+        """the schedule: (i, StepCoefs) = denoise at spaced index i, (i, None) = forward "undo" step with beta[i]"""
+        if inp is not None and run.mode == 'ddim' and not getattr(self.opt, 'no_repaint', False):
+            if run.num_steps is not None:
                 raise ValueError('num_steps truncation is not defined for the resampling schedule')
             n_ddim = int(str(self.opt.timestep_respacing)[4:])
             if getattr(self.opt, 'no_resample', False):
@@ -313,50 +306,58 @@ class GaussianDiffusion:
             if max(times) >= self.num_timesteps:
                 raise ValueError(f'opt.timestep_respacing={self.opt.timestep_respacing!r} starts the resampling loop at '
                                  f'step {max(times)} of a {self.num_timesteps}-step schedule')
-            plan = [(a, b < a) for a, b in zip(times[:-1], times[1:])]
+            visits = [(a, b < a) for a, b in zip(times[:-1], times[1:])]
         else:
-            indices = list(range(self.num_timesteps))[::-1]
-            if num_steps is not None:
-                indices = indices[:num_steps]
-            plan = [(i, True) for i in indices]
-        if progress:
-            from tqdm.auto import tqdm
-            plan = tqdm(plan)
-        seeded = pre_seq is not None or bool(transl_req)
-        if seeded:
-            # p_sample :664-674 / ddim_sample :816-820: every step re-noises pre_seq (and the requested translation
-            # channels of frames 0-1) to the step's level and writes it over the first frames of x before the network call
-            if inp is not None:
-                raise NotImplementedError('pre_seq / transl_req together with the outpainting mask: no reference tool combines them')
-            if pre_seq is not None:
-                pre_seq = pre_seq.to(device=device, dtype=torch.float32).contiguous()
-                if pre_seq.dim() != 3 or pre_seq.shape[0] != B or pre_seq.shape[2] != C or pre_seq.shape[1] > T:
-                    raise RuntimeError(f'pre_seq of shape {tuple(pre_seq.shape)} cannot be written into x[:, :T, :] of {tuple(shape)}')
-            transl_req = [list(it) for it in (transl_req or [])]
-            if transl_req and B > 2:
-                # _extract_into_tensor(arr, t, (2,)) expands a [B] tensor to (2,): the reference raises for B > 2 as well
-                raise RuntimeError(f'transl_req: the expanded size of the tensor (2) must match the batch size ({B})')
-            if any(len(it) != 3 for it in transl_req):
-                raise ValueError('transl_req items are [channel, value_frame0, value_frame1]')
-            if step_noise is not None and not hasattr(step_noise, '__next__'):
-                raise ValueError('with pre_seq / transl_req several tensors of different shapes are drawn per step: '
-                                 'step_noise must be an iterator yielding them in the order the reference draws them '
-                                 '(randn_like(pre_seq), one randn(2) per transl_req item, randn_like(x))')
-        draw_no = [0]
+            visits = [(i, True) for i in list(range(self.num_timesteps))[::-1][:run.num_steps]]
+        coefs = iter(self._coefs(run, [i for i, down in visits if down]))
+        return [(i, next(coefs) if down else None) for i, down in visits]
+
+    @staticmethod
+    def _seeding(run, inp):
+        """p_sample :664-674 / ddim_sample :816-820: every step re-noises pre_seq (and the requested translation channels of frames
+        0-1) to the step's level and writes it over the first frames of x before the network call.  -> None (no seeding), or
+        (pre_seq on the device or None, the transl_req items as lists)"""
+        pre_seq, step_noise = run.pre_seq, run.step_noise
+        if pre_seq is None and not run.transl_req:
+            return None
+        if inp is not None:
+            raise NotImplementedError('pre_seq / transl_req together with the outpainting mask: no reference tool combines them')
+        B, T, C = run.shape
+        if pre_seq is not None:
+            pre_seq = pre_seq.to(device=run.device, dtype=torch.float32).contiguous()
+            if pre_seq.dim() != 3 or pre_seq.shape[0] != B or pre_seq.shape[2] != C or pre_seq.shape[1] > T:
+                raise RuntimeError(f'pre_seq of shape {tuple(pre_seq.shape)} cannot be written into x[:, :T, :] of {tuple(run.shape)}')
+        transl_req = [list(it) for it in (run.transl_req or [])]
+        if transl_req and B > 2:
+            # _extract_into_tensor(arr, t, (2,)) expands a [B] tensor to (2,): the reference raises for B > 2 as well
+            raise RuntimeError(f'transl_req: the expanded size of the tensor (2) must match the batch size ({B})')
+        if any(len(it) != 3 for it in transl_req):
+            raise ValueError('transl_req items are [channel, value_frame0, value_frame1]')
+        if step_noise is not None and not hasattr(step_noise, '__next__'):
+            raise ValueError('with pre_seq / transl_req several tensors of different shapes are drawn per step: '
+                             'step_noise must be an iterator yielding them in the order the reference draws them '
+                             '(randn_like(pre_seq), one randn(2) per transl_req item, randn_like(x))')
+        return pre_seq, transl_req
+
+    @staticmethod
+    def _draws(ctx, run, inp):
+        """-> ``draw(i)``: the next randn_like(x) of the reference loop; in the outpainting mode several are drawn per step, so there
+        ``step_noise`` is an iterator (or a callable of the running draw number).  The multistep walk draws nothing."""
+        if run.mode == 'dpmpp':
+            return lambda i: None
+        step_noise, device = run.step_noise, run.device
         if inp is not None and step_noise is not None and not (hasattr(step_noise, '__next__') or callable(step_noise)):
             raise ValueError('the outpainting mode draws several independent randn_like tensors per step index: '
                              'step_noise must be an iterator or a callable of the running draw number there, not a '
                              'sequence indexed by step (every draw of a step would get the same tensor)')
+        count = itertools.count()
 
         def draw(i):
-            """the next randn_like(x) of the reference loop; in the outpainting mode several are drawn per step,
-            so there ``step_noise`` is an iterator (or a callable of the running draw number)."""
-            n = draw_no[0]
-            draw_no[0] += 1
-            if seeds is not None:
+            n = next(count)
+            if run.seeds is not None:
                 return ctx.draw_rows(1 + n)                                   # the n-th randn_like of the walk: draw 1 + n
             if step_noise is None:
-                return torch.randn(*shape, device=device, generator=generator)
+                return torch.randn(*run.shape, device=device, generator=run.generator)
             if hasattr(step_noise, '__next__'):
                 e = next(step_noise)
             elif callable(step_noise):
@@ -364,108 +365,113 @@ class GaussianDiffusion:
             else:
                 e = step_noise[i]
             return e.to(device=device, dtype=torch.float32).contiguous()
+        return draw
 
-        blend_w = None
-        if inp is not None and mode == 'ddim':
+    def _seeded_step(self, ctx, run, seeding, draw):
+        pre_seq, transl_req = seeding
+        step_noise, generator, device = run.step_noise, run.generator, run.device
+
+        def step(i, c, x, nxt, x0):
+            a_, b_ = np.float32(self.sqrt_alphas_cumprod[i]), np.float32(self.sqrt_one_minus_alphas_cumprod[i])
+            pre_noise = None
+            if pre_seq is not None and run.seeds is not None:
+                pre_noise = draw(i)[:, :pre_seq.shape[1]].contiguous()        # a smaller tensor: the leading elements of each row's draw
+            elif pre_seq is not None:
+                pre_noise = (next(step_noise).to(device=device, dtype=torch.float32).contiguous() if step_noise is not None
+                             else torch.randn(*pre_seq.shape, device=device, generator=generator))
+            transl = []
+            for it in transl_req:                                            # th.randn(2) on the host, then q_sample in fp32
+                n2 = (next(step_noise) if step_noise is not None else torch.randn(2, generator=generator if generator is not None and generator.device.type == 'cpu' else None))
+                n2 = n2.detach().cpu().numpy().astype(np.float32)
+                v = a_ * np.asarray(it[1:], dtype=np.float32) + b_ * n2
+                transl.append((int(it[0]), float(v[0]), float(v[1])))
+            ctx.sample_step_seeded(x, i, c, draw(i), a_, b_, pre_seq=pre_seq, pre_noise=pre_noise, transl=transl, x_prev=nxt, x0=x0)
+        return step
+
+    def _inpaint_step(self, ctx, run, inp, draw):
+        T, blend_w = run.shape[1], None
+        if run.mode == 'ddim':
             ov = int(self.opt.overlap_len)
             if not 0 <= ov <= T:
                 raise ValueError(f'opt.overlap_len={ov} outside the {T}-frame window')
-            blend_w = torch.linspace(0, 1, ov, device=device) if ov > 0 else None
-        nxt = torch.empty_like(img)
-        x0 = torch.empty_like(img) if trajectory is not None else None
-        if graph:
+            blend_w = torch.linspace(0, 1, ov, device=run.device) if ov > 0 else None
+
+        def step(i, c, x, nxt, x0):
+            eps = draw(i)
+            gt_noise, blend_len = None, 0
+            if run.mode == 'ddim':
+                gt_noise = draw(i)                                            # :868
+                noise_weight = np.sqrt(np.float32(1) - np.float32(self.alphas_cumprod_prev[i]))
+                if noise_weight < np.float32(0.2) and getattr(self.opt, 'addBlend', True) and blend_w is not None:
+                    blend_len = int(self.opt.overlap_len)                     # :872-875
+            ctx.sample_step_inpaint(x, i, c, eps, inp['gt'], inp['keep'], gt_noise=gt_noise, blend_w=blend_w, blend_len=blend_len,
+                                    x_prev=nxt, x0=x0)
+        return step
+
+    def _walk(self, ctx, run, inp, img):
+        mode, scale = run.mode, run.model.cfg_scale
+        plan = self._plan(run, inp)
+        if run.progress:
+            from tqdm.auto import tqdm
+            plan = tqdm(plan)
+        seeding = self._seeding(run, inp)
+        draw = self._draws(ctx, run, inp)
+        if seeding is not None:
+            denoise = self._seeded_step(ctx, run, seeding, draw)
+        elif inp is not None:
+            denoise = self._inpaint_step(ctx, run, inp, draw)
+        else:                                                                 # (eps is drawn every step, DDIM too; None in the multistep walk)
+            denoise = lambda i, c, x, nxt, x0: ctx.sample_step(x, i, c, draw(i), x_prev=nxt, x0=x0)    # noqa: E731
+        plain = inp is None and seeding is None and run.trajectory is None
+        if run.graph:
             # hipGraph replay (BASELINE configs[4]): one captured graph of the step for the whole schedule, x updated in
             # place, the per-step noise refilled in place; bit-identical to the eager sequence, 2-3 % faster for B <= 4
             # (profiles/r02_graph_vs_eager.txt)
-            if inp is not None or seeded or trajectory is not None:
-                raise ValueError('graph replay covers the plain p_sample / ddim_sample step (no outpainting, seeding or trajectory)')
-            # the graph (and the x / noise buffers baked into it) lives on the context and is reused by later calls with the
-            # same schedule: capture + instantiate cost a few ms, more than one small-batch loop gains
-            key = (mode, float(eta), float(model.cfg_scale), tuple(int(t) for t in self.timestep_map))
-            st = getattr(ctx, '_graph_state', None)
-            if st is None or st['key'] != key:
-                side = torch.cuda.Stream(device=device)
-                side.wait_stream(torch.cuda.current_stream(device))
-                with torch.cuda.stream(side):
-                    gx, nbuf = torch.empty_like(img), torch.empty_like(img)
-                    coefs = [self.step_coefs(j, mode, model.cfg_scale, eta) for j in range(self.num_timesteps)]
-                    ctx.graph_capture(gx, nbuf, coefs)
-                st = ctx._graph_state = dict(key=key, stream=side, x=gx, noise=nbuf)
-            side = st['stream']
-            side.wait_stream(torch.cuda.current_stream(device))
-            with torch.cuda.stream(side):
-                st['x'].copy_(img)
-                for i, _ in plan:
-                    st['noise'].copy_(draw(i))
-                    ctx.graph_step(i)
-                img.copy_(st['x'])
-            torch.cuda.current_stream(device).wait_stream(side)
-            if getattr(ctx, 'uses_coop_routing', False):
-                ctx.check()
+            if not plain:
+                raise ValueError('graph replay covers the plain step (no trajectory)' if mode == 'dpmpp' else
+                                 'graph replay covers the plain p_sample / ddim_sample step (no outpainting, seeding or trajectory)')
+            key = (mode, int(run.order) if mode == 'dpmpp' else float(run.eta), float(scale), tuple(int(t) for t in self.timestep_map))
+            return _replay(ctx, run.device, img, key, lambda: self._coefs(run, range(self.num_timesteps)), (i for i, _ in plan),
+                           None if mode == 'dpmpp' else draw)
+        if run.fused and plain and not run.progress:
+            self._fused(ctx, run, img, plan, draw)
             return img
-        if (fused and inp is None and not seeded and trajectory is None and not progress and all(d for _, d in plan)):
-            # the whole loop inside the library (mc_sample_loop): no return to Python between steps.  Without step_noise the
-            # per-step randn_like is drawn INSIDE the sampler-update kernel (Philox4x32-10; the loop's 64-bit key is one draw from
-            # `generator`, so a seeded generator reproduces the run and successive calls differ); with step_noise the draws are
-            # gathered into [steps, B, T, C] chunks of at most ~512 MB and the same entry point reads them
-            idx = [i for i, _ in plan]
-            coefs = [self.step_coefs(i, mode, model.cfg_scale, eta) for i in idx]
-            if seeds is not None:
-                ctx.sample_loop(img, idx, coefs, noise=None, seed=0, draw0=1)     # step k: draw 1 + k of every row's own stream
-            elif step_noise is None:
-                gdev = generator.device if generator is not None else torch.device('cpu')
-                key = int(torch.randint(0, 2 ** 62, (1,), generator=generator, device=gdev).item())
-                ctx.sample_loop(img, idx, coefs, noise=None, seed=key, draw0=0)
-            else:
-                chunk = max(1, int((512 << 20) // (4 * B * T * C)))
-                for k0 in range(0, len(idx), chunk):
-                    part = idx[k0:k0 + chunk]
-                    nz = torch.stack([draw(i) for i in part])
-                    ctx.sample_loop(img, part, coefs[k0:k0 + chunk], noise=nz)
-            if getattr(ctx, 'uses_coop_routing', False):
-                ctx.check()
-            return img
-        for i, denoise in plan:
-            if not denoise:                                                   # _undo (:429-435)
+        nxt = torch.empty_like(img)
+        x0 = torch.empty_like(img) if run.trajectory is not None else None
+        for i, c in plan:
+            if c is None:                                                     # _undo (:429-435)
                 beta = np.float32(self.betas[i])
                 ctx.renoise(img, draw(i), np.sqrt(np.float32(1) - beta), np.sqrt(beta), out=nxt)
-            elif seeded:
-                a_, b_ = np.float32(self.sqrt_alphas_cumprod[i]), np.float32(self.sqrt_one_minus_alphas_cumprod[i])
-                pre_noise = None
-                if pre_seq is not None and seeds is not None:
-                    pre_noise = draw(i)[:, :pre_seq.shape[1]].contiguous()    # a smaller tensor: the leading elements of each row's draw
-                elif pre_seq is not None:
-                    pre_noise = (next(step_noise).to(device=device, dtype=torch.float32).contiguous() if step_noise is not None
-                                 else torch.randn(*pre_seq.shape, device=device, generator=generator))
-                transl = []
-                for it in transl_req:                                        # th.randn(2) on the host, then q_sample in fp32
-                    n2 = (next(step_noise) if step_noise is not None else torch.randn(2, generator=generator if generator is not None and generator.device.type == 'cpu' else None))
-                    n2 = n2.detach().cpu().numpy().astype(np.float32)
-                    v = a_ * np.asarray(it[1:], dtype=np.float32) + b_ * n2
-                    transl.append((int(it[0]), float(v[0]), float(v[1])))
-                eps = draw(i)
-                ctx.sample_step_seeded(img, i, self.step_coefs(i, mode, model.cfg_scale, eta), eps, a_, b_, pre_seq=pre_seq,
-                                       pre_noise=pre_noise, transl=transl, x_prev=nxt, x0=x0)
-            elif inp is None:
-                eps = draw(i)                                                 # drawn every step, DDIM too
-                ctx.sample_step(img, i, self.step_coefs(i, mode, model.cfg_scale, eta), eps, x_prev=nxt, x0=x0)
             else:
-                eps = draw(i)
-                gt_noise, blend_len = None, 0
-                if mode == 'ddim':
-                    gt_noise = draw(i)                                        # :868
-                    noise_weight = np.sqrt(np.float32(1) - np.float32(self.alphas_cumprod_prev[i]))
-                    if noise_weight < np.float32(0.2) and getattr(self.opt, 'addBlend', True) and blend_w is not None:
-                        blend_len = int(self.opt.overlap_len)                 # :872-875
-                ctx.sample_step_inpaint(img, i, self.step_coefs(i, mode, model.cfg_scale, eta), eps, inp['gt'],
-                                        inp['keep'], gt_noise=gt_noise, blend_w=blend_w, blend_len=blend_len,
-                                        x_prev=nxt, x0=x0)
+                denoise(i, c, img, nxt, x0)
             img, nxt = nxt, img
-            if trajectory is not None:
-                trajectory.append((i, img.clone(), x0.clone()))
-        if getattr(ctx, 'uses_coop_routing', False):
-            ctx.check()            # one sync after the last step: a timed-out grid barrier of the routing kernel raises here
+            if run.trajectory is not None:
+                run.trajectory.append((i, img.clone(), x0.clone()))
         return img
+
+    @staticmethod
+    def _fused(ctx, run, img, plan, draw):
+        """The whole loop inside the library (mc_sample_loop): no return to Python between steps.  Without step_noise the per-step
+        randn_like is drawn INSIDE the sampler-update kernel (Philox4x32-10; the loop's 64-bit key is one draw from `generator`, so a
+        seeded generator reproduces the run and successive calls differ; with ``seeds`` step k is draw 1 + k of every row's own stream;
+        the multistep walk draws nothing); with step_noise the draws are gathered into [steps, B, T, C] chunks of at most
+        ``FUSED_NOISE_CHUNK_BYTES`` and the same entry point reads them"""
+        idx, coefs = [i for i, _ in plan], [c for _, c in plan]
+        if run.step_noise is not None:
+            chunk = max(1, int(FUSED_NOISE_CHUNK_BYTES // (4 * img.numel())))
+            for k0 in range(0, len(idx), chunk):
+                part = idx[k0:k0 + chunk]
+                ctx.sample_loop(img, part, coefs[k0:k0 + chunk], noise=torch.stack([draw(i) for i in part]))
+            return
+        seed, draw0 = 0, 0
+        if run.mode == 'dpmpp':
+            pass
+        elif run.seeds is not None:
+            draw0 = 1
+        else:
+            gdev = run.generator.device if run.generator is not None else torch.device('cpu')
+            seed = int(torch.randint(0, 2 ** 62, (1,), generator=run.generator, device=gdev).item())
+        ctx.sample_loop(img, idx, coefs, noise=None, seed=seed, draw0=draw0)
 
     def p_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                       model_kwargs=None, device=None, pre_seq=None, transl_req=None, progress=False,
@@ -477,8 +483,9 @@ class GaussianDiffusion:
         every per-step draw then come from the row's own Philox stream (``_seeds_of``), the same bits on the fused, the per-step and
         the graph path; exclusive with ``noise``, ``step_noise`` and ``generator``."""
         self._check_supported(clip_denoised, denoised_fn, cond_fn, model_kwargs, pre_seq, transl_req)
-        return self._loop('ddpm', model, shape, noise, model_kwargs, device, progress, 0.0, step_noise, generator,
-                          num_steps, trajectory, pre_seq=pre_seq, transl_req=transl_req, graph=graph, fused=fused, seeds=seeds)
+        return self._sample(_Run('ddpm', model, shape, noise=noise, model_kwargs=model_kwargs, device=device, progress=progress,
+                                             step_noise=step_noise, generator=generator, num_steps=num_steps, trajectory=trajectory,
+                                             pre_seq=pre_seq, transl_req=transl_req, graph=graph, fused=fused, seeds=seeds))
 
     def ddim_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                          model_kwargs=None, device=None, progress=False, eta=0.0, pre_seq=None,
@@ -488,9 +495,9 @@ class GaussianDiffusion:
             raise NotImplementedError('opt.same_overlap_noisy: the reference writes self.saved_noisy_tail '
                                       '(gaussian_diffusion.py:879-881) without ever creating it, so that option has '
                                       'no defined behaviour to reproduce')
-        return self._loop('ddim', model, shape, noise, model_kwargs, device, progress, float(eta), step_noise,
-                          generator, num_steps, trajectory, pre_seq=pre_seq, graph=graph, fused=fused, seeds=seeds)
-
+        return self._sample(_Run('ddim', model, shape, noise=noise, model_kwargs=model_kwargs, device=device, progress=progress,
+                                             eta=float(eta), step_noise=step_noise, generator=generator, num_steps=num_steps,
+                                             trajectory=trajectory, pre_seq=pre_seq, graph=graph, fused=fused, seeds=seeds))
 
     def dpm_solver_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                                model_kwargs=None, device=None, progress=False, order=2, generator=None, num_steps=None,
@@ -505,11 +512,10 @@ class GaussianDiffusion:
         self._check_supported(clip_denoised, denoised_fn, cond_fn, model_kwargs, pre_seq, transl_req)
         if order not in (1, 2):
             raise ValueError(f'order={order!r}: the multistep solver is implemented for order 1 and 2')
-        if model_kwargs is None:
-            model_kwargs = {}
-        seams = self._seams_of(model_kwargs, graph, pre_seq, transl_req)
-        seeds = self._seeds_of(seeds, shape, noise, None, generator)
-        keep = ((model_kwargs.get('y', {}) or {}).get('outpainting_mask', None))
+        run = _Run('dpmpp', model, shape, noise=noise, model_kwargs=model_kwargs, device=device, progress=progress, order=order,
+                   generator=generator, num_steps=num_steps, trajectory=trajectory, pre_seq=pre_seq, transl_req=transl_req, graph=graph,
+                   fused=fused, seeds=seeds)
+        keep = (((model_kwargs or {}).get('y', {}) or {}).get('outpainting_mask', None))
         if keep is not None and bool(keep.any()):
             raise NotImplementedError('dpm_solver_sample_loop with an outpainting mask (RePaint): not implemented for the '
                                       'multistep sampler, use ddim_sample_loop')
@@ -517,78 +523,66 @@ class GaussianDiffusion:
             raise NotImplementedError('dpm_solver_sample_loop with pre_seq seeding: not implemented for the multistep sampler')
         if transl_req:
             raise NotImplementedError('dpm_solver_sample_loop with transl_req seeding: not implemented for the multistep sampler')
-        if not isinstance(shape, (tuple, list)):
-            raise AssertionError('shape must be a tuple or list')
-        B, T, C = shape
-        if device is None:
-            device = torch.device('cuda', torch.cuda.current_device())
-        ctx = model.sampling_context(B, T, self.timestep_map, model_kwargs, device)
-        if seams is None and seeds is None:
-            return self._multistep_walk(ctx, model, shape, noise, device, progress, order, generator, num_steps, trajectory, graph, fused)
-        try:                                                  # coupled windows / row seeds: the tables are set for this walk only
-            if seams is not None:
-                ctx.set_seams(**seams)
-            if seeds is not None:
-                ctx.set_row_seeds(seeds)
-            return self._multistep_walk(ctx, model, shape, noise, device, progress, order, generator, num_steps, trajectory, graph, fused,
-                                        seeded=seeds is not None)
-        finally:
-            if seams is not None:
-                ctx.clear_seams()
-            if seeds is not None:
-                ctx.clear_row_seeds()
+        return self._sample(run)
 
-    def _multistep_walk(self, ctx, model, shape, noise, device, progress, order, generator, num_steps, trajectory, graph, fused,
-                        seeded=False):
-        if seeded:
-            img = ctx.draw_rows(0)                                # x_T: draw 0 of every row's own stream
-        elif noise is not None:
-            img = noise.to(device=device, dtype=torch.float32).contiguous().clone()
-        else:
-            img = torch.randn(*shape, device=device, generator=generator)
-        indices = list(range(self.num_timesteps))[::-1]
-        # k1 of a step belongs to the walk: the coefficients of the whole descent; a truncated run is a prefix of it
-        coefs = self.multistep_coefs(indices, model.cfg_scale, order)
-        if num_steps is not None:
-            indices, coefs = indices[:num_steps], coefs[:num_steps]
-        if graph:
-            if trajectory is not None:
-                raise ValueError('graph replay covers the plain step (no trajectory)')
-            key = ('dpmpp', int(order), float(model.cfg_scale), tuple(int(t) for t in self.timestep_map))
-            st = getattr(ctx, '_graph_state', None)
-            if st is None or st['key'] != key:
-                side = torch.cuda.Stream(device=device)
-                side.wait_stream(torch.cuda.current_stream(device))
-                with torch.cuda.stream(side):
-                    gx = torch.empty_like(img)
-                    table = self.multistep_coefs(list(range(self.num_timesteps))[::-1], model.cfg_scale, order)[::-1]
-                    ctx.graph_capture(gx, None, table)            # table[i]: schedule index i of the descent
-                st = ctx._graph_state = dict(key=key, stream=side, x=gx, noise=None)
-            side = st['stream']
-            side.wait_stream(torch.cuda.current_stream(device))
-            with torch.cuda.stream(side):
-                st['x'].copy_(img)
-                for i in indices:
-                    ctx.graph_step(i)
-                img.copy_(st['x'])
-            torch.cuda.current_stream(device).wait_stream(side)
-        elif fused and trajectory is None and not progress:
-            ctx.sample_loop(img, indices, coefs, noise=None)
-        else:
-            plan = list(zip(indices, coefs))
-            if progress:
-                from tqdm.auto import tqdm
-                plan = tqdm(plan)
-            nxt = torch.empty_like(img)
-            x0 = torch.empty_like(img) if trajectory is not None else None
-            for i, c in plan:
-                ctx.sample_step(img, i, c, None, x_prev=nxt, x0=x0)
-                img, nxt = nxt, img
-                if trajectory is not None:
-                    trajectory.append((i, img.clone(), x0.clone()))
-        if getattr(ctx, 'uses_coop_routing', False):
-            ctx.check()
-        return img
+
+class _Run:
+    """What one call of a sampler loop asked for: ``mode`` ('ddpm', 'ddim' or 'dpmpp'), the model, the shape of the sample and the
+    loop's keywords.  What does not go with coupled windows or row seeds raises here, first of all; ``seams`` / ``seeds`` are the
+    checked tables."""
+    noise = step_noise = generator = num_steps = trajectory = pre_seq = transl_req = seeds = model_kwargs = device = None
+    progress, graph, fused, eta, order = False, False, True, 0.0, 2
+
+    def __init__(self, mode, model, shape, **asked):
+        self.mode, self.model, self.shape = mode, model, shape
+        self.__dict__.update(asked)
+        self.seams = GaussianDiffusion._seams_of(self.model_kwargs, self.graph, self.pre_seq, self.transl_req)
+        transl_req = None if mode == 'dpmpp' else self.transl_req          # (the multistep loop refuses it under its own name)
+        self.seeds = GaussianDiffusion._seeds_of(self.seeds, shape, self.noise, self.step_noise, self.generator, transl_req)
+
+
+@contextlib.contextmanager
+def _tables(ctx, seams, seeds):
+    """the seam table, then the seed table, set on ``ctx`` for the ``with`` block only: each one that was attempted is cleared once"""
+    clear = []
+    try:
+        if seams is not None:
+            clear.append(ctx.clear_seams)
+            ctx.set_seams(**seams)
+        if seeds is not None:
+            clear.append(ctx.clear_row_seeds)
+            ctx.set_row_seeds(seeds)
+        yield
+    finally:
+        for f in clear:
+            f()
+
+
+def _replay(ctx, device, img, key, table, steps, refill=None):
+    """``img`` through the schedule indices ``steps`` by replaying the captured graph of the step.  The graph (and the x / noise buffers
+    baked into it) lives on the context and is reused by later calls with the same ``key``: capture + instantiate cost a few ms,
+    more than one small-batch loop gains.  ``table()``: the ``StepCoefs`` of every schedule index, asked for when a graph is captured;
+    ``refill(i)``: the noise of step i (None: the captured step reads none)."""
+    now = torch.cuda.current_stream(device)
+    st = getattr(ctx, '_graph_state', None)
+    if st is None or st['key'] != key:
+        side = torch.cuda.Stream(device=device)
+        side.wait_stream(now)
+        with torch.cuda.stream(side):
+            gx, nbuf = torch.empty_like(img), (torch.empty_like(img) if refill is not None else None)
+            ctx.graph_capture(gx, nbuf, table())
+        st = ctx._graph_state = dict(key=key, stream=side, x=gx, noise=nbuf)
+    side = st['stream']
+    side.wait_stream(now)
+    with torch.cuda.stream(side):
+        st['x'].copy_(img)
+        for i in steps:
+            if refill is not None:
+                st['noise'].copy_(refill(i))
+            ctx.graph_step(i)
+        img.copy_(st['x'])
+    now.wait_stream(side)
+    return img
 
 
 def get_schedule_jump_cjm_ddim(time_respacing=25, jump_length=1, jump_n_sample=1):

@@ -169,18 +169,10 @@ def plan_windows(length, frames, overlap):
     return [(j * stride, min(T, F - j * stride)) for j in range(W)]
 
 
-class RequestBatcher:
-    """``submit()`` requests, ``run()`` them ``batch`` at a time through one (batch, frames) context.
+class _Batcher:
+    """what the two batchers share: the sampler settings, the respaced schedule and the queue"""
 
-    ``model``: a ``MotionDiffusion`` (its denoiser and its test schedule's configuration are used).  ``sampler`` in ``SAMPLERS``;
-    ``steps``: respace the schedule to that many steps (None: the configured schedule).  ``runner`` replaces the model call (tests):
-    ``runner(xf_out [B,Nt,Dt], lengths [B], seeds [B], c [B,Tc,Fc] or None) -> [B, frames, C]``; a batch that holds a request with an
-    ``Edit`` calls it with ``edits=[Edit or None] * B`` too.
-
-    A batch with an edit runs through ``mc_sample_rows`` with uniform tables (every row at walk position k in tick k, draw 1 + k): the
-    path ``ContinuousBatcher`` takes, so a request gets the same bits from both.  Batches without one take the fused loop as before."""
-
-    def __init__(self, model, batch, frames, sampler='ddim', steps=None, capacity_factor=0, eta=0.0, order=2, runner=None):
+    def __init__(self, model, batch, frames, sampler, steps, capacity_factor, eta, order):
         if sampler not in SAMPLERS:
             raise ValueError(f'sampler {sampler!r}: one of {SAMPLERS}')
         if int(batch) < 1 or int(frames) < 1:
@@ -192,27 +184,57 @@ class RequestBatcher:
         self.model, self.batch, self.frames = model, int(batch), int(frames)
         self.sampler, self.steps, self.capacity_factor = sampler, None if steps is None else int(steps), float(capacity_factor)
         self.eta, self.order = float(eta), int(order)
-        self.runner = runner if runner is not None else self._run_model
-        self._diffusion = None
         self._pending = []             # (handle, Request with xf_out set)
         self._next = 0
+
+    def _respaced(self):
+        """the model's test schedule, respaced to ``steps``"""
+        from .diffusion import build_diffusion
+        cfg = dict(self.model.diffusion_test_cfg)
+        if self.steps is not None:
+            cfg['respace'] = str(self.steps) if self.sampler == 'ddpm' else f'ddim{self.steps}'
+        return build_diffusion(cfg, opt=self.model.opt)
+
+    def _is_long(self, request):
+        return request.length > self.frames
+
+    def _queue(self, request):
+        """``request`` with its text encoded and every other field carried, into the queue; -> its handle"""
+        _check_edit(self.model, request)
+        if request.xf_out is None:
+            # one prompt per encoder call: the condition of a request must not depend on what it is encoded beside
+            xf = self.model.model.encode_text([request.text], None, None)[0]
+            request = Request(request.length, request.seed, xf_out=xf, c=request.c, guidance_scale=request.guidance_scale, edit=request.edit)
+        handle = self._next
+        self._next += 1
+        self._pending.append((handle, request))
+        return handle
+
+
+class RequestBatcher(_Batcher):
+    """``submit()`` requests, ``run()`` them ``batch`` at a time through one (batch, frames) context.
+
+    ``model``: a ``MotionDiffusion`` (its denoiser and its test schedule's configuration are used).  ``sampler`` in ``SAMPLERS``;
+    ``steps``: respace the schedule to that many steps (None: the configured schedule).  ``runner`` replaces the model call (tests):
+    ``runner(xf_out [B,Nt,Dt], lengths [B], seeds [B], c [B,Tc,Fc] or None) -> [B, frames, C]``; a batch that holds a request with an
+    ``Edit`` calls it with ``edits=[Edit or None] * B`` too.
+
+    A batch with an edit runs through ``mc_sample_rows`` with uniform tables (every row at walk position k in tick k, draw 1 + k): the
+    path ``ContinuousBatcher`` takes, so a request gets the same bits from both.  Batches without one take the fused loop as before."""
+
+    def __init__(self, model, batch, frames, sampler='ddim', steps=None, capacity_factor=0, eta=0.0, order=2, runner=None):
+        super().__init__(model, batch, frames, sampler, steps, capacity_factor, eta, order)
+        self.runner = runner if runner is not None else self._run_model
+        self._diffusion = None
 
     # ---- queue ------------------------------------------------------------------------------------
     def submit(self, request):
         """Queue ``request``; -> its handle (the key of ``run()``'s result)."""
         if not isinstance(request, Request):
             raise ValueError('submit() takes a Request')
-        if request.length > self.frames:
+        if self._is_long(request):
             raise ValueError(f'request of {request.length} frames in a batcher of {self.frames}')
-        _check_edit(self.model, request)
-        if request.xf_out is None:
-            # one prompt per encoder call: the condition of a request must not depend on what it is encoded beside
-            xf = self.model.model.encode_text([request.text], None, None)[0]
-            request = Request(request.length, request.seed, xf_out=xf, c=request.c, edit=request.edit)
-        handle = self._next
-        self._next += 1
-        self._pending.append((handle, request))
-        return handle
+        return self._queue(request)
 
     def plan(self):
         """The model calls ``run()`` will make: a list of batches, each a list of ``batch`` entries -- a pending handle, or None for a
@@ -251,11 +273,7 @@ class RequestBatcher:
     # ---- the model call ---------------------------------------------------------------------------
     def _schedule(self):
         if self._diffusion is None:
-            from .diffusion import build_diffusion
-            cfg = dict(self.model.diffusion_test_cfg)
-            if self.steps is not None:
-                cfg['respace'] = str(self.steps) if self.sampler == 'ddpm' else f'ddim{self.steps}'
-            self._diffusion = build_diffusion(cfg, opt=self.model.opt)
+            self._diffusion = self._respaced()
         return self._diffusion
 
     def _run_model(self, xf_out, lengths, seeds, c, edits=None):
@@ -290,7 +308,7 @@ class RequestBatcher:
             rr.clear_edits()           # (the context is the model's cached one: the fused loop refuses it while a table is set)
 
 
-class ContinuousBatcher:
+class ContinuousBatcher(_Batcher):
     """Requests join a running batch at any step and leave when their own walk ends.
 
     Every row of the (batch, frames) context walks the same schedule, each from its own start: a row admitted at tick t sits at walk
@@ -353,17 +371,7 @@ class ContinuousBatcher:
 
     def __init__(self, model, batch, frames, sampler='ddim', steps=None, capacity_factor=0, eta=0.0, order=2, runner=None, overlap=None,
                  seam_weights=None, long_edits=False):
-        if sampler not in SAMPLERS:
-            raise ValueError(f'sampler {sampler!r}: one of {SAMPLERS}')
-        if int(batch) < 1 or int(frames) < 1:
-            raise ValueError(f'batch and frames must be positive, got {batch!r}, {frames!r}')
-        if steps is not None and int(steps) < 1:
-            raise ValueError(f'steps must be positive, got {steps!r}')
-        if float(capacity_factor) < 0:
-            raise ValueError(f'capacity_factor must be >= 0, got {capacity_factor!r}')
-        self.model, self.batch, self.frames = model, int(batch), int(frames)
-        self.sampler, self.steps, self.capacity_factor = sampler, None if steps is None else int(steps), float(capacity_factor)
-        self.eta, self.order = float(eta), int(order)
+        super().__init__(model, batch, frames, sampler, steps, capacity_factor, eta, order)
         if overlap is None:
             if seam_weights is not None:
                 raise ValueError('seam_weights without overlap')
@@ -384,9 +392,7 @@ class ContinuousBatcher:
         if self.walk < 1:
             raise ValueError(f'the schedule has {self.walk} steps')
         self._rows = [None] * self.batch              # per row: None (open) or [handle, Request, walk position, window of the request]
-        self._pending = []
         self._done = {}
-        self._next = 0
         self._conditioned = False
         self._edit_on = False                         # the runner holds an edit table
         self._stale = [False] * self.batch            # rows retired since the last condition call (still holding their old condition)
@@ -398,7 +404,7 @@ class ContinuousBatcher:
         """Queue ``request``; -> its handle (the key of ``poll()``'s result)."""
         if not isinstance(request, Request):
             raise ValueError('submit() takes a Request')
-        if request.length > self.frames:
+        if self._is_long(request):
             if self.overlap is None:
                 raise ValueError(f'request of {request.length} frames in a batcher of {self.frames}')
             if request.edit is not None and not self.long_edits:
@@ -408,13 +414,7 @@ class ContinuousBatcher:
                 raise ValueError(f'request of {request.length} frames is {W} windows of {self.frames} (overlap {self.overlap}) in a batcher of {self.batch} rows')
             if request.c is not None and request.c.shape[0] % request.length:
                 raise ValueError(f'the control condition has {request.c.shape[0]} rows for {request.length} frames: a whole number of rows per frame')
-        _check_edit(self.model, request)
-        if request.xf_out is None:
-            xf = self.model.model.encode_text([request.text], None, None)[0]
-            request = Request(request.length, request.seed, xf_out=xf, c=request.c, guidance_scale=request.guidance_scale, edit=request.edit)
-        handle = self._next
-        self._next += 1
-        self._pending.append((handle, request))
+        handle = self._queue(request)
         self.submitted_at[handle] = self.ticks
         return handle
 
@@ -427,12 +427,12 @@ class ContinuousBatcher:
         """the shape of one row's control condition (None: no control); the windows of a long request hold ``frames`` frames of it"""
         if r.c is None:
             return None
-        if r.length > self.frames:
+        if self._is_long(r):
             return (self.frames * (r.c.shape[0] // r.length), int(r.c.shape[1]))
         return tuple(r.c.shape)
 
     def _windows(self, r):
-        return plan_windows(r.length, self.frames, self.overlap) if r.length > self.frames else [(0, r.length)]
+        return plan_windows(r.length, self.frames, self.overlap) if self._is_long(r) else [(0, r.length)]
 
     def _admit_fifo(self, group):
         """``_admit`` with ``overlap`` set: strict FIFO, the head of the queue takes the lowest open rows or everyone waits"""
@@ -441,9 +441,9 @@ class ContinuousBatcher:
             handle, r = self._pending[0]
             if self._group(r) != group:
                 break
-            long_runs = any(q is not None and q[1].length > self.frames for q in self._rows)
+            long_runs = any(q is not None and self._is_long(q[1]) for q in self._rows)
             edit_runs = self._edit_on or any(q is not None and q[1].edit is not None for q in self._rows)
-            if not self.long_edits and ((r.length > self.frames and edit_runs) or (r.edit is not None and long_runs)):
+            if not self.long_edits and ((self._is_long(r) and edit_runs) or (r.edit is not None and long_runs)):
                 break                                 # the edit table and the row seam table exclude each other (without long_edits)
             wins = self._windows(r)
             open_rows = [b for b in range(self.batch) if self._rows[b] is None]
@@ -493,21 +493,18 @@ class ContinuousBatcher:
         if first.c is not None:
             c = torch.stack([self._row_control(r, wins[b], first) for b, r in enumerate(self._rows)])
         edits = [r[1].edit if r is not None else None for r in self._rows]
-        long_rows = any(r is not None and r[1].length > self.frames for r in self._rows)
+        more = {}                                     # the keywords a runner sees only while edits / long requests are involved
         if self._edit_on or any(e is not None for e in edits):
-            if long_rows:                             # (long_edits: every row's slice of its request's edit starts at its first frame)
-                self.runner.condition(xf, lengths, seeds, flags, c, edits=edits, first_frames=[f for f, _ in wins])
-            else:
-                self.runner.condition(xf, lengths, seeds, flags, c, edits=edits)
+            more['edits'] = edits
+        if any(r is not None and self._is_long(r[1]) for r in self._rows):
+            more['first_frames'] = [f for f, _ in wins]   # (long_edits: every row's slice of its request's edit starts at its first frame)
+        self.runner.condition(xf, lengths, seeds, flags, c, **more)
+        if 'edits' in more:
             self._edit_on = True
             self._settle_edits()
-        elif long_rows:
-            self.runner.condition(xf, lengths, seeds, flags, c, first_frames=[f for f, _ in wins])
-        else:
-            self.runner.condition(xf, lengths, seeds, flags, c)
         self._conditioned = True
         self._stale = [False] * self.batch
-        if any(self._rows[b] is not None and self._rows[b][1].length > self.frames for b in fresh):
+        if any(self._rows[b] is not None and self._is_long(self._rows[b][1]) for b in fresh):
             self._send_seams()
 
     def _row_control(self, r, win, first):
@@ -517,7 +514,7 @@ class ContinuousBatcher:
         if r is None:
             return torch.zeros(shape, dtype=first.c.dtype)
         c = r[1].c
-        if r[1].length <= self.frames:
+        if not self._is_long(r[1]):
             return c
         per = c.shape[0] // r[1].length
         out = torch.zeros(shape, dtype=c.dtype)
@@ -528,7 +525,7 @@ class ContinuousBatcher:
         """the row seam table as the rows now stand (after an admission or a retirement of a long request), or none"""
         by_handle = {}
         for b, r in enumerate(self._rows):
-            if r is not None and r[1].length > self.frames:
+            if r is not None and self._is_long(r[1]):
                 by_handle.setdefault(r[0], {})[r[3]] = b
         if not by_handle:
             if self._seams_on:
@@ -574,7 +571,7 @@ class ContinuousBatcher:
             if r[2] == self.walk:
                 if out is None:
                     out = self.runner.result()
-                if r[1].length > self.frames:         # (the rows of a request were admitted together: they all retire in this round)
+                if self._is_long(r[1]):               # (the rows of a request were admitted together: they all retire in this round)
                     parts.setdefault(r[0], (r[1].length, {}))[1][r[3]] = out[b]
                 else:
                     self._done[r[0]] = out[b, :r[1].length].clone()
@@ -611,12 +608,8 @@ class _RowsRunner:
     """the model behind ``ContinuousBatcher``: the (batch, frames) context of the model, ``x`` [B, frames, C] in place"""
 
     def __init__(self, owner):
-        from .diffusion import build_diffusion
         self.o = owner
-        cfg = dict(owner.model.diffusion_test_cfg)
-        if owner.steps is not None:
-            cfg['respace'] = str(owner.steps) if owner.sampler == 'ddpm' else f'ddim{owner.steps}'
-        self.diffusion = build_diffusion(cfg, opt=owner.model.opt)
+        self.diffusion = owner._respaced()
         self.steps = self.diffusion.num_timesteps
         self.ctx, self.x, self.group = None, None, ()
         self._coefs = {}                              # scale -> the StepCoefs of a whole walk, by walk position
